@@ -1,23 +1,36 @@
 #!/usr/bin/env python3
 """Benchmark of the WISECONDOR hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One step = one pass of the `newref` reference-bin selection over the whole workload
 (BASELINE.json config 2 by default: 100 samples x 250 kb bins) with the corrected matrix
-already resident in HBM, followed (timed separately) by batched `test` passes (PCA-apply ->
-5 masked z-score repeats -> Stouffer segmentation) over --test-samples samples per GPU at the
-same bin size.
+already resident in HBM.
+
+A plain run does what the headline figure needs and nothing else: it builds the inputs, runs
+K untimed passes (the clocks settle under load) and W warm-up passes, times K passes, writes
+the outputs of the last timed pass if --dump-outputs is given, and prints the result line.
+
+--full adds everything else, as before: the stage times and roofline objects (K passes with
+events between the stages, run instead of the untimed settle passes), batched `test` passes
+(PCA-apply -> 5 masked z-score repeats -> Stouffer segmentation) over --test-samples samples
+per GPU at the same bin size, the latency and whole-cohort calls, the 600 x 50 kb extra, the
+ingest run and the CPU baseline, with the full record written to --detail.
+
+--dump-outputs DIR: after the timed steps rank 0 writes what the last timed pass delivered,
+DIR/indexes.npy and DIR/distances.npy ([bins, refsize] float64), or a fixed seeded sample of
+their rows (DIR/rows.npy) when the whole pair would exceed 64 MB.  The inputs are synthetic
+and seeded (wisecondor_amd/synth.py): the same arguments give the same inputs on every run.
 
 With --gpus N > 1 and no torchrun environment the script starts N ranks of itself (fresh
 processes, before anything touches the GPU); under torchrun it checks that WORLD_SIZE == N.
 
 Rank 0 prints ONE JSON line: `value` is the newref metric of BASELINE.json (ordered
-cross-chromosome bin-pair distances per second, whole job), `test` carries samples/s,
-`roofline` describes the kernel that takes longest per step (timed live with events on the
-launch stream), `stages_ms` every stage of the step, and `cpu_baseline` the CPU oracle timed
-on this box (rank 0, N=1 only; one core and all cores).  Inputs are synthetic (seeded), see
-wisecondor_amd/synth.py.
+cross-chromosome bin-pair distances per second, whole job) and `ms_per_step` the time of one
+timed pass.  With --full the line also carries `test` (samples/s), `roofline` (the kernel that
+takes longest per step, timed live with events on the launch stream), `stages_ms` (every stage
+of the step) and `cpu_baseline` (the CPU oracle timed on this box; rank 0, N=1 only; one core
+and all cores).
 """
 import argparse
 import json
@@ -101,25 +114,28 @@ def launch_check(args):
 
 
 # ------------------------------------------------------------------- inputs ----
-def build_inputs(binsize, n_ref, n_test, seed0=0, device=0):
-    """Pipeline-level synthetic inputs: reference samples -> prep (GPU, untimed) and test samples."""
+def build_inputs(binsize, n_ref, n_test, seed0=0, device=0, time_prep=True):
+    """Pipeline-level synthetic inputs: reference samples -> prep (GPU, untimed) and test samples.
+    time_prep=False (a plain bench run) skips the timed second prep; prep_ms is then None."""
     import numpy as np
     from wisecondor_amd import synth
     from wisecondor_amd import wisetools as wt
     profile = synth.bin_profile(binsize)
     samples = [synth.make_sample(profile, seed=seed0 + i) for i in range(n_ref)]
     _, chrom_bins, mask, corrected, comps, mean, masked_bins = wt.prepReference(samples, device=device)
-    # the same prep again, device resident and timed (SURVEY.md 8 f1: newrefprep's numerics; host counts in,
-    # correctedData left in HBM for newref): what a caller pays between `convert`ed samples and stage A
-    import time as _time
-    import torch as _torch
-    dense = wt.samples_to_counts(samples, chrom_bins)           # what an ingest loop holds (wisecondor_amd/ingest.py)
-    wt.prepReference(None, device=device, device_out=True, counts=dense, chrom_bins=chrom_bins)
-    _torch.cuda.synchronize()
-    _t0 = _time.perf_counter()
-    wt.prepReference(None, device=device, device_out=True, counts=dense, chrom_bins=chrom_bins)
-    _torch.cuda.synchronize()
-    prep_ms = 1e3 * (_time.perf_counter() - _t0)
+    prep_ms = None
+    if time_prep:
+        # the same prep again, device resident and timed (SURVEY.md 8 f1: newrefprep's numerics; host counts in,
+        # correctedData left in HBM for newref): what a caller pays between `convert`ed samples and stage A
+        import time as _time
+        import torch as _torch
+        dense = wt.samples_to_counts(samples, chrom_bins)           # what an ingest loop holds (wisecondor_amd/ingest.py)
+        wt.prepReference(None, device=device, device_out=True, counts=dense, chrom_bins=chrom_bins)
+        _torch.cuda.synchronize()
+        _t0 = _time.perf_counter()
+        wt.prepReference(None, device=device, device_out=True, counts=dense, chrom_bins=chrom_bins)
+        _torch.cuda.synchronize()
+        prep_ms = 1e3 * (_time.perf_counter() - _t0)
     masked_bins = np.asarray(masked_bins, dtype=np.int64)
     tests = make_tests(profile, n_test)
     return dict(corrected=corrected, chrom_bins=np.asarray(chrom_bins, dtype=np.int64), mask=mask,
@@ -769,6 +785,47 @@ def emit(detail, path):
     sys.stdout.flush()
 
 
+def emit_plain(record, path=None):
+    """The line of a plain run: the record itself (scalars and `config`), printed LAST; written to `path` too
+    when --detail names one."""
+    if path:
+        try:
+            with open(path, "w") as fh:
+                json.dump(record, fh, indent=1)
+            record["detail_file"] = os.path.relpath(path, ROOT) if path.startswith(ROOT) else path
+        except Exception as exc:
+            record["detail_file"] = "not written: %s" % exc
+    line = json.dumps(_num(record), allow_nan=False, separators=(",", ":"))
+    sys.stdout.flush()
+    print(line)
+    sys.stdout.flush()
+
+
+DUMP_LIMIT = 64 * 1000 * 1000      # bytes of .npy data that --dump-outputs writes at most
+
+
+def dump_outputs(out_dir, idx, dst, seed=0):
+    """What the timed path delivered in its last pass -- the newref indexes and distances -- as float64 .npy
+    files under out_dir (int32 indexes are exact in float64).  When the pair would exceed DUMP_LIMIT, a fixed
+    seeded sample of rows is written instead, and its row numbers as rows.npy."""
+    import numpy as np
+    idx_h = idx.cpu().numpy()
+    dst_h = dst.cpu().numpy()
+    n_rows, k = idx_h.shape
+    files = {}
+    if 2 * n_rows * k * 8 > DUMP_LIMIT:
+        keep = max(1, (DUMP_LIMIT - 4096) // (2 * k * 8 + 8))
+        rows = np.sort(np.random.RandomState(seed).choice(n_rows, size=keep, replace=False))
+        idx_h, dst_h = idx_h[rows], dst_h[rows]
+        files["rows"] = rows.astype(np.float64)
+    files["indexes"] = idx_h.astype(np.float64)
+    files["distances"] = np.ascontiguousarray(dst_h, dtype=np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in files.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+    return sorted(files)
+
+
 # --------------------------------------------------------------------- main ----
 def main():
     ap = argparse.ArgumentParser()
@@ -776,18 +833,28 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="cfg2", choices=sorted(WORKLOADS))
-    ap.add_argument("--test-samples", type=int, default=128, help="test samples per GPU in the batched test pass")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline: stage times, rooflines, the batched / latency / "
+                         "whole-cohort test, the 600 x 50 kb extra, ingest, the CPU baseline (off: the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed pass's outputs (indexes, distances) as float64 .npy files to DIR")
+    ap.add_argument("--test-samples", type=int, default=128, help="test samples per GPU in the batched test pass (--full)")
     ap.add_argument("--refsize", type=int, default=100)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the extra 600 x 50 kb newref measurement")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="(--full) skip the extra 600 x 50 kb newref measurement")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only for "
                     "functional tests of the multi-rank path on a box with fewer GPUs than ranks)")
-    ap.add_argument("--detail", default=os.path.join(ROOT, "bench_detail.json"),
+    ap.add_argument("--detail", default=None,
                     help="where the full measurement record goes (stage tables, per-rank lists, emulated world, "
-                         "every roofline object); the LAST stdout line is a compact summary of it")
+                         "every roofline object); the LAST stdout line is a compact summary of it.  Default with "
+                         "--full: bench_detail.json in the repository; a plain run writes one only when asked")
     ap.add_argument("--launch-check", action="store_true",
                     help="only start the ranks, rendezvous (gloo) and report the world size: no GPU work")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.full and args.detail is None:
+        args.detail = os.path.join(ROOT, "bench_detail.json")
 
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
@@ -830,7 +897,8 @@ def main():
 
     binsize, n_ref = WORKLOADS[args.workload]
     k = args.refsize
-    inp = build_inputs(binsize, n_ref, args.test_samples, seed0=0, device=local_rank)
+    inp = build_inputs(binsize, n_ref, args.test_samples if args.full else 0, seed0=0, device=local_rank,
+                       time_prep=args.full)
     corrected = inp["corrected"]                       # Fortran-ordered, like the reference's prep file
     order = wt.sum_order_of(corrected)
     B, S = corrected.shape
@@ -877,11 +945,15 @@ def main():
     # cost ~15 % of a 0.2 ms pass, so they stay out of `value`.  They run FIRST (round 6; behind the timed region
     # before): the chip's clocks settle over the first ~15 ms of load (consecutive groups of 20
     # passes read 0.212, 0.208, 0.203, 0.198 ms on a GPU that has just been idle), and this leg is load like any other.
+    # A plain run (no --full) runs the same K passes without the events: the timed region sees the same clocks.
     marks, comms = [], []
     for s in range(args.steps):
-        idx, dst = job.run(timing=True)
-        marks.append(job.last_marks)
-        comms.append(job.last_comm)
+        if args.full:
+            idx, dst = job.run(timing=True)
+            marks.append(job.last_marks)
+            comms.append(job.last_comm)
+        else:
+            idx, dst = job.run()
     sync_all()
     for _ in range(max(1, args.warmup)):              # W untimed passes ...
         idx, dst = job.run()
@@ -891,6 +963,44 @@ def main():
         idx, dst = job.run()                          # ... then the timed region: K plain passes, nothing else
     sync_all()
     t_newref = max_over_ranks(time.perf_counter() - t0)
+    ms_per_step = 1e3 * t_newref / args.steps
+    value = pairs * args.steps / t_newref
+    dumped = dump_outputs(args.dump_outputs, idx, dst) if (args.dump_outputs and rank == 0) else None
+    shard = {"rows": "row bands (all-gather only)", "tiles": "symmetric tiles (threshold all-gather, list "
+             "all-to-all, result all-gather)"}.get(job.mode, "single rank, symmetric tiles")
+    head = {
+        "metric": "newref bin-pair distances/sec",
+        "value": value,
+        "unit": "bin-pair distances/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms_per_step,
+        "higher_is_better": True,
+        "scaling": "strong",
+        "vs_baseline": None,
+        # every delivered index and distance is decided in float64 (numpy's bits); the matrix
+        # cores only bound the distances to pick the candidates that get re-scored
+        "dtype": "f64",
+        "dtype_detail": "f16 MFMA (one product per multiply, f32 accumulate, per-row representation error in the "
+                        "bounds) distance bounds + f64 exact re-score",
+        "data": "synthetic",
+    }
+    if not args.full:
+        if rank == 0:
+            head["timing"] = ("value / ms_per_step: %d plain passes between two synchronizes, after %d untimed passes "
+                              "(the clocks settle over the first ~15 ms of load) and %d warm-up passes"
+                              % (args.steps, args.steps, max(1, args.warmup)))
+            head["config"] = {"workload": "%s: newref %d samples x %d kb bins (%d masked bins, refsize %d)"
+                                          % (args.workload, S, binsize // 1000, B, k),
+                              "parallelism": "newref sharded by %s, %d rank(s)" % (shard, world),
+                              "world_size": world, "shard_mode": job.mode or "single"}
+            head["outputs"] = dumped
+            emit_plain(head, args.detail)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     stages = mean_stages(job, marks)             # every interval booked under the stage that ended it (bands add up)
     collectives = mean_collectives(job, comms)
     gram_ms = stages.get("collected")
@@ -905,8 +1015,6 @@ def main():
     stats = wt.newref_stats(local_rank)
     gram_mode = "f16"
     variants = {}
-    ms_per_step = 1e3 * t_newref / args.steps
-    value = pairs * args.steps / t_newref
 
     # -------------------------------------------------------------- test ----
     idx_h, dst_h = idx.cpu().numpy(), dst.cpu().numpy()
@@ -1311,28 +1419,11 @@ def main():
             dominant, other = roof_finish, roof_gram
         else:
             dominant, other = roof_gram, roof_finish
-        shard = {"rows": "row bands (all-gather only)", "tiles": "symmetric tiles (threshold all-gather, list "
-                 "all-to-all, result all-gather)"}.get(job.mode, "single rank, symmetric tiles")
-        out = {
-            "metric": "newref bin-pair distances/sec",
-            "value": value,
-            "unit": "bin-pair distances/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": ms_per_step,
-            "higher_is_better": True,
-            "scaling": "strong",
-            "vs_baseline": None,
-            # every delivered index and distance is decided in float64 (numpy's bits); the matrix
-            # cores only bound the distances to pick the candidates that get re-scored
-            "dtype": "f64",
-            "dtype_detail": "f16 MFMA (one product per multiply, f32 accumulate, per-row representation error in the "
-                            "bounds) distance bounds + f64 exact re-score",
+        out = dict(head)
+        out.update({
             "timing": "value / ms_per_step: %d plain passes between two synchronizes; stages_ms and the roofline "
                       "kernel times: %d passes with events between the stages, run BEFORE the %d warm-up passes and the timed "
                       "region (they are load like any other: the clocks settle over the first ~15 ms)" % (args.steps, args.steps, args.warmup),
-            "data": "synthetic",
             "config": {"workload": "%s: newref %d samples x %d kb bins (%d masked bins, refsize %d), "
                                    "then batched test of %d samples/GPU at the same bin size"
                                    % (args.workload, S, binsize // 1000, B, k, args.test_samples),
@@ -1366,7 +1457,8 @@ def main():
             "newref_stats": stats,
             "extra": extra,
             "cpu_baseline": cpu,
-        }
+            "outputs": dumped,
+        })
         emit(out, args.detail)
     if world > 1:
         dist.barrier()

@@ -198,7 +198,7 @@ def _strict_json(text):
 
 
 def _run_bench(tmp_path, argv, timeout):
-    """bench.py as the driver runs it: the LAST stdout line is the record the driver parses (compact: it lost a
+    """bench.py --full as the driver runs it: the LAST stdout line is the record the driver parses (compact: it lost a
     21 KB line in round 5), the full record goes to the --detail file.  Returns (line, detail)."""
     import json
     import subprocess
@@ -206,7 +206,7 @@ def _run_bench(tmp_path, argv, timeout):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     detail_path = os.path.join(str(tmp_path), "bench_detail.json")
-    p = subprocess.run([sys.executable, "bench.py"] + argv + ["--detail", detail_path], cwd=root, env=env,
+    p = subprocess.run([sys.executable, "bench.py", "--full"] + argv + ["--detail", detail_path], cwd=root, env=env,
                        capture_output=True, text=True, timeout=timeout)
     assert p.returncode == 0, p.stderr[-2000:]
     last = p.stdout.rstrip("\n").splitlines()[-1]
@@ -256,7 +256,7 @@ def test_bench_eight_ranks_on_one_gpu(tmp_path):
 
 
 def test_bench_line_is_complete_on_one_gpu(tmp_path):
-    """The default bench command in a short form (cfg2, the 600 x 50 kb extra, no CPU leg): ONE compact last
+    """The full bench command in a short form (cfg2, the 600 x 50 kb extra, no CPU leg): ONE compact last
     line (< 8 000 bytes, strict JSON) with the contract's keys, and a detail record with every object the
     measurement contract names, every fraction at most 1, no swallowed error."""
     short, line = _run_bench(tmp_path, ["--steps", "4", "--warmup", "1", "--test-samples", "32", "--no-cpu-baseline"], 900)
@@ -314,3 +314,35 @@ def test_bench_line_is_complete_on_one_gpu(tmp_path):
     assert t50["whole_job_1000_samples"]["samples_per_s"] > 0.8 * t50["value"]
     assert line["rescore_stage"]["k_rescore_ms"] > 0 and line["roofline_other"] is not None
     assert extra["ingest"]["files_per_s"] > 100
+
+
+def test_bench_plain_run_and_its_outputs(tmp_path):
+    """A plain bench run (no --full): the headline keys only, `steps` as asked, and --dump-outputs writes the last
+    timed pass's indexes and distances as float64 -- the same arrays on a second run with the same arguments."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    outs = []
+    for run in range(2):
+        out_dir = str(tmp_path / ("out_%d" % run))
+        p = subprocess.run([sys.executable, "bench.py", "--workload", "cfg1", "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", out_dir], cwd=root, env=env, capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-2000:]
+        line = _strict_json(p.stdout.rstrip("\n").splitlines()[-1])
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "n_gpus"):
+            assert key in line, key
+        assert line["metric"] == "newref bin-pair distances/sec" and line["unit"] == "bin-pair distances/s"
+        assert line["higher_is_better"] is True and line["dtype"] == "f64"
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["n_gpus"] == 1
+        assert line["value"] > 0 and line["ms_per_step"] > 0
+        assert "roofline" not in line and "test" not in line and "cpu_baseline" not in line
+        assert sorted(line["outputs"]) == ["distances", "indexes"]
+        idx = np.load(os.path.join(out_dir, "indexes.npy"))
+        dst = np.load(os.path.join(out_dir, "distances.npy"))
+        assert idx.dtype == np.float64 and dst.dtype == np.float64 and idx.shape == dst.shape and idx.shape[1] == 100
+        assert np.array_equal(idx, np.round(idx)) and idx.min() >= 0 and idx.max() < idx.shape[0]
+        assert np.all(np.diff(dst, axis=1) >= 0)
+        outs.append((idx, dst))
+    assert np.array_equal(outs[0][0], outs[1][0]) and np.array_equal(outs[0][1], outs[1][1])

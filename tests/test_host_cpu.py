@@ -272,3 +272,29 @@ def test_bench_compact_line_from_a_full_record():
     # NaN / infinity never reach the line
     full["value"] = float("nan")
     assert json.loads(json.dumps(bench.compact_line(full), allow_nan=False))["value"] is None
+
+
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the last pass's indexes and distances as float64 .npy files, whole while they fit the
+    limit, otherwise a fixed seeded sample of rows (the same rows every time) with their row numbers beside them."""
+    import torch
+    import bench
+    rng = np.random.RandomState(5)
+    idx = torch.from_numpy(rng.randint(0, 1000, size=(1000, 10)).astype(np.int32))
+    dst = torch.from_numpy(np.sort(rng.rand(1000, 10), axis=1))
+    assert bench.dump_outputs(str(tmp_path / "whole"), idx, dst) == ["distances", "indexes"]
+    got_i = np.load(str(tmp_path / "whole" / "indexes.npy"))
+    got_d = np.load(str(tmp_path / "whole" / "distances.npy"))
+    assert got_i.dtype == np.float64 and np.array_equal(got_i, idx.numpy()) and np.array_equal(got_d, dst.numpy())
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 2 * 100 * 10 * 8 + 4096 + 800)
+    rows = []
+    for run in ("a", "b"):
+        assert bench.dump_outputs(str(tmp_path / run), idx, dst) == ["distances", "indexes", "rows"]
+        r = np.load(str(tmp_path / run / "rows.npy"))
+        sub_i = np.load(str(tmp_path / run / "indexes.npy"))
+        sub_d = np.load(str(tmp_path / run / "distances.npy"))
+        assert r.dtype == np.float64 and len(r) == 100 and np.all(np.diff(r) > 0)
+        assert np.array_equal(sub_i, idx.numpy()[r.astype(np.int64)]) and np.array_equal(sub_d, dst.numpy()[r.astype(np.int64)])
+        assert sum(os.path.getsize(str(tmp_path / run / f)) for f in os.listdir(str(tmp_path / run))) <= bench.DUMP_LIMIT
+        rows.append(r)
+    assert np.array_equal(rows[0], rows[1])

@@ -13,7 +13,7 @@ PMC=0 bash tools/profile_gpu.sh ${TAG}_cfg2 --no-extra > "$OUT/cfg2_profile.log"
 P=$REPO/gpurun_out/prof_${TAG}_cfg2
 cp "$(find $P/trace -name '*kernel_stats.csv' | head -1)" "$OUT/${TAG}_cfg2_kernel_stats.csv"
 grep '"metric"' $P/bench.log | tail -1 > "$OUT/${TAG}_cfg2_bench_under_rocprof.json"
-timeout 1200 python3 bench.py 2> "$OUT/bench_stderr.log" | tail -1 > "$OUT/${TAG}_bench_cfg2_unprofiled.json"
+timeout 1200 python3 bench.py --full 2> "$OUT/bench_stderr.log" | tail -1 > "$OUT/${TAG}_bench_cfg2_unprofiled.json"
 cp bench_detail.json "$OUT/${TAG}_bench_detail.json" 2>/dev/null
 ( cd /tmp && export TMPDIR=/tmp
   timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$REPO/gpurun_out/prof_${TAG}_cfg5" -o t -- python3 "$REPO/tools/gpu_test_scale.py" 125 50000 10 > "$OUT/cfg5_run.log" 2>&1
