@@ -443,12 +443,8 @@ def test_whole_region_values_at_every_tree_shape(wt):
     assert same_bits(whole, want), [n for n, a, b in zip(lengths, whole, want) if not same_bits([a], [b])]
 
 
-def test_late_repeats_in_one_launch(wt, monkeypatch, capfd):
-    """Batches run repeats 3 .. as ONE launch of one workgroup (k_lat_repeats from repeat 3 on) -- as a rule nothing is
-    queued by then.  Samples with scattered loud bins, where repeats 3 and 4 still have pairs queued: the outputs of that form,
-    of a launch pair per repeat (WC_TEST_TAIL_REPEATS=0) and of the forced overflow (a cap of 0 pairs: the batch is
-    repeated with launch pairs) are the same bits, and the later repeats really had pairs queued."""
-    import re
+def _late_repeats_case(wt):
+    """A reference and 48 samples with scattered loud bins, where repeats 3 and 4 still have pairs queued."""
     rng = np.random.RandomState(77)
     sizes = np.array([260, 240, 230, 210, 200, 190, 180, 170, 160, 150, 150, 140, 120, 110, 100, 90, 90, 80, 60, 60, 50, 50], dtype=np.int64)
     total = int(sizes.sum())
@@ -468,6 +464,16 @@ def test_late_repeats_in_one_launch(wt, monkeypatch, capfd):
         counts = r2.poisson(lam).astype(np.int32)
         samples.append({str(c + 1): counts[offs[c]:offs[c + 1]] for c in range(22)})
     thr = 5.0                                                   # (pairs queued per repeat here: 14 797, 1 016, 96, 0)
+    return reference, samples, thr
+
+
+def test_late_repeats_in_one_launch(wt, monkeypatch, capfd):
+    """Batches run repeats 3 .. as ONE launch of one workgroup (k_lat_repeats from repeat 3 on) -- as a rule nothing is
+    queued by then.  Samples with scattered loud bins, where repeats 3 and 4 still have pairs queued: the outputs of that form,
+    of a launch pair per repeat (WC_TEST_TAIL_REPEATS=0) and of the forced overflow (a cap of 0 pairs: the batch is
+    repeated with launch pairs) are the same bits, and the later repeats really had pairs queued."""
+    import re
+    reference, samples, thr = _late_repeats_case(wt)
     monkeypatch.setenv("WC_TEST_VERBOSE", "1")
     capfd.readouterr()
     got = wt.test_batch(reference, samples, thr)
@@ -489,4 +495,52 @@ def test_late_repeats_in_one_launch(wt, monkeypatch, capfd):
             assert same_bits(np.concatenate([np.asarray(v) for v in a["results_r"]]), np.concatenate([np.asarray(v) for v in b["results_r"]]))
             assert same_bits(np.asarray(a["results_cwz"], dtype=np.float64), np.asarray(b["results_cwz"], dtype=np.float64))
             assert same_bits([a["asdef"]], [b["asdef"]])
+    reference.close()
+
+
+def test_late_repeats_without_chromosomes(wt, monkeypatch):
+    """A batch that selects no chromosome has no segmentation to bring the late repeats' overflow word back: its late
+    repeats run as a launch pair each.  With a cap of 0 pairs for the one-workgroup form (WC_TEST_TAIL_CAP=0) its
+    outputs are the launch-pair form's (WC_TEST_TAIL_REPEATS=0), bit for bit.  The first of them runs as the first batch
+    of a fresh context, whose segmentation workspaces have never been sized."""
+    from wisecondor_amd import _lib
+    reference, samples, thr = _late_repeats_case(wt)
+    ctx = _lib.new_context(0)
+    fresh = None
+    try:
+        fresh = reference.clone(ctx)
+        monkeypatch.setenv("WC_TEST_TAIL_CAP", "0")
+        got = wt.test_batch(fresh, samples, thr, chromosomes=[])
+        monkeypatch.delenv("WC_TEST_TAIL_CAP")
+        monkeypatch.setenv("WC_TEST_TAIL_REPEATS", "0")
+        want = wt.test_batch(reference, samples, thr, chromosomes=[])
+    finally:
+        if fresh is not None:
+            fresh.close()
+        _lib.destroy_context(ctx)
+    for a, b in zip(got, want):
+        assert len(a["results_calls"]) == 0 and len(a["results_cwz"]) == 0
+        assert same_bits(np.concatenate([np.asarray(v) for v in a["results_z"]]), np.concatenate([np.asarray(v) for v in b["results_z"]]))
+        assert same_bits(np.concatenate([np.asarray(v) for v in a["results_r"]]), np.concatenate([np.asarray(v) for v in b["results_r"]]))
+        assert same_bits([a["asdef"]], [b["asdef"]])
+    reference.close()
+
+
+def test_segments_after_a_batch_with_late_repeats(wt):
+    """wc_stouffer_segments has no late repeats: right after a batch whose late repeats ran as one workgroup it gives
+    the same bits as before that batch."""
+    reference, samples, thr = _late_repeats_case(wt)
+    rng = np.random.RandomState(11)
+    regions = []
+    for n in (40, 150, 600, 1300):
+        z = rng.standard_normal(n)
+        z[n // 3:n // 3 + n // 5] += 2.5                        # a call in every region
+        regions.append(z)
+    before = wt.stouffer_segments(regions, 3.0, 3)
+    wt.test_batch(reference, samples, thr)
+    after = wt.stouffer_segments(regions, 3.0, 3)
+    assert same_bits(before[0], after[0])
+    assert [[xy for _, xy in r] for r in before[1]] == [[xy for _, xy in r] for r in after[1]]
+    assert all(len(r) > 0 for r in before[1])
+    assert same_bits([v for r in before[1] for v, _ in r], [v for r in after[1] for v, _ in r])
     reference.close()

@@ -39,37 +39,25 @@ struct NewrefState {
 struct TestState {
     std::vector<int> sel_host;      // chromosome selection currently held by `sel`
     wc::DevBuf counts, totals, raw, proj, data, xt, xc, zt, rt, nt, sdt, z, r, n, sd_avg;
-    wc::DevBuf zc, rc, gpos, clean_n, regions, sel;
+    wc::DevBuf zc, rc, gpos, regions, sel;
     wc::DevBuf res_z, res_r, cwz, calls, n_calls;
     // Stouffer search
     wc::DevBuf zs, rs2, ns2, sds, sub, tmin, tmax, tmin2, tmax2, cell_state, cell_rec, prefix, reg_abs, reg_flag, rs, jobs_a, jobs_b, job_cnt, partial, cbound, cuts, job_res, hot, cand, cand_cnt;
-    wc::DevBuf seg, seg_cnt, out_val, out_x, out_y, out_n, whole, effect, misc, misc2, reduce_tmp, win_bits, bit_off, pairs_a, pairs_b, cut_vals;
+    wc::DevBuf seg, out_val, out_x, out_y, out_n, whole, effect, misc, misc2, reduce_tmp, win_bits, bit_off, pairs_a, pairs_b, cut_vals;
     wc::DevBuf walk_hot;             // k_seg_walk's early starters: [0] count, [16 ..] the list, [16 + 4096 ..] every region's place in it
-    void *walk_hot_clean = nullptr;  // the buffer whose count has been zeroed once (k_walk_rows resets it after every walk)
-    bool tail_used = false, no_tail = false;   // run_repeat: the late repeats ran as ONE workgroup (k_lat_repeats); no_tail: the batch is being repeated without that
-    int *tail_flag = nullptr;                  // ... its overflow word (device)
     int64_t rs_len = 0;
-    int64_t last_segs = 0;       // segments of the last segmentation call; negative: -(bound), the count is on the device
-    int lat_left = 1;
     // latency mode: the captured call (hipGraph), the arguments it was captured for, and whether
     // an eager call of that shape has sized the workspaces
     hipGraphExec_t lat_exec = nullptr;
     std::vector<int64_t> lat_key, lat_fail_key;   // lat_fail_key: a shape whose capture failed stays on the eager latency kernels
     bool lat_warm = false;
-    unsigned long long lat_epoch = 0;   // wc::realloc_epoch() at capture time            // latency mode: index of the counter that holds the jobs left after the last round
+    unsigned long long lat_epoch = 0;   // wc::realloc_epoch() at capture time
     // optional stage timing of wc_test_batch_dev (wc_test_profile): events on the launch stream
     // between the stages, and counts of the window evaluations the search kernels executed
     bool profile = false;
     std::vector<hipEvent_t> prof_ev;    // event pool, grown on demand
     std::vector<int> prof_tag;          // tag of every mark of the last batch, in record order
     wc::DevBuf sd_fail;                 // per-sample flags of k_sd_fast (1: the serial kernel takes the sample)
-    bool tree_done = false;             // run_stouffer: the tree kernel finished the recursion and wrote the call rows
-    bool tree_pending = false;          // ... but its status words are still on their way to pinned memory (deferred check)
-    bool sm_out = false;                // run_repeat: zt / rt / nt / sdt of the last call are sample-major [Ns, B] (tiled first repeat)
-    bool no_tree = false;               // repeat of a batch the tree kernel passed on: host-driven rounds only
-    int64_t tree_seg_cap = 0;
-    bool lat_ride = false;              // latency mode: stdDevAvg rides in k_seg_tree's grid (run_repeat -> run_seg_lat)
-    double *lat_ride_out2 = nullptr;
     wc::DevBuf prof_work;               // u64[2]: windows evaluated by k_seg_search, evaluations by k_seg_quiet
     void mark(int tag, hipStream_t stream) {
         if (!profile) return;
@@ -140,10 +128,10 @@ struct wc_ctx {
                 &nr.thr, &nr.cnt, &nr.list, &nr.tiles, &nr.fb_rows, &nr.fb_count, &nr.fb_scratch,
                 &nr.stats, &nr.tiles0, &nr.pw_prog, &nr.pairs, &nr.x64, &nr.m2, &nr.a16, &nr.s16, &tmp_a, &tmp_b, &tmp_c, &tmp_d,
                 &ts.counts, &ts.totals, &ts.raw, &ts.proj, &ts.data, &ts.xt, &ts.xc, &ts.zt, &ts.rt, &ts.nt,
-                &ts.sdt, &ts.z, &ts.r, &ts.n, &ts.sd_avg, &ts.zc, &ts.rc, &ts.gpos, &ts.clean_n, &ts.regions,
+                &ts.sdt, &ts.z, &ts.r, &ts.n, &ts.sd_avg, &ts.zc, &ts.rc, &ts.gpos, &ts.regions,
                 &ts.sel, &ts.res_z, &ts.res_r, &ts.cwz, &ts.calls, &ts.n_calls, &ts.zs, &ts.rs2, &ts.ns2, &ts.sds, &ts.sub, &ts.tmin, &ts.tmax, &ts.tmin2, &ts.tmax2, &ts.cell_state, &ts.cell_rec, &ts.prefix, &ts.reg_abs,
                 &ts.reg_flag, &ts.rs, &ts.jobs_a, &ts.jobs_b, &ts.job_cnt, &ts.partial, &ts.cbound, &ts.cuts, &ts.job_res, &ts.hot,
-                &ts.cand, &ts.cand_cnt, &ts.seg, &ts.seg_cnt, &ts.out_val, &ts.out_x, &ts.out_y, &ts.out_n,
+                &ts.cand, &ts.cand_cnt, &ts.seg, &ts.out_val, &ts.out_x, &ts.out_y, &ts.out_n,
                 &ts.whole, &ts.effect, &ts.misc, &ts.misc2, &ts.reduce_tmp, &ts.win_bits, &ts.bit_off, &ts.pairs_a, &ts.pairs_b, &ts.cut_vals, &ts.prof_work, &ts.sd_fail, &ts.walk_hot, &prep.eig_ws};
     }
 };

@@ -1855,10 +1855,11 @@ struct SdRider {
 };
 
 void launch_sd_fast(hipStream_t stream, const double *sdT, int64_t B, int64_t Ns, double *out, int *fail, double *out2,
-                    int64_t sb, int64_t si) {
+                    int64_t sb, int64_t si, bool stage) {
     const int64_t per = (B + 1023) / 1024;
-    // (a sample's values contiguous -- every batch: the cooperative loads; WC_TEST_SD_STAGE=0: a lane per run, round 5's form)
-    const bool staged = sb == 1 && !(getenv("WC_TEST_SD_STAGE") && getenv("WC_TEST_SD_STAGE")[0] == '0');
+    // (a sample's values contiguous -- every batch: the cooperative loads; stage false (WC_TEST_SD_STAGE=0): a lane per
+    //  run, round 5's form)
+    const bool staged = sb == 1 && stage;
     if (per <= 12 && staged)
         hipLaunchKernelGGL((k_sd_fast<12, true>), dim3((unsigned)Ns), dim3(1024), 0, stream, sdT, B, Ns, out, fail, out2, sb, si);
     else if (per <= 12)
@@ -5283,6 +5284,37 @@ __global__ __launch_bounds__(256) void k_walk_rows(const Seg *__restrict__ wsegs
 }
 
 // ------------------------------------------------------------ host drivers ----
+// The test path's environment switches (A/B forms for experiments and the test suite).  Every C-ABI entry that reaches
+// the test path reads them once per call -- a test may change them between two calls -- and passes them down.
+struct TestSwitches {
+    bool zscore_tiled, zscore_sm, sd_stage, tail_repeats, mineffect_sorted, walk, walk_hot, tree_tail, cells, latency,
+        latency_eager, verbose;
+    int tail_cap, side2_from, cell_parts;
+    bool second_side(int64_t n_samples) const { return side2_from > 0 && n_samples >= side2_from; }
+};
+static TestSwitches read_switches() {
+    auto is = [](const char *name, char c) { const char *v = getenv(name); return v && v[0] == c; };
+    auto num = [](const char *name, int unset) { const char *v = getenv(name); return v ? atoi(v) : unset; };
+    const char *me = getenv("WC_MINEFFECT"), *cp = getenv("WC_CELL_PARTS");
+    TestSwitches sw;
+    sw.zscore_tiled = !is("WC_ZSCORE_TILED", '0');      // 0: the untiled first repeat (a wave = one bin x 64 samples)
+    sw.zscore_sm = !is("WC_ZSCORE_SM", '0');            // 0: bin-major outputs + the transposes (round 5's form)
+    sw.sd_stage = !is("WC_TEST_SD_STAGE", '0');         // 0: k_sd_fast without the cooperative loads (a lane per run)
+    sw.tail_repeats = !is("WC_TEST_TAIL_REPEATS", '0'); // 0: a batch's late repeats as a launch pair each
+    sw.tail_cap = num("WC_TEST_TAIL_CAP", TAIL_PAIR_CAP);   // pairs a late repeat may hold for the one-workgroup form
+    sw.side2_from = num("WC_TEST_SIDE2", 768);          // second side stream from this many samples on (0: never)
+    sw.mineffect_sorted = me && strcmp(me, "sorted") == 0;  // the O(n) per window sorted-insert kernel
+    sw.walk = !is("WC_TEST_WALK", '0');                 // 0: the tree kernel up to TREE_MAXLEN, host-driven rounds beyond
+    sw.walk_hot = !is("WC_TEST_WALK_HOT", '0');         // 0: k_seg_walk without its early starters
+    sw.tree_tail = !is("WC_TEST_TREE_TAIL", '0');       // 0: host-driven rounds only
+    sw.cells = !is("WC_TEST_CELLS", '0');               // 0: the row-block kernels (k_seg_seed / k_seg_bound / k_seg_bcollect)
+    sw.cell_parts = cp ? std::max(1, atoi(cp)) : 0;     // at most this many workgroups per k_seg_job job (0: not set)
+    sw.latency = !is("WC_TEST_LATENCY_MODE", '0');      // 0: the general path for every call
+    sw.latency_eager = is("WC_TEST_LATENCY_MODE", '2'); // 2: the latency kernels launched one by one, never captured
+    sw.verbose = getenv("WC_TEST_VERBOSE") != nullptr;  // (set) retries and repeat statistics on stderr
+    return sw;
+}
+
 int run_prepare(wc_ctx *ctx, const wc_reference *ref, const int *counts_dev, int64_t Ns, hipStream_t stream) {
     TestState &ts = ctx->ts;
     int rc;
@@ -5339,28 +5371,34 @@ static int reserve_repeat_arrays(TestState &ts, int64_t n, int64_t Ns) {
     return ts.sd_avg.reserve(sizeof(double) * Ns);
 }
 
+struct RepeatOut {                    // what run_repeat tells its caller
+    bool sm_out = false;              // zt / rt / nt / sdt are sample-major [Ns, B] (the tiled first repeat wrote them)
+    const int *tail_flag = nullptr;   // repeats 3 .. ran as ONE workgroup: its overflow word (device); else NULL
+    SdRider sd_ride{};                // latency mode: stdDevAvg rides in k_seg_tree's grid (blocks 0: it ran here)
+};
+
 // repeatTest on device data [Ns, B]; leaves zt/rt/nt/sdt as [B, Ns] and sd_avg[Ns]
 // lat: latency mode -- k_lat_prepare has already written xt / xc and cleared the counters; the first
 // repeat runs as usual, repeats 2.. in one launch (k_lat_repeats; its overflow flag is pair_counts[repeats + 1])
 // allow_sm: the caller reads z / ratio / counts / sd per SAMPLE and takes them in either layout: when the first repeat
-// runs the tiled kernel they are written sample-major [Ns, B] straight away (ts.sm_out tells which it was)
-int run_repeat(wc_ctx *ctx, const wc_reference *ref, const double *data_dev, int64_t Ns, double thr, int repeats,
-               hipStream_t stream, bool lat = false, double *asdef_out = nullptr, bool xt_ready = false,
-               bool allow_sm = false, bool allow_tail = false) {
+// runs the tiled kernel they are written sample-major [Ns, B] straight away (out.sm_out tells which it was)
+// allow_tail: repeats 3 .. may run as one workgroup (the caller reads out.tail_flag after its synchronize)
+int run_repeat(wc_ctx *ctx, const TestSwitches &sw, const wc_reference *ref, const double *data_dev, int64_t Ns,
+               double thr, int repeats, hipStream_t stream, RepeatOut &out, bool lat = false, double *asdef_out = nullptr,
+               bool xt_ready = false, bool allow_sm = false, bool allow_tail = false) {
     TestState &ts = ctx->ts;
     const int64_t n = ref->B * Ns;
     int rc;
-    const char *tiled_env = getenv("WC_ZSCORE_TILED");       // "0": the untiled kernel (a wave = one bin x 64 samples)
-    const char *sm_env = getenv("WC_ZSCORE_SM");             // "0": bin-major outputs + the transposes (round 5's form)
+    out = RepeatOut{};
     // (fewer than eight tiles would leave XCDs idle or without a column of their own: the untiled kernel)
     const bool tiled = !lat && repeats >= 1 && ref->k <= 128 && Ns >= 128 && (Ns & 15) == 0 &&
                        (ref->B + 1) * Ns * 8 < ((int64_t)1 << 32) && ref->B < (1 << 24) && Ns * 8 < (1 << 24) &&
-                       !(tiled_env && tiled_env[0] == '0');
+                       sw.zscore_tiled;
     // (a list stride above 100 -- refsize 101 .. 128 -- needs 104 value slots: with the output permutation that form
     //  spills six registers, so those references keep the bin-major outputs and the transposes)
-    const bool sm_out = tiled && allow_sm && ref->k <= 100 && !(sm_env && sm_env[0] == '0');
+    const bool sm_out = tiled && allow_sm && ref->k <= 100 && sw.zscore_sm;
     const int64_t osm = sm_out ? ref->B : 0;
-    ts.sm_out = sm_out;
+    out.sm_out = sm_out;
     // a caller whose prepare kernel has ALREADY written xt / xc must have sized them with reserve_repeat_arrays: a
     // reserve that grows a buffer frees it (DevBuf keeps no contents) and the z-scores would read fresh memory
     if (lat || xt_ready)
@@ -5389,20 +5427,20 @@ int run_repeat(wc_ctx *ctx, const wc_reference *ref, const double *data_dev, int
     }
     const int *uoff = ref->users_off.as<int>(), *ulst = ref->users.as<int>();
     // batches whose caller can repeat them (allow_tail): repeats 3 .. by one workgroup in one launch
-    ts.tail_used = false;
-    ts.tail_flag = nullptr;
-    const bool tail_ok = allow_tail && !lat && !ts.no_tail && repeats > 2 && ref->k <= 128 &&
-                         !(getenv("WC_TEST_TAIL_REPEATS") && getenv("WC_TEST_TAIL_REPEATS")[0] == '0');
+    const bool tail_ok = allow_tail && !lat && repeats > 2 && ref->k <= 128 && sw.tail_repeats;
     // latency mode, a sample or two: the first repeat's flag pass runs at the head of k_lat_repeats
     const bool lat_flag_inside = lat && repeats > 1 && ref->k <= 128 && n <= 16384;
     for (int it = 0; it < repeats; ++it) {
-        if (lat && it == 1) {
+        if ((lat && it == 1) || (tail_ok && it == 2)) {
+            // the remaining repeats in ONE launch of one workgroup (latency mode: from repeat 2 on; a batch: from repeat
+            // 3 on -- its overflow word reaches the caller through the segmentation's set-up kernel, misc[1])
             hipLaunchKernelGGL(k_lat_repeats, dim3(1), dim3(1024), 0, stream, ts.pairs_a.as<unsigned int>(),
                                ts.pairs_b.as<unsigned int>(), pair_counts, repeats, dirty,
                                (const double *)ts.xt.as<double>(), ts.xc.as<double>(), (const int *)ref->gidx.as<int>(),
                                (const int *)ref->nref.as<int>(), ref->k, Ns, thr, uoff, ulst, ts.zt.as<double>(),
                                ts.rt.as<double>(), ts.nt.as<double>(), ts.sdt.as<double>(), pair_counts + repeats + 1,
-                               lat_flag_inside ? (int)n : 0);
+                               lat_flag_inside ? (int)n : 0, it, osm, lat ? LAT_PAIR_CAP : sw.tail_cap);
+            if (!lat) out.tail_flag = pair_counts + repeats + 1;
             break;
         }
         // repeat `it` recomputes the pairs queued in its list (all pairs in the first repeat) and
@@ -5471,18 +5509,6 @@ int run_repeat(wc_ctx *ctx, const wc_reference *ref, const double *data_dev, int
             else if (!lat_flag_inside)
                 hipLaunchKernelGGL(k_flag, dim3(g), dim3(256), 0, stream, (const double *)ts.zt.as<double>(), thr, n, Ns,
                                    ts.xc.as<double>(), uoff, ulst, dirty, next, pair_counts + it + 1);
-        } else if (it == 2 && tail_ok) {
-            // repeats 3 .. in ONE launch of one workgroup (see k_lat_repeats); its overflow word reaches the caller through
-            // the segmentation's set-up kernel (ts.tail_flag -> misc[1])
-            ts.tail_used = true;
-            ts.tail_flag = pair_counts + repeats + 1;
-            hipLaunchKernelGGL(k_lat_repeats, dim3(1), dim3(1024), 0, stream, ts.pairs_a.as<unsigned int>(),
-                               ts.pairs_b.as<unsigned int>(), pair_counts, repeats, dirty,
-                               (const double *)ts.xt.as<double>(), ts.xc.as<double>(), (const int *)ref->gidx.as<int>(),
-                               (const int *)ref->nref.as<int>(), ref->k, Ns, thr, uoff, ulst, ts.zt.as<double>(),
-                               ts.rt.as<double>(), ts.nt.as<double>(), ts.sdt.as<double>(), pair_counts + repeats + 1,
-                               0, 2, osm, getenv("WC_TEST_TAIL_CAP") ? atoi(getenv("WC_TEST_TAIL_CAP")) : TAIL_PAIR_CAP);   // (the test suite forces the overflow with a cap of 0)
-            break;
         } else {
             // repeat 2 recomputes the users of the first repeat's flags (10^3 .. 10^5 pairs); repeats 3 .. are a few
             // hundred pairs at most -- their time is the dispatch of workgroups that find nothing to do: an eighth of the
@@ -5501,13 +5527,12 @@ int run_repeat(wc_ctx *ctx, const wc_reference *ref, const double *data_dev, int
     // stdDevAvg only feeds the asdef output: it runs on the context's side stream under the
     // segmentation work (latency mode: on the launch stream -- the parallel form takes a few
     // microseconds, a second stream in the captured graph costs more -- straight into `asdef_out`).
-    ts.lat_ride = false;
     if (lat && ref->B <= 65536) {
         // latency mode: the parallel form rides in k_seg_tree's grid (run_seg_lat) -- no second stream,
         // whose fork and join cost more than the kernel; a sample it gives up on raises status word 33
         if ((rc = ts.sd_fail.reserve(sizeof(int) * Ns))) return rc;
-        ts.lat_ride = true;
-        ts.lat_ride_out2 = asdef_out;
+        out.sd_ride = SdRider{(int)Ns, ts.sdt.as<double>(), ref->B, Ns, ts.sd_avg.as<double>(), asdef_out,
+                              ts.sd_fail.as<int>(), Ns, 1};
         return WC_OK;
     }
     hipStream_t sds = stream;
@@ -5525,7 +5550,7 @@ int run_repeat(wc_ctx *ctx, const wc_reference *ref, const double *data_dev, int
         if (sm_out) {
             // the first repeat wrote the standard deviations sample-major already
             launch_sd_fast(sds, ts.sdt.as<double>(), ref->B, Ns, ts.sd_avg.as<double>(), ts.sd_fail.as<int>(), out2, 1,
-                           ref->B);
+                           ref->B, sw.sd_stage);
         } else if (Ns > 8) {
             // a batch: the sums run over a sample-major copy (a sample's standard deviations contiguous): in
             // the bin-major array every element of a sample sits in a cache line of its own, and 125
@@ -5533,9 +5558,10 @@ int run_repeat(wc_ctx *ctx, const wc_reference *ref, const double *data_dev, int
             if ((rc = ts.sds.reserve(sizeof(double) * n))) return rc;
             launch_transpose((const double *)ts.sdt.as<double>(), ref->B, Ns, ts.sds.as<double>(), sds);
             launch_sd_fast(sds, ts.sds.as<double>(), ref->B, Ns, ts.sd_avg.as<double>(), ts.sd_fail.as<int>(), out2, 1,
-                           ref->B);
+                           ref->B, sw.sd_stage);
         } else {
-            launch_sd_fast(sds, ts.sdt.as<double>(), ref->B, Ns, ts.sd_avg.as<double>(), ts.sd_fail.as<int>(), out2, Ns, 1);
+            launch_sd_fast(sds, ts.sdt.as<double>(), ref->B, Ns, ts.sd_avg.as<double>(), ts.sd_fail.as<int>(), out2, Ns, 1,
+                           sw.sd_stage);
         }
         only = ts.sd_fail.as<int>();
     }
@@ -5565,10 +5591,6 @@ int run_repeat(wc_ctx *ctx, const wc_reference *ref, const double *data_dev, int
 // second: the SECOND side stream.  In a big batch stdDevAvg (k_sd_fast: a 1 024-thread workgroup per sample) is as long
 // as the whole segmentation -- 1.8 ms of a 1 000 x 50 kb batch -- and the inflated outputs and whole-region values
 // behind it on one stream ended 0.5 ms after the launch stream (kernel trace, round 6): they get a stream of their own.
-static bool side_second(int64_t n_samples) {
-    static const int from = getenv("WC_TEST_SIDE2") ? atoi(getenv("WC_TEST_SIDE2")) : 768;   // (0: never; from 256 on: 256 x 50 kb and 512 x 250 kb are 1 % slower with it)
-    return from > 0 && n_samples >= from;
-}
 static int side_begin(wc_ctx *ctx, hipStream_t stream, bool second = false) {
     int rc;
     if ((rc = ctx->ensure_side_stream())) return rc;
@@ -5607,19 +5629,34 @@ int join_side(wc_ctx *ctx, hipStream_t stream) {
     return WC_OK;
 }
 
+// The words in ctx->pinned (ensure_pinned(256)) the host reads after a synchronize; their writers use plain indexes (the
+// batch's copy of job_cnt[0 .. 11], k_assemble_calls' host_status[16 ..]), which the asserts tie to the names.
+struct HostStatus {
+    int counters[8];            // [0..7]   the segmentation counters: [1] next jobs [2] hot [3] brute [4] segments [6] gave up
+    int call_overflow;          // [8]      a batch: a sample has more than max_calls calls
+    int tail_overflow;          // [9]      a batch: the late repeats' overflow word (copied there by the set-up kernel)
+    int unused0[6];
+    int lat_call_overflow;      // [16]     latency mode: a sample has more than max_calls calls
+    int unused1[7];
+    int lat_counters[8];        // [24..31] latency mode: the segmentation counters
+    int lat_tail_overflow;      // [32]     latency mode: k_lat_repeats' overflow word
+    int lat_sd_fail;            // [33]     latency mode: stdDevAvg left a sample to the serial kernel
+};
+static_assert(offsetof(HostStatus, call_overflow) == 8 * sizeof(int) && offsetof(HostStatus, tail_overflow) == 9 * sizeof(int),
+              "batch status words");
+static_assert(offsetof(HostStatus, lat_call_overflow) == 16 * sizeof(int) && offsetof(HostStatus, lat_counters) == 24 * sizeof(int) &&
+              offsetof(HostStatus, lat_tail_overflow) == 32 * sizeof(int) && offsetof(HostStatus, lat_sd_fail) == 33 * sizeof(int),
+              "latency-mode status words (k_assemble_calls)");
+static_assert(sizeof(HostStatus) <= 256, "the status words fit the pinned block the callers ensure");
+
 // Segment search over device regions.  Results: ts.out_val/out_x/out_y [n_regions, max_calls],
 // ts.out_n [n_regions], ts.whole [n_regions].
-// lat_rounds > 0 (latency mode, small batches): no host round trips -- that many search rounds are
-// enqueued with grids sized for the most jobs a round can hold (every job has at most two children)
-// and the kernels read the real job / segment counts on the device; *lat_incomplete (pinned, valid
-// after the stream has been synchronised) tells whether jobs were left over or a bound was
-// exceeded, in which case the caller runs the call again with the host-driven loop.
 // `tail` (optional; the batched `test` call): where call rows go.  When the regions fit the tree kernel
 // (<= TREE_MAXLEN bins, no -mineffectsize mask) the first round's hot regions are walked to the end by
 // k_seg_tree, one workgroup per region -- collect, decide, every child range, the order of the
 // segments and the call rows -- instead of one host-driven round per recursion level: rounds two and
 // later are a handful of short ranges each and cost a launch series and a count read-back apiece.
-// ts.tree_done tells the caller that ts.effect / ts.out_n already hold the calls.
+// tail_flag: the late repeats' overflow word (RepeatOut::tail_flag) the set-up kernel copies for the host, or NULL.
 struct TreeTail {
     const double *ratio;     // cleaned ratios, as z_dev
     const int *gpos;         // genomic position of every kept bin
@@ -5628,6 +5665,12 @@ struct TreeTail {
     double *cwz_out;         // where the whole-region values go besides ts.whole (written on the side stream), or NULL
     int per_sample = 0;      // regions per sample (sample-major region list), or 0: k_seg_walk then takes every sample's
                              // first region first -- chromosome 1, the longest -- so that the launch ends on short ones
+    bool host_rounds = false;  // the walker and the tree kernel stay off (a repeat of a batch they gave up on)
+};
+struct SegOut {                     // what run_stouffer leaves for its caller
+    bool status_deferred = false;  // the walker / tree kernel wrote the call rows; the caller checks its counters after
+    int64_t seg_bound = 0;         // its synchronize: [3] / [6] non-zero = it gave up, [4] beyond seg_bound = too many
+    int64_t segs = 0;              // segments in ts.seg whose call rows are still to be written (k_call_post)
 };
 // Batches whose regions fit the fused set-up kernel (<= TREE_MAXLEN bins, no -mineffectsize mask): cleaning,
 // prefix sums, whole-region values and the root jobs in ONE launch (k_lat_setup<256>) instead of k_clean +
@@ -5644,42 +5687,52 @@ struct FusedSetup {
     Region *regions;
     double *whole_copy;
 };
-int run_stouffer(wc_ctx *ctx, const double *z_dev, const Region *regions_dev, int64_t n_regions, int64_t total_len,
-                 int64_t max_n, double thr, int min_search, int max_calls, hipStream_t stream,
-                 const double *ratio_dev = nullptr, double min_effect = 0.0, int64_t bits_upper = 0,
-                 int lat_rounds = 0, double *whole_copy = nullptr, const TreeTail *tail = nullptr,
-                 const FusedSetup *fused = nullptr) {
-    TestState &ts = ctx->ts;
+// The workspaces both segmentation drivers (run_stouffer, run_seg_lat) use for n_regions regions of total_len bins and
+// `jobs` root jobs; the table of 1 / sqrt(length) grows to rs_need entries.
+static int reserve_segmentation(TestState &ts, int64_t n_regions, int64_t total_len, int64_t jobs, int max_calls,
+                                int64_t rs_need, hipStream_t stream) {
     int rc;
-    ts.last_segs = 0;
-    ts.tree_done = false;
-    ts.tree_pending = false;
-    if (n_regions == 0) return WC_OK;
-    const int64_t job_cap = n_regions + total_len / 4 + 64;
-    const int64_t seg_cap = n_regions * (int64_t)max_calls + 64;
-    const int max_chunks = (int)std::max<int64_t>(1, cdiv((max_n + 1) / 2, ROWS_HALF));
+    const int64_t seg_cap = n_regions * (int64_t)max_calls + 64, nblk = cdiv(total_len + n_regions, QB);
     if ((rc = ts.prefix.reserve(sizeof(double) * (total_len + n_regions + 8)))) return rc;
     if ((rc = ts.reg_abs.reserve(sizeof(double) * n_regions))) return rc;
     if ((rc = ts.reg_flag.reserve(sizeof(int) * n_regions))) return rc;
-    const int64_t rs_need = std::max<int64_t>(max_n + 80 + QB2, 2 * QB + 80 + QB2);   // the search reads four lengths at a time (the candidate scan one trip ahead); the bound scan min len + 128
-                                                                        // past the longest window, the certificate 1..64
     if (ts.rs_len < rs_need) {
         if ((rc = ts.rs.reserve(sizeof(double) * rs_need))) return rc;
         ts.rs_len = rs_need;
         hipLaunchKernelGGL(k_fill_rs, dim3((unsigned)cdiv(ts.rs_len, 256)), dim3(256), 0, stream, ts.rs.as<double>(),
                            ts.rs_len);
     }
-    if ((rc = ts.jobs_a.reserve(sizeof(Job) * job_cap))) return rc;
-    if ((rc = ts.jobs_b.reserve(sizeof(Job) * job_cap))) return rc;
+    if ((rc = ts.jobs_a.reserve(sizeof(Job) * jobs))) return rc;
     if ((rc = ts.job_cnt.reserve(sizeof(int) * 16))) return rc;
-    if ((rc = ts.job_res.reserve(sizeof(Extreme) * job_cap))) return rc;
-    if ((rc = ts.hot.reserve(sizeof(int) * 2 * job_cap))) return rc;
     if ((rc = ts.seg.reserve(sizeof(Seg) * seg_cap))) return rc;
     if ((rc = ts.out_val.reserve(sizeof(double) * n_regions * max_calls))) return rc;
     if ((rc = ts.out_x.reserve(sizeof(int) * n_regions * max_calls))) return rc;
     if ((rc = ts.out_y.reserve(sizeof(int) * n_regions * max_calls))) return rc;
     if ((rc = ts.out_n.reserve(sizeof(int) * n_regions))) return rc;
     if ((rc = ts.whole.reserve(sizeof(double) * n_regions))) return rc;
+    if ((rc = ts.tmin.reserve(sizeof(double) * nblk))) return rc;
+    return ts.tmax.reserve(sizeof(double) * nblk);
+}
+
+int run_stouffer(wc_ctx *ctx, const TestSwitches &sw, const double *z_dev, const Region *regions_dev, int64_t n_regions,
+                 int64_t total_len, int64_t max_n, double thr, int min_search, int max_calls, hipStream_t stream,
+                 SegOut &out, const int *tail_flag, const double *ratio_dev = nullptr, double min_effect = 0.0,
+                 int64_t bits_upper = 0, const TreeTail *tail = nullptr, const FusedSetup *fused = nullptr) {
+    TestState &ts = ctx->ts;
+    int rc;
+    out = SegOut{};
+    if (n_regions == 0) return WC_OK;
+    const int64_t job_cap = n_regions + total_len / 4 + 64;
+    const int64_t seg_cap = n_regions * (int64_t)max_calls + 64;
+    const int max_chunks = (int)std::max<int64_t>(1, cdiv((max_n + 1) / 2, ROWS_HALF));
+    // (rs: the search reads four lengths at a time (the candidate scan one trip ahead); the bound scan min len + 128 past
+    //  the longest window, the certificate 1..64)
+    if ((rc = reserve_segmentation(ts, n_regions, total_len, job_cap, max_calls,
+                                   std::max<int64_t>(max_n + 80 + QB2, 2 * QB + 80 + QB2), stream)))
+        return rc;
+    if ((rc = ts.jobs_b.reserve(sizeof(Job) * job_cap))) return rc;
+    if ((rc = ts.job_res.reserve(sizeof(Extreme) * job_cap))) return rc;
+    if ((rc = ts.hot.reserve(sizeof(int) * 2 * job_cap))) return rc;
 
     // -mineffectsize: one validity bit per window (wisetools.py:479-487)
     const unsigned int *bits = nullptr;
@@ -5691,8 +5744,7 @@ int run_stouffer(wc_ctx *ctx, const double *z_dev, const Region *regions_dev, in
         if ((rc = ts.bit_off.reserve(sizeof(long long) * n_regions))) return rc;
         WC_HIP(hipMemsetAsync(ts.win_bits.p, 0, sizeof(unsigned int) * words, stream));
         hipLaunchKernelGGL(k_bit_offsets, dim3(1), dim3(1), 0, stream, regions_dev, n_regions, ts.bit_off.as<long long>());
-        const char *me = getenv("WC_MINEFFECT");         // "sorted": the O(n) per window sorted-insert kernel
-        if (me && strcmp(me, "sorted") == 0) {
+        if (sw.mineffect_sorted) {
             WC_CHECK(max_n * 8 <= 64 * 1024 - 1024, WC_E_LIMIT, "segments: region too long for the sorted-insert median filter");
             hipLaunchKernelGGL(k_window_valid, dim3((unsigned)max_n, (unsigned)n_regions), dim3(64),
                                sizeof(double) * (max_n + 1), stream, ratio_dev, regions_dev,
@@ -5736,22 +5788,18 @@ int run_stouffer(wc_ctx *ctx, const double *z_dev, const Region *regions_dev, in
     int *counters = ts.job_cnt.as<int>();  // [1] next jobs [2] hot [3] brute [4] segments
     int *hot = ts.hot.as<int>();
     int *brute = hot + job_cap;
-    if ((rc = ts.job_cnt.reserve(sizeof(int) * 16))) return rc;
     if (fused)
         hipLaunchKernelGGL(k_lat_setup<256>, dim3((unsigned)n_regions), dim3(256), sizeof(double) * (max_n + 1), stream,
                            fused->zsrc, fused->rsrc, fused->nsrc, fused->str_i, fused->str_b, fused->B, fused->moff,
                            fused->goff, fused->m2g, fused->sel, fused->n_sel, fused->minref, fused->zc, fused->rc,
                            fused->gpos, fused->regions, ts.prefix.as<double>(), ts.reg_abs.as<double>(),
                            ts.reg_flag.as<int>(), ts.whole.as<double>(), fused->whole_copy, ts.jobs_a.as<Job>(), counters,
-                           ts.out_n.as<int>(), (ts.job_cnt.as<int>() + 8), n_regions, ts.tail_used ? (const int *)ts.tail_flag : (const int *)nullptr);
+                           ts.out_n.as<int>(), (ts.job_cnt.as<int>() + 8), n_regions, tail_flag);
     // Callers with call rows, regions up to CJ_MAXLEN bins, no -mineffectsize mask: the whole recursion of every region
     // in ONE launch (k_seg_walk), no host round trip.  WC_TEST_WALK=0: the paths it replaces (tree kernel up to
     // TREE_MAXLEN, host-driven rounds beyond).
-    const char *walk_env = getenv("WC_TEST_WALK");
-    const bool walk_path = tail && !bits && max_n <= CJ_MAXLEN && !ts.no_tree && !(walk_env && walk_env[0] == '0');
+    const bool walk_path = tail && !bits && max_n <= CJ_MAXLEN && !tail->host_rounds && sw.walk;
     const int64_t total = total_len + n_regions, nblk = cdiv(total, QB);
-    if ((rc = ts.tmin.reserve(sizeof(double) * nblk))) return rc;
-    if ((rc = ts.tmax.reserve(sizeof(double) * nblk))) return rc;
     const int64_t nblk2 = cdiv(nblk, 4);
     if ((rc = ts.tmin2.reserve(sizeof(double) * nblk2))) return rc;
     if ((rc = ts.tmax2.reserve(sizeof(double) * nblk2))) return rc;
@@ -5768,14 +5816,13 @@ int run_stouffer(wc_ctx *ctx, const double *z_dev, const Region *regions_dev, in
     //  against this kernel's 49 at 125 x 50 kb: what these set-up launches wait for is the half of the chip k_sd_fast's
     //  1 024-thread workgroups hold on the side stream, not their own parallelism)
     // k_seg_walk's early starters (WalkHot): listed by k_region_prefix; WC_TEST_WALK_HOT=0 switches them off
-    WalkHot whot{nullptr, nullptr, nullptr, 0, 0.0, ts.tail_used ? ts.tail_flag : nullptr};
-    if (walk_path && !fused && !(getenv("WC_TEST_WALK_HOT") && getenv("WC_TEST_WALK_HOT")[0] == '0')) {
+    WalkHot whot{nullptr, nullptr, nullptr, 0, 0.0, tail_flag};
+    if (walk_path && !fused && sw.walk_hot) {
         const int cap = n_regions >= 4096 ? 4096 : 512;
+        const size_t had = ts.walk_hot.bytes;
         if ((rc = ts.walk_hot.reserve(sizeof(int) * (16 + 4096 + n_regions)))) return rc;
-        if (ts.walk_hot.p != ts.walk_hot_clean) {
+        if (ts.walk_hot.bytes != had)      // a new buffer: its count starts at zero (k_walk_rows resets it after every walk)
             WC_HIP(hipMemsetAsync(ts.walk_hot.p, 0, sizeof(int) * 16, stream));
-            ts.walk_hot_clean = ts.walk_hot.p;
-        }
         whot.count = ts.walk_hot.as<int>();
         whot.list = whot.count + 16;
         whot.index = whot.count + 16 + 4096;
@@ -5799,13 +5846,13 @@ int run_stouffer(wc_ctx *ctx, const double *z_dev, const Region *regions_dev, in
         // the whole-region values are an output only -> side stream (one wave per region walks
         // the region in numpy's order: 0.1 ms at 50 kb that the search does not have to wait for)
         hipStream_t ws = stream;
-        double *wcopy = whole_copy;
+        double *wcopy = nullptr;
         int rc2;
         if (tail && tail->cwz_out && !bits) {
             // (a second side stream for this launch alone was measured: it then runs beside the walk -- 180 us instead
             //  of 105, the walk 277 instead of 267, 1 000 x 50 kb 7.69 instead of 7.34 ms; one side stream)
-            //  (big batches: the second side stream, see side_second)
-            const bool second = side_second(tail->per_sample > 0 ? n_regions / tail->per_sample : 0);
+            //  (big batches: the second side stream, see side_begin)
+            const bool second = sw.second_side(tail->per_sample > 0 ? n_regions / tail->per_sample : 0);
             if ((rc2 = side_begin(ctx, stream, second))) return rc2;
             ws = second ? ctx->side2 : ctx->side;
             wcopy = tail->cwz_out;
@@ -5827,12 +5874,25 @@ int run_stouffer(wc_ctx *ctx, const double *z_dev, const Region *regions_dev, in
     // Rounds that the tree kernel does not take over (regions beyond TREE_MAXLEN, callers without call rows) and
     // that carry no -mineffectsize mask locate the extremes from the block bounds (k_seg_bound / k_seg_refine /
     // k_seg_bcollect) instead of evaluating every window of every job that may hold a call.
-    const char *tree_env = getenv("WC_TEST_TREE_TAIL");        // "0": host-driven rounds only
-    const bool tree_ok0 = tail && !bits && max_n <= TREE_MAXLEN && !ts.no_tree && !(tree_env && tree_env[0] == '0');
-    const char *cells_env = getenv("WC_TEST_CELLS");
+    const bool tree_ok0 = tail && !bits && max_n <= TREE_MAXLEN && !tail->host_rounds && sw.tree_tail;
     if ((rc = ctx->ensure_pinned(256))) return rc;
-    int *h = (int *)ctx->pinned;          // counter read-backs land in pinned memory
+    int *h = ((HostStatus *)ctx->pinned)->counters;   // counter read-backs land in pinned memory
     h[4] = 0;
+    // the walker or the tree kernel gave up: its call counts and counters [4] (segments) and [6] (gave up) start again
+    auto restart_counts = [&]() -> int {
+        WC_HIP(hipMemsetAsync(ts.out_n.p, 0, sizeof(int) * n_regions, stream));
+        WC_HIP(hipMemsetAsync(counters + 4, 0, sizeof(int), stream));
+        WC_HIP(hipMemsetAsync(counters + 6, 0, sizeof(int), stream));
+        return WC_OK;
+    };
+    // the caller looks at the status after ITS synchronize (one host round trip per batch instead of two; its ONE copy
+    // brings the counters and the flag words behind them) and repeats the batch with host-driven rounds if need be
+    auto defer_status = [&]() -> int {
+        out.status_deferred = true;
+        out.seg_bound = seg_cap;
+        WC_HIP(hipGetLastError());
+        return WC_OK;
+    };
     if (walk_path) {
         ts.mark(10, stream);
         hipLaunchKernelGGL(k_seg_walk, dim3((unsigned)(n_regions + whot.cap)), dim3(256), 0, stream, counters, regions_dev,
@@ -5847,40 +5907,45 @@ int run_stouffer(wc_ctx *ctx, const double *z_dev, const Region *regions_dev, in
                            (const int *)(counters + 4), (int)seg_cap, regions_dev, tail->ratio, tail->gpos,
                            max_calls, tail->reg_calls, whot.count);
         ts.mark(11, stream);
-        const int64_t bound = seg_cap;
-        if (!tail->defer_status) WC_HIP(hipMemcpyAsync(h, counters, sizeof(int) * 8, hipMemcpyDeviceToHost, stream));
-        if (tail->defer_status) {
-            // (the caller's ONE copy at the end of the batch brings the counters and the flag words behind them)
-            // the caller looks at the counters after ITS synchronize: h[6] non-zero = the walk gave up on some
-            // region, h[4] beyond the bound = more segments than k_call_post's grid covers; it then repeats the
-            // batch with the host-driven rounds
-            ts.tree_done = true;
-            ts.tree_pending = true;
-            ts.tree_seg_cap = bound;
-            WC_HIP(hipGetLastError());
-            return WC_OK;
-        }
+        // (h[6] non-zero = the walk gave up on some region, h[4] beyond seg_cap = more segments than the call rows hold)
+        if (tail->defer_status) return defer_status();
+        WC_HIP(hipMemcpyAsync(h, counters, sizeof(int) * 8, hipMemcpyDeviceToHost, stream));
         WC_HIP(hipStreamSynchronize(stream));
-        if (h[6] == 0 && h[4] <= bound) {
-            ts.tree_done = true;
+        if (h[6] == 0 && h[4] <= seg_cap) {
             WC_HIP(hipGetLastError());
             return WC_OK;
         }
         // rare: again on the host-driven path
-        if (getenv("WC_TEST_VERBOSE"))
+        if (sw.verbose)
             fprintf(stderr, "wisecondor_amd: segmentation repeated on the host-driven rounds (walk status %d: 1 = region beyond %d "
                             "bins, 2 = non-finite z, 4 = ties beyond the record, 8 = more than %d segments, 16 = stack; %d segments)\n",
                     h[6], CJ_MAXLEN, TREE_SEGS, h[4]);
-        WC_HIP(hipMemsetAsync(ts.out_n.p, 0, sizeof(int) * n_regions, stream));
-        WC_HIP(hipMemsetAsync(counters + 4, 0, sizeof(int), stream));
-        WC_HIP(hipMemsetAsync(counters + 6, 0, sizeof(int), stream));
+        if ((rc = restart_counts())) return rc;
         h[4] = 0;
         if (walker_owns_setup)             // the root jobs the walker did not need
             hipLaunchKernelGGL(k_init_jobs, dim3((unsigned)cdiv(n_regions, 256)), dim3(256), 0, stream, regions_dev, n_regions,
                                ts.jobs_a.as<Job>(), counters);
     }
-    const bool tree_ok = tree_ok0 && (walk_env && walk_env[0] == '0');
+    const bool tree_ok = tree_ok0 && !sw.walk;
     const bool bound_path = !bits && !tree_ok;
+    // the end of a host-driven round: decide, the brute-force scan (its list grows in decide), the counters back
+    auto end_round = [&](int64_t n_hot) -> int {
+        if (n_hot > 0)
+            hipLaunchKernelGGL(k_seg_decide, dim3((unsigned)n_hot), dim3(256), 0, stream, (const Job *)cur,
+                               (const int *)hot, counters, regions_dev, z_dev, (const int2 *)ts.cand.as<int2>(),
+                               (const int *)ts.cand_cnt.as<int>(), thr, min_search, bits, bit_off, ts.seg.as<Seg>(),
+                               (int)seg_cap, next, (int)job_cap, brute, counters + 1);
+        hipLaunchKernelGGL(k_seg_brute, dim3((unsigned)n_jobs), dim3(256), 0, stream, (const Job *)cur,
+                           (const int *)brute, counters, regions_dev, z_dev, thr, min_search, bits, bit_off,
+                           ts.seg.as<Seg>(), (int)seg_cap, next, (int)job_cap, counters + 1);
+        WC_HIP(hipMemcpyAsync(h, counters, sizeof(int) * 8, hipMemcpyDeviceToHost, stream));
+        WC_HIP(hipStreamSynchronize(stream));
+        WC_CHECK(h[1] <= job_cap, WC_E_INTERNAL, "stouffer: job list overflow");
+        WC_CHECK(h[4] <= seg_cap, WC_E_LIMIT, "stouffer: more than max_calls=%d segments per region", max_calls);
+        n_jobs = h[1];
+        std::swap(cur, next);
+        return WC_OK;
+    };
     while (n_jobs > 0) {
         WC_CHECK(++guard < 100000, WC_E_INTERNAL, "stouffer: recursion did not terminate");
         // per-round scratch is sized by the jobs of this round, not by the worst case
@@ -5899,7 +5964,7 @@ int run_stouffer(wc_ctx *ctx, const double *z_dev, const Region *regions_dev, in
         const unsigned per_job_quiet = (unsigned)std::min<int64_t>(max_chunks, std::max<int64_t>(1, 8192 / n_jobs));
         // jobs up to CJ_MAXLEN bins: one workgroup per job finds the extremes from cell bounds and lists the candidates
         // (k_seg_job); WC_TEST_CELLS=0 keeps the row-block kernels (k_seg_seed / k_seg_bound / k_seg_bcollect)
-        const bool cell_path = bound_path && max_n <= CJ_MAXLEN && !(cells_env && cells_env[0] == '0');
+        const bool cell_path = bound_path && max_n <= CJ_MAXLEN && sw.cells;
         if (cell_path) {
             WC_HIP(hipMemsetAsync(counters + 1, 0, sizeof(int) * 3, stream));      // next jobs, hot, brute
             if ((rc = ts.cell_state.reserve(sizeof(CellJobState) * n_jobs))) return rc;
@@ -5907,8 +5972,8 @@ int run_stouffer(wc_ctx *ctx, const double *z_dev, const Region *regions_dev, in
             WC_HIP(hipMemsetAsync(ts.cell_state.p, 0, sizeof(CellJobState) * n_jobs, stream));
             // a round of many jobs fills the chip with one workgroup per job (parts repeat the set-up and the seed);
             // a round of few jobs -- the later rounds -- is as long as its longest job: several workgroups per job
-            const char *parts_env = getenv("WC_CELL_PARTS");               // experiments: at most this many workgroups per job
-            const int max_parts = std::max(1, std::min(cell_parts((int)max_n), parts_env ? atoi(parts_env) : (n_jobs >= 2048 ? 1 : CJ_MAXPARTS)));
+            const int max_parts =
+                std::max(1, std::min(cell_parts((int)max_n), sw.cell_parts ? sw.cell_parts : (n_jobs >= 2048 ? 1 : CJ_MAXPARTS)));
             hipLaunchKernelGGL(k_seg_job, dim3((unsigned)max_parts, (unsigned)n_jobs), dim3(256), 0, stream,
                                (const Job *)cur, (int)n_jobs,
                                regions_dev, (const double *)ts.prefix.as<double>(), (const double *)ts.rs.as<double>(),
@@ -5925,19 +5990,7 @@ int run_stouffer(wc_ctx *ctx, const double *z_dev, const Region *regions_dev, in
                                (const CellRec *)ts.cell_rec.as<CellRec>(), hot, brute, counters, ts.cand.as<int2>(),
                                ts.cand_cnt.as<int>(), work);
             ts.mark(11, stream);
-            hipLaunchKernelGGL(k_seg_decide, dim3((unsigned)n_jobs), dim3(256), 0, stream, (const Job *)cur,
-                               (const int *)hot, counters, regions_dev, z_dev, (const int2 *)ts.cand.as<int2>(),
-                               (const int *)ts.cand_cnt.as<int>(), thr, min_search, bits, bit_off, ts.seg.as<Seg>(),
-                               (int)seg_cap, next, (int)job_cap, brute, counters + 1);
-            hipLaunchKernelGGL(k_seg_brute, dim3((unsigned)n_jobs), dim3(256), 0, stream, (const Job *)cur,
-                               (const int *)brute, counters, regions_dev, z_dev, thr, min_search, bits, bit_off,
-                               ts.seg.as<Seg>(), (int)seg_cap, next, (int)job_cap, counters + 1);
-            WC_HIP(hipMemcpyAsync(h, counters, sizeof(int) * 8, hipMemcpyDeviceToHost, stream));
-            WC_HIP(hipStreamSynchronize(stream));
-            WC_CHECK(h[1] <= job_cap, WC_E_INTERNAL, "stouffer: job list overflow");
-            WC_CHECK(h[4] <= seg_cap, WC_E_LIMIT, "stouffer: more than max_calls=%d segments per region", max_calls);
-            n_jobs = h[1];
-            std::swap(cur, next);
+            if ((rc = end_round(n_jobs))) return rc;
             continue;
         }
         if (bound_path) {
@@ -6008,27 +6061,15 @@ int run_stouffer(wc_ctx *ctx, const double *z_dev, const Region *regions_dev, in
                                (const double2 *)ts.sub.as<double2>(), max_chunks, no_sd, no_inf,
                                (const int *)hot, (const int *)(counters + 2));
             WC_HIP(hipMemcpyAsync(h, counters, sizeof(int) * 8, hipMemcpyDeviceToHost, stream));
-            if (tail->defer_status) {
-                // the caller looks at the counters after ITS synchronize (one host round trip per batch
-                // instead of two): h[3] / h[6] non-zero = the tree kernel passed on some region, and the
-                // caller repeats the batch with host-driven rounds
-                ts.tree_done = true;
-                ts.tree_pending = true;
-                ts.tree_seg_cap = seg_cap;
-                WC_HIP(hipGetLastError());
-                return WC_OK;
-            }
+            if (tail->defer_status) return defer_status();
             WC_HIP(hipStreamSynchronize(stream));
             if (h[3] == 0 && h[6] == 0) {          // no job for the exact scan, nothing the tree kernel gave up on
                 WC_CHECK(h[4] <= seg_cap, WC_E_LIMIT, "stouffer: more than max_calls=%d segments per region", max_calls);
-                ts.tree_done = true;
                 WC_HIP(hipGetLastError());
                 return WC_OK;
             }
             // rare: start the round's second half again on the host-driven path
-            WC_HIP(hipMemsetAsync(ts.out_n.p, 0, sizeof(int) * n_regions, stream));
-            WC_HIP(hipMemsetAsync(counters + 4, 0, sizeof(int), stream));
-            WC_HIP(hipMemsetAsync(counters + 6, 0, sizeof(int), stream));
+            if ((rc = restart_counts())) return rc;
         }
         if (n_hot > 0 && bound_path) {
             const unsigned per_hot = (unsigned)std::min<int64_t>(max_chunks, std::max<int64_t>(1, 16384 / n_hot));
@@ -6049,24 +6090,9 @@ int run_stouffer(wc_ctx *ctx, const double *z_dev, const Region *regions_dev, in
                                (const double2 *)ts.sub.as<double2>(), bits, bit_off, ts.cand.as<int2>(),
                                ts.cand_cnt.as<int>());
         }
-        if (n_hot > 0) {
-            hipLaunchKernelGGL(k_seg_decide, dim3((unsigned)n_hot), dim3(256), 0, stream, (const Job *)cur,
-                               (const int *)hot, counters, regions_dev, z_dev, (const int2 *)ts.cand.as<int2>(),
-                               (const int *)ts.cand_cnt.as<int>(), thr, min_search, bits, bit_off, ts.seg.as<Seg>(),
-                               (int)seg_cap, next, (int)job_cap, brute, counters + 1);
-        }
-        // brute list may have grown in decide; its length is only known on the device
-        hipLaunchKernelGGL(k_seg_brute, dim3((unsigned)n_jobs), dim3(256), 0, stream, (const Job *)cur,
-                           (const int *)brute, counters, regions_dev, z_dev, thr, min_search, bits, bit_off,
-                           ts.seg.as<Seg>(), (int)seg_cap, next, (int)job_cap, counters + 1);
-        WC_HIP(hipMemcpyAsync(h, counters, sizeof(int) * 8, hipMemcpyDeviceToHost, stream));
-        WC_HIP(hipStreamSynchronize(stream));
-        WC_CHECK(h[1] <= job_cap, WC_E_INTERNAL, "stouffer: job list overflow");
-        WC_CHECK(h[4] <= seg_cap, WC_E_LIMIT, "stouffer: more than max_calls=%d segments per region", max_calls);
-        n_jobs = h[1];
-        std::swap(cur, next);
+        if ((rc = end_round(n_hot))) return rc;
     }
-    ts.last_segs = h[4];                  // from the last round's read-back
+    out.segs = h[4];                      // from the last round's read-back
     if (h[4] > 0)
         hipLaunchKernelGGL(k_seg_gather, dim3((unsigned)cdiv(h[4], 256)), dim3(256), 0, stream,
                            (const Seg *)ts.seg.as<Seg>(), h[4], max_calls, ts.out_val.as<double>(), ts.out_x.as<int>(),
@@ -6077,38 +6103,18 @@ int run_stouffer(wc_ctx *ctx, const double *z_dev, const Region *regions_dev, in
 
 // Latency mode's cleaning + segmentation: k_lat_setup, k_seg_search (root windows of every region, all
 // row blocks in parallel), k_seg_tree (one workgroup per region walks the recursion and writes the call
-// rows; stdDevAvg and the result inflation ride in its grid) -- no host round trip; counters[4]
+// rows; stdDevAvg (`rider`, from run_repeat) and the result inflation ride in its grid) -- no host round trip; counters[4]
 // (segments) and [6] (give-up flag) are looked at by the caller after it synchronised.  The calls are
 // left in ts.effect / ts.out_n, the whole-chromosome values in ts.whole.
 int run_seg_lat(wc_ctx *ctx, const wc_reference *ref, const double *zsrc, const double *rsrc, const double *nsrc,
                 int64_t str_i, int64_t str_b, int64_t Ns, int n_sel, int64_t max_n, double thr, int min_ref_bins,
-                int max_calls, hipStream_t stream, double *whole_copy, InflateRider inf) {
+                int max_calls, hipStream_t stream, double *whole_copy, SdRider rider, InflateRider inf) {
     TestState &ts = ctx->ts;
     const int64_t B = ref->B, n_regions = Ns * n_sel, total_len = Ns * B;
     int rc;
-    const int64_t seg_cap = n_regions * (int64_t)max_calls + 64;
-    if ((rc = ts.prefix.reserve(sizeof(double) * (total_len + n_regions + 8)))) return rc;
-    if ((rc = ts.reg_abs.reserve(sizeof(double) * n_regions))) return rc;
-    if ((rc = ts.reg_flag.reserve(sizeof(int) * n_regions))) return rc;
-    const int64_t rs_need = std::max<int64_t>(max_n + 80, 2 * QB + 80);
-    if (ts.rs_len < rs_need) {
-        if ((rc = ts.rs.reserve(sizeof(double) * rs_need))) return rc;
-        ts.rs_len = rs_need;
-        hipLaunchKernelGGL(k_fill_rs, dim3((unsigned)cdiv(ts.rs_len, 256)), dim3(256), 0, stream, ts.rs.as<double>(),
-                           ts.rs_len);
-    }
-    if ((rc = ts.jobs_a.reserve(sizeof(Job) * (n_regions + 64)))) return rc;
-    if ((rc = ts.job_cnt.reserve(sizeof(int) * 16))) return rc;
-    if ((rc = ts.seg.reserve(sizeof(Seg) * seg_cap))) return rc;
-    if ((rc = ts.out_val.reserve(sizeof(double) * n_regions * max_calls))) return rc;
-    if ((rc = ts.out_x.reserve(sizeof(int) * n_regions * max_calls))) return rc;
-    if ((rc = ts.out_y.reserve(sizeof(int) * n_regions * max_calls))) return rc;
-    if ((rc = ts.out_n.reserve(sizeof(int) * n_regions))) return rc;
-    if ((rc = ts.whole.reserve(sizeof(double) * n_regions))) return rc;
-    if ((rc = ts.job_cnt.reserve(sizeof(int) * 16))) return rc;
-    const int64_t total = total_len + n_regions, nblk = cdiv(total, QB);
-    if ((rc = ts.tmin.reserve(sizeof(double) * nblk))) return rc;
-    if ((rc = ts.tmax.reserve(sizeof(double) * nblk))) return rc;
+    if ((rc = reserve_segmentation(ts, n_regions, total_len, n_regions + 64, max_calls,
+                                   std::max<int64_t>(max_n + 80, 2 * QB + 80), stream)))
+        return rc;
     int *counters = ts.job_cnt.as<int>();
     hipLaunchKernelGGL(k_lat_setup<1024>, dim3((unsigned)n_regions), dim3(1024), sizeof(double) * (max_n + 1), stream, zsrc, rsrc, nsrc, str_i, str_b, B,
                        (const int64_t *)ref->moff_dev.as<int64_t>(), (const int64_t *)ref->goff_dev.as<int64_t>(),
@@ -6134,18 +6140,6 @@ int run_seg_lat(wc_ctx *ctx, const wc_reference *ref, const double *zsrc, const 
         if (n_regions * max_chunks <= 2048) WC_LSEARCH(16); else WC_LSEARCH(4);
 #undef WC_LSEARCH
     }
-    SdRider rider{};
-    if (ts.lat_ride) {
-        rider.blocks = (int)Ns;
-        rider.sdT = ts.sdt.as<double>();
-        rider.B = B;
-        rider.Ns = Ns;
-        rider.out = ts.sd_avg.as<double>();
-        rider.out2 = ts.lat_ride_out2;
-        rider.fail = ts.sd_fail.as<int>();
-        rider.sb = Ns;
-        rider.si = 1;
-    }
     const size_t tree_lds = std::max<size_t>(sizeof(double) * (2 * max_n + 2), rider.blocks ? sizeof(SdShared) : 0);
     hipLaunchKernelGGL(k_seg_tree, dim3((unsigned)(n_regions + rider.blocks + inf.blocks)), dim3(1024), tree_lds, stream, counters,
                        (const Region *)ts.regions.as<Region>(), n_regions, (const int *)ts.reg_flag.as<int>(),
@@ -6155,7 +6149,6 @@ int run_seg_lat(wc_ctx *ctx, const wc_reference *ref, const double *zsrc, const 
                        ts.effect.as<double>(), ts.out_n.as<int>(), (const Extreme *)ts.partial.as<Extreme>(),
                        (const double2 *)ts.sub.as<double2>(), max_chunks, rider, inf, (const int *)nullptr,
                        (const int *)nullptr);
-    ts.last_segs = 0;                     // the calls are already in ts.effect / ts.out_n
     WC_HIP(hipGetLastError());
     return WC_OK;
 }
@@ -6380,13 +6373,15 @@ int wc_repeat_test(wc_ctx *ctx, const wc_reference *ref, const double *data, int
                    int repeats, double *z, double *r, double *ref_sizes, double *sd_avg) {
     WC_CHECK(ctx && ref && data && n_samples > 0, WC_E_ARG, "repeatTest: bad argument");
     WC_HIP(hipSetDevice(ctx->device));
+    const TestSwitches sw = read_switches();
     TestState &ts = ctx->ts;
     const int64_t n = n_samples * ref->B;
     int rc;
     if ((rc = ts.data.reserve(sizeof(double) * n))) return rc;
     if ((rc = ts.z.reserve(sizeof(double) * n))) return rc;
     WC_HIP(hipMemcpy(ts.data.p, data, sizeof(double) * n, hipMemcpyHostToDevice));
-    if ((rc = run_repeat(ctx, ref, ts.data.as<double>(), n_samples, threshold, repeats, nullptr))) return rc;
+    RepeatOut rep;
+    if ((rc = run_repeat(ctx, sw, ref, ts.data.as<double>(), n_samples, threshold, repeats, nullptr, rep))) return rc;
     if ((rc = join_side(ctx, nullptr))) return rc;
     struct { wc::DevBuf *src; double *dst; } outs[] = {{&ts.zt, z}, {&ts.rt, r}, {&ts.nt, ref_sizes}};
     for (auto &o : outs) {
@@ -6404,6 +6399,7 @@ int wc_std_dev_avg(wc_ctx *ctx, const double *sd, int64_t n_samples, int64_t n_b
                    int32_t *serial_samples) {
     WC_CHECK(ctx && sd && out && n_samples > 0 && n_bins > 0, WC_E_ARG, "stdDevAvg: bad argument");
     WC_HIP(hipSetDevice(ctx->device));
+    const TestSwitches sw = read_switches();
     TestState &ts = ctx->ts;
     const int64_t n = n_samples * n_bins;
     int rc;
@@ -6417,7 +6413,7 @@ int wc_std_dev_avg(wc_ctx *ctx, const double *sd, int64_t n_samples, int64_t n_b
     const int *only = nullptr;
     if (n_bins <= 65536) {
         launch_sd_fast(nullptr, ts.data.as<double>(), n_bins, n_samples, ts.sd_avg.as<double>(), ts.sd_fail.as<int>(),
-                       nullptr, 1, n_bins);       // the caller's layout: a sample's values contiguous
+                       nullptr, 1, n_bins, sw.sd_stage);       // the caller's layout: a sample's values contiguous
         only = ts.sd_fail.as<int>();
     }
     hipLaunchKernelGGL(k_sd_avg<64>, dim3((unsigned)cdiv(n_samples, 64)), dim3(256), 0, nullptr,
@@ -6443,6 +6439,7 @@ int wc_stouffer_segments(wc_ctx *ctx, const double *z, const double *ratio, doub
     if (n_regions == 0) return WC_OK;
     WC_CHECK(n_regions <= 60000, WC_E_LIMIT, "segments: more than 60000 regions per call");
     WC_HIP(hipSetDevice(ctx->device));
+    const TestSwitches sw = read_switches();
     TestState &ts = ctx->ts;
     const int64_t total = region_offsets[n_regions];
     std::vector<Region> regs(n_regions);
@@ -6467,8 +6464,9 @@ int wc_stouffer_segments(wc_ctx *ctx, const double *z, const double *ratio, doub
         WC_HIP(hipMemcpy(ts.rc.p, ratio, sizeof(double) * total, hipMemcpyHostToDevice));
         for (int64_t r = 0; r < n_regions; ++r) bits_upper += (int64_t)regs[r].n * (regs[r].n + 1) / 2;
     }
-    if ((rc = run_stouffer(ctx, ts.zc.as<double>(), ts.regions.as<Region>(), n_regions, total, max_n, threshold,
-                           min_search, max_calls, nullptr, ts.rc.as<double>(), min_effect, bits_upper)))
+    SegOut seg;
+    if ((rc = run_stouffer(ctx, sw, ts.zc.as<double>(), ts.regions.as<Region>(), n_regions, total, max_n, threshold,
+                           min_search, max_calls, nullptr, seg, nullptr, ts.rc.as<double>(), min_effect, bits_upper)))
         return rc;
     WC_HIP(hipDeviceSynchronize());
     if (region_z) WC_HIP(hipMemcpy(region_z, ts.whole.p, sizeof(double) * n_regions, hipMemcpyDeviceToHost));
@@ -6486,36 +6484,42 @@ int wc_stouffer_segments(wc_ctx *ctx, const double *z, const double *ratio, doub
     return WC_OK;
 }
 
-// Everything wc_test_batch_dev enqueues.  lat_rounds == 0: the general path (host-driven segmentation
-// rounds, synchronises per round and at the end).  lat_rounds > 0: latency mode -- no host round
-// trip at all (capturable in a hipGraph); the read-backs the caller has to look at after it
-// synchronised the stream land in ctx->pinned: int[16] = call overflow flag, int[24..31] = the
-// segmentation counters ([6] a round bound was exceeded, [lat_left] jobs left after the last round).
-static int test_batch_body(wc_ctx *ctx, hipStream_t stream, const wc_reference *ref, const int32_t *counts, int64_t Ns,
-                           double threshold, int min_ref_bins, int repeats, double min_effect,
-                           const std::vector<int> &sel, int64_t max_n, int max_calls, double *results_z,
-                           double *results_r, double *results_cwz, double *calls, int32_t *n_calls, double *asdef,
-                           int lat_rounds) {
+struct BatchPlan {           // how one attempt of a batch runs
+    bool lat = false;        // latency mode: no host round trip at all (capturable in a hipGraph)
+    bool no_tail = false;    // the late repeats as a launch pair each (the one-workgroup form overflowed before)
+    bool no_tree = false;    // host-driven segmentation rounds only (the walker or the tree kernel gave up before)
+};
+enum class BatchStatus { ok, tail_overflow, tree_gave_up };    // what a general-path attempt's last synchronize found
+
+// Everything wc_test_batch_dev enqueues for one attempt.  The general path synchronises per round and at the end and
+// reports in `status` whether the attempt has to be repeated.  Latency mode (plan.lat) has no host round trip at all;
+// the status words the caller reads after its synchronize land in ctx->pinned (HostStatus::lat_*).
+static int test_batch_body(wc_ctx *ctx, hipStream_t stream, const TestSwitches &sw, const BatchPlan &plan,
+                           const wc_reference *ref, const int32_t *counts, int64_t Ns, double threshold, int min_ref_bins,
+                           int repeats, double min_effect, const std::vector<int> &sel, int64_t max_n, int max_calls,
+                           double *results_z, double *results_r, double *results_cwz, double *calls, int32_t *n_calls,
+                           double *asdef, BatchStatus &status) {
     TestState &ts = ctx->ts;
     const int64_t B = ref->B;
     const int n_sel = (int)sel.size();
     int rc;
+    status = BatchStatus::ok;
     ts.prof_tag.clear();
     ts.mark(0, stream);
-    const bool lat = lat_rounds > 0;
+    const bool lat = plan.lat;
     // The z-score stage of a batch works on bin-major arrays [bins, Np], Np = the sample count padded to a multiple of
     // 16: a reference bin's row then starts on a 128-byte line and the tiled z-score kernel's 16-sample columns are
     // whole lines; the extra samples are copies of sample 0 whose results nobody reads.
     const int64_t Np = (!lat && Ns >= 32) ? ((Ns + 15) & ~(int64_t)15) : Ns;
+    const int64_t n = B * Np, n_words = cdiv(n, 32);
+    if ((rc = reserve_repeat_arrays(ts, n, Np))) return rc;
+    if ((rc = ts.misc2.reserve(sizeof(int) * (repeats + 2 + n_words)))) return rc;
+    if ((rc = ts.proj.reserve(sizeof(double) * Ns * MAX_COMP * PROJ_SPLIT))) return rc;
     if (lat) {
-        // totals, normalisation, PCA and the repeats' working arrays in one launch
-        const int64_t n = B * Ns, n_words = cdiv(n, 32);
+        // totals, normalisation, PCA and the repeats' working arrays in one launch (Np == Ns)
         if ((rc = ts.totals.reserve(sizeof(double) * Ns))) return rc;
         if ((rc = ts.raw.reserve(sizeof(double) * n))) return rc;
         if ((rc = ts.data.reserve(sizeof(double) * n))) return rc;
-        if ((rc = reserve_repeat_arrays(ts, n, Np))) return rc;
-        if ((rc = ts.misc2.reserve(sizeof(int) * (repeats + 2 + n_words)))) return rc;
-        if ((rc = ts.proj.reserve(sizeof(double) * Ns * MAX_COMP * PROJ_SPLIT))) return rc;
         hipLaunchKernelGGL(k_lat_project, dim3((unsigned)Ns, PROJ_SPLIT), dim3(256), 0, stream, counts, ref->Btot,
                            (const int *)ref->m2g.as<int>(), B, (const double *)ref->pca_mean.as<double>(),
                            (const double *)ref->pca_comp.as<double>(), ref->n_comp, ts.totals.as<double>(),
@@ -6528,11 +6532,7 @@ static int test_batch_body(wc_ctx *ctx, hipStream_t stream, const wc_reference *
     } else {
         // totals -> projection partial sums (normalised values on the fly) -> corrected values straight into the
         // repeats' bin-major arrays: three launches, no sample-major intermediate
-        const int64_t n = B * Np, n_words = cdiv(n, 32);
         if ((rc = ts.totals.reserve(sizeof(long long) * Ns * TOT_SPLIT))) return rc;
-        if ((rc = ts.proj.reserve(sizeof(double) * Ns * MAX_COMP * PROJ_SPLIT))) return rc;
-        if ((rc = reserve_repeat_arrays(ts, n, Np))) return rc;
-        if ((rc = ts.misc2.reserve(sizeof(int) * (repeats + 2 + n_words)))) return rc;
         hipLaunchKernelGGL(k_sample_totals, dim3((unsigned)Ns, TOT_SPLIT), dim3(256), 0, stream, counts, ref->Btot,
                            ts.totals.as<long long>());
         hipLaunchKernelGGL(k_pca_project, dim3((unsigned)Ns, PROJ_SPLIT), dim3(256), 0, stream, (const double *)nullptr, B,
@@ -6546,12 +6546,14 @@ static int test_batch_body(wc_ctx *ctx, hipStream_t stream, const wc_reference *
                            ts.misc2.as<int>(), repeats > 0 ? repeats + 2 + n_words : 0);
     }
     ts.mark(1, stream);
-    if ((rc = run_repeat(ctx, ref, ts.data.as<double>(), Np, threshold, repeats, stream, lat, asdef, !lat, !lat,
-                         !lat && calls && n_calls)))      // (the late repeats as one launch: only where the status check below runs)
+    // (the late repeats as one launch: only where the status check below reads their overflow word)
+    RepeatOut rep;
+    if ((rc = run_repeat(ctx, sw, ref, ts.data.as<double>(), Np, threshold, repeats, stream, rep, lat, asdef, !lat, !lat,
+                         !lat && calls && n_calls && n_sel > 0 && !plan.no_tail)))
         return rc;
     // run_repeat forked the side stream for stdDevAvg at its very end; with sample-major outputs nothing is enqueued on
     // the launch stream before the inflated outputs go to the side stream too: they ride on the same fork
-    ctx->side_fresh = !lat && ts.sm_out && ctx->side_pending && !ts.profile;
+    ctx->side_fresh = !lat && rep.sm_out && ctx->side_pending && !ts.profile;
     ts.mark(2, stream);
     struct Joiner {   // asdef is copied out once the side stream's sum is done, on every exit path
         wc_ctx *c; hipStream_t s; double *dst; int64_t n; bool on;
@@ -6570,7 +6572,7 @@ static int test_batch_body(wc_ctx *ctx, hipStream_t stream, const wc_reference *
     // (latency mode: the few samples are read straight from the bin-major arrays)
     const double *zsrc = ts.zt.as<double>(), *rsrc = ts.rt.as<double>(), *nsrc = ts.nt.as<double>();
     int64_t str_i = 1, str_b = Ns;
-    if (!lat && ts.sm_out) {
+    if (!lat && rep.sm_out) {
         // the tiled first repeat (and the later repeats behind it) wrote them sample-major: nothing to transpose
         str_i = B; str_b = 1;
     } else if (!lat) {
@@ -6591,7 +6593,7 @@ static int test_batch_body(wc_ctx *ctx, hipStream_t stream, const wc_reference *
         dim3 g((unsigned)cdiv(ref->Btot, 256), (unsigned)Ns);
         // a batch: the inflated outputs feed nothing downstream -> side stream, under the segmentation
         hipStream_t is = stream;
-        const bool second = side_second(Ns);
+        const bool second = sw.second_side(Ns);
         if (!lat && Ns > 8) {
             if ((rc = side_begin(ctx, stream, second))) return rc;
             is = second ? ctx->side2 : ctx->side;
@@ -6612,22 +6614,19 @@ static int test_batch_body(wc_ctx *ctx, hipStream_t stream, const wc_reference *
     if ((rc = ts.gpos.reserve(sizeof(int) * Ns * B))) return rc;
     if ((rc = ts.regions.reserve(sizeof(Region) * n_regions))) return rc;
     if ((rc = ts.effect.reserve(sizeof(double) * n_regions * max_calls * 5))) return rc;
-    if ((rc = ts.job_cnt.reserve(sizeof(int) * 16))) return rc;
+    SegOut seg;
     if (lat) {
-        if ((rc = ctx->ensure_pinned(256))) return rc;
         InflateRider inf{};
         if (ride_inf && (results_z || results_r)) {
-            {
-                inf.blocks = (int)std::min<int64_t>(16, cdiv(ref->Btot * Ns, 1024));
-                inf.zs = zsrc; inf.rs = rsrc; inf.ns = nsrc;
-                inf.B = B; inf.Btot = ref->Btot; inf.Ns = Ns; inf.si = str_i; inf.sb = str_b;
-                inf.g2m = ref->g2m.as<int>();
-                inf.minref = (double)min_ref_bins;
-                inf.res_z = results_z; inf.res_r = results_r;
-            }
+            inf.blocks = (int)std::min<int64_t>(16, cdiv(ref->Btot * Ns, 1024));
+            inf.zs = zsrc; inf.rs = rsrc; inf.ns = nsrc;
+            inf.B = B; inf.Btot = ref->Btot; inf.Ns = Ns; inf.si = str_i; inf.sb = str_b;
+            inf.g2m = ref->g2m.as<int>();
+            inf.minref = (double)min_ref_bins;
+            inf.res_z = results_z; inf.res_r = results_r;
         }
         if ((rc = run_seg_lat(ctx, ref, zsrc, rsrc, nsrc, str_i, str_b, Ns, n_sel, max_n, threshold, min_ref_bins,
-                              max_calls, stream, results_cwz, inf)))
+                              max_calls, stream, results_cwz, rep.sd_ride, inf)))
             return rc;
     } else {
         const bool fuse = min_effect == 0.0 && max_n <= TREE_MAXLEN;       // regions that fit the fused set-up kernel
@@ -6648,13 +6647,13 @@ static int test_batch_body(wc_ctx *ctx, hipStream_t stream, const wc_reference *
             }
         ts.mark(3, stream);
         const TreeTail tail{ts.rc.as<double>(), ts.gpos.as<int>(), ts.effect.as<double>(), calls && n_calls && !ts.profile,
-                            (!fuse && min_effect == 0.0) ? results_cwz : nullptr, n_sel};
+                            (!fuse && min_effect == 0.0) ? results_cwz : nullptr, n_sel, plan.no_tree};
         const FusedSetup fsu{zsrc, rsrc, nsrc, str_i, str_b, B, ref->moff_dev.as<int64_t>(), ref->goff_dev.as<int64_t>(),
                              ref->m2g.as<int>(), ts.sel.as<int>(), n_sel, (double)min_ref_bins, ts.zc.as<double>(),
                              ts.rc.as<double>(), ts.gpos.as<int>(), ts.regions.as<Region>(), results_cwz};
         cwz_done = results_cwz && (fuse || (min_effect == 0.0 && calls && n_calls));
-        if ((rc = run_stouffer(ctx, ts.zc.as<double>(), ts.regions.as<Region>(), n_regions, Ns * B, max_n, threshold, 3,
-                               max_calls, stream, ts.rc.as<double>(), min_effect, bits_upper, 0, nullptr,
+        if ((rc = run_stouffer(ctx, sw, ts.zc.as<double>(), ts.regions.as<Region>(), n_regions, Ns * B, max_n, threshold,
+                               3, max_calls, stream, seg, rep.tail_flag, ts.rc.as<double>(), min_effect, bits_upper,
                                calls && n_calls ? &tail : nullptr, fuse ? &fsu : nullptr)))
             return rc;
     }
@@ -6662,11 +6661,12 @@ static int test_batch_body(wc_ctx *ctx, hipStream_t stream, const wc_reference *
     if (results_cwz && !lat && !cwz_done)
         WC_HIP(hipMemcpyAsync(results_cwz, ts.whole.p, sizeof(double) * n_regions, hipMemcpyDeviceToDevice, stream));
     if ((rc = ctx->ensure_pinned(256))) return rc;
+    HostStatus *hs = (HostStatus *)ctx->pinned;
     if (calls && n_calls) {
         // the overflow flag (counters + 8) was cleared by k_region_prefix
-        if (ts.last_segs > 0)
-            hipLaunchKernelGGL(k_call_post, dim3((unsigned)ts.last_segs), dim3(CP_THREADS), 0, stream,
-                               (const Seg *)ts.seg.as<Seg>(), (int)ts.last_segs,
+        if (seg.segs > 0)
+            hipLaunchKernelGGL(k_call_post, dim3((unsigned)seg.segs), dim3(CP_THREADS), 0, stream,
+                               (const Seg *)ts.seg.as<Seg>(), (int)seg.segs,
                                (const Region *)ts.regions.as<Region>(), (const double *)ts.rc.as<double>(),
                                (const int *)ts.gpos.as<int>(), max_calls, ts.effect.as<double>(), (const int *)nullptr);
         if (lat && (rc = join_side(ctx, stream))) return rc;      // the status words read k_sd_fast's flags
@@ -6676,49 +6676,40 @@ static int test_batch_body(wc_ctx *ctx, hipStream_t stream, const wc_reference *
         else
         hipLaunchKernelGGL(k_assemble_calls, dim3((unsigned)cdiv(Ns, 64)), dim3(64), 0, stream,   // latency mode: Ns <= 8, one workgroup
                            (const double *)ts.effect.as<double>(), (const int *)ts.out_n.as<int>(), n_sel, max_calls, Ns,
-                           calls, n_calls, (ts.job_cnt.as<int>() + 8), lat ? (int *)ctx->pinned : (int *)nullptr,
+                           calls, n_calls, (ts.job_cnt.as<int>() + 8), lat ? (int *)hs : (int *)nullptr,
                            (const int *)ts.job_cnt.as<int>(), (const int *)(ts.misc2.as<int>() + repeats + 1),
                            (const int *)ts.sd_fail.as<int>());
-        // batches: the segmentation's counters [0..7] and the flag words behind them ([8] a sample with more than max_calls
-        // calls, [9] the late repeats' overflow) come back in ONE copy
-        int *overflow = (int *)ctx->pinned + (lat ? 16 : 8);
         if (!lat) {
             // the side stream rejoins and asdef is copied out IN FRONT of the synchronize: enqueued behind it (the
             // destructor's place) they were one more host round trip -- 25 us of idle GPU -- at the end of every batch
             joiner.now();
-            WC_HIP(hipMemcpyAsync(ctx->pinned, ts.job_cnt.p, 12 * sizeof(int), hipMemcpyDeviceToHost, stream));
+            // the segmentation's counters [0..7] and the flag words behind them (call_overflow, tail_overflow) come back
+            // in ONE copy
+            WC_HIP(hipMemcpyAsync(hs, ts.job_cnt.p, 12 * sizeof(int), hipMemcpyDeviceToHost, stream));
             WC_HIP(hipStreamSynchronize(stream));
-            if (ts.tail_used && overflow[1] != 0) {
+            if (rep.tail_flag && hs->tail_overflow != 0) {
                 // a late repeat had more pairs queued than the one-workgroup form takes: the batch again, a launch pair per repeat
-                if (getenv("WC_TEST_VERBOSE")) fprintf(stderr, "wisecondor_amd: batch repeated with a launch pair per late repeat\n");
-                ts.tree_pending = false;
-                ts.no_tail = true;
-                rc = test_batch_body(ctx, stream, ref, counts, Ns, threshold, min_ref_bins, repeats, min_effect, sel,
-                                     max_n, max_calls, results_z, results_r, results_cwz, calls, n_calls, asdef, lat_rounds);
-                ts.no_tail = false;
-                return rc;
+                if (sw.verbose) fprintf(stderr, "wisecondor_amd: batch repeated with a launch pair per late repeat\n");
+                status = BatchStatus::tail_overflow;
+                return WC_OK;
             }
-            if (ts.tree_pending) {
-                // the tree kernel's status words arrived with this synchronize (run_stouffer queued the copy)
-                ts.tree_pending = false;
-                const int *h = (const int *)ctx->pinned;
+            if (seg.status_deferred) {
+                // the walker's / tree kernel's status words arrived with this synchronize
+                const int *h = hs->counters;
                 if (h[3] != 0 || h[6] != 0) {
-                    if (getenv("WC_TEST_VERBOSE"))
+                    if (sw.verbose)
                         fprintf(stderr, "wisecondor_amd: batch repeated on the host-driven rounds (tree status %d, walk status %d: 1 = region "
                                         "beyond %d bins, 2 = non-finite z, 4 = ties beyond the record, 8 = more than %d segments, 16 = stack)\n",
                                 h[3], h[6], CJ_MAXLEN, TREE_SEGS);
                     // rare (non-finite region, tie overflow, deep recursion): the whole batch again with
                     // host-driven rounds -- the same results by construction, one batch time lost
-                    ts.no_tree = true;
-                    rc = test_batch_body(ctx, stream, ref, counts, Ns, threshold, min_ref_bins, repeats, min_effect, sel,
-                                         max_n, max_calls, results_z, results_r, results_cwz, calls, n_calls, asdef, lat_rounds);
-                    ts.no_tree = false;
-                    return rc;
+                    status = BatchStatus::tree_gave_up;
+                    return WC_OK;
                 }
-                WC_CHECK(h[4] <= ts.tree_seg_cap, WC_E_LIMIT, "stouffer: more than max_calls=%d segments per region", max_calls);
+                WC_CHECK(h[4] <= seg.seg_bound, WC_E_LIMIT, "stouffer: more than max_calls=%d segments per region", max_calls);
             }
-            WC_CHECK(!*overflow, WC_E_LIMIT, "test: a sample has more than max_calls=%d calls", max_calls);
-            if (getenv("WC_TEST_VERBOSE") && ts.misc2.p && repeats > 0 && repeats < 16) {
+            WC_CHECK(!hs->call_overflow, WC_E_LIMIT, "test: a sample has more than max_calls=%d calls", max_calls);
+            if (sw.verbose && ts.misc2.p && repeats > 0 && repeats < 16) {
                 // the (bin, sample) pairs every repeat had queued: [0] the first repeat's threshold hits (tiled kernel), [it] the pairs repeat it + 1 recomputed
                 int pc[18];
                 if (hipMemcpy(pc, ts.misc2.p, sizeof(int) * (repeats + 2), hipMemcpyDeviceToHost) == hipSuccess) {
@@ -6727,7 +6718,7 @@ static int test_batch_body(wc_ctx *ctx, hipStream_t stream, const wc_reference *
                     fprintf(stderr, "\n");
                 }
             }
-            if (getenv("WC_TEST_VERBOSE") && ts.sd_fail.p && ref->B <= 65536 && ctx->side) {
+            if (sw.verbose && ts.sd_fail.p && ref->B <= 65536 && ctx->side) {
                 // how many samples the parallel stdDevAvg gave up on (the serial kernel computed them)
                 (void)hipStreamSynchronize(ctx->side);
                 std::vector<int> f((size_t)Ns);
@@ -6755,6 +6746,7 @@ int wc_test_batch_dev(wc_ctx *ctx, void *stream_, const wc_reference *ref, const
     WC_CHECK(n_sel == 0 || chromosomes_host, WC_E_ARG, "test: NULL chromosome list");
     hipStream_t stream = (hipStream_t)stream_;
     WC_HIP(hipSetDevice(ctx->device));
+    const TestSwitches sw = read_switches();
     TestState &ts = ctx->ts;
     const int64_t Ns = n_samples;
     int rc;
@@ -6781,14 +6773,28 @@ int wc_test_batch_dev(wc_ctx *ctx, void *stream_, const wc_reference *ref, const
     // recursions, too many queued pairs, a failed stdDevAvg assumption) is detected afterwards through
     // status words and the call is repeated on the general path.  The first call of a shape runs
     // eagerly (it sizes every workspace), the second one is captured, later ones replay.
-    constexpr int LAT_MAX_SAMPLES = 8, LAT_ROUNDS = 1;
-    const char *lat_env = getenv("WC_TEST_LATENCY_MODE");          // "0": general path for every call
+    constexpr int LAT_MAX_SAMPLES = 8;
     const bool lat = Ns <= LAT_MAX_SAMPLES && min_effect == 0.0 && n_sel > 0 && calls && n_calls && !ts.profile &&
-                     ref->k <= 128 && repeats >= 1 && max_n <= 2048 && ref->B * Ns < (1ll << 31) &&
-                     !(lat_env && lat_env[0] == '0');
-    if (!lat)
-        return test_batch_body(ctx, stream, ref, counts, Ns, threshold, min_ref_bins, repeats, min_effect, sel, max_n,
-                               max_calls, results_z, results_r, results_cwz, calls, n_calls, asdef, 0);
+                     ref->k <= 128 && repeats >= 1 && max_n <= 2048 && ref->B * Ns < (1ll << 31) && sw.latency;
+    auto body = [&](hipStream_t s, const BatchPlan &plan, BatchStatus &status) {
+        return test_batch_body(ctx, s, sw, plan, ref, counts, Ns, threshold, min_ref_bins, repeats, min_effect, sel, max_n,
+                               max_calls, results_z, results_r, results_cwz, calls, n_calls, asdef, status);
+    };
+    // The general path: the batch again with what the attempt before could not hold switched off (the late repeats'
+    // overflow is looked at first).  Each switch goes off once: three attempts at most.
+    auto general = [&]() -> int {
+        BatchPlan plan;
+        for (int attempt = 0; attempt < 3; ++attempt) {
+            BatchStatus status;
+            const int rc2 = body(stream, plan, status);
+            if (rc2 || status == BatchStatus::ok) return rc2;
+            (status == BatchStatus::tail_overflow ? plan.no_tail : plan.no_tree) = true;
+        }
+        wc::set_error("test: the batch did not complete in three attempts");
+        return WC_E_INTERNAL;
+    };
+    if (!lat) return general();
+    BatchStatus lat_status;          // (latency mode reports through HostStatus::lat_*, read below)
     std::vector<int64_t> key = {(int64_t)ref->serial, (int64_t)(intptr_t)counts, Ns, min_ref_bins, repeats, max_calls,
                                 (int64_t)(intptr_t)results_z, (int64_t)(intptr_t)results_r,
                                 (int64_t)(intptr_t)results_cwz, (int64_t)(intptr_t)calls, (int64_t)(intptr_t)n_calls,
@@ -6799,10 +6805,6 @@ int wc_test_batch_dev(wc_ctx *ctx, void *stream_, const wc_reference *ref, const
         key.push_back(tbits);
         for (int c : sel) key.push_back(c);
     }
-    auto fall_back = [&]() {
-        return test_batch_body(ctx, stream, ref, counts, Ns, threshold, min_ref_bins, repeats, min_effect, sel, max_n,
-                               max_calls, results_z, results_r, results_cwz, calls, n_calls, asdef, 0);
-    };
     if (ts.lat_exec && ts.lat_epoch != wc::realloc_epoch()) ts.lat_key.clear();   // a workspace moved since the capture
     if (key != ts.lat_key) {
         // new shape: drop the old graph, run eagerly once (reserves every buffer), capture next time
@@ -6825,23 +6827,22 @@ int wc_test_batch_dev(wc_ctx *ctx, void *stream_, const wc_reference *ref, const
         WC_HIP(hipStreamWaitEvent(ls, ctx->ev_lat_in, 0));
     }
     // "2": the latency kernels, launched one by one; a shape whose capture failed once stays there
-    const bool eager = (lat_env && lat_env[0] == '2') || key == ts.lat_fail_key;
+    const bool eager = sw.latency_eager || key == ts.lat_fail_key;
     if (!ts.lat_exec && ts.lat_warm && ts.lat_epoch != wc::realloc_epoch()) ts.lat_warm = false;   // workspaces moved: size them again
     if (!ts.lat_exec && ts.lat_warm && !eager) {
         hipGraph_t graph = nullptr;
         if (hipStreamBeginCapture(ls, hipStreamCaptureModeThreadLocal) != hipSuccess) {
             (void)hipGetLastError();
             ts.lat_fail_key = key;
-            return fall_back();
+            return general();
         }
-        rc = test_batch_body(ctx, ls, ref, counts, Ns, threshold, min_ref_bins, repeats, min_effect, sel, max_n,
-                             max_calls, results_z, results_r, results_cwz, calls, n_calls, asdef, LAT_ROUNDS);
+        rc = body(ls, BatchPlan{true}, lat_status);
         const hipError_t e = hipStreamEndCapture(ls, &graph);
         if (rc != WC_OK || e != hipSuccess || !graph) {
             if (graph) (void)hipGraphDestroy(graph);
             (void)hipGetLastError();
             ts.lat_fail_key = key;
-            return fall_back();
+            return general();
         }
         const hipError_t ei = hipGraphInstantiate(&ts.lat_exec, graph, nullptr, nullptr, 0);
         (void)hipGraphDestroy(graph);
@@ -6850,24 +6851,22 @@ int wc_test_batch_dev(wc_ctx *ctx, void *stream_, const wc_reference *ref, const
             ts.lat_exec = nullptr;
             ts.lat_fail_key = key;
             (void)hipGetLastError();
-            return fall_back();
+            return general();
         }
     }
     if (ts.lat_exec) {
         WC_HIP(hipGraphLaunch(ts.lat_exec, ls));
     } else {
-        if ((rc = test_batch_body(ctx, ls, ref, counts, Ns, threshold, min_ref_bins, repeats, min_effect, sel, max_n,
-                                  max_calls, results_z, results_r, results_cwz, calls, n_calls, asdef, LAT_ROUNDS)))
-            return rc;
+        if ((rc = body(ls, BatchPlan{true}, lat_status))) return rc;
         ts.lat_warm = true;
         ts.lat_epoch = wc::realloc_epoch();
     }
     WC_HIP(hipStreamSynchronize(ls));
-    const int *overflow = (const int *)ctx->pinned + 16, *cnt = (const int *)ctx->pinned + 24;
+    const HostStatus *hs = (const HostStatus *)ctx->pinned;
     // anything the latency kernels are not built for -> the general path computes the call again
-    // (non-finite region, tie overflow, deep stack: cnt[6]; many segments; many queued pairs)
-    if (cnt[6] || ((const int *)ctx->pinned)[32] || ((const int *)ctx->pinned)[33]) return fall_back();
-    WC_CHECK(!*overflow, WC_E_LIMIT, "test: a sample has more than max_calls=%d calls", max_calls);
+    // (non-finite region, tie overflow, deep stack: lat_counters[6]; many queued pairs; stdDevAvg's serial kernel)
+    if (hs->lat_counters[6] || hs->lat_tail_overflow || hs->lat_sd_fail) return general();
+    WC_CHECK(!hs->lat_call_overflow, WC_E_LIMIT, "test: a sample has more than max_calls=%d calls", max_calls);
     return WC_OK;
 }
 
