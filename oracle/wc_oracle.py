@@ -172,6 +172,28 @@ def get_reference(corrected, chrom_bins, chrom_bin_sums, select_ref_amount=100,
     return np.array(big_idx), np.array(big_dst)
 
 
+def oracle_rows(corrected, chrom_bins, chrom_bin_sums, select_ref_amount, rows):
+    """get_reference(..., fast=True) for the listed target rows only: (idx[len(rows), k], dst[len(rows), k]).
+
+    For matrices whose whole-matrix oracle is too dear (thousands of samples).  Each row sees the same
+    chromData = concatenate(rows before its chromosome, rows after it) as in get_reference, so layout
+    and summation order are numpy's own; tests/test_exactpath_cpu.py holds it against get_reference.
+    """
+    rows = [int(r) for r in rows]
+    out_idx = np.full((len(rows), select_ref_amount), SENTINEL_INDEX, dtype=np.int32)
+    out_dst = np.full((len(rows), select_ref_amount), SENTINEL_DISTANCE)
+    sums = np.asarray(chrom_bin_sums, dtype=np.int64)
+    chrom_data = {}
+    for n, row in enumerate(rows):
+        chrom = int(np.searchsorted(sums, row, side="right"))     # skips chromosomes without bins
+        if chrom not in chrom_data:
+            lo, hi = int(sums[chrom] - chrom_bins[chrom]), int(sums[chrom])
+            chrom_data[chrom] = np.concatenate((corrected[:lo, :], corrected[hi:, :]))
+        idx, dst = get_ref_for_bins_fast(select_ref_amount, row, row + 1, corrected, chrom_data[chrom])
+        out_idx[n], out_dst[n] = idx[0], dst[0]
+    return out_idx, out_dst
+
+
 # --------------------------------------------------------------------------
 # newref prep (upstream of the hot path; needed to drive the CLI end to end)
 # --------------------------------------------------------------------------
