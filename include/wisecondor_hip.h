@@ -227,6 +227,61 @@ int wc_newref_prep(wc_ctx *ctx, const int32_t *counts, int64_t n_samples, int64_
                    int64_t *masked_chrom_bins_out, int64_t *n_masked_out, double *masked_data_out,
                    double *corrected_t_out, double *pca_components_out, double *pca_mean_out);
 
+/* ---- convert: BAM -> binned sample ----------------------------------------- */
+#define WC_E_IO (-5)       /* a file could not be opened or read               */
+#define WC_E_FORMAT (-6)   /* a file is damaged or not of the expected format  */
+#define WC_CV_MAX_CHROM 256 /* chromosomes per wc_convert_reads call           */
+
+/*
+ * Native BAM reader (host only, no GPU; replaces pysam in convertBam, wisetools.py:134-155).  wc_bam_open reads the
+ * whole file: BGZF blocks inflated by n_threads threads (1..64), records walked by their block_size chain.  The handle
+ * then holds, until wc_bam_close:
+ *   wc_bam_info   out[0] references in the header, [1] placed records (refID >= 0), [2] mapped (refID >= 0, flag 0x4
+ *                 clear), [3] unmapped (flag 0x4 set), [4] no_coordinate (refID < 0), [5] bytes wc_bam_refs writes to
+ *                 names_out.  The three counts stand in for pysam's index statistics (no .bai is read); that mapping
+ *                 is not verified against pysam.
+ *   wc_bam_refs   names_out: the reference names in header order, each followed by '\n'; lengths_out [n_refs];
+ *                 offsets_out [n_refs + 1]: the placed records of reference r are [offsets[r], offsets[r+1]) of
+ *   wc_bam_pos    int32, the 0-based position field, and
+ *   wc_bam_mapq   uint8, of every placed record in file order (no flag filter).
+ * Errors (never a crash; wc_last_error has the text): WC_E_IO cannot open; WC_E_FORMAT bad magic, a damaged or
+ * truncated BGZF block, a record that overruns its block_size or the data (a missing EOF block is accepted);
+ * WC_E_ARG the file is not coordinate-sorted (positions decrease within a reference, or a reference's records are
+ * not contiguous in header order); WC_E_LIMIT more than 2^31 - 1 placed records.
+ */
+typedef struct wc_bam wc_bam;
+int wc_bam_open(const char *path, int n_threads, wc_bam **out);
+int wc_bam_info(const wc_bam *bam, int64_t out[8]);
+int wc_bam_refs(const wc_bam *bam, char *names_out, int64_t names_cap, int64_t *lengths_out, int64_t *offsets_out);
+const int32_t *wc_bam_pos(const wc_bam *bam);
+const uint8_t *wc_bam_mapq(const wc_bam *bam);
+void wc_bam_close(wc_bam *bam);
+
+/*
+ * The numeric part of convertBam (wisetools.py:116-217, as toolConvert calls it: mapq 1, demandPair False) for all
+ * chromosomes of one file in one call: duplicate removal, mapping-quality filter, the tower (RETRO) filter, binning.
+ *   pos, mapq       the reads of the processed chromosomes, concatenated in header order (device pointers for _dev)
+ *   read_offsets    HOST int64 [n_chrom + 1], read_offsets[0] == 0: chromosome c owns [read_offsets[c], [c+1])
+ *   bin_offsets     HOST int64 [n_chrom + 1], bin_offsets[0] == 0: its bins in counts_out (int(length / binsize + 1) each)
+ *   min_shift, threshold   -retdist / -retthres, any value (threshold < 0: no tower filter)
+ *   counts_out      int32 [bin_offsets[n_chrom]], zeroed by the call
+ *   stats_out       int64 [8]: [0] filter_rmdup [1] filter_mapq [2] pre_retro [3] post_retro [4] counted reads whose
+ *                   bin (int64)((double)pos / binsize) lies outside their chromosome's bins -- the status word: the
+ *                   reference raises IndexError there, the host form returns WC_E_ARG, nothing is written out of
+ *                   range -- [5] reads kept by the first two filters
+ * The first read of every chromosome is consumed uncounted and `larp` is carried from chromosome to chromosome on the
+ * device, as in the reference.  Where the reference dies (a chromosome without reads: StopIteration) the chromosome
+ * gets all-zero counts and leaves `larp` alone; a chromosome with one read likewise.  n_chrom <= WC_CV_MAX_CHROM,
+ * fewer than 2^31 - 4096 reads.  wc_convert_tile_reads: reads per workgroup of the kernels (their tile boundaries).
+ */
+int wc_convert_tile_reads(void);
+int wc_convert_reads_dev(wc_ctx *ctx, void *stream, const int32_t *pos, const uint8_t *mapq, const int64_t *read_offsets,
+                         int n_chrom, double binsize, int min_shift, int threshold, const int64_t *bin_offsets,
+                         int32_t *counts_out, int64_t *stats_out);
+int wc_convert_reads(wc_ctx *ctx, const int32_t *pos, const uint8_t *mapq, const int64_t *read_offsets, int n_chrom,
+                     double binsize, int min_shift, int threshold, const int64_t *bin_offsets, int32_t *counts_out,
+                     int64_t *stats_out);
+
 /* ---- test: per-reference state -------------------------------------------- */
 typedef struct wc_reference wc_reference;
 

@@ -47,6 +47,15 @@ SIGNATURES = {
     "wc_read_sample_lengths": (_i32, [_vp, _i32, _i32, _i32, _dbl, _vp, _vp, _vp]),
     "wc_write_test_results": (_i32, [_i32, _i32, _vp, _vp, _vp, _vp, _i64, _dbl, _i32, _dbl, _vp, _i32, _vp, _vp, _i64, _vp,
                                      _i32, _vp, _vp, _i32, _vp, _i32, _vp]),
+    "wc_bam_open": (_i32, [_c.c_char_p, _i32, _vp]),
+    "wc_bam_info": (_i32, [_vp, _vp]),
+    "wc_bam_refs": (_i32, [_vp, _vp, _i64, _vp, _vp]),
+    "wc_bam_pos": (_vp, [_vp]),
+    "wc_bam_mapq": (_vp, [_vp]),
+    "wc_bam_close": (None, [_vp]),
+    "wc_convert_tile_reads": (_i32, []),
+    "wc_convert_reads_dev": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _dbl, _i32, _i32, _vp, _vp, _vp]),
+    "wc_convert_reads": (_i32, [_vp, _vp, _vp, _vp, _i32, _dbl, _i32, _i32, _vp, _vp, _vp]),
     "wc_newref_prep_gram": (_i32, [_vp, _vp, _i64, _i64, _vp, _i32, _vp, _vp, _vp, _vp]),
     "wc_newref_prep_eig": (_i32, [_vp, _i32, _vp, _vp]),
     "wc_sym_eigh_leading_dev": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp]),
@@ -74,7 +83,7 @@ SIGNATURES = {
 
 SUM_PAIRWISE = 0
 SUM_SEQUENTIAL = 1
-E_ARG, E_HIP, E_LIMIT, E_INTERNAL = -1, -2, -3, -4     # WC_E_* of include/wisecondor_hip.h
+E_ARG, E_HIP, E_LIMIT, E_INTERNAL, E_IO, E_FORMAT = -1, -2, -3, -4, -5, -6     # WC_E_* of include/wisecondor_hip.h
 
 _lib = None
 
@@ -151,7 +160,7 @@ def _warn_if_two_hip_runtimes():
 def check(rc):
     if rc != 0:
         err = WisecondorHipError("wisecondor_hip error %d: %s" % (rc, load().wc_last_error().decode()))
-        err.code = rc          # one of E_ARG / E_HIP / E_LIMIT / E_INTERNAL
+        err.code = rc          # one of the E_* above
         raise err
 
 

@@ -1,0 +1,432 @@
+// `convert`: the numeric part of convertBam (wisetools.py:116-217) for one BAM file's reads, all chromosomes in one call.
+//
+// What the reference's per-read loop computes, restated (tests/convert_restated.py; the reads of a chromosome are
+// pos[ro[c] .. ro[c+1]), the first one is consumed uncounted by `sam_iter.next()`):
+//   prev[i]  = pos[i - 1], and for the second read of a chromosome `larp`: the position of the last read of the nearest
+//              earlier chromosome with at least two reads (-1 if none)
+//   dup[i]   = pos[i] == prev[i];   keep[i] = !dup[i] && mapq[i] >= 1
+//   k[]      = the kept positions in order; a run starts at the chromosome's first kept read and wherever
+//              k[j] - k[j-1] > min_shift; a run of L reads is counted iff threshold < 0 || L <= threshold
+//   counts[(int64)((double)pos / binsize)] += 1 for every counted read
+// Everything is integer, so the order of accumulation is free.  Order between workgroups comes from kernel boundaries
+// only (no workgroup waits for another one):
+//   k_cv_tables   larp per chromosome from the offsets table                               (1 workgroup)
+//   k_cv_flags    classes of CV_TILE reads per workgroup: kept count per tile, the filter counters
+//   k_cv_scan<0>  exclusive sum of the tile counts                                          (1 workgroup)
+//   k_cv_compact  kept positions -> kpos[], and the kept rank of every chromosome's first read -> koff[]
+//   k_cv_heads    run heads of a tile of kpos[]: the tile's first and last head
+//   k_cv_scan<1>, <2>  last head before / first head after every tile                       (1 workgroup each)
+//   k_cv_count    run start / end of every kept read -> run length -> bin -> histogram
+// Inside a tile everything is a wave ballot: reads are striped (round r, thread t -> tile_base + r * CV_BLOCK + t), so
+// a (round, wave) pair is a SEGMENT of 64 consecutive reads, ranks are popcounts below the lane and the nearest head
+// is a count of leading / trailing zeros of the head mask; 32 segment values per tile go through LDS.
+// Positions are sorted, so the lanes of a segment hit one or two bins: equal bins are matched within the wave and
+// one lane issues one atomicAdd per (segment, bin).
+#include "ctx.h"
+
+#include <limits.h>
+
+#define CV_BLOCK 256
+#define CV_ROUNDS 8
+#define CV_TILE (CV_BLOCK * CV_ROUNDS)      // reads per workgroup; exported by wc_convert_tile_reads()
+#define CV_SEGS (CV_TILE / 64)
+#define CV_SCAN_BLOCK 1024
+static_assert(CV_BLOCK == 256 && CV_SEGS == 32, "segment = (round, wave): 4 waves per round, 32 segments fit half a wave");
+
+namespace {
+
+// device image of the small tables (int32 each)
+struct CvTab {
+    int ro[WC_CV_MAX_CHROM + 1];      // first read of chromosome c; ro[n_chrom] = number of reads
+    int bo[WC_CV_MAX_CHROM + 1];      // first bin of chromosome c in counts_out
+    int larp[WC_CV_MAX_CHROM + 1];    // `prev` of the chromosome's second read
+    int koff[WC_CV_MAX_CHROM + 1];    // kept reads in front of chromosome c; koff[n_chrom] = kept reads in all
+};
+
+// largest c in [0, n] with tab[c] <= i (tab ascending, tab[0] <= i): with equal entries (empty chromosomes) the last
+__device__ __forceinline__ int cv_find(const int *tab, int n, int i) {
+    int lo = 0, hi = n + 1;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (tab[mid] <= i) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+__device__ __forceinline__ int cv_lane() { return (int)(threadIdx.x & 63); }
+
+// class of read i: 0 not a counted read (a chromosome's consumed first read, or past the end), 1 duplicate,
+// 2 mapping quality below 1, 3 kept; p = its position
+__device__ __forceinline__ int cv_class(const int32_t *__restrict__ pos, const uint8_t *__restrict__ mapq, const int *s_ro,
+                                        const int *s_larp, int n_chrom, int i, int n, int &p) {
+    p = 0;
+    if (i >= n) return 0;
+    const int c = cv_find(s_ro, n_chrom, i);
+    const int first = s_ro[c];
+    if (i == first) return 0;
+    p = pos[i];
+    const int prev = i == first + 1 ? s_larp[c] : pos[i - 1];
+    if (p == prev) return 1;
+    return mapq[i] < 1 ? 2 : 3;
+}
+
+__global__ void __launch_bounds__(CV_BLOCK) k_cv_tables(const int32_t *__restrict__ pos, CvTab *tab, int n_chrom) {
+    for (int cc = (int)threadIdx.x; cc <= n_chrom; cc += CV_BLOCK) {
+        int l = -1;
+        for (int e = cc - 1; e >= 0; --e) {
+            if (tab->ro[e + 1] - tab->ro[e] >= 2) {
+                l = pos[tab->ro[e + 1] - 1];
+                break;
+            }
+        }
+        tab->larp[cc] = l;
+    }
+}
+
+__device__ __forceinline__ void cv_load_tab(const int *src, int *dst, int n) {
+    for (int i = (int)threadIdx.x; i < n; i += CV_BLOCK) dst[i] = src[i];
+}
+
+__global__ void __launch_bounds__(CV_BLOCK) k_cv_flags(const int32_t *__restrict__ pos, const uint8_t *__restrict__ mapq,
+                                                      const CvTab *__restrict__ tab, int n_chrom, int n,
+                                                      int *__restrict__ tile_keep, unsigned long long *stats) {
+    __shared__ int s_ro[WC_CV_MAX_CHROM + 1], s_larp[WC_CV_MAX_CHROM + 1];
+    __shared__ int s_cnt[4];
+    cv_load_tab(tab->ro, s_ro, n_chrom + 1);
+    cv_load_tab(tab->larp, s_larp, n_chrom + 1);
+    if (threadIdx.x < 4) s_cnt[threadIdx.x] = 0;
+    wc_sync();
+    const int base = (int)blockIdx.x * CV_TILE;
+    int n_dup = 0, n_low = 0, n_keep = 0;          // wave-uniform: popcounts of ballots
+#pragma unroll
+    for (int r = 0; r < CV_ROUNDS; ++r) {
+        const int i = base + r * CV_BLOCK + (int)threadIdx.x;
+        int p;
+        const int cls = cv_class(pos, mapq, s_ro, s_larp, n_chrom, i, n, p);
+        n_dup += __popcll(__ballot(cls == 1));
+        n_low += __popcll(__ballot(cls == 2));
+        n_keep += __popcll(__ballot(cls == 3));
+    }
+    if (cv_lane() == 0) {
+        atomicAdd(&s_cnt[0], n_dup);
+        atomicAdd(&s_cnt[1], n_low);
+        atomicAdd(&s_cnt[2], n_keep);
+    }
+    wc_sync();
+    if (threadIdx.x == 0) {
+        tile_keep[blockIdx.x] = s_cnt[2];
+        if (s_cnt[0]) atomicAdd(&stats[0], (unsigned long long)s_cnt[0]);
+        if (s_cnt[1]) atomicAdd(&stats[1], (unsigned long long)s_cnt[1]);
+        // pre_retro: every read but the consumed first one of each chromosome
+        const int total = s_cnt[0] + s_cnt[1] + s_cnt[2];
+        if (total) atomicAdd(&stats[2], (unsigned long long)total);
+    }
+}
+
+// One workgroup walks `in` in chunks.  MODE 0: out[t] = sum of in[0 .. t), *total = the whole sum; MODE 1: out[t] = max of
+// in[0 .. t) (-1 when empty); MODE 2: out[t] = min of in(t .. n) (INT_MAX when empty).
+template <int MODE> __device__ __forceinline__ int cv_op(int a, int b) {
+    if (MODE == 0) return a + b;
+    if (MODE == 1) return a > b ? a : b;
+    return a < b ? a : b;
+}
+template <int MODE>
+__global__ void __launch_bounds__(CV_SCAN_BLOCK) k_cv_scan(const int *__restrict__ in, int n, int *__restrict__ out,
+                                                          int *total) {
+    __shared__ int s_wave[CV_SCAN_BLOCK / 64];
+    __shared__ int s_vals[CV_SCAN_BLOCK];
+    const int ident = MODE == 0 ? 0 : (MODE == 1 ? -1 : INT_MAX);
+    const int tid = (int)threadIdx.x, lane = cv_lane(), w = tid >> 6;
+    int carry = ident;
+    for (int base = 0; base < n; base += CV_SCAN_BLOCK) {
+        const int k = base + tid;
+        const int idx = MODE == 2 ? n - 1 - k : k;
+        int v = k < n ? in[idx] : ident;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const int t = __shfl_up(v, d);
+            if (lane >= d) v = cv_op<MODE>(v, t);
+        }
+        if (lane == 63) s_wave[w] = v;
+        wc_sync();
+        int pre = ident;
+        for (int g = 0; g < w; ++g) pre = cv_op<MODE>(pre, s_wave[g]);
+        v = cv_op<MODE>(v, pre);
+        s_vals[tid] = v;
+        wc_sync();
+        const int excl = cv_op<MODE>(tid ? s_vals[tid - 1] : ident, carry);
+        if (k < n) out[idx] = excl;
+        carry = cv_op<MODE>(carry, s_vals[CV_SCAN_BLOCK - 1]);
+        wc_sync();                                  // the next chunk overwrites s_wave / s_vals
+    }
+    if (MODE == 0 && tid == 0 && total) *total = carry;
+}
+
+// exclusive prefix of the 32 segment values of a tile by one whole wave (lanes 0..31 hold a segment each), seeded with
+// `seed`; REVERSE: suffix (the segments behind the lane's own)
+template <int MODE, bool REVERSE> __device__ __forceinline__ void cv_seg_scan(const int *s_in, int *s_out, int seed) {
+    const int lane = cv_lane();
+    const int ident = MODE == 0 ? 0 : (MODE == 1 ? -1 : INT_MAX);
+    const int at = (REVERSE ? CV_SEGS - 1 - lane : lane) & (CV_SEGS - 1);
+    int v = lane < CV_SEGS ? s_in[at] : ident;
+#pragma unroll
+    for (int d = 1; d < CV_SEGS; d <<= 1) {
+        const int t = __shfl_up(v, d);
+        if (lane >= d) v = cv_op<MODE>(v, t);
+    }
+    int excl = __shfl_up(v, 1);
+    if (lane == 0) excl = ident;
+    if (lane < CV_SEGS) s_out[at] = cv_op<MODE>(excl, seed);
+}
+
+__global__ void __launch_bounds__(CV_BLOCK) k_cv_compact(const int32_t *__restrict__ pos, const uint8_t *__restrict__ mapq,
+                                                        CvTab *tab, int n_chrom, int n, const int *__restrict__ tile_off,
+                                                        int32_t *__restrict__ kpos) {
+    __shared__ int s_ro[WC_CV_MAX_CHROM + 1], s_larp[WC_CV_MAX_CHROM + 1];
+    __shared__ int s_seg[CV_SEGS], s_segoff[CV_SEGS];
+    cv_load_tab(tab->ro, s_ro, n_chrom + 1);
+    cv_load_tab(tab->larp, s_larp, n_chrom + 1);
+    wc_sync();
+    const int base = (int)blockIdx.x * CV_TILE;
+    const int lane = cv_lane(), w = (int)threadIdx.x >> 6;
+    int p[CV_ROUNDS];
+    unsigned long long mask[CV_ROUNDS];
+#pragma unroll
+    for (int r = 0; r < CV_ROUNDS; ++r) {
+        const int i = base + r * CV_BLOCK + (int)threadIdx.x;
+        const int cls = cv_class(pos, mapq, s_ro, s_larp, n_chrom, i, n, p[r]);
+        mask[r] = __ballot(cls == 3);
+        if (lane == 0) s_seg[r * (CV_BLOCK / 64) + w] = __popcll(mask[r]);
+    }
+    wc_sync();
+    if (w == 0) cv_seg_scan<0, false>(s_seg, s_segoff, tile_off[blockIdx.x]);
+    wc_sync();
+    const unsigned long long below = (1ull << lane) - 1ull;
+#pragma unroll
+    for (int r = 0; r < CV_ROUNDS; ++r) {
+        const int i = base + r * CV_BLOCK + (int)threadIdx.x;
+        const int rank = s_segoff[r * (CV_BLOCK / 64) + w] + __popcll(mask[r] & below);     // kept reads in front of i
+        if ((mask[r] >> lane) & 1ull) kpos[rank] = p[r];
+        if (i <= n) {
+            // i opens a chromosome (or several empty ones and one more; i == n: the end of the table)
+            for (int c = cv_find(s_ro, n_chrom, i); c >= 0 && s_ro[c] == i; --c) tab->koff[c] = rank;
+        }
+    }
+}
+
+// is kept read j (< the number of kept reads) the head of a run?  c = its chromosome
+__device__ __forceinline__ bool cv_head(const int32_t *__restrict__ kpos, const int *s_koff, int n_chrom, int j, int min_shift,
+                                        int &c) {
+    c = cv_find(s_koff, n_chrom, j);
+    if (j == s_koff[c]) return true;
+    return (long long)kpos[j] - (long long)kpos[j - 1] > (long long)min_shift;
+}
+
+__global__ void __launch_bounds__(CV_BLOCK) k_cv_heads(const int32_t *__restrict__ kpos, const CvTab *__restrict__ tab,
+                                                      int n_chrom, int min_shift, int *__restrict__ tile_last,
+                                                      int *__restrict__ tile_first) {
+    __shared__ int s_koff[WC_CV_MAX_CHROM + 1];
+    __shared__ int s_last[CV_SEGS], s_first[CV_SEGS];
+    cv_load_tab(tab->koff, s_koff, n_chrom + 1);
+    wc_sync();
+    const int m = s_koff[n_chrom];
+    const int base = (int)blockIdx.x * CV_TILE;
+    const int lane = cv_lane(), w = (int)threadIdx.x >> 6;
+#pragma unroll
+    for (int r = 0; r < CV_ROUNDS; ++r) {
+        const int seg_base = base + r * CV_BLOCK + w * 64;
+        const int j = seg_base + lane;
+        int c = 0;
+        const bool head = j < m && cv_head(kpos, s_koff, n_chrom, j, min_shift, c);
+        const unsigned long long mk = __ballot(head);
+        if (lane == 0) {
+            s_last[r * (CV_BLOCK / 64) + w] = mk ? seg_base + 63 - __clzll((long long)mk) : -1;
+            s_first[r * (CV_BLOCK / 64) + w] = mk ? seg_base + __ffsll((long long)mk) - 1 : INT_MAX;
+        }
+    }
+    wc_sync();
+    if (threadIdx.x == 0) {
+        int last = -1, first = INT_MAX;
+        for (int g = 0; g < CV_SEGS; ++g) {
+            last = s_last[g] > last ? s_last[g] : last;
+            first = s_first[g] < first ? s_first[g] : first;
+        }
+        tile_last[blockIdx.x] = last;
+        tile_first[blockIdx.x] = first;
+    }
+}
+
+__global__ void __launch_bounds__(CV_BLOCK) k_cv_count(const int32_t *__restrict__ kpos, const CvTab *__restrict__ tab,
+                                                      int n_chrom, int min_shift, int threshold, double binsize,
+                                                      const int *__restrict__ carry_last, const int *__restrict__ carry_next,
+                                                      int32_t *counts, unsigned long long *stats) {
+    __shared__ int s_koff[WC_CV_MAX_CHROM + 1], s_bo[WC_CV_MAX_CHROM + 1];
+    __shared__ int s_last[CV_SEGS], s_first[CV_SEGS], s_before[CV_SEGS], s_after[CV_SEGS];
+    __shared__ int s_cnt[2];
+    cv_load_tab(tab->koff, s_koff, n_chrom + 1);
+    cv_load_tab(tab->bo, s_bo, n_chrom + 1);
+    if (threadIdx.x < 2) s_cnt[threadIdx.x] = 0;
+    wc_sync();
+    const int m = s_koff[n_chrom];
+    const int base = (int)blockIdx.x * CV_TILE;
+    if (base >= m) return;                              // (the whole workgroup: m is uniform)
+    const int lane = cv_lane(), w = (int)threadIdx.x >> 6;
+    unsigned long long mask[CV_ROUNDS];
+    int chrom[CV_ROUNDS];
+#pragma unroll
+    for (int r = 0; r < CV_ROUNDS; ++r) {
+        const int seg_base = base + r * CV_BLOCK + w * 64;
+        const int j = seg_base + lane;
+        chrom[r] = 0;
+        const bool head = j < m && cv_head(kpos, s_koff, n_chrom, j, min_shift, chrom[r]);
+        mask[r] = __ballot(head);
+        if (lane == 0) {
+            s_last[r * (CV_BLOCK / 64) + w] = mask[r] ? seg_base + 63 - __clzll((long long)mask[r]) : -1;
+            s_first[r * (CV_BLOCK / 64) + w] = mask[r] ? seg_base + __ffsll((long long)mask[r]) - 1 : INT_MAX;
+        }
+    }
+    wc_sync();
+    if (w == 0) cv_seg_scan<1, false>(s_last, s_before, carry_last[blockIdx.x]);
+    if (w == 1) cv_seg_scan<2, true>(s_first, s_after, carry_next[blockIdx.x]);
+    wc_sync();
+    const unsigned long long upto = lane == 63 ? ~0ull : (2ull << lane) - 1ull;     // this lane and the ones below
+    int n_counted = 0, n_outside = 0;
+#pragma unroll
+    for (int r = 0; r < CV_ROUNDS; ++r) {
+        const int seg = r * (CV_BLOCK / 64) + w;
+        const int seg_base = base + r * CV_BLOCK + w * 64;
+        const int j = seg_base + lane;
+        const unsigned long long lo = mask[r] & upto, hi = mask[r] & ~upto;
+        const int start = lo ? seg_base + 63 - __clzll((long long)lo) : s_before[seg];
+        int end = hi ? seg_base + __ffsll((long long)hi) - 1 : s_after[seg];
+        end = end < m ? end : m;
+        int key = -1;                                   // the read's bin in counts[], -1: nothing to add
+        bool outside = false;
+        if (j < m && (threshold < 0 || end - start <= threshold)) {
+            const int c = chrom[r];
+            const double q = (double)kpos[j] / binsize;
+            const int n_bins = s_bo[c + 1] - s_bo[c];
+            if (q >= 0.0 && q < (double)n_bins) key = s_bo[c] + (int)(long long)q;
+            else if (q > -1.0 && q < 0.0 && n_bins > 0) key = s_bo[c];      // int() truncates towards zero
+            else outside = true;
+        }
+        n_outside += __popcll(__ballot(outside));
+        unsigned long long todo = __ballot(key >= 0);
+        n_counted += __popcll(todo);
+        while (todo) {                                  // (wave-uniform) one atomic per distinct bin of the segment
+            const int leader = __ffsll((long long)todo) - 1;
+            const int b = __shfl(key, leader);
+            const unsigned long long same = __ballot(key == b);
+            if (lane == leader) atomicAdd(&counts[b], (int)__popcll(same));
+            todo &= ~same;
+        }
+    }
+    if (lane == 0) {
+        atomicAdd(&s_cnt[0], n_counted);
+        atomicAdd(&s_cnt[1], n_outside);
+    }
+    wc_sync();
+    if (threadIdx.x == 0) {
+        if (s_cnt[0]) atomicAdd(&stats[3], (unsigned long long)s_cnt[0]);
+        if (s_cnt[1]) atomicAdd(&stats[4], (unsigned long long)s_cnt[1]);
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int wc_convert_tile_reads(void) { return CV_TILE; }
+
+int wc_convert_reads_dev(wc_ctx *ctx, void *stream_, const int32_t *pos, const uint8_t *mapq, const int64_t *read_offsets,
+                         int n_chrom, double binsize, int min_shift, int threshold, const int64_t *bin_offsets,
+                         int32_t *counts_out, int64_t *stats_out) {
+    WC_CHECK(ctx && read_offsets && bin_offsets && counts_out && stats_out, WC_E_ARG, "convert: NULL argument");
+    WC_CHECK(n_chrom >= 1 && n_chrom <= WC_CV_MAX_CHROM, WC_E_LIMIT, "convert: %d chromosomes (1..%d supported)", n_chrom,
+             WC_CV_MAX_CHROM);
+    WC_CHECK(binsize > 0.0 && binsize <= DBL_MAX, WC_E_ARG, "convert: bin size %g is not a positive finite number", binsize);
+    WC_CHECK(read_offsets[0] == 0 && bin_offsets[0] == 0, WC_E_ARG, "convert: the offset tables must start at 0");
+    for (int c = 0; c < n_chrom; ++c)
+        WC_CHECK(read_offsets[c + 1] >= read_offsets[c] && bin_offsets[c + 1] >= bin_offsets[c], WC_E_ARG,
+                 "convert: offsets of chromosome %d decrease", c);
+    const int64_t n64 = read_offsets[n_chrom], bins64 = bin_offsets[n_chrom];
+    WC_CHECK(n64 <= (int64_t)INT_MAX - 2 * CV_TILE, WC_E_LIMIT, "convert: %lld reads in one call (limit %d)", (long long)n64,
+             INT_MAX - 2 * CV_TILE);
+    WC_CHECK(bins64 <= (int64_t)INT_MAX, WC_E_LIMIT, "convert: %lld bins in one call", (long long)bins64);
+    WC_CHECK(n64 == 0 || (pos && mapq), WC_E_ARG, "convert: NULL read arrays");
+    WC_HIP(hipSetDevice(ctx->device));
+    hipStream_t stream = (hipStream_t)stream_;
+    ConvertState &cv = ctx->cv;
+    const int n = (int)n64;
+    const int n_tiles = (n + 1 + CV_TILE - 1) / CV_TILE;         // read n is the end marker that closes the koff table
+    int rc;
+    if ((rc = cv.tab.reserve(sizeof(CvTab)))) return rc;
+    if ((rc = cv.tiles.reserve(sizeof(int) * 6 * (size_t)n_tiles))) return rc;
+    if ((rc = cv.kpos.reserve(sizeof(int32_t) * ((size_t)n + 1)))) return rc;
+    CvTab *tab = cv.tab.as<CvTab>();
+    int *tile_keep = cv.tiles.as<int>(), *tile_off = tile_keep + n_tiles, *tile_last = tile_off + n_tiles;
+    int *tile_first = tile_last + n_tiles, *carry_last = tile_first + n_tiles, *carry_next = carry_last + n_tiles;
+    std::vector<int> host(2 * (WC_CV_MAX_CHROM + 1), 0);
+    for (int c = 0; c <= n_chrom; ++c) {
+        host[c] = (int)read_offsets[c];
+        host[WC_CV_MAX_CHROM + 1 + c] = (int)bin_offsets[c];
+    }
+    WC_HIP(hipMemcpyAsync(tab, host.data(), sizeof(int) * host.size(), hipMemcpyHostToDevice, stream));   // ro, bo
+    WC_HIP(hipMemsetAsync(stats_out, 0, sizeof(int64_t) * 8, stream));
+    if (bins64) WC_HIP(hipMemsetAsync(counts_out, 0, sizeof(int32_t) * (size_t)bins64, stream));
+    unsigned long long *stats = reinterpret_cast<unsigned long long *>(stats_out);
+    hipLaunchKernelGGL(k_cv_tables, dim3(1), dim3(CV_BLOCK), 0, stream, pos, tab, n_chrom);
+    hipLaunchKernelGGL(k_cv_flags, dim3(n_tiles), dim3(CV_BLOCK), 0, stream, pos, mapq, (const CvTab *)tab, n_chrom, n,
+                       tile_keep, stats);
+    hipLaunchKernelGGL(k_cv_scan<0>, dim3(1), dim3(CV_SCAN_BLOCK), 0, stream, (const int *)tile_keep, n_tiles, tile_off,
+                       reinterpret_cast<int *>(stats + 5));       // [5]: kept reads (low word; the high word is zero)
+    hipLaunchKernelGGL(k_cv_compact, dim3(n_tiles), dim3(CV_BLOCK), 0, stream, pos, mapq, tab, n_chrom, n,
+                       (const int *)tile_off, cv.kpos.as<int32_t>());
+    hipLaunchKernelGGL(k_cv_heads, dim3(n_tiles), dim3(CV_BLOCK), 0, stream, (const int32_t *)cv.kpos.as<int32_t>(),
+                       (const CvTab *)tab, n_chrom, min_shift, tile_last, tile_first);
+    hipLaunchKernelGGL(k_cv_scan<1>, dim3(1), dim3(CV_SCAN_BLOCK), 0, stream, (const int *)tile_last, n_tiles, carry_last,
+                       (int *)nullptr);
+    hipLaunchKernelGGL(k_cv_scan<2>, dim3(1), dim3(CV_SCAN_BLOCK), 0, stream, (const int *)tile_first, n_tiles, carry_next,
+                       (int *)nullptr);
+    hipLaunchKernelGGL(k_cv_count, dim3(n_tiles), dim3(CV_BLOCK), 0, stream, (const int32_t *)cv.kpos.as<int32_t>(),
+                       (const CvTab *)tab, n_chrom, min_shift, threshold, binsize, (const int *)carry_last,
+                       (const int *)carry_next, counts_out, stats);
+    WC_HIP(hipGetLastError());
+    return WC_OK;
+}
+
+int wc_convert_reads(wc_ctx *ctx, const int32_t *pos, const uint8_t *mapq, const int64_t *read_offsets, int n_chrom,
+                     double binsize, int min_shift, int threshold, const int64_t *bin_offsets, int32_t *counts_out,
+                     int64_t *stats_out) {
+    WC_CHECK(ctx && read_offsets && bin_offsets && counts_out && stats_out, WC_E_ARG, "convert: NULL argument");
+    WC_CHECK(n_chrom >= 1 && n_chrom <= WC_CV_MAX_CHROM, WC_E_LIMIT, "convert: %d chromosomes (1..%d supported)", n_chrom,
+             WC_CV_MAX_CHROM);
+    const int64_t n = read_offsets[n_chrom], bins = bin_offsets[n_chrom];
+    WC_CHECK(n >= 0 && bins >= 0 && n <= (int64_t)INT_MAX && bins <= (int64_t)INT_MAX, WC_E_LIMIT,
+             "convert: %lld reads, %lld bins in one call", (long long)n, (long long)bins);
+    WC_CHECK(n == 0 || (pos && mapq), WC_E_ARG, "convert: NULL read arrays");
+    WC_HIP(hipSetDevice(ctx->device));
+    int rc;
+    if ((rc = ctx->tmp_a.reserve(sizeof(int32_t) * (size_t)(n + 1)))) return rc;
+    if ((rc = ctx->tmp_b.reserve((size_t)n + 1))) return rc;
+    if ((rc = ctx->tmp_c.reserve(sizeof(int32_t) * (size_t)(bins + 1) + 64))) return rc;
+    int64_t *stats_dev = ctx->tmp_c.as<int64_t>();               // 8 words, then the counts
+    int32_t *counts_dev = reinterpret_cast<int32_t *>(stats_dev + 8);
+    if (n) {
+        WC_HIP(hipMemcpy(ctx->tmp_a.p, pos, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice));
+        WC_HIP(hipMemcpy(ctx->tmp_b.p, mapq, (size_t)n, hipMemcpyHostToDevice));
+    }
+    rc = wc_convert_reads_dev(ctx, nullptr, ctx->tmp_a.as<int32_t>(), ctx->tmp_b.as<uint8_t>(), read_offsets, n_chrom, binsize,
+                              min_shift, threshold, bin_offsets, counts_dev, stats_dev);
+    if (rc) return rc;
+    WC_HIP(hipDeviceSynchronize());
+    WC_HIP(hipMemcpy(stats_out, stats_dev, sizeof(int64_t) * 8, hipMemcpyDeviceToHost));
+    if (bins) WC_HIP(hipMemcpy(counts_out, counts_dev, sizeof(int32_t) * (size_t)bins, hipMemcpyDeviceToHost));
+    WC_CHECK(stats_out[4] == 0, WC_E_ARG,
+             "convert: %lld read(s) lie beyond their chromosome's last bin (a position past the header's length)",
+             (long long)stats_out[4]);
+    return WC_OK;
+}
+
+}  // extern "C"

@@ -78,9 +78,15 @@ struct PrepState {
     wc::DevBuf eig_ws;          // eigh.hip: working copy, reflectors, tridiagonal, vectors
 };
 
+// workspaces of `convert` (convert.hip): the small tables, the per-tile words, the kept positions
+struct ConvertState {
+    wc::DevBuf tab, tiles, kpos;
+};
+
 struct wc_ctx {
     int device = 0;
     PrepState prep;
+    ConvertState cv;
     NewrefState nr;
     TestState ts;
     wc::DevBuf tmp_a, tmp_b, tmp_c, tmp_d;  // host-pointer API staging
@@ -132,7 +138,8 @@ struct wc_ctx {
                 &ts.sel, &ts.res_z, &ts.res_r, &ts.cwz, &ts.calls, &ts.n_calls, &ts.zs, &ts.rs2, &ts.ns2, &ts.sds, &ts.sub, &ts.tmin, &ts.tmax, &ts.tmin2, &ts.tmax2, &ts.cell_state, &ts.cell_rec, &ts.prefix, &ts.reg_abs,
                 &ts.reg_flag, &ts.rs, &ts.jobs_a, &ts.jobs_b, &ts.job_cnt, &ts.partial, &ts.cbound, &ts.cuts, &ts.job_res, &ts.hot,
                 &ts.cand, &ts.cand_cnt, &ts.seg, &ts.out_val, &ts.out_x, &ts.out_y, &ts.out_n,
-                &ts.whole, &ts.effect, &ts.misc, &ts.misc2, &ts.reduce_tmp, &ts.win_bits, &ts.bit_off, &ts.pairs_a, &ts.pairs_b, &ts.cut_vals, &ts.prof_work, &ts.sd_fail, &ts.walk_hot, &prep.eig_ws};
+                &ts.whole, &ts.effect, &ts.misc, &ts.misc2, &ts.reduce_tmp, &ts.win_bits, &ts.bit_off, &ts.pairs_a, &ts.pairs_b, &ts.cut_vals, &ts.prof_work, &ts.sd_fail, &ts.walk_hot, &prep.eig_ws,
+                &cv.tab, &cv.tiles, &cv.kpos};
     }
 };
 

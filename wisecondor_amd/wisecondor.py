@@ -1,4 +1,4 @@
-"""Command line of the MI355X build: the `newref*` and `test` sub-commands of WISECONDOR.
+"""Command line of the MI355X build: the `convert`, `newref*`, `test` and `report` sub-commands of WISECONDOR.
 
 Contract (taken from the upstream CLI at
 wisecondor.py:345-521): same sub-command names, positional arguments, single-dash
@@ -8,8 +8,9 @@ successful merge); same `.npz` keys and dtypes; `test` ends with exit status 0.
 Everything numeric runs on the GPU through libwisecondor_hip.so (no CPU path).
 
 Build-only additions, all off by default: `-gpus N` on `newref` / `testbatch`
-(one process per GPU), the `testbatch` sub-command (many samples per GPU batch).
-`convert`, `plot` and `report` are not part of this build.
+(one process per GPU), the `testbatch` sub-command (many samples per GPU batch), the `convertbatch`
+sub-command (many BAM files, reading file i + 1 while file i is on the GPU and file i - 1 is written).
+`plot` is not part of this build.
 """
 import argparse
 import copy
@@ -65,6 +66,113 @@ def _as_object_array(arrays):
     for at, item in enumerate(arrays):
         boxed[at] = item
     return boxed
+
+
+# --------------------------------------------------------------------- convert ----
+def writeConvertOutput(outfile, args, converted, qual_info):
+    """The `convert` output file (wisecondor.py:22-26; keys of SURVEY.md App. B)."""
+    write_npz(outfile, arguments=vars(args), runtime=getRuntime(), sample=converted, quality=qual_info)
+
+
+def toolConvert(args):
+    """`convert infile outfile`: BAM -> binned, filtered sample (wisecondor.py:20-27)."""
+    converted, qual_info = wt.convertBam(args.infile, binsize=args.binsize, minShift=args.retdist,
+                                         threshold=args.retthres)
+    writeConvertOutput(args.outfile, args, converted, qual_info)
+    print('Conversion finished')
+
+
+def convert_output_names(paths, outdir):
+    """<outdir>/<leaf without .bam>.npz per input; two inputs with the same leaf name are an error up front."""
+    names, seen = [], {}
+    for path in paths:
+        leaf = os.path.basename(path)
+        leaf = leaf[:-4] if leaf.lower().endswith('.bam') else leaf
+        if leaf in seen:
+            raise ValueError('convertbatch: %s and %s would both be written to %s.npz; rename one of them'
+                             % (seen[leaf], path, leaf))
+        seen[leaf] = path
+        names.append(os.path.join(outdir, leaf + '.npz'))
+    return names
+
+
+def toolConvertBatch(args):
+    """`convertbatch infiles... outdir` (build-only): the same file per BAM as one `convert` each.  A reader thread
+    opens (reads, inflates, parses: native code, no GIL) file i + 1 and a writer thread stores file i - 1 while
+    file i is on the GPU."""
+    import argparse
+    import concurrent.futures
+    outs = convert_output_names(args.infiles, args.outdir)
+    os.makedirs(args.outdir, exist_ok=True)
+    began = time.time()
+    reader = concurrent.futures.ThreadPoolExecutor(max_workers=1)
+    writer = concurrent.futures.ThreadPoolExecutor(max_workers=1)
+    written = []
+    try:
+        ahead = reader.submit(wt.BamReads, args.infiles[0], args.io)
+        for i, (path, out) in enumerate(zip(args.infiles, outs)):
+            bam = ahead.result()
+            if i + 1 < len(args.infiles):
+                ahead = reader.submit(wt.BamReads, args.infiles[i + 1], args.io)
+            try:
+                converted, qual_info = wt.convertBamReads(bam, args.binsize, args.retdist, args.retthres)
+            finally:
+                bam.close()
+            # what one `convert` call would record: its own infile / outfile, not the batch's list
+            one = argparse.Namespace(**{k: v for k, v in vars(args).items() if k not in ('infiles', 'outdir', 'io', 'func')})
+            one.infile, one.outfile, one.func = path, out, toolConvert
+            written.append(writer.submit(writeConvertOutput, out, one, converted, qual_info))
+        for job in written:
+            job.result()
+    finally:
+        reader.shutdown(wait=True)
+        writer.shutdown(wait=True)
+    print('%d BAM files converted in %.2f s' % (len(outs), time.time() - began))
+
+
+# ---------------------------------------------------------------------- report ----
+def toolReport(args):
+    """`report testfile resultfile`: the text summary of a `convert` file and a `test` file, line for line what
+    wisecondor.py:304-342 prints."""
+    test_file = _open_npz(args.testfile)
+    result_file = _open_npz(args.resultfile)
+    binSize = result_file['binsize'].item()
+
+    print('\n# Arguments used in convert: #')
+    test_args = test_file['arguments'].item()
+    for key in test_args:
+        print(key, '=', test_args[key])
+    print('\n# Arguments used in test: #')
+    result_args = result_file['arguments'].item()
+    for key in result_args:
+        print(key, '=', result_args[key])
+
+    quality = test_file['quality'].item()
+    print('\n# BAM information: #')
+    print('Reads mapped:  \t', quality['mapped'])
+    print('Reads unmapped:\t', quality['unmapped'])
+    print('Reads nocoord: \t', quality['no_coordinate'])
+    print('Reads rmdup:   \t', quality['filter_rmdup'])
+    print('Reads lowqual: \t', quality['filter_mapq'])
+
+    reads_in = quality['pre_retro'] - quality['no_coordinate'] + quality['filter_rmdup'] + quality['filter_mapq']
+    print('\n# RETRO filtering: #')
+    print('Reads in:     \t', reads_in)
+    print('Reads removed:\t', reads_in - quality['post_retro'])
+    print('Reads out:    \t', quality['post_retro'])
+
+    print('\n# Z-Score checks: #')
+    print('Z-Score used:\t', "{:.2f}".format(result_file['threshold_z'].item()))
+    print('AvgStdDev:   \t', "{:.2f}".format(result_file['asdef'] * 100) + '%')
+    print('AvgAllStdDev:\t', "{:.2f}".format(result_file['aasdef'] * 100) + '%')
+
+    print('\n# Test results: #')
+    print('z-score\teffect\tmbsize\tlocation')
+    for result in result_file['results_calls']:
+        if args.mineffect < abs(result[4] * 100):
+            print("{:.2f}\t{:.2f}\t{:.2f}\t{:.0f}:{:.0f}-{:.0f}".format(
+                result[3], result[4] * 100, (result[2] - result[1] + 1) * binSize / 1e6, result[0],
+                result[1] * binSize, (result[2] + 1) * binSize))
 
 
 # --------------------------------------------------------------- newref: files ----
@@ -372,7 +480,7 @@ def toolTestBatch(args):
 
 # ---------------------------------------------------------------------- parser ----
 def _not_in_this_build(args):
-    print('ERROR: this sub-command is not part of the MI355X build (newref*, test only); '
+    print('ERROR: this sub-command is not part of the MI355X build (convert, newref*, test, report only); '
           'run it with the upstream wisecondor.py')
     sys.exit(2)
 
@@ -403,10 +511,40 @@ def buildParser():
         description='WISECONDOR newref / test on AMD MI355X (drop-in for the upstream sub-commands)')
     sub = parser.add_subparsers()
 
-    for name in ('convert', 'plot', 'report'):
-        p = sub.add_parser(name, description='not provided by this build')
-        p.add_argument('rest', nargs=argparse.REMAINDER)
-        p.set_defaults(func=_not_in_this_build)
+    p = sub.add_parser('plot', description='not provided by this build')
+    p.add_argument('rest', nargs=argparse.REMAINDER)
+    p.set_defaults(func=_not_in_this_build)
+
+    #: the options `convert` and `convertbatch` share (upstream wisecondor.py:359-367)
+    convert_options = (
+        ('-binsize', dict(type=float, default=1e6, help='Size per bin in bp')),
+        ('-retdist', dict(type=int, default=4,
+                          help='Maximum amount of base pairs difference between sequential reads to consider them '
+                               'part of the same tower')),
+        ('-retthres', dict(type=int, default=4,
+                           help='Threshold for when a group of reads is considered a tower and will be removed')),
+    )
+    p = sub.add_parser('convert', description='Convert and filter a bam file to an npz')
+    p.add_argument('infile', type=str, help='Bam input file for conversion')
+    p.add_argument('outfile', type=str, help='File to write binned information to')
+    for flag, settings in convert_options:
+        p.add_argument(flag, **settings)
+    p.set_defaults(func=toolConvert)
+
+    p = sub.add_parser('convertbatch', description='convert for many bam files, file work overlapped (build-only)')
+    p.add_argument('infiles', type=str, nargs='+', help='Bam input files')
+    p.add_argument('outdir', type=str, help='directory receiving <name>.npz per bam file')
+    p.add_argument('-io', type=int, default=8, help='threads that inflate a bam file')
+    for flag, settings in convert_options:
+        p.add_argument(flag, **settings)
+    p.set_defaults(func=toolConvertBatch)
+
+    p = sub.add_parser('report', description='Print the text summary of a converted sample and its test result')
+    p.add_argument('testfile', type=str, help='converted sample (.npz) the test was run on')
+    p.add_argument('resultfile', type=str, help='result file written by test')
+    p.add_argument('-mineffect', type=float, default=1.5,
+                   help='Minimal percentual change in read depth of a call to report')
+    p.set_defaults(func=toolReport)
 
     p = sub.add_parser('newref', description='Build a reference from healthy samples in one go')
     p.add_argument('infiles', type=str, nargs='*', help='converted reference samples (.npz)')

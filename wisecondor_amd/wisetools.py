@@ -488,3 +488,103 @@ def prepReference(samples, pcacomp=3, device=0, device_out=False, counts=None, c
     _lib.check(lib.wc_newref_prep_finish(ctx, int(pcacomp), _lib.ptr(evecs), _lib.ptr(evals), _lib.ptr(masked),
                                          _lib.ptr(corrected_t), _lib.ptr(comps), _lib.ptr(mean)))
     return masked, chromBins, mask.astype(bool), corrected_t.T, comps, mean, [int(v) for v in mbins]
+
+
+# ---------------------------------------------------------------------------
+# convert: BAM -> binned sample
+# ---------------------------------------------------------------------------
+CONVERT_KEYS = [str(c) for c in range(1, 23)] + ['X', 'Y']
+
+
+class BamReads(object):
+    """The placed records of a BAM file as the native reader (csrc/bamio.cpp) leaves them: `names`, `lengths`
+    from the header, `offsets` [n_refs + 1] into `pos` (int32) / `mapq` (uint8) -- views of the library's own
+    memory, valid until close() -- and the record counts `mapped`, `unmapped`, `no_coordinate`."""
+
+    def __init__(self, path, threads=8):
+        lib = _lib.load()
+        handle = ctypes.c_void_p()
+        _lib.check(lib.wc_bam_open(os.fsencode(path), int(threads), ctypes.byref(handle)))
+        self._handle = handle
+        info = np.zeros(8, dtype=np.int64)
+        _lib.check(lib.wc_bam_info(handle, _lib.ptr(info)))
+        n_refs, n_reads, self.mapped, self.unmapped, self.no_coordinate, name_bytes = (int(v) for v in info[:6])
+        names = ctypes.create_string_buffer(name_bytes + 1)
+        self.lengths = np.zeros(n_refs, dtype=np.int64)
+        self.offsets = np.zeros(n_refs + 1, dtype=np.int64)
+        _lib.check(lib.wc_bam_refs(handle, ctypes.cast(names, ctypes.c_void_p), name_bytes + 1, _lib.ptr(self.lengths),
+                                   _lib.ptr(self.offsets)))
+        self.names = names.raw[:name_bytes].decode('latin1').split('\n')[:n_refs]
+        if n_reads:
+            self.pos = np.ctypeslib.as_array(ctypes.cast(lib.wc_bam_pos(handle), ctypes.POINTER(ctypes.c_int32)), (n_reads,))
+            self.mapq = np.ctypeslib.as_array(ctypes.cast(lib.wc_bam_mapq(handle), ctypes.POINTER(ctypes.c_uint8)), (n_reads,))
+        else:
+            self.pos, self.mapq = np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.uint8)
+
+    def close(self):
+        if self._handle is not None:
+            self.pos = self.mapq = None
+            _lib.load().wc_bam_close(self._handle)
+            self._handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def convert_chromosome_key(name):
+    """The sample-dict key of a BAM reference name (a leading 'chr' in any case dropped), None if it is skipped."""
+    key = name[3:] if name[:3].lower() == 'chr' else name
+    return key if key in CONVERT_KEYS else None
+
+
+def convertReads(names, lengths, offsets, pos, mapq, binsize=1000000, minShift=4, threshold=4, device=0, verbose=False):
+    """convertBam's filters and binning (wisetools.py:143-206) on reads that are already in arrays: references
+    `names` / `lengths` in header order, reference r owning pos / mapq [offsets[r], offsets[r+1]).  One GPU call
+    for all chromosomes (wc_convert_reads).  Returns (chromosomes dict, the four filter counters + pair_fail)."""
+    lib = _lib.load()
+    chromosomes = dict((key, None) for key in CONVERT_KEYS)
+    picked = [(r, convert_chromosome_key(name)) for r, name in enumerate(names)]
+    picked = [(r, key) for r, key in picked if key is not None]
+    stats = np.zeros(8, dtype=np.int64)
+    if picked:
+        spans = [(int(offsets[r]), int(offsets[r + 1])) for r, _ in picked]
+        n_bins = [int(int(lengths[r]) / float(binsize) + 1) for r, _ in picked]
+        if verbose:
+            for (r, _), bins in zip(picked, n_bins):
+                print(names[r], 'length:', int(lengths[r]), 'bins:', bins)
+        if all(spans[i][1] == spans[i + 1][0] for i in range(len(spans) - 1)):
+            p, q = pos[spans[0][0]:spans[-1][1]], mapq[spans[0][0]:spans[-1][1]]      # no copy: the usual header order
+        else:
+            p = np.concatenate([pos[a:b] for a, b in spans])
+            q = np.concatenate([mapq[a:b] for a, b in spans])
+        p = np.ascontiguousarray(p, dtype=np.int32)
+        q = np.ascontiguousarray(q, dtype=np.uint8)
+        read_offsets = np.concatenate([[0], np.cumsum([b - a for a, b in spans])]).astype(np.int64)
+        bin_offsets = np.concatenate([[0], np.cumsum(n_bins)]).astype(np.int64)
+        counts = np.zeros(int(bin_offsets[-1]), dtype=np.int32)
+        _lib.check(lib.wc_convert_reads(_lib.context(device), _lib.ptr(p), _lib.ptr(q), _lib.ptr(read_offsets), len(picked),
+                                        float(binsize), int(minShift), int(threshold), _lib.ptr(bin_offsets),
+                                        _lib.ptr(counts), _lib.ptr(stats)))
+        for i, (_, key) in enumerate(picked):
+            chromosomes[key] = counts[bin_offsets[i]:bin_offsets[i + 1]].copy()
+    return chromosomes, {'filter_rmdup': int(stats[0]), 'filter_mapq': int(stats[1]), 'pre_retro': int(stats[2]),
+                         'post_retro': int(stats[3]), 'pair_fail': 0}
+
+
+def convertBamReads(bam, binsize=1000000, minShift=4, threshold=4, device=0, verbose=False):
+    """convertBam on an opened BamReads: (chromosomes, qual_info)."""
+    chromosomes, counters = convertReads(bam.names, bam.lengths, bam.offsets, bam.pos, bam.mapq, binsize, minShift,
+                                         threshold, device=device, verbose=verbose)
+    qual_info = {'mapped': bam.mapped, 'unmapped': bam.unmapped, 'no_coordinate': bam.no_coordinate}
+    qual_info.update(counters)
+    return chromosomes, qual_info
+
+
+def convertBam(bamfile, binsize=1000000, minShift=4, threshold=4, threads=8, device=0):
+    """BAM file -> (dict chromosome -> int32[bins] or None, quality dict), wisetools.py:116-217 as toolConvert
+    calls it (mapq 1, demandPair False).  The file is read by the native reader, the filters run on the GPU."""
+    with BamReads(bamfile, threads=threads) as bam:
+        return convertBamReads(bam, binsize, minShift, threshold, device=device, verbose=True)
