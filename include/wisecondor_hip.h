@@ -243,7 +243,10 @@ int wc_newref_prep(wc_ctx *ctx, const int32_t *counts, int64_t n_samples, int64_
  *   wc_bam_refs   names_out: the reference names in header order, each followed by '\n'; lengths_out [n_refs];
  *                 offsets_out [n_refs + 1]: the placed records of reference r are [offsets[r], offsets[r+1]) of
  *   wc_bam_pos    int32, the 0-based position field, and
- *   wc_bam_mapq   uint8, of every placed record in file order (no flag filter).
+ *   wc_bam_mapq   uint8, of every placed record in file order (no flag filter), and for the paired mode of convert
+ *   wc_bam_flag   uint16, the flag word (0x2 proper pair, 0x40 first in pair: pysam's is_proper_pair / is_read1), and
+ *   wc_bam_mate_pos  int32, the 0-based next_pos field (pysam's next_reference_start; -1: none), in the same order.
+ *                 That mapping follows the SAM specification; it is not verified against pysam either.
  * Errors (never a crash; wc_last_error has the text): WC_E_IO cannot open; WC_E_FORMAT bad magic, a damaged or
  * truncated BGZF block, a record that overruns its block_size or the data (a missing EOF block is accepted);
  * WC_E_ARG the file is not coordinate-sorted (positions decrease within a reference, or a reference's records are
@@ -255,11 +258,14 @@ int wc_bam_info(const wc_bam *bam, int64_t out[8]);
 int wc_bam_refs(const wc_bam *bam, char *names_out, int64_t names_cap, int64_t *lengths_out, int64_t *offsets_out);
 const int32_t *wc_bam_pos(const wc_bam *bam);
 const uint8_t *wc_bam_mapq(const wc_bam *bam);
+const uint16_t *wc_bam_flag(const wc_bam *bam);
+const int32_t *wc_bam_mate_pos(const wc_bam *bam);
 void wc_bam_close(wc_bam *bam);
 
 /*
- * The numeric part of convertBam (wisetools.py:116-217, as toolConvert calls it: mapq 1, demandPair False) for all
- * chromosomes of one file in one call: duplicate removal, mapping-quality filter, the tower (RETRO) filter, binning.
+ * The numeric part of convertBam (wisetools.py:116-217) for all chromosomes of one file in one call: the paired-end
+ * selection, duplicate removal, mapping-quality filter, the tower (RETRO) filter, binning.  wc_convert_reads[_dev] is
+ * the function as toolConvert calls it (mapq 1, demandPair False); wc_convert_reads_ex[_dev] takes both parameters.
  *   pos, mapq       the reads of the processed chromosomes, concatenated in header order (device pointers for _dev)
  *   read_offsets    HOST int64 [n_chrom + 1], read_offsets[0] == 0: chromosome c owns [read_offsets[c], [c+1])
  *   bin_offsets     HOST int64 [n_chrom + 1], bin_offsets[0] == 0: its bins in counts_out (int(length / binsize + 1) each)
@@ -268,11 +274,21 @@ void wc_bam_close(wc_bam *bam);
  *   stats_out       int64 [8]: [0] filter_rmdup [1] filter_mapq [2] pre_retro [3] post_retro [4] counted reads whose
  *                   bin (int64)((double)pos / binsize) lies outside their chromosome's bins -- the status word: the
  *                   reference raises IndexError there, the host form returns WC_E_ARG, nothing is written out of
- *                   range -- [5] reads kept by the first two filters
+ *                   range -- [5] reads kept by the first two filters [6] pair_fail (0 unless demand_pair)
+ *   min_mapq        (_ex) a read below it is counted in filter_mapq; any int (<= 0: nothing is filtered, > 255: every
+ *                   eligible read that is no duplicate)
+ *   demand_pair     (_ex) != 0: the paired-end branch (wisetools.py:160-183).  Only reads whose flag has 0x2 and 0x40 take
+ *                   part; every other counted read adds one to pair_fail and nothing else.  A duplicate is a read whose
+ *                   pos AND mate_pos equal those of the previous read that took part -- however many reads or
+ *                   chromosomes back; before the first one (-1, -1) is compared.  pre_retro counts the reads that took
+ *                   part.  flag (uint16) and mate_pos (int32) run parallel to pos; they may be NULL when demand_pair
+ *                   == 0 and are WC_E_ARG when it is not.
  * The first read of every chromosome is consumed uncounted and `larp` is carried from chromosome to chromosome on the
  * device, as in the reference.  Where the reference dies (a chromosome without reads: StopIteration) the chromosome
  * gets all-zero counts and leaves `larp` alone; a chromosome with one read likewise.  n_chrom <= WC_CV_MAX_CHROM,
- * fewer than 2^31 - 4096 reads.  wc_convert_tile_reads: reads per workgroup of the kernels (their tile boundaries).
+ * fewer than 2^31 - 4096 reads.  In the paired mode the carried state is the previous read that took part, so such a
+ * chromosome changes nothing there either.  wc_convert_tile_reads: reads per workgroup of the kernels (their tile
+ * boundaries).
  */
 int wc_convert_tile_reads(void);
 int wc_convert_reads_dev(wc_ctx *ctx, void *stream, const int32_t *pos, const uint8_t *mapq, const int64_t *read_offsets,
@@ -281,6 +297,13 @@ int wc_convert_reads_dev(wc_ctx *ctx, void *stream, const int32_t *pos, const ui
 int wc_convert_reads(wc_ctx *ctx, const int32_t *pos, const uint8_t *mapq, const int64_t *read_offsets, int n_chrom,
                      double binsize, int min_shift, int threshold, const int64_t *bin_offsets, int32_t *counts_out,
                      int64_t *stats_out);
+int wc_convert_reads_ex_dev(wc_ctx *ctx, void *stream, const int32_t *pos, const uint8_t *mapq, const uint16_t *flag,
+                            const int32_t *mate_pos, const int64_t *read_offsets, int n_chrom, double binsize, int min_shift,
+                            int threshold, int min_mapq, int demand_pair, const int64_t *bin_offsets, int32_t *counts_out,
+                            int64_t *stats_out);
+int wc_convert_reads_ex(wc_ctx *ctx, const int32_t *pos, const uint8_t *mapq, const uint16_t *flag, const int32_t *mate_pos,
+                        const int64_t *read_offsets, int n_chrom, double binsize, int min_shift, int threshold, int min_mapq,
+                        int demand_pair, const int64_t *bin_offsets, int32_t *counts_out, int64_t *stats_out);
 
 /* ---- test: per-reference state -------------------------------------------- */
 typedef struct wc_reference wc_reference;

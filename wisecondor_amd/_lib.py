@@ -52,10 +52,14 @@ SIGNATURES = {
     "wc_bam_refs": (_i32, [_vp, _vp, _i64, _vp, _vp]),
     "wc_bam_pos": (_vp, [_vp]),
     "wc_bam_mapq": (_vp, [_vp]),
+    "wc_bam_flag": (_vp, [_vp]),
+    "wc_bam_mate_pos": (_vp, [_vp]),
     "wc_bam_close": (None, [_vp]),
     "wc_convert_tile_reads": (_i32, []),
     "wc_convert_reads_dev": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _dbl, _i32, _i32, _vp, _vp, _vp]),
     "wc_convert_reads": (_i32, [_vp, _vp, _vp, _vp, _i32, _dbl, _i32, _i32, _vp, _vp, _vp]),
+    "wc_convert_reads_ex_dev": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _dbl, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "wc_convert_reads_ex": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _dbl, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "wc_newref_prep_gram": (_i32, [_vp, _vp, _i64, _i64, _vp, _i32, _vp, _vp, _vp, _vp]),
     "wc_newref_prep_eig": (_i32, [_vp, _i32, _vp, _vp]),
     "wc_sym_eigh_leading_dev": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp]),

@@ -1,12 +1,14 @@
 // Native BAM reader for `convert` (the reference goes through pysam, wisetools.py:134-155): BGZF blocks inflated by a
 // pool of threads, records walked by their block_size chain (records cross block boundaries), output as
-// structure-of-arrays in file order = grouped by reference: pos[], mapq[], per-reference offsets, names and lengths
-// from the header.  No index file is needed.
+// structure-of-arrays in file order = grouped by reference: pos[], mapq[], flag[], mate_pos[], per-reference offsets,
+// names and lengths from the header.  No index file is needed.
 //
 // The three record counts of the `quality` dict come from the records themselves instead of pysam's index statistics:
 //   mapped = refID >= 0 and flag 0x4 clear;  no_coordinate = refID < 0;  unmapped = flag 0x4 set
 // (pysam documents its `unmapped` as including the reads without coordinates).  pysam is not available where this was
-// written, so this one mapping is NOT verified against it.
+// written, so this one mapping is NOT verified against it.  The same holds for the paired-end fields: flag bits 0x2 /
+// 0x40 stand for pysam's is_proper_pair / is_read1 and next_pos (record offset 24) for next_reference_start, after the
+// SAM specification.
 //
 // The file is read in chunks of WC_BAM_CHUNK blocks: compressed bytes in, blocks inflated in parallel into one buffer,
 // records parsed from it, the unfinished tail of the buffer carried to the front of the next chunk.  Errors, never
@@ -32,6 +34,8 @@ struct wc_bam {
     std::vector<int64_t> lengths, offsets;      // offsets: n_refs + 1
     std::vector<int32_t> pos;
     std::vector<uint8_t> mapq;
+    std::vector<uint16_t> flag;
+    std::vector<int32_t> mate_pos;
     int64_t mapped = 0, unmapped = 0, no_coordinate = 0, name_bytes = 0;
 };
 
@@ -163,6 +167,8 @@ struct Parser {
                 last_pos = ps;
                 b.pos.push_back(ps);
                 b.mapq.push_back(r[9]);
+                b.flag.push_back((uint16_t)flag);
+                b.mate_pos.push_back((int32_t)rd32(r + 24));
                 ++b.offsets[(size_t)ref + 1];
             }
             ++records;
@@ -302,6 +308,8 @@ int wc_bam_refs(const wc_bam *bam, char *names_out, int64_t names_cap, int64_t *
 
 const int32_t *wc_bam_pos(const wc_bam *bam) { return bam ? bam->pos.data() : nullptr; }
 const uint8_t *wc_bam_mapq(const wc_bam *bam) { return bam ? bam->mapq.data() : nullptr; }
+const uint16_t *wc_bam_flag(const wc_bam *bam) { return bam ? bam->flag.data() : nullptr; }
+const int32_t *wc_bam_mate_pos(const wc_bam *bam) { return bam ? bam->mate_pos.data() : nullptr; }
 
 void wc_bam_close(wc_bam *bam) { delete bam; }
 

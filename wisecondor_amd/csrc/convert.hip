@@ -22,6 +22,20 @@
 // is a count of leading / trailing zeros of the head mask; 32 segment values per tile go through LDS.
 // Positions are sorted, so the lanes of a segment hit one or two bins: equal bins are matched within the wave and
 // one lane issues one atomicAdd per (segment, bin).
+//
+// The two other parameters of convertBam: `min_mapq` replaces the 1 of keep[i]; `demandPair` (paired mode,
+// wisetools.py:160-183, tests/convert_paired_restated.py) is a second instance of the first kernels:
+//   elig[i]  = flag[i] has 0x2 (proper pair) and 0x40 (first in pair); a counted read that is not eligible adds one to
+//              pair_fail and touches nothing else
+//   e(i)     = the nearest earlier eligible counted read, in ANY earlier chromosome (none: (-1, -1) is compared)
+//   dup[i]   = pos[i] == pos[e] && mate_pos[i] == mate_pos[e];   keep[i] = elig[i] && !dup[i] && mapq[i] >= min_mapq
+// so `larp` is not used; instead
+//   k_cv_elig         the last eligible counted read of every tile
+//   k_cv_scan<1>      the last eligible counted read before every tile                      (1 workgroup)
+//   k_cv_flags<true>  e(i) from the segment's ballot, the tile's 32 segment values or that carry; gathers pos[e] and
+//                     mate_pos[e]; writes the class of every read as a byte, which k_cv_compact<true> reads back
+//                     (the plain mode recomputes the class there: it needs one neighbouring load, not a scan)
+// From kpos[] on the two modes are the same kernels.
 #include "ctx.h"
 
 #include <limits.h>
@@ -57,9 +71,9 @@ __device__ __forceinline__ int cv_find(const int *tab, int n, int i) {
 __device__ __forceinline__ int cv_lane() { return (int)(threadIdx.x & 63); }
 
 // class of read i: 0 not a counted read (a chromosome's consumed first read, or past the end), 1 duplicate,
-// 2 mapping quality below 1, 3 kept; p = its position
+// 2 mapping quality below min_mapq, 3 kept (paired mode adds 4: not eligible); p = its position
 __device__ __forceinline__ int cv_class(const int32_t *__restrict__ pos, const uint8_t *__restrict__ mapq, const int *s_ro,
-                                        const int *s_larp, int n_chrom, int i, int n, int &p) {
+                                        const int *s_larp, int n_chrom, int i, int n, int min_mapq, int &p) {
     p = 0;
     if (i >= n) return 0;
     const int c = cv_find(s_ro, n_chrom, i);
@@ -68,7 +82,19 @@ __device__ __forceinline__ int cv_class(const int32_t *__restrict__ pos, const u
     p = pos[i];
     const int prev = i == first + 1 ? s_larp[c] : pos[i - 1];
     if (p == prev) return 1;
-    return mapq[i] < 1 ? 2 : 3;
+    return (int)mapq[i] < min_mapq ? 2 : 3;
+}
+
+// paired mode: is read i an eligible counted read?  counted: is it a counted read at all
+__device__ __forceinline__ bool cv_elig(const uint16_t *__restrict__ flag, const int *s_ro, int n_chrom, int i, int n,
+                                        bool &counted) {
+    counted = false;
+    if (i >= n) return false;
+    const int c = cv_find(s_ro, n_chrom, i);
+    if (i == s_ro[c]) return false;
+    counted = true;
+    const unsigned f = flag[i];
+    return (f & 0x2u) && (f & 0x40u);
 }
 
 __global__ void __launch_bounds__(CV_BLOCK) k_cv_tables(const int32_t *__restrict__ pos, CvTab *tab, int n_chrom) {
@@ -88,39 +114,111 @@ __device__ __forceinline__ void cv_load_tab(const int *src, int *dst, int n) {
     for (int i = (int)threadIdx.x; i < n; i += CV_BLOCK) dst[i] = src[i];
 }
 
+template <int MODE, bool REVERSE> __device__ __forceinline__ void cv_seg_scan(const int *s_in, int *s_out, int seed);
+
+// paired mode: the last eligible counted read of the tile (-1: none)
+__global__ void __launch_bounds__(CV_BLOCK) k_cv_elig(const uint16_t *__restrict__ flag, const CvTab *__restrict__ tab,
+                                                     int n_chrom, int n, int *__restrict__ tile_elast) {
+    __shared__ int s_ro[WC_CV_MAX_CHROM + 1];
+    __shared__ int s_last;
+    cv_load_tab(tab->ro, s_ro, n_chrom + 1);
+    if (threadIdx.x == 0) s_last = -1;
+    wc_sync();
+    const int base = (int)blockIdx.x * CV_TILE;
+    const int w = (int)threadIdx.x >> 6;
+    int last = -1;                                  // wave-uniform; the rounds ascend, so the latest hit is the largest
+#pragma unroll
+    for (int r = 0; r < CV_ROUNDS; ++r) {
+        const int seg_base = base + r * CV_BLOCK + w * 64;
+        bool counted;
+        const unsigned long long mk = __ballot(cv_elig(flag, s_ro, n_chrom, seg_base + cv_lane(), n, counted));
+        if (mk) last = seg_base + 63 - __clzll((long long)mk);
+    }
+    if (cv_lane() == 0 && last >= 0) atomicMax(&s_last, last);
+    wc_sync();
+    if (threadIdx.x == 0) tile_elast[blockIdx.x] = s_last;
+}
+
+// PAIRED: flag, mate, carry_e (the last eligible counted read before the tile) and cls_out (a byte per read of the
+// tile, reads past the end included) are used; otherwise they may be NULL
+template <bool PAIRED>
 __global__ void __launch_bounds__(CV_BLOCK) k_cv_flags(const int32_t *__restrict__ pos, const uint8_t *__restrict__ mapq,
-                                                      const CvTab *__restrict__ tab, int n_chrom, int n,
+                                                      const uint16_t *__restrict__ flag, const int32_t *__restrict__ mate,
+                                                      const CvTab *__restrict__ tab, int n_chrom, int n, int min_mapq,
+                                                      const int *__restrict__ carry_e, uint8_t *__restrict__ cls_out,
                                                       int *__restrict__ tile_keep, unsigned long long *stats) {
     __shared__ int s_ro[WC_CV_MAX_CHROM + 1], s_larp[WC_CV_MAX_CHROM + 1];
+    __shared__ int s_elast[CV_SEGS], s_ebefore[CV_SEGS];
     __shared__ int s_cnt[4];
     cv_load_tab(tab->ro, s_ro, n_chrom + 1);
-    cv_load_tab(tab->larp, s_larp, n_chrom + 1);
+    if (!PAIRED) cv_load_tab(tab->larp, s_larp, n_chrom + 1);
     if (threadIdx.x < 4) s_cnt[threadIdx.x] = 0;
     wc_sync();
     const int base = (int)blockIdx.x * CV_TILE;
-    int n_dup = 0, n_low = 0, n_keep = 0;          // wave-uniform: popcounts of ballots
+    int n_dup = 0, n_low = 0, n_keep = 0, n_fail = 0;       // wave-uniform: popcounts of ballots
+    if (PAIRED) {
+        const int lane = cv_lane(), w = (int)threadIdx.x >> 6;
+        unsigned long long emask[CV_ROUNDS];
+        unsigned counted_bits = 0;
 #pragma unroll
-    for (int r = 0; r < CV_ROUNDS; ++r) {
-        const int i = base + r * CV_BLOCK + (int)threadIdx.x;
-        int p;
-        const int cls = cv_class(pos, mapq, s_ro, s_larp, n_chrom, i, n, p);
-        n_dup += __popcll(__ballot(cls == 1));
-        n_low += __popcll(__ballot(cls == 2));
-        n_keep += __popcll(__ballot(cls == 3));
+        for (int r = 0; r < CV_ROUNDS; ++r) {
+            const int seg_base = base + r * CV_BLOCK + w * 64;
+            bool counted;
+            emask[r] = __ballot(cv_elig(flag, s_ro, n_chrom, seg_base + lane, n, counted));
+            if (counted) counted_bits |= 1u << r;
+            if (lane == 0) s_elast[r * (CV_BLOCK / 64) + w] = emask[r] ? seg_base + 63 - __clzll((long long)emask[r]) : -1;
+        }
+        wc_sync();
+        if (w == 0) cv_seg_scan<1, false>(s_elast, s_ebefore, carry_e[blockIdx.x]);
+        wc_sync();
+        const unsigned long long below = (1ull << lane) - 1ull;
+#pragma unroll
+        for (int r = 0; r < CV_ROUNDS; ++r) {
+            const int seg_base = base + r * CV_BLOCK + w * 64;
+            const int i = seg_base + lane;
+            int cls = ((counted_bits >> r) & 1u) ? 4 : 0;
+            if ((emask[r] >> lane) & 1ull) {
+                const unsigned long long lo = emask[r] & below;
+                const int e = lo ? seg_base + 63 - __clzll((long long)lo) : s_ebefore[r * (CV_BLOCK / 64) + w];
+                int pe = -1, me = -1;                       // no earlier eligible read: (-1, -1) is compared as it stands
+                if (e >= 0) {
+                    pe = pos[e];
+                    me = mate[e];
+                }
+                cls = (pos[i] == pe && mate[i] == me) ? 1 : ((int)mapq[i] < min_mapq ? 2 : 3);
+            }
+            cls_out[i] = (uint8_t)cls;
+            n_dup += __popcll(__ballot(cls == 1));
+            n_low += __popcll(__ballot(cls == 2));
+            n_keep += __popcll(__ballot(cls == 3));
+            n_fail += __popcll(__ballot(cls == 4));
+        }
+    } else {
+#pragma unroll
+        for (int r = 0; r < CV_ROUNDS; ++r) {
+            const int i = base + r * CV_BLOCK + (int)threadIdx.x;
+            int p;
+            const int cls = cv_class(pos, mapq, s_ro, s_larp, n_chrom, i, n, min_mapq, p);
+            n_dup += __popcll(__ballot(cls == 1));
+            n_low += __popcll(__ballot(cls == 2));
+            n_keep += __popcll(__ballot(cls == 3));
+        }
     }
     if (cv_lane() == 0) {
         atomicAdd(&s_cnt[0], n_dup);
         atomicAdd(&s_cnt[1], n_low);
         atomicAdd(&s_cnt[2], n_keep);
+        if (PAIRED) atomicAdd(&s_cnt[3], n_fail);
     }
     wc_sync();
     if (threadIdx.x == 0) {
         tile_keep[blockIdx.x] = s_cnt[2];
         if (s_cnt[0]) atomicAdd(&stats[0], (unsigned long long)s_cnt[0]);
         if (s_cnt[1]) atomicAdd(&stats[1], (unsigned long long)s_cnt[1]);
-        // pre_retro: every read but the consumed first one of each chromosome
+        // pre_retro: every read but the consumed first one of each chromosome (paired: every eligible one of them)
         const int total = s_cnt[0] + s_cnt[1] + s_cnt[2];
         if (total) atomicAdd(&stats[2], (unsigned long long)total);
+        if (PAIRED && s_cnt[3]) atomicAdd(&stats[6], (unsigned long long)s_cnt[3]);
     }
 }
 
@@ -180,13 +278,16 @@ template <int MODE, bool REVERSE> __device__ __forceinline__ void cv_seg_scan(co
     if (lane < CV_SEGS) s_out[at] = cv_op<MODE>(excl, seed);
 }
 
+// PAIRED: the class comes from cls_in (k_cv_flags<true>), mapq and min_mapq are not used
+template <bool PAIRED>
 __global__ void __launch_bounds__(CV_BLOCK) k_cv_compact(const int32_t *__restrict__ pos, const uint8_t *__restrict__ mapq,
-                                                        CvTab *tab, int n_chrom, int n, const int *__restrict__ tile_off,
+                                                        const uint8_t *__restrict__ cls_in, CvTab *tab, int n_chrom, int n,
+                                                        int min_mapq, const int *__restrict__ tile_off,
                                                         int32_t *__restrict__ kpos) {
     __shared__ int s_ro[WC_CV_MAX_CHROM + 1], s_larp[WC_CV_MAX_CHROM + 1];
     __shared__ int s_seg[CV_SEGS], s_segoff[CV_SEGS];
     cv_load_tab(tab->ro, s_ro, n_chrom + 1);
-    cv_load_tab(tab->larp, s_larp, n_chrom + 1);
+    if (!PAIRED) cv_load_tab(tab->larp, s_larp, n_chrom + 1);
     wc_sync();
     const int base = (int)blockIdx.x * CV_TILE;
     const int lane = cv_lane(), w = (int)threadIdx.x >> 6;
@@ -195,7 +296,13 @@ __global__ void __launch_bounds__(CV_BLOCK) k_cv_compact(const int32_t *__restri
 #pragma unroll
     for (int r = 0; r < CV_ROUNDS; ++r) {
         const int i = base + r * CV_BLOCK + (int)threadIdx.x;
-        const int cls = cv_class(pos, mapq, s_ro, s_larp, n_chrom, i, n, p[r]);
+        int cls;
+        if (PAIRED) {
+            cls = cls_in[i];
+            p[r] = cls == 3 ? pos[i] : 0;
+        } else {
+            cls = cv_class(pos, mapq, s_ro, s_larp, n_chrom, i, n, min_mapq, p[r]);
+        }
         mask[r] = __ballot(cls == 3);
         if (lane == 0) s_seg[r * (CV_BLOCK / 64) + w] = __popcll(mask[r]);
     }
@@ -339,9 +446,10 @@ extern "C" {
 
 int wc_convert_tile_reads(void) { return CV_TILE; }
 
-int wc_convert_reads_dev(wc_ctx *ctx, void *stream_, const int32_t *pos, const uint8_t *mapq, const int64_t *read_offsets,
-                         int n_chrom, double binsize, int min_shift, int threshold, const int64_t *bin_offsets,
-                         int32_t *counts_out, int64_t *stats_out) {
+int wc_convert_reads_ex_dev(wc_ctx *ctx, void *stream_, const int32_t *pos, const uint8_t *mapq, const uint16_t *flag,
+                            const int32_t *mate_pos, const int64_t *read_offsets, int n_chrom, double binsize, int min_shift,
+                            int threshold, int min_mapq, int demand_pair, const int64_t *bin_offsets, int32_t *counts_out,
+                            int64_t *stats_out) {
     WC_CHECK(ctx && read_offsets && bin_offsets && counts_out && stats_out, WC_E_ARG, "convert: NULL argument");
     WC_CHECK(n_chrom >= 1 && n_chrom <= WC_CV_MAX_CHROM, WC_E_LIMIT, "convert: %d chromosomes (1..%d supported)", n_chrom,
              WC_CV_MAX_CHROM);
@@ -355,6 +463,8 @@ int wc_convert_reads_dev(wc_ctx *ctx, void *stream_, const int32_t *pos, const u
              INT_MAX - 2 * CV_TILE);
     WC_CHECK(bins64 <= (int64_t)INT_MAX, WC_E_LIMIT, "convert: %lld bins in one call", (long long)bins64);
     WC_CHECK(n64 == 0 || (pos && mapq), WC_E_ARG, "convert: NULL read arrays");
+    const bool paired = demand_pair != 0;
+    WC_CHECK(!paired || (flag && mate_pos), WC_E_ARG, "convert: the paired mode needs the flag and mate position arrays");
     WC_HIP(hipSetDevice(ctx->device));
     hipStream_t stream = (hipStream_t)stream_;
     ConvertState &cv = ctx->cv;
@@ -362,11 +472,13 @@ int wc_convert_reads_dev(wc_ctx *ctx, void *stream_, const int32_t *pos, const u
     const int n_tiles = (n + 1 + CV_TILE - 1) / CV_TILE;         // read n is the end marker that closes the koff table
     int rc;
     if ((rc = cv.tab.reserve(sizeof(CvTab)))) return rc;
-    if ((rc = cv.tiles.reserve(sizeof(int) * 6 * (size_t)n_tiles))) return rc;
+    if ((rc = cv.tiles.reserve(sizeof(int) * 8 * (size_t)n_tiles))) return rc;
     if ((rc = cv.kpos.reserve(sizeof(int32_t) * ((size_t)n + 1)))) return rc;
+    if (paired && (rc = cv.cls.reserve((size_t)n_tiles * CV_TILE))) return rc;      // whole tiles: no bound in the kernels
     CvTab *tab = cv.tab.as<CvTab>();
     int *tile_keep = cv.tiles.as<int>(), *tile_off = tile_keep + n_tiles, *tile_last = tile_off + n_tiles;
     int *tile_first = tile_last + n_tiles, *carry_last = tile_first + n_tiles, *carry_next = carry_last + n_tiles;
+    int *tile_elast = carry_next + n_tiles, *carry_e = tile_elast + n_tiles;
     std::vector<int> host(2 * (WC_CV_MAX_CHROM + 1), 0);
     for (int c = 0; c <= n_chrom; ++c) {
         host[c] = (int)read_offsets[c];
@@ -376,13 +488,29 @@ int wc_convert_reads_dev(wc_ctx *ctx, void *stream_, const int32_t *pos, const u
     WC_HIP(hipMemsetAsync(stats_out, 0, sizeof(int64_t) * 8, stream));
     if (bins64) WC_HIP(hipMemsetAsync(counts_out, 0, sizeof(int32_t) * (size_t)bins64, stream));
     unsigned long long *stats = reinterpret_cast<unsigned long long *>(stats_out);
-    hipLaunchKernelGGL(k_cv_tables, dim3(1), dim3(CV_BLOCK), 0, stream, pos, tab, n_chrom);
-    hipLaunchKernelGGL(k_cv_flags, dim3(n_tiles), dim3(CV_BLOCK), 0, stream, pos, mapq, (const CvTab *)tab, n_chrom, n,
-                       tile_keep, stats);
+    if (paired) {
+        hipLaunchKernelGGL(k_cv_elig, dim3(n_tiles), dim3(CV_BLOCK), 0, stream, flag, (const CvTab *)tab, n_chrom, n,
+                           tile_elast);
+        hipLaunchKernelGGL(k_cv_scan<1>, dim3(1), dim3(CV_SCAN_BLOCK), 0, stream, (const int *)tile_elast, n_tiles, carry_e,
+                           (int *)nullptr);
+        hipLaunchKernelGGL(k_cv_flags<true>, dim3(n_tiles), dim3(CV_BLOCK), 0, stream, pos, mapq, flag, mate_pos,
+                           (const CvTab *)tab, n_chrom, n, min_mapq, (const int *)carry_e, cv.cls.as<uint8_t>(), tile_keep,
+                           stats);
+    } else {
+        hipLaunchKernelGGL(k_cv_tables, dim3(1), dim3(CV_BLOCK), 0, stream, pos, tab, n_chrom);
+        hipLaunchKernelGGL(k_cv_flags<false>, dim3(n_tiles), dim3(CV_BLOCK), 0, stream, pos, mapq, (const uint16_t *)nullptr,
+                           (const int32_t *)nullptr, (const CvTab *)tab, n_chrom, n, min_mapq, (const int *)nullptr,
+                           (uint8_t *)nullptr, tile_keep, stats);
+    }
     hipLaunchKernelGGL(k_cv_scan<0>, dim3(1), dim3(CV_SCAN_BLOCK), 0, stream, (const int *)tile_keep, n_tiles, tile_off,
                        reinterpret_cast<int *>(stats + 5));       // [5]: kept reads (low word; the high word is zero)
-    hipLaunchKernelGGL(k_cv_compact, dim3(n_tiles), dim3(CV_BLOCK), 0, stream, pos, mapq, tab, n_chrom, n,
-                       (const int *)tile_off, cv.kpos.as<int32_t>());
+    if (paired)
+        hipLaunchKernelGGL(k_cv_compact<true>, dim3(n_tiles), dim3(CV_BLOCK), 0, stream, pos, mapq,
+                           (const uint8_t *)cv.cls.as<uint8_t>(), tab, n_chrom, n, min_mapq, (const int *)tile_off,
+                           cv.kpos.as<int32_t>());
+    else
+        hipLaunchKernelGGL(k_cv_compact<false>, dim3(n_tiles), dim3(CV_BLOCK), 0, stream, pos, mapq, (const uint8_t *)nullptr,
+                           tab, n_chrom, n, min_mapq, (const int *)tile_off, cv.kpos.as<int32_t>());
     hipLaunchKernelGGL(k_cv_heads, dim3(n_tiles), dim3(CV_BLOCK), 0, stream, (const int32_t *)cv.kpos.as<int32_t>(),
                        (const CvTab *)tab, n_chrom, min_shift, tile_last, tile_first);
     hipLaunchKernelGGL(k_cv_scan<1>, dim3(1), dim3(CV_SCAN_BLOCK), 0, stream, (const int *)tile_last, n_tiles, carry_last,
@@ -396,9 +524,16 @@ int wc_convert_reads_dev(wc_ctx *ctx, void *stream_, const int32_t *pos, const u
     return WC_OK;
 }
 
-int wc_convert_reads(wc_ctx *ctx, const int32_t *pos, const uint8_t *mapq, const int64_t *read_offsets, int n_chrom,
-                     double binsize, int min_shift, int threshold, const int64_t *bin_offsets, int32_t *counts_out,
-                     int64_t *stats_out) {
+int wc_convert_reads_dev(wc_ctx *ctx, void *stream, const int32_t *pos, const uint8_t *mapq, const int64_t *read_offsets,
+                         int n_chrom, double binsize, int min_shift, int threshold, const int64_t *bin_offsets,
+                         int32_t *counts_out, int64_t *stats_out) {
+    return wc_convert_reads_ex_dev(ctx, stream, pos, mapq, nullptr, nullptr, read_offsets, n_chrom, binsize, min_shift,
+                                   threshold, 1, 0, bin_offsets, counts_out, stats_out);
+}
+
+int wc_convert_reads_ex(wc_ctx *ctx, const int32_t *pos, const uint8_t *mapq, const uint16_t *flag, const int32_t *mate_pos,
+                        const int64_t *read_offsets, int n_chrom, double binsize, int min_shift, int threshold, int min_mapq,
+                        int demand_pair, const int64_t *bin_offsets, int32_t *counts_out, int64_t *stats_out) {
     WC_CHECK(ctx && read_offsets && bin_offsets && counts_out && stats_out, WC_E_ARG, "convert: NULL argument");
     WC_CHECK(n_chrom >= 1 && n_chrom <= WC_CV_MAX_CHROM, WC_E_LIMIT, "convert: %d chromosomes (1..%d supported)", n_chrom,
              WC_CV_MAX_CHROM);
@@ -406,19 +541,29 @@ int wc_convert_reads(wc_ctx *ctx, const int32_t *pos, const uint8_t *mapq, const
     WC_CHECK(n >= 0 && bins >= 0 && n <= (int64_t)INT_MAX && bins <= (int64_t)INT_MAX, WC_E_LIMIT,
              "convert: %lld reads, %lld bins in one call", (long long)n, (long long)bins);
     WC_CHECK(n == 0 || (pos && mapq), WC_E_ARG, "convert: NULL read arrays");
+    const bool paired = demand_pair != 0;
+    WC_CHECK(!paired || (flag && mate_pos), WC_E_ARG, "convert: the paired mode needs the flag and mate position arrays");
     WC_HIP(hipSetDevice(ctx->device));
     int rc;
     if ((rc = ctx->tmp_a.reserve(sizeof(int32_t) * (size_t)(n + 1)))) return rc;
     if ((rc = ctx->tmp_b.reserve((size_t)n + 1))) return rc;
     if ((rc = ctx->tmp_c.reserve(sizeof(int32_t) * (size_t)(bins + 1) + 64))) return rc;
+    if (paired && (rc = ctx->tmp_d.reserve((sizeof(int32_t) + sizeof(uint16_t)) * (size_t)(n + 1)))) return rc;
     int64_t *stats_dev = ctx->tmp_c.as<int64_t>();               // 8 words, then the counts
     int32_t *counts_dev = reinterpret_cast<int32_t *>(stats_dev + 8);
+    int32_t *mate_dev = paired ? ctx->tmp_d.as<int32_t>() : nullptr;      // n + 1 mate positions, then the flags
+    uint16_t *flag_dev = paired ? reinterpret_cast<uint16_t *>(mate_dev + n + 1) : nullptr;
     if (n) {
         WC_HIP(hipMemcpy(ctx->tmp_a.p, pos, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice));
         WC_HIP(hipMemcpy(ctx->tmp_b.p, mapq, (size_t)n, hipMemcpyHostToDevice));
+        if (paired) {
+            WC_HIP(hipMemcpy(mate_dev, mate_pos, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice));
+            WC_HIP(hipMemcpy(flag_dev, flag, sizeof(uint16_t) * (size_t)n, hipMemcpyHostToDevice));
+        }
     }
-    rc = wc_convert_reads_dev(ctx, nullptr, ctx->tmp_a.as<int32_t>(), ctx->tmp_b.as<uint8_t>(), read_offsets, n_chrom, binsize,
-                              min_shift, threshold, bin_offsets, counts_dev, stats_dev);
+    rc = wc_convert_reads_ex_dev(ctx, nullptr, ctx->tmp_a.as<int32_t>(), ctx->tmp_b.as<uint8_t>(), flag_dev, mate_dev,
+                                 read_offsets, n_chrom, binsize, min_shift, threshold, min_mapq, demand_pair, bin_offsets,
+                                 counts_dev, stats_dev);
     if (rc) return rc;
     WC_HIP(hipDeviceSynchronize());
     WC_HIP(hipMemcpy(stats_out, stats_dev, sizeof(int64_t) * 8, hipMemcpyDeviceToHost));
@@ -427,6 +572,13 @@ int wc_convert_reads(wc_ctx *ctx, const int32_t *pos, const uint8_t *mapq, const
              "convert: %lld read(s) lie beyond their chromosome's last bin (a position past the header's length)",
              (long long)stats_out[4]);
     return WC_OK;
+}
+
+int wc_convert_reads(wc_ctx *ctx, const int32_t *pos, const uint8_t *mapq, const int64_t *read_offsets, int n_chrom,
+                     double binsize, int min_shift, int threshold, const int64_t *bin_offsets, int32_t *counts_out,
+                     int64_t *stats_out) {
+    return wc_convert_reads_ex(ctx, pos, mapq, nullptr, nullptr, read_offsets, n_chrom, binsize, min_shift, threshold, 1, 0,
+                               bin_offsets, counts_out, stats_out);
 }
 
 }  // extern "C"

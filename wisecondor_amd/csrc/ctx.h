@@ -78,9 +78,10 @@ struct PrepState {
     wc::DevBuf eig_ws;          // eigh.hip: working copy, reflectors, tridiagonal, vectors
 };
 
-// workspaces of `convert` (convert.hip): the small tables, the per-tile words, the kept positions
+// workspaces of `convert` (convert.hip): the small tables, the per-tile words, the kept positions, and in paired mode
+// the class byte of every read
 struct ConvertState {
-    wc::DevBuf tab, tiles, kpos;
+    wc::DevBuf tab, tiles, kpos, cls;
 };
 
 struct wc_ctx {
@@ -139,7 +140,7 @@ struct wc_ctx {
                 &ts.reg_flag, &ts.rs, &ts.jobs_a, &ts.jobs_b, &ts.job_cnt, &ts.partial, &ts.cbound, &ts.cuts, &ts.job_res, &ts.hot,
                 &ts.cand, &ts.cand_cnt, &ts.seg, &ts.out_val, &ts.out_x, &ts.out_y, &ts.out_n,
                 &ts.whole, &ts.effect, &ts.misc, &ts.misc2, &ts.reduce_tmp, &ts.win_bits, &ts.bit_off, &ts.pairs_a, &ts.pairs_b, &ts.cut_vals, &ts.prof_work, &ts.sd_fail, &ts.walk_hot, &prep.eig_ws,
-                &cv.tab, &cv.tiles, &cv.kpos};
+                &cv.tab, &cv.tiles, &cv.kpos, &cv.cls};
     }
 };
 

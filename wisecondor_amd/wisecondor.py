@@ -77,7 +77,8 @@ def writeConvertOutput(outfile, args, converted, qual_info):
 def toolConvert(args):
     """`convert infile outfile`: BAM -> binned, filtered sample (wisecondor.py:20-27)."""
     converted, qual_info = wt.convertBam(args.infile, binsize=args.binsize, minShift=args.retdist,
-                                         threshold=args.retthres)
+                                         threshold=args.retthres, mapq=getattr(args, 'mapq', 1),
+                                         demandPair=getattr(args, 'paired', False))
     writeConvertOutput(args.outfile, args, converted, qual_info)
     print('Conversion finished')
 
@@ -115,7 +116,9 @@ def toolConvertBatch(args):
             if i + 1 < len(args.infiles):
                 ahead = reader.submit(wt.BamReads, args.infiles[i + 1], args.io)
             try:
-                converted, qual_info = wt.convertBamReads(bam, args.binsize, args.retdist, args.retthres)
+                converted, qual_info = wt.convertBamReads(bam, args.binsize, args.retdist, args.retthres,
+                                                          mapq=getattr(args, 'mapq', 1),
+                                                          demandPair=getattr(args, 'paired', False))
             finally:
                 bam.close()
             # what one `convert` call would record: its own infile / outfile, not the batch's list
@@ -523,6 +526,13 @@ def buildParser():
                                'part of the same tower')),
         ('-retthres', dict(type=int, default=4,
                            help='Threshold for when a group of reads is considered a tower and will be removed')),
+        # build-only: convertBam's mapq / demandPair, which the upstream command line does not reach.  SUPPRESS keeps them
+        # out of the namespace (the `arguments` of the output file, which `report` prints) unless they are given
+        ('-mapq', dict(type=int, default=argparse.SUPPRESS,
+                       help='Lowest mapping quality of a read that is counted (default 1)')),
+        ('-paired', dict(action='store_true', default=argparse.SUPPRESS,
+                         help='Paired-end mode: count proper-pair first-in-pair reads only, a duplicate repeats the '
+                              'previous read\'s position and mate position')),
     )
     p = sub.add_parser('convert', description='Convert and filter a bam file to an npz')
     p.add_argument('infile', type=str, help='Bam input file for conversion')

@@ -498,8 +498,9 @@ CONVERT_KEYS = [str(c) for c in range(1, 23)] + ['X', 'Y']
 
 class BamReads(object):
     """The placed records of a BAM file as the native reader (csrc/bamio.cpp) leaves them: `names`, `lengths`
-    from the header, `offsets` [n_refs + 1] into `pos` (int32) / `mapq` (uint8) -- views of the library's own
-    memory, valid until close() -- and the record counts `mapped`, `unmapped`, `no_coordinate`."""
+    from the header, `offsets` [n_refs + 1] into `pos` (int32) / `mapq` (uint8) / `flag` (uint16) / `mate_pos` (int32,
+    the next_pos field) -- views of the library's own memory, valid until close() -- and the record counts `mapped`,
+    `unmapped`, `no_coordinate`."""
 
     def __init__(self, path, threads=8):
         lib = _lib.load()
@@ -518,12 +519,16 @@ class BamReads(object):
         if n_reads:
             self.pos = np.ctypeslib.as_array(ctypes.cast(lib.wc_bam_pos(handle), ctypes.POINTER(ctypes.c_int32)), (n_reads,))
             self.mapq = np.ctypeslib.as_array(ctypes.cast(lib.wc_bam_mapq(handle), ctypes.POINTER(ctypes.c_uint8)), (n_reads,))
+            self.flag = np.ctypeslib.as_array(ctypes.cast(lib.wc_bam_flag(handle), ctypes.POINTER(ctypes.c_uint16)), (n_reads,))
+            self.mate_pos = np.ctypeslib.as_array(ctypes.cast(lib.wc_bam_mate_pos(handle), ctypes.POINTER(ctypes.c_int32)),
+                                                  (n_reads,))
         else:
             self.pos, self.mapq = np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.uint8)
+            self.flag, self.mate_pos = np.zeros(0, dtype=np.uint16), np.zeros(0, dtype=np.int32)
 
     def close(self):
         if self._handle is not None:
-            self.pos = self.mapq = None
+            self.pos = self.mapq = self.flag = self.mate_pos = None
             _lib.load().wc_bam_close(self._handle)
             self._handle = None
 
@@ -540,11 +545,17 @@ def convert_chromosome_key(name):
     return key if key in CONVERT_KEYS else None
 
 
-def convertReads(names, lengths, offsets, pos, mapq, binsize=1000000, minShift=4, threshold=4, device=0, verbose=False):
+def convertReads(names, lengths, offsets, pos, mapq, binsize=1000000, minShift=4, threshold=4, device=0, verbose=False,
+                 flag=None, mate_pos=None, minMapq=1, demandPair=False):
     """convertBam's filters and binning (wisetools.py:143-206) on reads that are already in arrays: references
     `names` / `lengths` in header order, reference r owning pos / mapq [offsets[r], offsets[r+1]).  One GPU call
-    for all chromosomes (wc_convert_reads).  Returns (chromosomes dict, the four filter counters + pair_fail)."""
+    for all chromosomes (wc_convert_reads_ex).  `minMapq` is convertBam's `mapq` (the name is taken by the array);
+    `demandPair` needs `flag` (uint16 flag words) and `mate_pos` parallel to `pos`.  Returns (chromosomes dict, the
+    four filter counters + pair_fail)."""
     lib = _lib.load()
+    demandPair = bool(demandPair)
+    if demandPair and (flag is None or mate_pos is None):
+        raise ValueError('convertReads: demandPair needs the flag and mate_pos arrays')
     chromosomes = dict((key, None) for key in CONVERT_KEYS)
     picked = [(r, convert_chromosome_key(name)) for r, name in enumerate(names)]
     picked = [(r, key) for r, key in picked if key is not None]
@@ -556,35 +567,44 @@ def convertReads(names, lengths, offsets, pos, mapq, binsize=1000000, minShift=4
             for (r, _), bins in zip(picked, n_bins):
                 print(names[r], 'length:', int(lengths[r]), 'bins:', bins)
         if all(spans[i][1] == spans[i + 1][0] for i in range(len(spans) - 1)):
-            p, q = pos[spans[0][0]:spans[-1][1]], mapq[spans[0][0]:spans[-1][1]]      # no copy: the usual header order
+            def gather(a):
+                return a[spans[0][0]:spans[-1][1]]                              # no copy: the usual header order
         else:
-            p = np.concatenate([pos[a:b] for a, b in spans])
-            q = np.concatenate([mapq[a:b] for a, b in spans])
-        p = np.ascontiguousarray(p, dtype=np.int32)
-        q = np.ascontiguousarray(q, dtype=np.uint8)
+            def gather(a):
+                return np.concatenate([a[lo:hi] for lo, hi in spans])
+        p = np.ascontiguousarray(gather(pos), dtype=np.int32)
+        q = np.ascontiguousarray(gather(mapq), dtype=np.uint8)
+        f = np.ascontiguousarray(gather(np.asarray(flag)), dtype=np.uint16) if demandPair else None
+        m = np.ascontiguousarray(gather(np.asarray(mate_pos)), dtype=np.int32) if demandPair else None
         read_offsets = np.concatenate([[0], np.cumsum([b - a for a, b in spans])]).astype(np.int64)
         bin_offsets = np.concatenate([[0], np.cumsum(n_bins)]).astype(np.int64)
         counts = np.zeros(int(bin_offsets[-1]), dtype=np.int32)
-        _lib.check(lib.wc_convert_reads(_lib.context(device), _lib.ptr(p), _lib.ptr(q), _lib.ptr(read_offsets), len(picked),
-                                        float(binsize), int(minShift), int(threshold), _lib.ptr(bin_offsets),
-                                        _lib.ptr(counts), _lib.ptr(stats)))
+        _lib.check(lib.wc_convert_reads_ex(_lib.context(device), _lib.ptr(p), _lib.ptr(q),
+                                           _lib.ptr(f) if demandPair else None, _lib.ptr(m) if demandPair else None,
+                                           _lib.ptr(read_offsets), len(picked), float(binsize), int(minShift),
+                                           int(threshold), int(minMapq), int(demandPair), _lib.ptr(bin_offsets),
+                                           _lib.ptr(counts), _lib.ptr(stats)))
         for i, (_, key) in enumerate(picked):
             chromosomes[key] = counts[bin_offsets[i]:bin_offsets[i + 1]].copy()
     return chromosomes, {'filter_rmdup': int(stats[0]), 'filter_mapq': int(stats[1]), 'pre_retro': int(stats[2]),
-                         'post_retro': int(stats[3]), 'pair_fail': 0}
+                         'post_retro': int(stats[3]), 'pair_fail': int(stats[6])}
 
 
-def convertBamReads(bam, binsize=1000000, minShift=4, threshold=4, device=0, verbose=False):
+def convertBamReads(bam, binsize=1000000, minShift=4, threshold=4, device=0, verbose=False, mapq=1, demandPair=False):
     """convertBam on an opened BamReads: (chromosomes, qual_info)."""
     chromosomes, counters = convertReads(bam.names, bam.lengths, bam.offsets, bam.pos, bam.mapq, binsize, minShift,
-                                         threshold, device=device, verbose=verbose)
+                                         threshold, device=device, verbose=verbose, flag=bam.flag, mate_pos=bam.mate_pos,
+                                         minMapq=mapq, demandPair=demandPair)
     qual_info = {'mapped': bam.mapped, 'unmapped': bam.unmapped, 'no_coordinate': bam.no_coordinate}
     qual_info.update(counters)
     return chromosomes, qual_info
 
 
-def convertBam(bamfile, binsize=1000000, minShift=4, threshold=4, threads=8, device=0):
-    """BAM file -> (dict chromosome -> int32[bins] or None, quality dict), wisetools.py:116-217 as toolConvert
-    calls it (mapq 1, demandPair False).  The file is read by the native reader, the filters run on the GPU."""
+def convertBam(bamfile, binsize=1000000, minShift=4, threshold=4, threads=8, device=0, mapq=1, demandPair=False):
+    """BAM file -> (dict chromosome -> int32[bins] or None, quality dict), wisetools.py:116-217: `mapq` the
+    mapping-quality floor, `demandPair` the paired-end branch (only proper-pair first-in-pair reads take part, a
+    duplicate has the previous such read's position and mate position, the rest is counted in pair_fail).  The file
+    is read by the native reader, the filters run on the GPU."""
     with BamReads(bamfile, threads=threads) as bam:
-        return convertBamReads(bam, binsize, minShift, threshold, device=device, verbose=True)
+        return convertBamReads(bam, binsize, minShift, threshold, device=device, verbose=True, mapq=mapq,
+                               demandPair=demandPair)
