@@ -369,14 +369,13 @@ def test_std_dev_avg_parallel_form_is_exact(wt):
     assert got == _seq_mean(v) and serial == 1
 
 
-@pytest.mark.parametrize("env", [{"WC_TEST_WALK": "0"}, {"WC_TEST_WALK": "0", "WC_TEST_TREE_TAIL": "0"},
-                                 {"WC_TEST_WALK": "0", "WC_TEST_TREE_TAIL": "0", "WC_TEST_CELLS": "0"},
-                                 {"WC_TEST_WALK": "0", "WC_TEST_TREE_TAIL": "0", "WC_CELL_PARTS": "1"}])
+@pytest.mark.parametrize("env", [{"WC_TEST_WALK": "0"}, {"WC_TEST_WALK": "0", "WC_TEST_CELLS": "0"},
+                                 {"WC_TEST_WALK": "0", "WC_CELL_PARTS": "1"}])
 def test_every_segmentation_path_gives_the_walkers_outputs(wt, cfg1, reference, monkeypatch, env):
-    """The batched `test` through the paths k_seg_walk replaced (the switches are read per call): the tree kernel
-    after k_seg_quiet / k_seg_search / k_seg_classify, the host-driven levels with the cell search (k_seg_job /
-    k_seg_merge; one workgroup per range or several), and those levels with the row-block kernels -- bit-identical
-    calls, z, ratios and chromosome-wide values for a batch of 48 samples (the six cfg1 samples repeated)."""
+    """The batched `test` through the host-driven levels k_seg_walk replaced (the switches are read per call): with
+    the cell search (k_seg_job / k_seg_merge; several workgroups per range or one), and with the row-block kernels
+    -- bit-identical calls, z, ratios and chromosome-wide values for a batch of 48 samples (the six cfg1 samples
+    repeated)."""
     g = cfg1
     thr = float(g["t_mild18_threshold_z"])
     samples = [_split(g["t_%s_sample" % n], g["sample_chrom_lengths"]) for n in NAMES] * 8

@@ -1855,11 +1855,11 @@ struct SdRider {
 };
 
 void launch_sd_fast(hipStream_t stream, const double *sdT, int64_t B, int64_t Ns, double *out, int *fail, double *out2,
-                    int64_t sb, int64_t si, bool stage) {
+                    int64_t sb, int64_t si) {
     const int64_t per = (B + 1023) / 1024;
-    // (a sample's values contiguous -- every batch: the cooperative loads; stage false (WC_TEST_SD_STAGE=0): a lane per
-    //  run, round 5's form)
-    const bool staged = sb == 1 && stage;
+    // (a sample's values contiguous -- every batch: the cooperative loads; otherwise -- the latency rider's layout, up to
+    //  8 samples -- a lane per run, round 5's form)
+    const bool staged = sb == 1;
     if (per <= 12 && staged)
         hipLaunchKernelGGL((k_sd_fast<12, true>), dim3((unsigned)Ns), dim3(1024), 0, stream, sdT, B, Ns, out, fail, out2, sb, si);
     else if (per <= 12)
@@ -2587,8 +2587,8 @@ __global__ __launch_bounds__(256) void k_seg_quiet(Job *__restrict__ jobs, int n
 }
 
 // ------------------------------------------------------------ bound-driven search ----
-// The host-driven rounds (regions beyond the tree kernel, i.e. bin sizes below ~125 kb; every call of
-// wc_stouffer_segments without -mineffectsize) do not evaluate every window of a job that may hold a call.
+// The host-driven rounds without a -mineffectsize mask (wc_stouffer_segments; a batch the walker gave up on or whose
+// regions are beyond CJ_MAXLEN bins) do not evaluate every window of a job that may hold a call.
 // The same per-(row, 32-end block) bounds that certify a quiet job also LOCATE the extremes of a loud one:
 //     ub(x, k) = max(max P over block k - P[x], 0) * rs[min len]  >=  every window value of the pair
 // (subtraction, scaling and rounding are monotone, so the bound covers the values exactly as the search would
@@ -4914,6 +4914,7 @@ struct InflateRider {
     double minref;
     double *res_z, *res_r;
 };
+// (hot_list / hot_count: always NULL now -- latency mode is the kernel's only caller, a workgroup per region)
 __global__ __launch_bounds__(1024) void k_seg_tree(int *__restrict__ counters, const Region *__restrict__ regions,
                                                    int64_t n_regions, const int *__restrict__ reg_flag,
                                                    const double *__restrict__ prefix, const double *__restrict__ rs,
@@ -5287,7 +5288,7 @@ __global__ __launch_bounds__(256) void k_walk_rows(const Seg *__restrict__ wsegs
 // The test path's environment switches (A/B forms for experiments and the test suite).  Every C-ABI entry that reaches
 // the test path reads them once per call -- a test may change them between two calls -- and passes them down.
 struct TestSwitches {
-    bool zscore_tiled, zscore_sm, sd_stage, tail_repeats, mineffect_sorted, walk, walk_hot, tree_tail, cells, latency,
+    bool zscore_tiled, zscore_sm, tail_repeats, mineffect_sorted, walk, walk_hot, cells, latency,
         latency_eager, verbose;
     int tail_cap, side2_from, cell_parts;
     bool second_side(int64_t n_samples) const { return side2_from > 0 && n_samples >= side2_from; }
@@ -5299,14 +5300,12 @@ static TestSwitches read_switches() {
     TestSwitches sw;
     sw.zscore_tiled = !is("WC_ZSCORE_TILED", '0');      // 0: the untiled first repeat (a wave = one bin x 64 samples)
     sw.zscore_sm = !is("WC_ZSCORE_SM", '0');            // 0: bin-major outputs + the transposes (round 5's form)
-    sw.sd_stage = !is("WC_TEST_SD_STAGE", '0');         // 0: k_sd_fast without the cooperative loads (a lane per run)
     sw.tail_repeats = !is("WC_TEST_TAIL_REPEATS", '0'); // 0: a batch's late repeats as a launch pair each
     sw.tail_cap = num("WC_TEST_TAIL_CAP", TAIL_PAIR_CAP);   // pairs a late repeat may hold for the one-workgroup form
     sw.side2_from = num("WC_TEST_SIDE2", 768);          // second side stream from this many samples on (0: never)
     sw.mineffect_sorted = me && strcmp(me, "sorted") == 0;  // the O(n) per window sorted-insert kernel
-    sw.walk = !is("WC_TEST_WALK", '0');                 // 0: the tree kernel up to TREE_MAXLEN, host-driven rounds beyond
+    sw.walk = !is("WC_TEST_WALK", '0');                 // 0: host-driven rounds at every region length
     sw.walk_hot = !is("WC_TEST_WALK_HOT", '0');         // 0: k_seg_walk without its early starters
-    sw.tree_tail = !is("WC_TEST_TREE_TAIL", '0');       // 0: host-driven rounds only
     sw.cells = !is("WC_TEST_CELLS", '0');               // 0: the row-block kernels (k_seg_seed / k_seg_bound / k_seg_bcollect)
     sw.cell_parts = cp ? std::max(1, atoi(cp)) : 0;     // at most this many workgroups per k_seg_job job (0: not set)
     sw.latency = !is("WC_TEST_LATENCY_MODE", '0');      // 0: the general path for every call
@@ -5549,19 +5548,16 @@ int run_repeat(wc_ctx *ctx, const TestSwitches &sw, const wc_reference *ref, con
         if ((rc = ts.sd_fail.reserve(sizeof(int) * Ns))) return rc;
         if (sm_out) {
             // the first repeat wrote the standard deviations sample-major already
-            launch_sd_fast(sds, ts.sdt.as<double>(), ref->B, Ns, ts.sd_avg.as<double>(), ts.sd_fail.as<int>(), out2, 1,
-                           ref->B, sw.sd_stage);
+            launch_sd_fast(sds, ts.sdt.as<double>(), ref->B, Ns, ts.sd_avg.as<double>(), ts.sd_fail.as<int>(), out2, 1, ref->B);
         } else if (Ns > 8) {
             // a batch: the sums run over a sample-major copy (a sample's standard deviations contiguous): in
             // the bin-major array every element of a sample sits in a cache line of its own, and 125
             // workgroups walking 55 337 such lines three times kept the side stream busy for 0.4 ms
             if ((rc = ts.sds.reserve(sizeof(double) * n))) return rc;
             launch_transpose((const double *)ts.sdt.as<double>(), ref->B, Ns, ts.sds.as<double>(), sds);
-            launch_sd_fast(sds, ts.sds.as<double>(), ref->B, Ns, ts.sd_avg.as<double>(), ts.sd_fail.as<int>(), out2, 1,
-                           ref->B, sw.sd_stage);
+            launch_sd_fast(sds, ts.sds.as<double>(), ref->B, Ns, ts.sd_avg.as<double>(), ts.sd_fail.as<int>(), out2, 1, ref->B);
         } else {
-            launch_sd_fast(sds, ts.sdt.as<double>(), ref->B, Ns, ts.sd_avg.as<double>(), ts.sd_fail.as<int>(), out2, Ns, 1,
-                           sw.sd_stage);
+            launch_sd_fast(sds, ts.sdt.as<double>(), ref->B, Ns, ts.sd_avg.as<double>(), ts.sd_fail.as<int>(), out2, Ns, 1);
         }
         only = ts.sd_fail.as<int>();
     }
@@ -5651,25 +5647,23 @@ static_assert(sizeof(HostStatus) <= 256, "the status words fit the pinned block 
 
 // Segment search over device regions.  Results: ts.out_val/out_x/out_y [n_regions, max_calls],
 // ts.out_n [n_regions], ts.whole [n_regions].
-// `tail` (optional; the batched `test` call): where call rows go.  When the regions fit the tree kernel
-// (<= TREE_MAXLEN bins, no -mineffectsize mask) the first round's hot regions are walked to the end by
-// k_seg_tree, one workgroup per region -- collect, decide, every child range, the order of the
-// segments and the call rows -- instead of one host-driven round per recursion level: rounds two and
-// later are a handful of short ranges each and cost a launch series and a count read-back apiece.
+// `rows` (optional; the batched `test` call): where call rows go.  With them, regions up to CJ_MAXLEN bins and no
+// -mineffectsize mask, k_seg_walk walks the whole recursion of every region in one launch and k_walk_rows writes the
+// call rows; every other call, and a call the walker gave up on, takes one host-driven round per recursion level.
 // tail_flag: the late repeats' overflow word (RepeatOut::tail_flag) the set-up kernel copies for the host, or NULL.
-struct TreeTail {
+struct CallRows {
     const double *ratio;     // cleaned ratios, as z_dev
     const int *gpos;         // genomic position of every kept bin
     double *reg_calls;       // [n_regions, max_calls, 5]
-    bool defer_status;       // the caller reads the tree kernel's status words after its own synchronize
+    bool defer_status;       // the caller reads the walker's status words after its own synchronize
     double *cwz_out;         // where the whole-region values go besides ts.whole (written on the side stream), or NULL
     int per_sample = 0;      // regions per sample (sample-major region list), or 0: k_seg_walk then takes every sample's
                              // first region first -- chromosome 1, the longest -- so that the launch ends on short ones
-    bool host_rounds = false;  // the walker and the tree kernel stay off (a repeat of a batch they gave up on)
+    bool host_rounds = false;  // the walker stays off (a repeat of a batch it gave up on)
 };
 struct SegOut {                     // what run_stouffer leaves for its caller
-    bool status_deferred = false;  // the walker / tree kernel wrote the call rows; the caller checks its counters after
-    int64_t seg_bound = 0;         // its synchronize: [3] / [6] non-zero = it gave up, [4] beyond seg_bound = too many
+    bool status_deferred = false;  // the walker wrote the call rows; the caller checks its counters after its
+    int64_t seg_bound = 0;         // synchronize: [6] non-zero = it gave up, [4] beyond seg_bound = too many
     int64_t segs = 0;              // segments in ts.seg whose call rows are still to be written (k_call_post)
 };
 // Batches whose regions fit the fused set-up kernel (<= TREE_MAXLEN bins, no -mineffectsize mask): cleaning,
@@ -5714,100 +5708,123 @@ static int reserve_segmentation(TestState &ts, int64_t n_regions, int64_t total_
     return ts.tmax.reserve(sizeof(double) * nblk);
 }
 
-int run_stouffer(wc_ctx *ctx, const TestSwitches &sw, const double *z_dev, const Region *regions_dev, int64_t n_regions,
-                 int64_t total_len, int64_t max_n, double thr, int min_search, int max_calls, hipStream_t stream,
-                 SegOut &out, const int *tail_flag, const double *ratio_dev = nullptr, double min_effect = 0.0,
-                 int64_t bits_upper = 0, const TreeTail *tail = nullptr, const FusedSetup *fused = nullptr) {
+// What the stages of one run_stouffer call share: the caller's arguments, the capacities and pointers of the
+// workspaces, and the job lists of the host-driven rounds.
+struct SegCall {
+    const double *z;
+    const Region *regions;
+    int64_t n_regions, total_len, max_n;
+    double thr;
+    int min_search, max_calls;
+    hipStream_t stream;
+    int64_t job_cap, seg_cap, n_jobs;        // n_jobs: the jobs of this round (cur); the next round's grow in next
+    int max_chunks;
+    int *counters, *hot, *brute;             // counters: [1] next jobs [2] hot [3] brute [4] segments [6] the walker gave up
+    Job *cur, *next;
+    int *h = nullptr;                        // where the counters' read-backs land (pinned)
+    const unsigned int *bits = nullptr;      // -mineffectsize: one validity bit per window (wisetools.py:479-487), or NULL
+    const long long *bit_off = nullptr;
+    unsigned long long *work = nullptr;      // profiling: evaluation counters of the search kernels, or NULL
+};
+
+// -mineffectsize: u_hi, the smallest double >= 1 with fabs(u - 1.0) >= min_effect, and u_lo, the largest <= 1 -- found
+// with k_window_valid_count's own expression by bisection over the ordered bit patterns (monotone on each side).
+// NaN where no double on that side passes.
+static void mineffect_thresholds(double min_effect, double &u_hi, double &u_lo) {
+    auto passes = [min_effect](double u) { return fabs(u - 1.0) >= min_effect; };
+    u_hi = u_lo = NAN;
+    if (passes(INFINITY)) {
+        uint64_t lo = wc::f64_ordered(1.0), hi = wc::f64_ordered(INFINITY);     // passes(hi) holds
+        if (passes(1.0)) hi = lo;
+        while (lo < hi) {
+            const uint64_t mid = lo + ((hi - lo) >> 1);
+            if (passes(wc::f64_from_ordered(mid))) hi = mid; else lo = mid + 1;
+        }
+        u_hi = wc::f64_from_ordered(hi);
+    }
+    if (passes(-INFINITY)) {
+        uint64_t lo = wc::f64_ordered(-INFINITY), hi = wc::f64_ordered(1.0);     // passes(lo) holds
+        if (passes(1.0)) lo = hi;
+        while (lo < hi) {
+            const uint64_t mid = lo + ((hi - lo + 1) >> 1);
+            if (passes(wc::f64_from_ordered(mid))) lo = mid; else hi = mid - 1;
+        }
+        u_lo = wc::f64_from_ordered(lo);
+    }
+}
+
+// -mineffectsize: one validity bit per window (wisetools.py:479-487)
+static int seg_mask(TestState &ts, SegCall &c, bool sorted, const double *ratio_dev, double min_effect, int64_t bits_upper) {
+    int rc;
+    WC_CHECK(ratio_dev, WC_E_ARG, "segments: mineffectsize needs the ratio vector");
+    const int64_t words = bits_upper / 32 + 2;
+    if ((rc = ts.win_bits.reserve(sizeof(unsigned int) * words))) return rc;
+    if ((rc = ts.bit_off.reserve(sizeof(long long) * c.n_regions))) return rc;
+    WC_HIP(hipMemsetAsync(ts.win_bits.p, 0, sizeof(unsigned int) * words, c.stream));
+    hipLaunchKernelGGL(k_bit_offsets, dim3(1), dim3(1), 0, c.stream, c.regions, c.n_regions, ts.bit_off.as<long long>());
+    if (sorted) {
+        WC_CHECK(c.max_n * 8 <= 64 * 1024 - 1024, WC_E_LIMIT, "segments: region too long for the sorted-insert median filter");
+        hipLaunchKernelGGL(k_window_valid, dim3((unsigned)c.max_n, (unsigned)c.n_regions), dim3(64),
+                           sizeof(double) * (c.max_n + 1), c.stream, ratio_dev, c.regions, ts.bit_off.as<long long>(),
+                           min_effect, ts.win_bits.as<unsigned int>());
+    } else {
+        double u_hi, u_lo;
+        mineffect_thresholds(min_effect, u_hi, u_lo);
+        hipLaunchKernelGGL(k_window_valid_count, dim3((unsigned)cdiv(c.max_n, 256), (unsigned)c.n_regions), dim3(256),
+                           0, c.stream, ratio_dev, c.regions, ts.bit_off.as<long long>(), min_effect, u_hi, u_lo,
+                           ts.win_bits.as<unsigned int>());
+    }
+    c.bits = ts.win_bits.as<unsigned int>();
+    c.bit_off = ts.bit_off.as<long long>();
+    return WC_OK;
+}
+
+static void init_jobs(TestState &ts, const SegCall &c) {        // the root jobs of the host-driven rounds: one per region
+    hipLaunchKernelGGL(k_init_jobs, dim3((unsigned)cdiv(c.n_regions, 256)), dim3(256), 0, c.stream, c.regions, c.n_regions,
+                       ts.jobs_a.as<Job>(), c.counters);
+}
+
+// Everything in front of the search: the -mineffectsize mask; prefix sums (they zero the counters), whole-region values
+// and root jobs, or the `fused` launch for all three; the block tables.  The walker needs no job list: k_init_jobs stays
+// off its path (walk_attempt launches it if the walker gives up).
+static int seg_setup(wc_ctx *ctx, const TestSwitches &sw, SegCall &c, const double *ratio_dev, double min_effect,
+                     int64_t bits_upper, const CallRows *rows, const FusedSetup *fused, bool walk_path, WalkHot &whot) {
     TestState &ts = ctx->ts;
     int rc;
-    out = SegOut{};
-    if (n_regions == 0) return WC_OK;
-    const int64_t job_cap = n_regions + total_len / 4 + 64;
-    const int64_t seg_cap = n_regions * (int64_t)max_calls + 64;
-    const int max_chunks = (int)std::max<int64_t>(1, cdiv((max_n + 1) / 2, ROWS_HALF));
-    // (rs: the search reads four lengths at a time (the candidate scan one trip ahead); the bound scan min len + 128 past
-    //  the longest window, the certificate 1..64)
-    if ((rc = reserve_segmentation(ts, n_regions, total_len, job_cap, max_calls,
-                                   std::max<int64_t>(max_n + 80 + QB2, 2 * QB + 80 + QB2), stream)))
-        return rc;
-    if ((rc = ts.jobs_b.reserve(sizeof(Job) * job_cap))) return rc;
-    if ((rc = ts.job_res.reserve(sizeof(Extreme) * job_cap))) return rc;
-    if ((rc = ts.hot.reserve(sizeof(int) * 2 * job_cap))) return rc;
-
-    // -mineffectsize: one validity bit per window (wisetools.py:479-487)
-    const unsigned int *bits = nullptr;
-    const long long *bit_off = nullptr;
-    if (min_effect != 0.0) {
-        WC_CHECK(ratio_dev, WC_E_ARG, "segments: mineffectsize needs the ratio vector");
-        const int64_t words = bits_upper / 32 + 2;
-        if ((rc = ts.win_bits.reserve(sizeof(unsigned int) * words))) return rc;
-        if ((rc = ts.bit_off.reserve(sizeof(long long) * n_regions))) return rc;
-        WC_HIP(hipMemsetAsync(ts.win_bits.p, 0, sizeof(unsigned int) * words, stream));
-        hipLaunchKernelGGL(k_bit_offsets, dim3(1), dim3(1), 0, stream, regions_dev, n_regions, ts.bit_off.as<long long>());
-        if (sw.mineffect_sorted) {
-            WC_CHECK(max_n * 8 <= 64 * 1024 - 1024, WC_E_LIMIT, "segments: region too long for the sorted-insert median filter");
-            hipLaunchKernelGGL(k_window_valid, dim3((unsigned)max_n, (unsigned)n_regions), dim3(64),
-                               sizeof(double) * (max_n + 1), stream, ratio_dev, regions_dev,
-                               (const long long *)ts.bit_off.as<long long>(), min_effect, ts.win_bits.as<unsigned int>());
-        } else {
-            // u_hi: the smallest double >= 1 with fabs(u - 1.0) >= min_effect; u_lo: the largest <= 1 -- found
-            // with the kernel's own expression by bisection over the ordered bit patterns (monotone on each side)
-            auto passes = [&](double u) { return fabs(u - 1.0) >= min_effect; };
-            double u_hi = NAN, u_lo = NAN;
-            if (passes(INFINITY)) {
-                uint64_t lo = wc::f64_ordered(1.0), hi = wc::f64_ordered(INFINITY);     // passes(hi) holds
-                if (passes(1.0)) hi = lo;
-                while (lo < hi) {
-                    const uint64_t mid = lo + ((hi - lo) >> 1);
-                    if (passes(wc::f64_from_ordered(mid))) hi = mid; else lo = mid + 1;
-                }
-                u_hi = wc::f64_from_ordered(hi);
-            }
-            if (passes(-INFINITY)) {
-                uint64_t lo = wc::f64_ordered(-INFINITY), hi = wc::f64_ordered(1.0);     // passes(lo) holds
-                if (passes(1.0)) lo = hi;
-                while (lo < hi) {
-                    const uint64_t mid = lo + ((hi - lo + 1) >> 1);
-                    if (passes(wc::f64_from_ordered(mid))) lo = mid; else hi = mid - 1;
-                }
-                u_lo = wc::f64_from_ordered(lo);
-            }
-            hipLaunchKernelGGL(k_window_valid_count, dim3((unsigned)cdiv(max_n, 256), (unsigned)n_regions), dim3(256), 0,
-                               stream, ratio_dev, regions_dev, (const long long *)ts.bit_off.as<long long>(), min_effect,
-                               u_hi, u_lo, ts.win_bits.as<unsigned int>());
-        }
-        bits = ts.win_bits.as<unsigned int>();
-        bit_off = ts.bit_off.as<long long>();
-    }
-    unsigned long long *work = nullptr;     // profiling: evaluation counters of the search kernels
+    if (min_effect != 0.0 && (rc = seg_mask(ts, c, sw.mineffect_sorted, ratio_dev, min_effect, bits_upper))) return rc;
     if (ts.profile) {
         if ((rc = ts.prof_work.reserve(sizeof(unsigned long long) * 128))) return rc;      // 64 pairs {windows, bounds}
-        WC_HIP(hipMemsetAsync(ts.prof_work.p, 0, sizeof(unsigned long long) * 128, stream));
-        work = ts.prof_work.as<unsigned long long>();
+        WC_HIP(hipMemsetAsync(ts.prof_work.p, 0, sizeof(unsigned long long) * 128, c.stream));
+        c.work = ts.prof_work.as<unsigned long long>();
     }
-    int *counters = ts.job_cnt.as<int>();  // [1] next jobs [2] hot [3] brute [4] segments
-    int *hot = ts.hot.as<int>();
-    int *brute = hot + job_cap;
     if (fused)
-        hipLaunchKernelGGL(k_lat_setup<256>, dim3((unsigned)n_regions), dim3(256), sizeof(double) * (max_n + 1), stream,
-                           fused->zsrc, fused->rsrc, fused->nsrc, fused->str_i, fused->str_b, fused->B, fused->moff,
-                           fused->goff, fused->m2g, fused->sel, fused->n_sel, fused->minref, fused->zc, fused->rc,
-                           fused->gpos, fused->regions, ts.prefix.as<double>(), ts.reg_abs.as<double>(),
-                           ts.reg_flag.as<int>(), ts.whole.as<double>(), fused->whole_copy, ts.jobs_a.as<Job>(), counters,
-                           ts.out_n.as<int>(), (ts.job_cnt.as<int>() + 8), n_regions, tail_flag);
-    // Callers with call rows, regions up to CJ_MAXLEN bins, no -mineffectsize mask: the whole recursion of every region
-    // in ONE launch (k_seg_walk), no host round trip.  WC_TEST_WALK=0: the paths it replaces (tree kernel up to
-    // TREE_MAXLEN, host-driven rounds beyond).
-    const bool walk_path = tail && !bits && max_n <= CJ_MAXLEN && !tail->host_rounds && sw.walk;
-    const int64_t total = total_len + n_regions, nblk = cdiv(total, QB);
-    const int64_t nblk2 = cdiv(nblk, 4);
+        hipLaunchKernelGGL(k_lat_setup<256>, dim3((unsigned)c.n_regions), dim3(256), sizeof(double) * (c.max_n + 1),
+                           c.stream, fused->zsrc, fused->rsrc, fused->nsrc, fused->str_i, fused->str_b, fused->B,
+                           fused->moff, fused->goff, fused->m2g, fused->sel, fused->n_sel, fused->minref, fused->zc,
+                           fused->rc, fused->gpos, fused->regions, ts.prefix.as<double>(), ts.reg_abs.as<double>(),
+                           ts.reg_flag.as<int>(), ts.whole.as<double>(), fused->whole_copy, ts.jobs_a.as<Job>(),
+                           c.counters, ts.out_n.as<int>(), (ts.job_cnt.as<int>() + 8), c.n_regions, whot.tail_flag);
+    const int64_t total = c.total_len + c.n_regions, nblk2 = cdiv(cdiv(total, QB), 4);
     if ((rc = ts.tmin2.reserve(sizeof(double) * nblk2))) return rc;
     if ((rc = ts.tmax2.reserve(sizeof(double) * nblk2))) return rc;
-    auto block_tables = [&]() {
-        hipLaunchKernelGGL(k_block_minmax, dim3((unsigned)cdiv(total, 1024)), dim3(256), 0, stream,
-                           (const double *)ts.prefix.as<double>(), total, ts.tmin.as<double>(), ts.tmax.as<double>(),
-                           ts.tmin2.as<double>(), ts.tmax2.as<double>());
-    };
+    // k_seg_walk's early starters (WalkHot): listed by k_region_prefix; WC_TEST_WALK_HOT=0 switches them off
+    if (walk_path && !fused && sw.walk_hot) {
+        const size_t had = ts.walk_hot.bytes;
+        if ((rc = ts.walk_hot.reserve(sizeof(int) * (16 + 4096 + c.n_regions)))) return rc;
+        if (ts.walk_hot.bytes != had)      // a new buffer: its count starts at zero (k_walk_rows resets it after every walk)
+            WC_HIP(hipMemsetAsync(ts.walk_hot.p, 0, sizeof(int) * 16, c.stream));
+        whot.count = ts.walk_hot.as<int>();
+        whot.list = whot.count + 16;
+        whot.index = whot.count + 16 + 4096;
+        whot.cap = c.n_regions >= 4096 ? 4096 : 512;
+        whot.cut = 0.75 * c.thr;
+    }
+    if (!fused)
+        hipLaunchKernelGGL(k_region_prefix, dim3((unsigned)cdiv(c.n_regions, 4)), dim3(256), 0, c.stream, c.z,
+                           c.regions, c.n_regions, ts.prefix.as<double>(), ts.reg_abs.as<double>(),
+                           ts.reg_flag.as<int>(), c.counters, ts.out_n.as<int>(), (ts.job_cnt.as<int>() + 8), whot);
+    // The block tables: the walker's cell search, the quiet-job certificate (k_seg_quiet; measured -7 % per 250 kb batch
+    // and -17 % per 50 kb batch on data where 10-40 % of the regions hold a call) and the bound-driven rounds read them
     // (measured and not kept: ONE fork of the side stream behind k_clean for stdDevAvg + inflated outputs + whole-region
     //  values -- k_clean is as long without k_sd_fast beside it, k_block_minmax twice as long with it: 1.15 against 1.115 ms)
     // (prefix sums AND block tables by one 256-thread workgroup per region -- a thread per 16 consecutive bins, the tables
@@ -5815,288 +5832,270 @@ int run_stouffer(wc_ctx *ctx, const TestSwitches &sw, const double *z_dev, const
     // (a 256-thread workgroup per region -- 1 024 coalesced bins per trip, four wave scans, one barrier -- measured 53 us
     //  against this kernel's 49 at 125 x 50 kb: what these set-up launches wait for is the half of the chip k_sd_fast's
     //  1 024-thread workgroups hold on the side stream, not their own parallelism)
-    // k_seg_walk's early starters (WalkHot): listed by k_region_prefix; WC_TEST_WALK_HOT=0 switches them off
-    WalkHot whot{nullptr, nullptr, nullptr, 0, 0.0, tail_flag};
-    if (walk_path && !fused && sw.walk_hot) {
-        const int cap = n_regions >= 4096 ? 4096 : 512;
-        const size_t had = ts.walk_hot.bytes;
-        if ((rc = ts.walk_hot.reserve(sizeof(int) * (16 + 4096 + n_regions)))) return rc;
-        if (ts.walk_hot.bytes != had)      // a new buffer: its count starts at zero (k_walk_rows resets it after every walk)
-            WC_HIP(hipMemsetAsync(ts.walk_hot.p, 0, sizeof(int) * 16, stream));
-        whot.count = ts.walk_hot.as<int>();
-        whot.list = whot.count + 16;
-        whot.index = whot.count + 16 + 4096;
-        whot.cap = cap;
-        whot.cut = 0.75 * thr;
+    hipLaunchKernelGGL(k_block_minmax, dim3((unsigned)cdiv(total, 1024)), dim3(256), 0, c.stream, ts.prefix.as<double>(),
+                       total, ts.tmin.as<double>(), ts.tmax.as<double>(), ts.tmin2.as<double>(), ts.tmax2.as<double>());
+    if (fused) return WC_OK;
+    // The whole-region values are an output only: with somewhere to copy them (rows->cwz_out) they go to the side stream
+    // (one wave per region walks the region in numpy's order: 0.1 ms at 50 kb that the search does not have to wait for).
+    // (By the walker's own workgroups -- its last wave before the walk starts -- they were measured: k_seg_walk 265 -> 385 us
+    // at 125 x 50 kb, a 4 700-bin pairwise tree walked by one wave costs ~40 us; they stay a side-stream launch.)
+    hipStream_t ws = c.stream;
+    double *wcopy = nullptr;
+    const bool second = sw.second_side(rows && rows->per_sample > 0 ? c.n_regions / rows->per_sample : 0);
+    if (rows && rows->cwz_out && !c.bits) {
+        // (a second side stream for this launch alone was measured: it then runs beside the walk -- 180 us instead of 105,
+        //  the walk 277 instead of 267, 1 000 x 50 kb 7.69 instead of 7.34 ms; one side stream.  Big batches: see side_begin)
+        if ((rc = side_begin(ctx, c.stream, second))) return rc;
+        ws = second ? ctx->side2 : ctx->side;
+        wcopy = rows->cwz_out;
     }
-    if (!fused)
-    hipLaunchKernelGGL(k_region_prefix, dim3((unsigned)cdiv(n_regions, 4)), dim3(256), 0, stream, z_dev, regions_dev,
-                       n_regions, ts.prefix.as<double>(), ts.reg_abs.as<double>(), ts.reg_flag.as<int>(), counters,
-                       ts.out_n.as<int>(), (ts.job_cnt.as<int>() + 8), whot);
-    // The block tables: the walker's cell search, the quiet-job certificate (k_seg_quiet; measured -7 % per 250 kb batch
-    // and -17 % per 50 kb batch on data where 10-40 % of the regions hold a call) and the bound-driven rounds read them
-    block_tables();
-    const bool certify = true;         // (the certificate runs before every search round of the tree / masked paths)
-    // whole-region values (an output) and the root jobs of the host-driven rounds.  The walker needs no job list:
-    // k_init_jobs stays off its path.  (The whole-region values by the walker's own workgroups -- its last wave before
-    // the walk starts -- were measured: k_seg_walk 265 -> 385 us at 125 x 50 kb, a 4 700-bin pairwise tree walked by
-    // one wave costs ~40 us; they stay a side-stream launch.)
-    bool whole_second = false;
-    auto whole_and_jobs = [&](const bool jobs_too) -> int {
-        // the whole-region values are an output only -> side stream (one wave per region walks
-        // the region in numpy's order: 0.1 ms at 50 kb that the search does not have to wait for)
-        hipStream_t ws = stream;
-        double *wcopy = nullptr;
-        int rc2;
-        if (tail && tail->cwz_out && !bits) {
-            // (a second side stream for this launch alone was measured: it then runs beside the walk -- 180 us instead
-            //  of 105, the walk 277 instead of 267, 1 000 x 50 kb 7.69 instead of 7.34 ms; one side stream)
-            //  (big batches: the second side stream, see side_begin)
-            const bool second = sw.second_side(tail->per_sample > 0 ? n_regions / tail->per_sample : 0);
-            if ((rc2 = side_begin(ctx, stream, second))) return rc2;
-            ws = second ? ctx->side2 : ctx->side;
-            wcopy = tail->cwz_out;
-            whole_second = second;
-        }
-        hipLaunchKernelGGL(k_region_whole, dim3((unsigned)cdiv(n_regions, 4)), dim3(256), 0, ws, z_dev, regions_dev,
-                           n_regions, bits, bit_off, ts.whole.as<double>(), wcopy);
-        if (ws != stream && (rc2 = side_end(ctx, whole_second))) return rc2;
-        if (jobs_too)
-            hipLaunchKernelGGL(k_init_jobs, dim3((unsigned)cdiv(n_regions, 256)), dim3(256), 0, stream, regions_dev, n_regions,
-                               ts.jobs_a.as<Job>(), counters);
-        return WC_OK;
-    };
-    const bool walker_owns_setup = walk_path && !fused;
-    if (!fused && (rc = whole_and_jobs(!walker_owns_setup))) return rc;
-    Job *cur = ts.jobs_a.as<Job>(), *next = ts.jobs_b.as<Job>();
-    int64_t n_jobs = n_regions;
-    int guard = 0;
-    // Rounds that the tree kernel does not take over (regions beyond TREE_MAXLEN, callers without call rows) and
-    // that carry no -mineffectsize mask locate the extremes from the block bounds (k_seg_bound / k_seg_refine /
-    // k_seg_bcollect) instead of evaluating every window of every job that may hold a call.
-    const bool tree_ok0 = tail && !bits && max_n <= TREE_MAXLEN && !tail->host_rounds && sw.tree_tail;
-    if ((rc = ctx->ensure_pinned(256))) return rc;
-    int *h = ((HostStatus *)ctx->pinned)->counters;   // counter read-backs land in pinned memory
-    h[4] = 0;
-    // the walker or the tree kernel gave up: its call counts and counters [4] (segments) and [6] (gave up) start again
-    auto restart_counts = [&]() -> int {
-        WC_HIP(hipMemsetAsync(ts.out_n.p, 0, sizeof(int) * n_regions, stream));
-        WC_HIP(hipMemsetAsync(counters + 4, 0, sizeof(int), stream));
-        WC_HIP(hipMemsetAsync(counters + 6, 0, sizeof(int), stream));
-        return WC_OK;
-    };
-    // the caller looks at the status after ITS synchronize (one host round trip per batch instead of two; its ONE copy
-    // brings the counters and the flag words behind them) and repeats the batch with host-driven rounds if need be
-    auto defer_status = [&]() -> int {
+    hipLaunchKernelGGL(k_region_whole, dim3((unsigned)cdiv(c.n_regions, 4)), dim3(256), 0, ws, c.z, c.regions, c.n_regions,
+                       c.bits, c.bit_off, ts.whole.as<double>(), wcopy);
+    if (ws != c.stream && (rc = side_end(ctx, second))) return rc;
+    if (!walk_path) init_jobs(ts, c);
+    return WC_OK;
+}
+
+// The whole recursion of every region in ONE launch (k_seg_walk) and the call rows in a second (k_walk_rows), no host
+// round trip.  done: the walk's rows stand, or (rows.defer_status) the caller looks at the status after ITS synchronize
+// -- one host round trip per batch instead of two; its ONE copy brings the counters and the flag words behind them --
+// and repeats the batch with host-driven rounds if need be.  Not done: the walker gave up; its call counts and counters
+// [4] (segments) and [6] (gave up) start again and the root jobs it did not need are listed (jobs_missing).
+static int walk_attempt(TestState &ts, SegCall &c, const CallRows &rows, const WalkHot &whot, bool jobs_missing,
+                        bool verbose, SegOut &out, bool &done) {
+    done = true;
+    ts.mark(10, c.stream);
+    hipLaunchKernelGGL(k_seg_walk, dim3((unsigned)(c.n_regions + whot.cap)), dim3(256), 0, c.stream, c.counters, c.regions,
+                       (int)c.n_regions, ts.reg_flag.as<int>(), ts.prefix.as<double>(), ts.rs.as<double>(),
+                       ts.reg_abs.as<double>(), c.z, c.thr, c.min_search, ts.tmin.as<double>(), ts.tmax.as<double>(),
+                       ts.tmin2.as<double>(), ts.tmax2.as<double>(), ts.seg.as<Seg>(), (int)c.seg_cap, ts.out_n.as<int>(), c.work,
+                       (rows.per_sample > 1 && c.n_regions % rows.per_sample == 0) ? rows.per_sample : 0,   // (125 x 50 kb: 287 -> 255 us)
+                       whot);
+    hipLaunchKernelGGL(k_walk_rows, dim3(WALK_ROWS_GRID), dim3(256), 0, c.stream, ts.seg.as<Seg>(),
+                       (const int *)(c.counters + 4), (int)c.seg_cap, c.regions, rows.ratio, rows.gpos, c.max_calls,
+                       rows.reg_calls, whot.count);
+    ts.mark(11, c.stream);
+    // (h[6] non-zero = the walk gave up on some region, h[4] beyond seg_cap = more segments than the call rows hold)
+    if (rows.defer_status) {
         out.status_deferred = true;
-        out.seg_bound = seg_cap;
+        out.seg_bound = c.seg_cap;
         WC_HIP(hipGetLastError());
         return WC_OK;
-    };
-    if (walk_path) {
-        ts.mark(10, stream);
-        hipLaunchKernelGGL(k_seg_walk, dim3((unsigned)(n_regions + whot.cap)), dim3(256), 0, stream, counters, regions_dev,
-                           (int)n_regions, (const int *)ts.reg_flag.as<int>(), (const double *)ts.prefix.as<double>(),
-                           (const double *)ts.rs.as<double>(), (const double *)ts.reg_abs.as<double>(), z_dev, thr,
-                           min_search, (const double *)ts.tmin.as<double>(), (const double *)ts.tmax.as<double>(),
-                           (const double *)ts.tmin2.as<double>(), (const double *)ts.tmax2.as<double>(), ts.seg.as<Seg>(),
-                           (int)seg_cap, ts.out_n.as<int>(), work,
-                           (tail->per_sample > 1 && n_regions % tail->per_sample == 0) ? tail->per_sample : 0,   // (125 x 50 kb: 287 -> 255 us)
-                           whot);
-        hipLaunchKernelGGL(k_walk_rows, dim3(WALK_ROWS_GRID), dim3(256), 0, stream, (const Seg *)ts.seg.as<Seg>(),
-                           (const int *)(counters + 4), (int)seg_cap, regions_dev, tail->ratio, tail->gpos,
-                           max_calls, tail->reg_calls, whot.count);
-        ts.mark(11, stream);
-        // (h[6] non-zero = the walk gave up on some region, h[4] beyond seg_cap = more segments than the call rows hold)
-        if (tail->defer_status) return defer_status();
-        WC_HIP(hipMemcpyAsync(h, counters, sizeof(int) * 8, hipMemcpyDeviceToHost, stream));
-        WC_HIP(hipStreamSynchronize(stream));
-        if (h[6] == 0 && h[4] <= seg_cap) {
-            WC_HIP(hipGetLastError());
-            return WC_OK;
-        }
-        // rare: again on the host-driven path
-        if (sw.verbose)
-            fprintf(stderr, "wisecondor_amd: segmentation repeated on the host-driven rounds (walk status %d: 1 = region beyond %d "
-                            "bins, 2 = non-finite z, 4 = ties beyond the record, 8 = more than %d segments, 16 = stack; %d segments)\n",
-                    h[6], CJ_MAXLEN, TREE_SEGS, h[4]);
-        if ((rc = restart_counts())) return rc;
-        h[4] = 0;
-        if (walker_owns_setup)             // the root jobs the walker did not need
-            hipLaunchKernelGGL(k_init_jobs, dim3((unsigned)cdiv(n_regions, 256)), dim3(256), 0, stream, regions_dev, n_regions,
-                               ts.jobs_a.as<Job>(), counters);
     }
-    const bool tree_ok = tree_ok0 && !sw.walk;
-    const bool bound_path = !bits && !tree_ok;
-    // the end of a host-driven round: decide, the brute-force scan (its list grows in decide), the counters back
-    auto end_round = [&](int64_t n_hot) -> int {
-        if (n_hot > 0)
-            hipLaunchKernelGGL(k_seg_decide, dim3((unsigned)n_hot), dim3(256), 0, stream, (const Job *)cur,
-                               (const int *)hot, counters, regions_dev, z_dev, (const int2 *)ts.cand.as<int2>(),
-                               (const int *)ts.cand_cnt.as<int>(), thr, min_search, bits, bit_off, ts.seg.as<Seg>(),
-                               (int)seg_cap, next, (int)job_cap, brute, counters + 1);
-        hipLaunchKernelGGL(k_seg_brute, dim3((unsigned)n_jobs), dim3(256), 0, stream, (const Job *)cur,
-                           (const int *)brute, counters, regions_dev, z_dev, thr, min_search, bits, bit_off,
-                           ts.seg.as<Seg>(), (int)seg_cap, next, (int)job_cap, counters + 1);
-        WC_HIP(hipMemcpyAsync(h, counters, sizeof(int) * 8, hipMemcpyDeviceToHost, stream));
-        WC_HIP(hipStreamSynchronize(stream));
-        WC_CHECK(h[1] <= job_cap, WC_E_INTERNAL, "stouffer: job list overflow");
-        WC_CHECK(h[4] <= seg_cap, WC_E_LIMIT, "stouffer: more than max_calls=%d segments per region", max_calls);
-        n_jobs = h[1];
-        std::swap(cur, next);
+    WC_HIP(hipMemcpyAsync(c.h, c.counters, sizeof(int) * 8, hipMemcpyDeviceToHost, c.stream));
+    WC_HIP(hipStreamSynchronize(c.stream));
+    if (c.h[6] == 0 && c.h[4] <= c.seg_cap) {
+        WC_HIP(hipGetLastError());
         return WC_OK;
-    };
-    while (n_jobs > 0) {
+    }
+    // rare: again on the host-driven path
+    if (verbose)
+        fprintf(stderr, "wisecondor_amd: segmentation repeated on the host-driven rounds (walk status %d: 1 = region beyond %d "
+                        "bins, 2 = non-finite z, 4 = ties beyond the record, 8 = more than %d segments, 16 = stack; %d segments)\n",
+                c.h[6], CJ_MAXLEN, TREE_SEGS, c.h[4]);
+    WC_HIP(hipMemsetAsync(ts.out_n.p, 0, sizeof(int) * c.n_regions, c.stream));
+    WC_HIP(hipMemsetAsync(c.counters + 4, 0, sizeof(int), c.stream));
+    WC_HIP(hipMemsetAsync(c.counters + 6, 0, sizeof(int), c.stream));
+    c.h[4] = 0;
+    if (jobs_missing) init_jobs(ts, c);
+    done = false;
+    return WC_OK;
+}
+
+// ---- the host-driven rounds: one round per recursion level, by one of three strategies
+// Jobs up to CJ_MAXLEN bins, no mask: one workgroup per job (or several: parts) finds the extremes from cell bounds and
+// lists the candidates (k_seg_job / k_seg_merge).  Every job goes on to k_seg_decide.
+static int round_cells(TestState &ts, const SegCall &c, int parts_switch) {
+    int rc;
+    const int64_t n_jobs = c.n_jobs;
+    WC_HIP(hipMemsetAsync(c.counters + 1, 0, sizeof(int) * 3, c.stream));      // next jobs, hot, brute
+    if ((rc = ts.cell_state.reserve(sizeof(CellJobState) * n_jobs))) return rc;
+    if ((rc = ts.cell_rec.reserve(sizeof(CellRec) * 2 * CJ_GREC * n_jobs))) return rc;
+    WC_HIP(hipMemsetAsync(ts.cell_state.p, 0, sizeof(CellJobState) * n_jobs, c.stream));
+    // a round of many jobs fills the chip with one workgroup per job (parts repeat the set-up and the seed);
+    // a round of few jobs -- the later rounds -- is as long as its longest job: several workgroups per job
+    const int max_parts =
+        std::max(1, std::min(cell_parts((int)c.max_n), parts_switch ? parts_switch : (n_jobs >= 2048 ? 1 : CJ_MAXPARTS)));
+    hipLaunchKernelGGL(k_seg_job, dim3((unsigned)max_parts, (unsigned)n_jobs), dim3(256), 0, c.stream, c.cur,
+                       (int)n_jobs, c.regions, ts.prefix.as<double>(), ts.rs.as<double>(), ts.reg_abs.as<double>(),
+                       ts.reg_flag.as<int>(), c.thr, ts.tmin.as<double>(), ts.tmax.as<double>(), ts.tmin2.as<double>(),
+                       ts.tmax2.as<double>(), ts.cell_state.as<CellJobState>(), ts.cell_rec.as<CellRec>(), c.work);
+    hipLaunchKernelGGL(k_seg_merge, dim3((unsigned)n_jobs), dim3(256), 0, c.stream, c.cur, (int)n_jobs, c.regions,
+                       ts.prefix.as<double>(), ts.rs.as<double>(), ts.reg_abs.as<double>(), ts.reg_flag.as<int>(),
+                       c.thr, ts.tmin.as<double>(), ts.tmax.as<double>(), ts.tmin2.as<double>(), ts.tmax2.as<double>(),
+                       ts.cell_state.as<CellJobState>(), ts.cell_rec.as<CellRec>(), c.hot, c.brute, c.counters,
+                       ts.cand.as<int2>(), ts.cand_cnt.as<int>(), c.work);
+    ts.mark(11, c.stream);
+    return WC_OK;
+}
+
+// The jobs whose extremes may hold a call (k_seg_classify) and how many they are.  The count lives on the device:
+// small rounds launch the follow-up kernels for the upper bound n_jobs and let surplus workgroups exit, which saves a
+// host round trip; big rounds read the count back.
+static int classify_round(TestState &ts, const SegCall &c, int certified, int &n_hot) {
+    ts.mark(11, c.stream);
+    hipLaunchKernelGGL(k_seg_classify, dim3((unsigned)c.n_jobs), dim3(64), 0, c.stream, c.cur, (int)c.n_jobs, c.regions,
+                       ts.reg_abs.as<double>(), ts.reg_flag.as<int>(), ts.partial.as<Extreme>(), c.max_chunks, c.thr,
+                       ts.job_res.as<Extreme>(), c.hot, c.brute, c.counters, ts.cand_cnt.as<int>(), certified, (const int *)nullptr);
+    n_hot = (int)c.n_jobs;
+    if (c.n_jobs * c.max_chunks > 65536) {
+        WC_HIP(hipMemcpyAsync(c.h, c.counters, sizeof(int) * 8, hipMemcpyDeviceToHost, c.stream));
+        WC_HIP(hipStreamSynchronize(c.stream));
+        n_hot = c.h[2];
+    }
+    return WC_OK;
+}
+
+// Jobs beyond CJ_MAXLEN bins (or WC_TEST_CELLS=0), no mask: the extremes located from the block bounds (k_seg_seed /
+// k_seg_bound / k_seg_bcollect) instead of evaluating every window of every job that may hold a call.
+static int round_row_blocks(TestState &ts, const SegCall &c, int &n_hot) {
+    int rc;
+    const int64_t n_jobs = c.n_jobs;
+    // about 16 384 workgroups in all: one per job when there are many jobs, every row block of a job in parallel when few
+    const unsigned per_job = (unsigned)std::min<int64_t>(c.max_chunks, std::max<int64_t>(1, 16384 / n_jobs));
+    if ((rc = ts.cbound.reserve(sizeof(ChunkBound) * n_jobs * c.max_chunks))) return rc;
+    if ((rc = ts.cuts.reserve(sizeof(unsigned long long) * 2 * n_jobs))) return rc;
+    hipLaunchKernelGGL(k_seg_seed, dim3((unsigned)n_jobs), dim3(256), 0, c.stream, c.cur, (int)n_jobs, c.regions,
+                       ts.rs.as<double>(), ts.reg_abs.as<double>(), ts.reg_flag.as<int>(), c.thr, ts.tmin.as<double>(),
+                       ts.tmax.as<double>(), ts.cuts.as<unsigned long long>());
+    hipLaunchKernelGGL(k_seg_bound, dim3(per_job, (unsigned)n_jobs), dim3(256), 0, c.stream, c.cur, (int)n_jobs,
+                       c.regions, ts.prefix.as<double>(), ts.rs.as<double>(), ts.reg_flag.as<int>(),
+                       ts.tmin.as<double>(), ts.tmax.as<double>(), ts.tmin2.as<double>(), ts.tmax2.as<double>(), c.max_chunks,
+                       ts.partial.as<Extreme>(), ts.cbound.as<ChunkBound>(), ts.cuts.as<unsigned long long>(), c.counters,
+                       c.counters + 1, c.work);
+    if ((rc = classify_round(ts, c, 0, n_hot))) return rc;
+    if (n_hot > 0) {
+        const unsigned per_hot = (unsigned)std::min<int64_t>(c.max_chunks, std::max<int64_t>(1, 16384 / n_hot));
+        hipLaunchKernelGGL(k_seg_bcollect, dim3(per_hot, (unsigned)n_hot), dim3(256), 0, c.stream, c.cur, c.hot,
+                           c.counters, c.regions, ts.prefix.as<double>(), ts.rs.as<double>(), ts.reg_abs.as<double>(),
+                           c.thr, ts.job_res.as<Extreme>(), ts.tmin.as<double>(), ts.tmax.as<double>(),
+                           ts.tmin2.as<double>(), ts.tmax2.as<double>(), c.max_chunks, ts.cbound.as<ChunkBound>(),
+                           ts.cand.as<int2>(), ts.cand_cnt.as<int>(), c.work);
+    }
+    return WC_OK;
+}
+
+// the masked value search: NW waves per block, the job's prefix slice in `dyn` bytes of LDS (PLDS) or read from memory
+template <bool PLDS, int NW>
+static void masked_search(TestState &ts, const SegCall &c, size_t dyn) {
+    hipLaunchKernelGGL((k_seg_search<true, PLDS, NW>), dim3((unsigned)c.max_chunks, (unsigned)c.n_jobs), dim3(64 * NW),
+                       dyn, c.stream, c.cur, (int)c.n_jobs, c.regions, ts.prefix.as<double>(), ts.rs.as<double>(),
+                       ts.reg_flag.as<int>(), c.max_chunks, c.bits, c.bit_off, ts.partial.as<Extreme>(), c.counters, 1,
+                       ts.sub.as<double2>(), c.work, (const int *)nullptr, c.counters + 1);
+}
+
+// -mineffectsize: the quiet-job certificate (k_seg_quiet), then every window of every job that is left (k_seg_search)
+// and the candidates of the hot ones (k_seg_collect), each under the mask.
+static int round_masked(TestState &ts, const SegCall &c, int &n_hot) {
+    int rc;
+    const int64_t n_jobs = c.n_jobs;
+    // about 8 192 workgroups in all (the certificate stages a job's block table per workgroup: half as many as the
+    // search's 16 384, each with two row blocks, measured 75 -> 61 us at 128 x 250 kb; the bound sweep loses with fewer)
+    const unsigned per_job_quiet = (unsigned)std::min<int64_t>(c.max_chunks, std::max<int64_t>(1, 8192 / n_jobs));
+    hipLaunchKernelGGL(k_seg_quiet, dim3(per_job_quiet, (unsigned)n_jobs), dim3(256), 0, c.stream, c.cur, (int)n_jobs,
+                       c.regions, ts.prefix.as<double>(), ts.rs.as<double>(), ts.reg_abs.as<double>(),
+                       ts.reg_flag.as<int>(), c.thr, ts.tmin.as<double>(), ts.tmax.as<double>(), c.work,
+                       (const int *)nullptr, (int)c.n_regions);
+    const bool plds = c.max_n + 1 <= 6144;                 // the longest region's prefix slice fits 48 KB of LDS
+    const bool wide = n_jobs * c.max_chunks <= 2048;         // few blocks: sixteen waves each
+    const size_t dyn = plds ? sizeof(double) * (c.max_n + 1) : 0;
+    if (plds) { if (wide) masked_search<true, 16>(ts, c, dyn); else masked_search<true, 4>(ts, c, dyn); }
+    else { if (wide) masked_search<false, 16>(ts, c, dyn); else masked_search<false, 4>(ts, c, dyn); }
+    if ((rc = classify_round(ts, c, 1, n_hot))) return rc;
+    if (n_hot > 0) {
+        // only a few blocks survive the pruning; sixteen waves each keep their scan short
+        hipLaunchKernelGGL(k_seg_collect, dim3((unsigned)c.max_chunks, (unsigned)n_hot), dim3(1024), 0, c.stream, c.cur,
+                           c.hot, c.counters, c.regions, ts.prefix.as<double>(), ts.rs.as<double>(),
+                           ts.reg_abs.as<double>(), ts.job_res.as<Extreme>(), ts.partial.as<Extreme>(), c.max_chunks,
+                           ts.sub.as<double2>(), c.bits, c.bit_off, ts.cand.as<int2>(), ts.cand_cnt.as<int>());
+    }
+    return WC_OK;
+}
+
+// the end of a host-driven round: decide, the brute-force scan (its list grows in decide), the counters back
+static int end_round(TestState &ts, SegCall &c, int n_hot) {
+    if (n_hot > 0)
+        hipLaunchKernelGGL(k_seg_decide, dim3((unsigned)n_hot), dim3(256), 0, c.stream, c.cur, c.hot, c.counters,
+                           c.regions, c.z, ts.cand.as<int2>(), ts.cand_cnt.as<int>(), c.thr, c.min_search, c.bits,
+                           c.bit_off, ts.seg.as<Seg>(), (int)c.seg_cap, c.next, (int)c.job_cap, c.brute, c.counters + 1);
+    hipLaunchKernelGGL(k_seg_brute, dim3((unsigned)c.n_jobs), dim3(256), 0, c.stream, c.cur, c.brute, c.counters,
+                       c.regions, c.z, c.thr, c.min_search, c.bits, c.bit_off, ts.seg.as<Seg>(), (int)c.seg_cap, c.next,
+                       (int)c.job_cap, c.counters + 1);
+    WC_HIP(hipMemcpyAsync(c.h, c.counters, sizeof(int) * 8, hipMemcpyDeviceToHost, c.stream));
+    WC_HIP(hipStreamSynchronize(c.stream));
+    WC_CHECK(c.h[1] <= c.job_cap, WC_E_INTERNAL, "stouffer: job list overflow");
+    WC_CHECK(c.h[4] <= c.seg_cap, WC_E_LIMIT, "stouffer: more than max_calls=%d segments per region", c.max_calls);
+    c.n_jobs = c.h[1];
+    std::swap(c.cur, c.next);
+    return WC_OK;
+}
+
+// cells: false = WC_TEST_CELLS=0, the row-block kernels at every length; parts_switch: WC_CELL_PARTS or 0
+static int host_rounds(TestState &ts, SegCall &c, bool cells, int parts_switch) {
+    enum { CELLS, ROW_BLOCKS, MASKED };
+    const int strategy = c.bits ? MASKED : (c.max_n <= CJ_MAXLEN && cells) ? CELLS : ROW_BLOCKS;
+    int rc, guard = 0;
+    while (c.n_jobs > 0) {
         WC_CHECK(++guard < 100000, WC_E_INTERNAL, "stouffer: recursion did not terminate");
         // per-round scratch is sized by the jobs of this round, not by the worst case
-        if ((rc = ts.partial.reserve(sizeof(Extreme) * n_jobs * max_chunks))) return rc;
-        if ((rc = ts.sub.reserve(sizeof(double2) * 8 * n_jobs * max_chunks))) return rc;
-        if ((rc = ts.cand.reserve(sizeof(int2) * 2 * CAND_CAP * n_jobs))) return rc;
-        if ((rc = ts.cand_cnt.reserve(sizeof(int) * 2 * n_jobs))) return rc;
-        // round counters are reset by the search kernel, candidate counts by classify
-        dim3 sg((unsigned)max_chunks, (unsigned)n_jobs);
-        ts.mark(10, stream);
-        // about 16 384 workgroups in all: one per job when there are many jobs, every row block of a job in
-        // parallel when there are few
-        const unsigned per_job = (unsigned)std::min<int64_t>(max_chunks, std::max<int64_t>(1, 16384 / n_jobs));
-        // (the certificate stages a job's block table per workgroup: half as many, each with two row blocks, measured
-        // 75 -> 61 us at 128 x 250 kb; the bound sweep loses with fewer)
-        const unsigned per_job_quiet = (unsigned)std::min<int64_t>(max_chunks, std::max<int64_t>(1, 8192 / n_jobs));
-        // jobs up to CJ_MAXLEN bins: one workgroup per job finds the extremes from cell bounds and lists the candidates
-        // (k_seg_job); WC_TEST_CELLS=0 keeps the row-block kernels (k_seg_seed / k_seg_bound / k_seg_bcollect)
-        const bool cell_path = bound_path && max_n <= CJ_MAXLEN && sw.cells;
-        if (cell_path) {
-            WC_HIP(hipMemsetAsync(counters + 1, 0, sizeof(int) * 3, stream));      // next jobs, hot, brute
-            if ((rc = ts.cell_state.reserve(sizeof(CellJobState) * n_jobs))) return rc;
-            if ((rc = ts.cell_rec.reserve(sizeof(CellRec) * 2 * CJ_GREC * n_jobs))) return rc;
-            WC_HIP(hipMemsetAsync(ts.cell_state.p, 0, sizeof(CellJobState) * n_jobs, stream));
-            // a round of many jobs fills the chip with one workgroup per job (parts repeat the set-up and the seed);
-            // a round of few jobs -- the later rounds -- is as long as its longest job: several workgroups per job
-            const int max_parts =
-                std::max(1, std::min(cell_parts((int)max_n), sw.cell_parts ? sw.cell_parts : (n_jobs >= 2048 ? 1 : CJ_MAXPARTS)));
-            hipLaunchKernelGGL(k_seg_job, dim3((unsigned)max_parts, (unsigned)n_jobs), dim3(256), 0, stream,
-                               (const Job *)cur, (int)n_jobs,
-                               regions_dev, (const double *)ts.prefix.as<double>(), (const double *)ts.rs.as<double>(),
-                               (const double *)ts.reg_abs.as<double>(), (const int *)ts.reg_flag.as<int>(), thr,
-                               (const double *)ts.tmin.as<double>(), (const double *)ts.tmax.as<double>(),
-                               (const double *)ts.tmin2.as<double>(), (const double *)ts.tmax2.as<double>(),
-                               ts.cell_state.as<CellJobState>(), ts.cell_rec.as<CellRec>(), work);
-            hipLaunchKernelGGL(k_seg_merge, dim3((unsigned)n_jobs), dim3(256), 0, stream, (const Job *)cur, (int)n_jobs,
-                               regions_dev, (const double *)ts.prefix.as<double>(), (const double *)ts.rs.as<double>(),
-                               (const double *)ts.reg_abs.as<double>(), (const int *)ts.reg_flag.as<int>(), thr,
-                               (const double *)ts.tmin.as<double>(), (const double *)ts.tmax.as<double>(),
-                               (const double *)ts.tmin2.as<double>(), (const double *)ts.tmax2.as<double>(),
-                               (const CellJobState *)ts.cell_state.as<CellJobState>(),
-                               (const CellRec *)ts.cell_rec.as<CellRec>(), hot, brute, counters, ts.cand.as<int2>(),
-                               ts.cand_cnt.as<int>(), work);
-            ts.mark(11, stream);
-            if ((rc = end_round(n_jobs))) return rc;
-            continue;
-        }
-        if (bound_path) {
-            if ((rc = ts.cbound.reserve(sizeof(ChunkBound) * n_jobs * max_chunks))) return rc;
-            if ((rc = ts.cuts.reserve(sizeof(unsigned long long) * 2 * n_jobs))) return rc;
-            hipLaunchKernelGGL(k_seg_seed, dim3((unsigned)n_jobs), dim3(256), 0, stream, (const Job *)cur, (int)n_jobs,
-                               regions_dev, (const double *)ts.rs.as<double>(), (const double *)ts.reg_abs.as<double>(),
-                               (const int *)ts.reg_flag.as<int>(), thr, (const double *)ts.tmin.as<double>(),
-                               (const double *)ts.tmax.as<double>(), ts.cuts.as<unsigned long long>());
-            hipLaunchKernelGGL(k_seg_bound, dim3(per_job, (unsigned)n_jobs), dim3(256), 0, stream, (const Job *)cur, (int)n_jobs,
-                               regions_dev, (const double *)ts.prefix.as<double>(), (const double *)ts.rs.as<double>(),
-                               (const int *)ts.reg_flag.as<int>(), (const double *)ts.tmin.as<double>(),
-                               (const double *)ts.tmax.as<double>(), (const double *)ts.tmin2.as<double>(),
-                               (const double *)ts.tmax2.as<double>(), max_chunks, ts.partial.as<Extreme>(),
-                               ts.cbound.as<ChunkBound>(), ts.cuts.as<unsigned long long>(), counters, counters + 1, work);
-        } else {
-        if (certify) {
-            // about 16 384 workgroups in all: one per job when there are many jobs, every row block
-            // of a job in parallel when there are few
-            hipLaunchKernelGGL(k_seg_quiet, dim3(per_job_quiet, (unsigned)n_jobs), dim3(256), 0, stream, cur, (int)n_jobs, regions_dev,
-                               (const double *)ts.prefix.as<double>(), (const double *)ts.rs.as<double>(),
-                               (const double *)ts.reg_abs.as<double>(), (const int *)ts.reg_flag.as<int>(), thr,
-                               (const double *)ts.tmin.as<double>(), (const double *)ts.tmax.as<double>(), work,
-                               (const int *)nullptr, (int)n_regions);
-        }
-        {
-            const bool plds = max_n + 1 <= 6144;      // the longest region's prefix slice fits 48 KB of LDS
-            const size_t dyn = plds ? sizeof(double) * (max_n + 1) : 0;
-#define WC_SEARCH(M, P_, NW_)                                                                                     \
-    hipLaunchKernelGGL((k_seg_search<M, P_, NW_>), sg, dim3(64 * NW_), dyn, stream, (const Job *)cur, (int)n_jobs,   \
-                       regions_dev, (const double *)ts.prefix.as<double>(), (const double *)ts.rs.as<double>(),     \
-                       (const int *)ts.reg_flag.as<int>(), max_chunks, bits, bit_off, ts.partial.as<Extreme>(), \
-                       counters, (int)certify, ts.sub.as<double2>(), work, (const int *)nullptr, counters + 1)
-#define WC_SEARCH_NW(M, P_) do { if (wide) WC_SEARCH(M, P_, 16); else WC_SEARCH(M, P_, 4); } while (0)
-            const bool wide = n_jobs * max_chunks <= 2048;     // few blocks: sixteen waves each
-            if (bits) { if (plds) WC_SEARCH_NW(true, true); else WC_SEARCH_NW(true, false); }
-            else {
-                // unmasked rounds get here only on the tree path (regions <= TREE_MAXLEN): the slice always fits
-                WC_CHECK(plds, WC_E_INTERNAL, "stouffer: unmasked value search beyond the LDS-staged sizes");
-                WC_SEARCH_NW(false, true);
-            }
-#undef WC_SEARCH_NW
-#undef WC_SEARCH
-        }
-        }   // !bound_path
-        ts.mark(11, stream);
-        hipLaunchKernelGGL(k_seg_classify, dim3((unsigned)n_jobs), dim3(64), 0, stream, (const Job *)cur, (int)n_jobs,
-                           regions_dev, (const double *)ts.reg_abs.as<double>(), (const int *)ts.reg_flag.as<int>(),
-                           (const Extreme *)ts.partial.as<Extreme>(), max_chunks, thr, ts.job_res.as<Extreme>(), hot,
-                           brute, counters, ts.cand_cnt.as<int>(), (int)(certify && !bound_path), (const int *)nullptr);
-        // The number of hot jobs lives on the device.  Small rounds (latency mode, child
-        // ranges) launch the follow-up kernels for the upper bound n_jobs and let surplus
-        // workgroups exit, which saves a host round trip; big rounds read the count back.
-        int n_hot = (int)n_jobs;
-        if (n_jobs * max_chunks > 65536) {
-            WC_HIP(hipMemcpyAsync(h, counters, sizeof(int) * 8, hipMemcpyDeviceToHost, stream));
-            WC_HIP(hipStreamSynchronize(stream));
-            n_hot = h[2];
-        }
-        if (guard == 1 && tree_ok && n_hot > 0) {
-            SdRider no_sd{};
-            InflateRider no_inf{};
-            hipLaunchKernelGGL(k_seg_tree, dim3((unsigned)n_hot), dim3(1024), sizeof(double) * (2 * max_n + 2), stream,
-                               counters, regions_dev, n_regions, (const int *)ts.reg_flag.as<int>(),
-                               (const double *)ts.prefix.as<double>(), (const double *)ts.rs.as<double>(),
-                               (const double *)ts.reg_abs.as<double>(), z_dev, tail->ratio, tail->gpos, thr, min_search,
-                               max_calls, tail->reg_calls, ts.out_n.as<int>(), (const Extreme *)ts.partial.as<Extreme>(),
-                               (const double2 *)ts.sub.as<double2>(), max_chunks, no_sd, no_inf,
-                               (const int *)hot, (const int *)(counters + 2));
-            WC_HIP(hipMemcpyAsync(h, counters, sizeof(int) * 8, hipMemcpyDeviceToHost, stream));
-            if (tail->defer_status) return defer_status();
-            WC_HIP(hipStreamSynchronize(stream));
-            if (h[3] == 0 && h[6] == 0) {          // no job for the exact scan, nothing the tree kernel gave up on
-                WC_CHECK(h[4] <= seg_cap, WC_E_LIMIT, "stouffer: more than max_calls=%d segments per region", max_calls);
-                WC_HIP(hipGetLastError());
-                return WC_OK;
-            }
-            // rare: start the round's second half again on the host-driven path
-            if ((rc = restart_counts())) return rc;
-        }
-        if (n_hot > 0 && bound_path) {
-            const unsigned per_hot = (unsigned)std::min<int64_t>(max_chunks, std::max<int64_t>(1, 16384 / n_hot));
-            hipLaunchKernelGGL(k_seg_bcollect, dim3(per_hot, (unsigned)n_hot), dim3(256), 0, stream, (const Job *)cur,
-                               (const int *)hot, (const int *)counters, regions_dev, (const double *)ts.prefix.as<double>(),
-                               (const double *)ts.rs.as<double>(), (const double *)ts.reg_abs.as<double>(), thr,
-                               (const Extreme *)ts.job_res.as<Extreme>(), (const double *)ts.tmin.as<double>(),
-                               (const double *)ts.tmax.as<double>(), (const double *)ts.tmin2.as<double>(),
-                               (const double *)ts.tmax2.as<double>(), max_chunks, (const ChunkBound *)ts.cbound.as<ChunkBound>(),
-                               ts.cand.as<int2>(), ts.cand_cnt.as<int>(), work);
-        } else if (n_hot > 0) {
-            // only a few blocks survive the pruning; sixteen waves each keep their scan short
-            hipLaunchKernelGGL(k_seg_collect, dim3((unsigned)max_chunks, (unsigned)n_hot), dim3(1024), 0, stream,
-                               (const Job *)cur, (const int *)hot, (const int *)counters, regions_dev,
-                               (const double *)ts.prefix.as<double>(), (const double *)ts.rs.as<double>(),
-                               (const double *)ts.reg_abs.as<double>(), (const Extreme *)ts.job_res.as<Extreme>(),
-                               (const Extreme *)ts.partial.as<Extreme>(), max_chunks,
-                               (const double2 *)ts.sub.as<double2>(), bits, bit_off, ts.cand.as<int2>(),
-                               ts.cand_cnt.as<int>());
-        }
-        if ((rc = end_round(n_hot))) return rc;
+        if ((rc = ts.partial.reserve(sizeof(Extreme) * c.n_jobs * c.max_chunks))) return rc;
+        if ((rc = ts.sub.reserve(sizeof(double2) * 8 * c.n_jobs * c.max_chunks))) return rc;
+        if ((rc = ts.cand.reserve(sizeof(int2) * 2 * CAND_CAP * c.n_jobs))) return rc;
+        if ((rc = ts.cand_cnt.reserve(sizeof(int) * 2 * c.n_jobs))) return rc;
+        // round counters are reset by the search kernel (the cell path: a memset), candidate counts by classify
+        ts.mark(10, c.stream);
+        int n_hot = (int)c.n_jobs;
+        if (strategy == CELLS) rc = round_cells(ts, c, parts_switch);
+        else if (strategy == ROW_BLOCKS) rc = round_row_blocks(ts, c, n_hot);
+        else rc = round_masked(ts, c, n_hot);
+        if (rc || (rc = end_round(ts, c, n_hot))) return rc;
     }
-    out.segs = h[4];                      // from the last round's read-back
-    if (h[4] > 0)
-        hipLaunchKernelGGL(k_seg_gather, dim3((unsigned)cdiv(h[4], 256)), dim3(256), 0, stream,
-                           (const Seg *)ts.seg.as<Seg>(), h[4], max_calls, ts.out_val.as<double>(), ts.out_x.as<int>(),
-                           ts.out_y.as<int>(), ts.out_n.as<int>(), (const int *)nullptr);
+    return WC_OK;
+}
+
+int run_stouffer(wc_ctx *ctx, const TestSwitches &sw, const double *z_dev, const Region *regions_dev, int64_t n_regions,
+                 int64_t total_len, int64_t max_n, double thr, int min_search, int max_calls, hipStream_t stream,
+                 SegOut &out, const int *tail_flag, const double *ratio_dev = nullptr, double min_effect = 0.0,
+                 int64_t bits_upper = 0, const CallRows *rows = nullptr, const FusedSetup *fused = nullptr) {
+    TestState &ts = ctx->ts;
+    int rc;
+    out = SegOut{};
+    if (n_regions == 0) return WC_OK;
+    SegCall c{z_dev, regions_dev, n_regions, total_len, max_n, thr, min_search, max_calls, stream};
+    c.job_cap = n_regions + total_len / 4 + 64;
+    c.seg_cap = n_regions * (int64_t)max_calls + 64;
+    c.max_chunks = (int)std::max<int64_t>(1, cdiv((max_n + 1) / 2, ROWS_HALF));
+    // (rs: the search reads four lengths at a time (the candidate scan one trip ahead); the bound scan min len + 128 past
+    //  the longest window, the certificate 1..64)
+    if ((rc = reserve_segmentation(ts, n_regions, total_len, c.job_cap, max_calls,
+                                   std::max<int64_t>(max_n + 80 + QB2, 2 * QB + 80 + QB2), stream)))
+        return rc;
+    if ((rc = ts.jobs_b.reserve(sizeof(Job) * c.job_cap))) return rc;
+    if ((rc = ts.job_res.reserve(sizeof(Extreme) * c.job_cap))) return rc;
+    if ((rc = ts.hot.reserve(sizeof(int) * 2 * c.job_cap))) return rc;
+    c.counters = ts.job_cnt.as<int>();
+    c.hot = ts.hot.as<int>();
+    c.brute = c.hot + c.job_cap;
+    c.cur = ts.jobs_a.as<Job>();
+    c.next = ts.jobs_b.as<Job>();
+    c.n_jobs = n_regions;
+    // WC_TEST_WALK=0: host-driven rounds at every region length
+    const bool walk_path = rows && min_effect == 0.0 && max_n <= CJ_MAXLEN && !rows->host_rounds && sw.walk;
+    WalkHot whot{nullptr, nullptr, nullptr, 0, 0.0, tail_flag};
+    if ((rc = seg_setup(ctx, sw, c, ratio_dev, min_effect, bits_upper, rows, fused, walk_path, whot))) return rc;
+    if ((rc = ctx->ensure_pinned(256))) return rc;
+    c.h = ((HostStatus *)ctx->pinned)->counters;   // counter read-backs land in pinned memory
+    c.h[4] = 0;
+    if (walk_path) {
+        bool done;
+        if ((rc = walk_attempt(ts, c, *rows, whot, !fused, sw.verbose, out, done)) || done) return rc;
+    }
+    if ((rc = host_rounds(ts, c, sw.cells, sw.cell_parts))) return rc;
+    out.segs = c.h[4];                    // from the last round's read-back
+    if (c.h[4] > 0)
+        hipLaunchKernelGGL(k_seg_gather, dim3((unsigned)cdiv(c.h[4], 256)), dim3(256), 0, stream, ts.seg.as<Seg>(),
+                           c.h[4], max_calls, ts.out_val.as<double>(), ts.out_x.as<int>(), ts.out_y.as<int>(),
+                           ts.out_n.as<int>(), (const int *)nullptr);
     WC_HIP(hipGetLastError());
     return WC_OK;
 }
@@ -6399,7 +6398,6 @@ int wc_std_dev_avg(wc_ctx *ctx, const double *sd, int64_t n_samples, int64_t n_b
                    int32_t *serial_samples) {
     WC_CHECK(ctx && sd && out && n_samples > 0 && n_bins > 0, WC_E_ARG, "stdDevAvg: bad argument");
     WC_HIP(hipSetDevice(ctx->device));
-    const TestSwitches sw = read_switches();
     TestState &ts = ctx->ts;
     const int64_t n = n_samples * n_bins;
     int rc;
@@ -6413,7 +6411,7 @@ int wc_std_dev_avg(wc_ctx *ctx, const double *sd, int64_t n_samples, int64_t n_b
     const int *only = nullptr;
     if (n_bins <= 65536) {
         launch_sd_fast(nullptr, ts.data.as<double>(), n_bins, n_samples, ts.sd_avg.as<double>(), ts.sd_fail.as<int>(),
-                       nullptr, 1, n_bins, sw.sd_stage);       // the caller's layout: a sample's values contiguous
+                       nullptr, 1, n_bins);       // the caller's layout: a sample's values contiguous
         only = ts.sd_fail.as<int>();
     }
     hipLaunchKernelGGL(k_sd_avg<64>, dim3((unsigned)cdiv(n_samples, 64)), dim3(256), 0, nullptr,
@@ -6487,9 +6485,9 @@ int wc_stouffer_segments(wc_ctx *ctx, const double *z, const double *ratio, doub
 struct BatchPlan {           // how one attempt of a batch runs
     bool lat = false;        // latency mode: no host round trip at all (capturable in a hipGraph)
     bool no_tail = false;    // the late repeats as a launch pair each (the one-workgroup form overflowed before)
-    bool no_tree = false;    // host-driven segmentation rounds only (the walker or the tree kernel gave up before)
+    bool host_rounds = false;    // host-driven segmentation rounds only (the walker gave up before)
 };
-enum class BatchStatus { ok, tail_overflow, tree_gave_up };    // what a general-path attempt's last synchronize found
+enum class BatchStatus { ok, tail_overflow, walk_gave_up };    // what a general-path attempt's last synchronize found
 
 // Everything wc_test_batch_dev enqueues for one attempt.  The general path synchronises per round and at the end and
 // reports in `status` whether the attempt has to be repeated.  Latency mode (plan.lat) has no host round trip at all;
@@ -6646,15 +6644,15 @@ static int test_batch_body(wc_ctx *ctx, hipStream_t stream, const TestSwitches &
                 bits_upper += Ns * (n * (n + 1) / 2);
             }
         ts.mark(3, stream);
-        const TreeTail tail{ts.rc.as<double>(), ts.gpos.as<int>(), ts.effect.as<double>(), calls && n_calls && !ts.profile,
-                            (!fuse && min_effect == 0.0) ? results_cwz : nullptr, n_sel, plan.no_tree};
+        const CallRows rows{ts.rc.as<double>(), ts.gpos.as<int>(), ts.effect.as<double>(), calls && n_calls && !ts.profile,
+                            (!fuse && min_effect == 0.0) ? results_cwz : nullptr, n_sel, plan.host_rounds};
         const FusedSetup fsu{zsrc, rsrc, nsrc, str_i, str_b, B, ref->moff_dev.as<int64_t>(), ref->goff_dev.as<int64_t>(),
                              ref->m2g.as<int>(), ts.sel.as<int>(), n_sel, (double)min_ref_bins, ts.zc.as<double>(),
                              ts.rc.as<double>(), ts.gpos.as<int>(), ts.regions.as<Region>(), results_cwz};
         cwz_done = results_cwz && (fuse || (min_effect == 0.0 && calls && n_calls));
         if ((rc = run_stouffer(ctx, sw, ts.zc.as<double>(), ts.regions.as<Region>(), n_regions, Ns * B, max_n, threshold,
                                3, max_calls, stream, seg, rep.tail_flag, ts.rc.as<double>(), min_effect, bits_upper,
-                               calls && n_calls ? &tail : nullptr, fuse ? &fsu : nullptr)))
+                               calls && n_calls ? &rows : nullptr, fuse ? &fsu : nullptr)))
             return rc;
     }
     ts.mark(4, stream);
@@ -6694,16 +6692,17 @@ static int test_batch_body(wc_ctx *ctx, hipStream_t stream, const TestSwitches &
                 return WC_OK;
             }
             if (seg.status_deferred) {
-                // the walker's / tree kernel's status words arrived with this synchronize
+                // the walker's status words arrived with this synchronize ([3], the exact scan's job count, stays as the
+                // set-up kernel zeroed it: k_seg_walk writes [4] and [6] only, k_walk_rows reads [4])
                 const int *h = hs->counters;
-                if (h[3] != 0 || h[6] != 0) {
+                if (h[6] != 0) {
                     if (sw.verbose)
-                        fprintf(stderr, "wisecondor_amd: batch repeated on the host-driven rounds (tree status %d, walk status %d: 1 = region "
+                        fprintf(stderr, "wisecondor_amd: batch repeated on the host-driven rounds (walk status %d: 1 = region "
                                         "beyond %d bins, 2 = non-finite z, 4 = ties beyond the record, 8 = more than %d segments, 16 = stack)\n",
-                                h[3], h[6], CJ_MAXLEN, TREE_SEGS);
+                                h[6], CJ_MAXLEN, TREE_SEGS);
                     // rare (non-finite region, tie overflow, deep recursion): the whole batch again with
                     // host-driven rounds -- the same results by construction, one batch time lost
-                    status = BatchStatus::tree_gave_up;
+                    status = BatchStatus::walk_gave_up;
                     return WC_OK;
                 }
                 WC_CHECK(h[4] <= seg.seg_bound, WC_E_LIMIT, "stouffer: more than max_calls=%d segments per region", max_calls);
@@ -6788,7 +6787,7 @@ int wc_test_batch_dev(wc_ctx *ctx, void *stream_, const wc_reference *ref, const
             BatchStatus status;
             const int rc2 = body(stream, plan, status);
             if (rc2 || status == BatchStatus::ok) return rc2;
-            (status == BatchStatus::tail_overflow ? plan.no_tail : plan.no_tree) = true;
+            (status == BatchStatus::tail_overflow ? plan.no_tail : plan.host_rounds) = true;
         }
         wc::set_error("test: the batch did not complete in three attempts");
         return WC_E_INTERNAL;
