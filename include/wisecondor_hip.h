@@ -263,6 +263,70 @@ const int32_t *wc_bam_mate_pos(const wc_bam *bam);
 void wc_bam_close(wc_bam *bam);
 
 /*
+ * The device reader: the same result as the reader above with the four arrays born on the device.  Only the compressed
+ * bytes cross to the device; BGZF inflate (one block per wave, CRC-32 checked), the record walk and the field extraction
+ * are HIP kernels (csrc/bamgpu.hip).
+ *
+ * Host stage (no GPU needed): wc_bamfile_open reads the whole file into host memory pinned for `device` (the calling
+ * thread's device is set to it; ordinary memory where device < 0 or no device is present), walks the BGZF block directory with the header checks of the reader above, inflates with zlib only
+ * the leading blocks the BAM header needs, and parses the header.  Its errors carry the codes the reader above returns
+ * for the same file: WC_E_IO cannot open; WC_E_FORMAT not BGZF, a truncated block or block header, an unusable BC field,
+ * a bad BAM\1 magic, data that ends inside the header.
+ *   wc_bamfile_info   out[0] references, [1] BGZF blocks, [2] the sum of their ISIZE fields (inflated bytes), [3] bytes of
+ *                     the file, [4] offset of the first record in the inflated stream, [5] bytes wc_bamfile_refs writes to
+ *                     names_out, [6] 1 when the buffer is pinned, [7] microseconds the pinned allocation took
+ *   wc_bamfile_refs   names_out / lengths_out as in wc_bam_refs
+ *
+ * Device stage: wc_bam_open_dev uploads the file of an opened host stage, runs the kernels on `stream` and returns when
+ * the arrays are complete; the host-stage handle may be closed afterwards.  The device memory the call needs is computed
+ * from the block directory before anything is allocated (compressed and inflated bytes, 2 bytes of record map per
+ * inflated byte, 15 bytes per possible record); budget_bytes <= 0 stands for 0.8 of the free device memory.  A need above
+ * the budget is WC_E_LIMIT ("needs X bytes, budget Y"): such a file takes the reader above.  Everything but the four
+ * arrays is freed before the call returns.  Further errors, with the codes of the reader above: WC_E_FORMAT a BGZF block
+ * whose deflate data or CRC is damaged, a record with block_size < 32, with fields that overrun its block_size, with a
+ * refID beyond the header, a chain of records that does not end exactly with the data; WC_E_ARG not coordinate-sorted;
+ * WC_E_LIMIT more than 2^31 - 1 placed records.  A file with ONE fault gets the code of the reader above.  With several
+ * the two may differ: the reader above reports the first fault in file order, this one reports a damaged BGZF block
+ * before any record fault, and a record-format fault (the first in file order) before an order fault -- so an unsorted
+ * pair followed by a bad record is WC_E_ARG there and WC_E_FORMAT here.
+ *   wc_bam_dev_info   as wc_bam_info; out[6] the device bytes the open needed, [7] the budget it was held against
+ *   wc_bam_dev_refs   as wc_bam_refs (host outputs)
+ *   wc_bam_dev_pos / _mapq / _flag / _mate_pos   DEVICE pointers, valid until wc_bam_dev_close
+ *   wc_bam_dev_fetch  copies of the four arrays in HOST memory (a NULL output is skipped); for tests
+ *   wc_bam_dev_times  milliseconds of the open's stages between device events: out[0] host to device copy, [1] inflate,
+ *                     [2] record starts (per-segment chain maps), [3] segment link, [4] record checks and counts,
+ *                     [5] field extraction, [6] order check and offsets; [7] the whole call by the host clock
+ * wc_bam_chain_segment: the record chain is resolved in segments of that many inflated bytes, segment s covering the
+ * offsets [s * segment, (s + 1) * segment) of the inflated stream (for tests that aim at the boundaries).
+ * wc_bgzf_inflate: the inflate kernel on any BGZF byte string (HOST pointers): bgzf_bytes [n] -> out [*out_len], cap the
+ * room in out (WC_E_ARG when it is too small); WC_E_FORMAT for a damaged block header, deflate stream or CRC.
+ * wc_convert_bam_dev: wc_convert_reads_ex_dev on the device arrays of an opened reader for the references refs[n_chrom]
+ * (header indices, ascending), gathered on the device where they are not contiguous; counts_out / stats_out are HOST
+ * memory, the call synchronises; a read beyond its chromosome's bins is WC_E_ARG as in wc_convert_reads_ex.
+ */
+typedef struct wc_bamfile wc_bamfile;
+typedef struct wc_bam_dev wc_bam_dev;
+int wc_bamfile_open(const char *path, int device, wc_bamfile **out);
+int wc_bamfile_info(const wc_bamfile *file, int64_t out[8]);
+int wc_bamfile_refs(const wc_bamfile *file, char *names_out, int64_t names_cap, int64_t *lengths_out);
+void wc_bamfile_close(wc_bamfile *file);
+int wc_bam_open_dev(wc_ctx *ctx, void *stream, const wc_bamfile *file, int64_t budget_bytes, wc_bam_dev **out);
+int wc_bam_dev_info(const wc_bam_dev *bam, int64_t out[8]);
+int wc_bam_dev_refs(const wc_bam_dev *bam, char *names_out, int64_t names_cap, int64_t *lengths_out, int64_t *offsets_out);
+const int32_t *wc_bam_dev_pos(const wc_bam_dev *bam);
+const uint8_t *wc_bam_dev_mapq(const wc_bam_dev *bam);
+const uint16_t *wc_bam_dev_flag(const wc_bam_dev *bam);
+const int32_t *wc_bam_dev_mate_pos(const wc_bam_dev *bam);
+int wc_bam_dev_times(const wc_bam_dev *bam, double out[8]);
+int wc_bam_dev_fetch(const wc_bam_dev *bam, int32_t *pos_out, uint8_t *mapq_out, uint16_t *flag_out, int32_t *mate_pos_out);
+void wc_bam_dev_close(wc_bam_dev *bam);
+int wc_bam_chain_segment(void);
+int wc_bgzf_inflate(wc_ctx *ctx, const unsigned char *bgzf_bytes, int64_t n, unsigned char *out, int64_t cap, int64_t *out_len);
+int wc_convert_bam_dev(wc_ctx *ctx, void *stream, const wc_bam_dev *bam, const int32_t *refs, int n_chrom, double binsize,
+                       int min_shift, int threshold, int min_mapq, int demand_pair, const int64_t *bin_offsets,
+                       int32_t *counts_out, int64_t *stats_out);
+
+/*
  * The numeric part of convertBam (wisetools.py:116-217) for all chromosomes of one file in one call: the paired-end
  * selection, duplicate removal, mapping-quality filter, the tower (RETRO) filter, binning.  wc_convert_reads[_dev] is
  * the function as toolConvert calls it (mapq 1, demandPair False); wc_convert_reads_ex[_dev] takes both parameters.

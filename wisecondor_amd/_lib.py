@@ -55,6 +55,23 @@ SIGNATURES = {
     "wc_bam_flag": (_vp, [_vp]),
     "wc_bam_mate_pos": (_vp, [_vp]),
     "wc_bam_close": (None, [_vp]),
+    "wc_bamfile_open": (_i32, [_c.c_char_p, _i32, _vp]),
+    "wc_bamfile_info": (_i32, [_vp, _vp]),
+    "wc_bamfile_refs": (_i32, [_vp, _vp, _i64, _vp]),
+    "wc_bamfile_close": (None, [_vp]),
+    "wc_bam_open_dev": (_i32, [_vp, _vp, _vp, _i64, _vp]),
+    "wc_bam_dev_info": (_i32, [_vp, _vp]),
+    "wc_bam_dev_refs": (_i32, [_vp, _vp, _i64, _vp, _vp]),
+    "wc_bam_dev_pos": (_vp, [_vp]),
+    "wc_bam_dev_mapq": (_vp, [_vp]),
+    "wc_bam_dev_flag": (_vp, [_vp]),
+    "wc_bam_dev_mate_pos": (_vp, [_vp]),
+    "wc_bam_dev_times": (_i32, [_vp, _vp]),
+    "wc_bam_dev_fetch": (_i32, [_vp, _vp, _vp, _vp, _vp]),
+    "wc_bam_dev_close": (None, [_vp]),
+    "wc_bam_chain_segment": (_i32, []),
+    "wc_bgzf_inflate": (_i32, [_vp, _vp, _i64, _vp, _i64, _vp]),
+    "wc_convert_bam_dev": (_i32, [_vp, _vp, _vp, _vp, _i32, _dbl, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "wc_convert_tile_reads": (_i32, []),
     "wc_convert_reads_dev": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _dbl, _i32, _i32, _vp, _vp, _vp]),
     "wc_convert_reads": (_i32, [_vp, _vp, _vp, _vp, _i32, _dbl, _i32, _i32, _vp, _vp, _vp]),

@@ -1,0 +1,862 @@
+// Device stage of the BAM reader: the compressed bytes of a whole file (host stage: bamfile.cpp) go to the device, where
+//   k_bg_inflate   one BGZF block per wave: raw deflate (stored / fixed / dynamic Huffman) into the block's place in one
+//                  contiguous inflated buffer, then the block's CRC-32 (sliced over the lanes, slices combined by
+//                  multiplication with x^(8 n) modulo the CRC polynomial); one status word per block
+//   k_bg_chain     record starts, by the block_size chain alone: per segment of BG_SEG inflated bytes, from its end towards
+//                  its start (a record is at least 36 bytes, so 36 consecutive offsets depend only on higher ones: 36
+//                  offsets per wave step), the map  entry offset -> where that chain leaves the segment
+//   k_bg_link      one wave walks the segments from the first record: the entry offset of every segment on the real chain
+//   k_bg_walk      one lane per segment follows the real chain through its segment: the format checks and counters of
+//                  bamio.cpp's Parser::feed; <false> counts the placed records, <true> (after k_bg_scan) writes their
+//                  fields in file order
+//   k_bg_order / k_bg_offsets   the coordinate-order check on neighbouring placed records, the per-reference offsets
+// Every loop is bounded by the bytes that are there (see the comments at the loops); a violation sets a status and the
+// wave stops.  The inflate kernel's back-references read the global output it has written itself: its LDS holds the
+// Huffman tables only ("convert: the device reader").
+#include <limits.h>
+
+#include <chrono>
+
+#include "bamfile.h"
+#include "ctx.h"
+
+namespace {
+
+const int BG_SEG = 65536;           // inflated bytes per segment of the record chain; offsets inside fit 16 bits
+const int BG_STEP = 36;             // the least record: block_size >= 32 plus its own 4 bytes
+const unsigned BG_FAR = 0xFFFEu;    // map word: the chain leaves the segment by 65 534 bytes or more (a record that long)
+const unsigned BG_BAD = 0xFFFFu;    // map word: the chain reaches a block_size below 32 or cut off by the end of the data
+const int BG_LIT_BITS = 10, BG_DIST_BITS = 9, BG_CL_BITS = 7;
+const double BG_BUDGET_FRACTION = 0.8;      // of the free device memory, when the caller names no budget
+
+enum { BG_E_DEFLATE = 1, BG_E_CRC = 2 };
+enum { BG_R_TRUNC = 0, BG_R_BS = 1, BG_R_FIELDS = 2, BG_R_REF = 3 };
+
+struct InflLds {
+    uint32_t crc_tab[256];
+    uint32_t lit_count[16], dist_count[16];
+    uint16_t lit[1 << BG_LIT_BITS];
+    uint16_t dist[1 << BG_DIST_BITS];           // the code-length code's table while a dynamic header is read
+    uint16_t lit_sorted[288];
+    uint16_t dist_sorted[32];
+    uint8_t lens[320];
+    uint8_t cl_lens[20];
+};
+
+__constant__ uint8_t bg_cl_order[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
+
+// a * b modulo the CRC-32 polynomial, reflected bit order (bit 31 is x^0): zlib's multmodp
+__device__ __forceinline__ uint32_t bg_multmodp(uint32_t a, uint32_t b) {
+    uint32_t p = 0;
+#pragma unroll 1
+    for (int i = 0; i < 32; ++i) {
+        if (a & (0x80000000u >> i)) p ^= b;
+        b = (b >> 1) ^ ((b & 1u) ? 0xEDB88320u : 0u);
+    }
+    return p;
+}
+
+// Canonical Huffman tables of `n` code lengths (LDS): `table` has 2^tbits entries (symbol << 4 | length; 0: the code is
+// longer than tbits, or absent), count[len] / sorted[] serve the longer codes as in zlib's puff.  Lane L assigns the codes
+// of length L.  Returns nonzero (in every lane) for an over-subscribed set, and for an incomplete one as zlib's
+// inflate_table judges it.  All 64 lanes call this together.
+__device__ __noinline__ int bg_build(const uint8_t *lens, int n, uint16_t *table, int tbits, uint32_t *count, uint16_t *sorted, bool strict,
+                        int lane) {
+    for (int i = lane; i < (1 << tbits); i += 64) table[i] = 0;
+    if (lane < 16) count[lane] = 0;
+    wc_sync();
+    for (int s = lane; s < n; s += 64) {
+        const int l = lens[s];
+        if (l) atomicAdd(&count[l], 1u);
+    }
+    wc_sync();
+    int left = 1, maxlen = 0;
+    bool over = false;
+#pragma unroll 1
+    for (int l = 1; l <= 15; ++l) {
+        const int c = (int)count[l];
+        left = (left << 1) - c;
+        if (left < 0) { over = true; left = 0; }
+        if (c) maxlen = l;
+    }
+    if (over || (left > 0 && maxlen != 0 && (strict || maxlen != 1))) return 1;
+    if (lane >= 1 && lane <= 15 && count[lane]) {
+        uint32_t code = 0, offs = 0;
+        for (int b = 1; b <= lane; ++b) {
+            code = (code + (b > 1 ? count[b - 1] : 0u)) << 1;
+            if (b < lane) offs += count[b];
+        }
+        for (int s = 0; s < n; ++s) {
+            if (lens[s] != lane) continue;
+            sorted[offs++] = (uint16_t)s;           // offs < n: the counts sum to at most n
+            if (lane <= tbits) {
+                const uint32_t rev = __brev(code) >> (32 - lane);
+                for (uint32_t e = rev; e < (1u << tbits); e += 1u << lane) table[e] = (uint16_t)((s << 4) | lane);
+            }
+            ++code;
+        }
+    }
+    wc_sync();
+    return 0;
+}
+
+// One symbol: at least one bit is consumed, or -1 is returned.  The caller has 15 bits or more in the buffer.
+__device__ __forceinline__ int bg_decode(uint64_t &bb, int &bc, const uint16_t *table, int tbits, const uint32_t *count,
+                                         const uint16_t *sorted) {
+    const uint32_t e = (uint32_t)__builtin_amdgcn_readfirstlane((int)table[(uint32_t)bb & ((1u << tbits) - 1u)]);
+    const int l = (int)(e & 15u);
+    if (l) {
+        bb >>= l;
+        bc -= l;
+        return (int)(e >> 4);
+    }
+    int code = 0, first = 0, index = 0;
+#pragma unroll 1
+    for (int len = 1; len <= 15; ++len) {
+        code |= (int)((bb >> (len - 1)) & 1u);
+        const int c = (int)count[len];
+        if (code - c < first) {
+            bb >>= len;
+            bc -= len;
+            return (int)sorted[index + (code - first)];
+        }
+        index += c;
+        first = (first + c) << 1;
+        code <<= 1;
+    }
+    return -1;
+}
+
+__global__ void __launch_bounds__(64) k_bg_inflate(const uint8_t *__restrict__ comp, const wc::BgzfBlock *__restrict__ dir,
+                                                   uint8_t *plain, int *__restrict__ status) {
+    __shared__ InflLds S;
+    const int lane = threadIdx.x;
+    const wc::BgzfBlock blk = dir[blockIdx.x];
+    const uint8_t *in = comp + blk.in_off;
+    uint8_t *dst = plain + blk.out_off;
+    const int in_len = blk.in_len, isize = (int)blk.isize;
+    const int in_bits = 8 * in_len;                 // in_len < 65536: BSIZE has 16 bits
+    const int skip0 = (int)((uintptr_t)in & 3);
+    const uint32_t *inw = reinterpret_cast<const uint32_t *>(in - skip0);   // aligned words; comp itself is aligned
+    const int lim_bytes = skip0 + in_len + 8;       // no load starts here or beyond (WC_BGZF_PAD covers the last block)
+
+    for (int k = 0; k < 4; ++k) {
+        uint32_t c = (uint32_t)(lane * 4 + k);
+        for (int j = 0; j < 8; ++j) c = (c >> 1) ^ ((c & 1u) ? 0xEDB88320u : 0u);
+        S.crc_tab[lane * 4 + k] = c;
+    }
+
+    // the bit reader: aligned 32-bit words; `loaded` counts the block's own bits that have entered the buffer, so
+    // loaded - bc bits are consumed.  Words from lim_bytes on are zeros: whoever consumes them fails the check below.
+    uint64_t bb = 0;
+    int bc = 0, loaded = 0, wi = 0;
+    auto init = [&](int bytepos) {                  // 0 <= bytepos <= in_len
+        const int at = skip0 + bytepos, skip = (at & 3) * 8;
+        wi = at >> 2;
+        bb = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)inw[wi]) >> skip;
+        ++wi;
+        bc = 32 - skip;
+        loaded = 8 * bytepos + bc;
+    };
+    auto refill = [&]() {                           // afterwards bc >= 33
+        if (bc <= 32) {
+            uint32_t w = 0;
+            if (4 * wi < lim_bytes) w = (uint32_t)__builtin_amdgcn_readfirstlane((int)inw[wi]);
+            ++wi;
+            bb |= (uint64_t)w << bc;
+            bc += 32;
+            loaded += 32;
+        }
+    };
+    auto bits = [&](int n) {
+        const uint32_t v = (uint32_t)bb & ((1u << n) - 1u);
+        bb >>= n;
+        bc -= n;
+        return (int)v;
+    };
+
+    int op = 0, err = 0;
+    bool last = false;
+    init(0);
+    // every pass consumes the 3 header bits; the test at the head ends the loop once the block's bits are used up
+    while (!last && !err) {
+        if (loaded - bc > in_bits) { err = 1; break; }
+        refill();
+        last = bits(1) != 0;
+        const int type = bits(2);
+        if (type == 0) {
+            bits(bc & 7);                           // to the byte boundary (loaded is a multiple of 8)
+            refill();
+            const int len = bits(16), nlen = bits(16);
+            const int bytepos = (loaded - bc) >> 3;
+            if ((len ^ 0xFFFF) != nlen || bytepos + len > in_len || op + len > isize) { err = 1; break; }
+            for (int i = lane; i < len; i += 64) dst[op + i] = in[bytepos + i];
+            op += len;
+            init(bytepos + len);
+            continue;
+        }
+        if (type == 3) { err = 1; break; }
+        int n_lit = 288, n_dist = 30;
+        if (type == 1) {
+            for (int s = lane; s < 288; s += 64) S.lens[s] = (uint8_t)(s < 144 ? 8 : s < 256 ? 9 : s < 280 ? 7 : 8);
+            if (lane < 32) S.lens[288 + lane] = 5;     // 32 codes of 5 bits: a complete set; 30 and 31 are refused below
+            n_dist = 32;
+        } else {
+            refill();
+            n_lit = bits(5) + 257;
+            n_dist = bits(5) + 1;
+            const int n_cl = bits(4) + 4;
+            if (n_lit > 286 || n_dist > 30) { err = 1; break; }
+            if (lane < 19) S.cl_lens[lane] = 0;
+            wc_sync();
+            for (int i = 0; i < n_cl; ++i) {
+                refill();
+                const int v = bits(3);
+                if (lane == 0) S.cl_lens[bg_cl_order[i]] = (uint8_t)v;
+            }
+            wc_sync();
+            if (bg_build(S.cl_lens, 19, S.dist, BG_CL_BITS, S.dist_count, S.dist_sorted, true, lane)) { err = 1; break; }
+            int i = 0, prev = 0;
+            const int n_all = n_lit + n_dist;
+            while (i < n_all) {                     // i grows in every pass
+                if (loaded - bc > in_bits) { err = 1; break; }
+                refill();
+                const int s = bg_decode(bb, bc, S.dist, BG_CL_BITS, S.dist_count, S.dist_sorted);
+                if (s < 0 || s > 18) { err = 1; break; }
+                if (s < 16) {
+                    if (lane == 0) S.lens[i] = (uint8_t)s;
+                    prev = s;
+                    ++i;
+                    continue;
+                }
+                int rep, val = 0;
+                if (s == 16) {
+                    if (i == 0) { err = 1; break; }
+                    val = prev;
+                    rep = 3 + bits(2);
+                } else if (s == 17) {
+                    rep = 3 + bits(3);
+                } else {
+                    rep = 11 + bits(7);
+                }
+                if (i + rep > n_all) { err = 1; break; }
+                for (int j = lane; j < rep; j += 64) S.lens[i + j] = (uint8_t)val;
+                prev = val;
+                i += rep;
+            }
+            if (err) break;
+        }
+        wc_sync();
+        if (type == 2 && S.lens[256] == 0) { err = 1; break; }
+        if (bg_build(S.lens, n_lit, S.lit, BG_LIT_BITS, S.lit_count, S.lit_sorted, false, lane)) { err = 1; break; }
+        if (bg_build(S.lens + n_lit, n_dist, S.dist, BG_DIST_BITS, S.dist_count, S.dist_sorted, false, lane)) { err = 1; break; }
+        // the symbols: every pass consumes a bit or more (bg_decode) or ends the loop
+        for (;;) {
+            if (loaded - bc > in_bits) { err = 1; break; }
+            refill();
+            const int sym = bg_decode(bb, bc, S.lit, BG_LIT_BITS, S.lit_count, S.lit_sorted);
+            if (sym < 0) { err = 1; break; }
+            if (sym < 256) {
+                if (op >= isize) { err = 1; break; }
+                if (lane == 0) dst[op] = (uint8_t)sym;
+                ++op;
+                continue;
+            }
+            if (sym == 256) break;
+            if (sym > 285) { err = 1; break; }
+            int len;
+            if (sym < 265) {
+                len = sym - 254;
+            } else if (sym == 285) {
+                len = 258;
+            } else {
+                const int eb = (sym - 261) >> 2;
+                len = 3 + ((4 + ((sym - 265) & 3)) << eb) + bits(eb);
+            }
+            refill();
+            const int ds = bg_decode(bb, bc, S.dist, BG_DIST_BITS, S.dist_count, S.dist_sorted);
+            if (ds < 0 || ds > 29) { err = 1; break; }
+            int dist;
+            if (ds < 4) {
+                dist = ds + 1;
+            } else {
+                const int eb = (ds >> 1) - 1;       // up to 13 bits; 15 + 13 <= the 33 bits refill() left
+                dist = 1 + ((2 + (ds & 1)) << eb) + bits(eb);
+            }
+            if (dist > op || op + len > isize) { err = 1; break; }
+            wc_sync();                              // this wave's earlier stores, before other lanes load them
+            uint8_t *to = dst + op;
+            const uint8_t *from = to - dist;        // every source byte lies below op: the lanes do not depend on each other
+            for (int i = lane; i < len; i += 64) to[i] = from[dist >= len ? i : i % dist];
+            op += len;
+        }
+    }
+    if (!err && (op != isize || loaded - bc > in_bits)) err = 1;
+    wc_sync();
+    int st = err ? BG_E_DEFLATE : 0;
+    if (!err) {
+        const int slice = (isize + 63) / 64;
+        const int begin = min(lane * slice, isize), end = min(begin + slice, isize);
+        uint32_t c = 0;
+        if (end > begin) {
+            c = 0xFFFFFFFFu;
+#pragma unroll 1
+            for (int i = begin; i < end; ++i) c = S.crc_tab[(c ^ dst[i]) & 0xFFu] ^ (c >> 8);
+            c ^= 0xFFFFFFFFu;
+            // crc(A B) = crc(A) x^(8 |B|) + crc(B): this slice's share of the block's CRC
+            uint32_t xp = 0x80000000u, b = 0x00800000u;         // x^0, x^8
+            for (int n = isize - end; n; n >>= 1) {
+                if (n & 1) xp = bg_multmodp(b, xp);
+                b = bg_multmodp(b, b);
+            }
+            c = bg_multmodp(xp, c);
+        }
+        for (int m = 1; m < 64; m <<= 1) c ^= (uint32_t)__shfl_xor((int)c, m);
+        if (c != blk.crc) st = BG_E_CRC;
+    }
+    if (lane == 0) status[blockIdx.x] = st;
+}
+
+__device__ __forceinline__ uint32_t bg_ld32(const uint8_t *p) {
+    return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+}
+__device__ __forceinline__ uint32_t bg_ld16(const uint8_t *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8); }
+
+// map[a], a an absolute inflated offset of segment s = a / BG_SEG ending at e = min((s + 1) BG_SEG, total): the chain
+// that starts at a leaves the segment at e + map[a] (BG_FAR: further than 16 bits say; BG_BAD: it does not leave it).
+__global__ void __launch_bounds__(64) k_bg_chain(const uint8_t *__restrict__ data, long long total, uint16_t *map) {
+    const int lane = threadIdx.x;
+    const long long base = (long long)blockIdx.x * BG_SEG;
+    const long long seg_end = min(base + BG_SEG, total);
+    const int n = (int)(seg_end - base);
+    for (int c = (n + BG_STEP - 1) / BG_STEP - 1; c >= 0; --c) {
+        const int o = c * BG_STEP + lane;
+        if (lane < BG_STEP && o < n) {
+            const long long a = base + o;
+            unsigned v = BG_BAD;
+            if (a + 4 <= total) {
+                const int bs = (int)bg_ld32(data + a);
+                if (bs >= 32) {
+                    const long long next = a + 4 + bs;      // >= a + 36: an offset of a step done before this one
+                    if (next >= seg_end) v = next - seg_end < (long long)BG_FAR ? (unsigned)(next - seg_end) : BG_FAR;
+                    else v = map[next];
+                }
+            }
+            map[a] = (uint16_t)v;
+        }
+        wc_sync();                                  // this step's stores, before the next step's loads
+    }
+}
+
+// entry[s]: the offset inside segment s at which the real chain enters it, -1 where it does not (a record covers the
+// whole segment, or the chain has ended).  One wave, every lane with the same values.
+__global__ void __launch_bounds__(64) k_bg_link(const uint8_t *__restrict__ data, long long total, long long first,
+                                                const uint16_t *__restrict__ map, int n_seg, int *entry) {
+    const int lane = threadIdx.x;
+    for (int s = lane; s < n_seg; s += 64) entry[s] = -1;
+    wc_sync();
+    long long a = first;
+    while (a < total) {                             // a moves to the end of its segment or beyond in every pass
+        const long long s = a / BG_SEG, seg_end = min((s + 1) * BG_SEG, total);
+        if (lane == 0) entry[s] = (int)(a - s * BG_SEG);
+        const unsigned v = map[a];
+        if (v == BG_BAD) break;
+        if (v != BG_FAR) { a = seg_end + v; continue; }
+        long long b = a;
+        while (b < seg_end) {                       // b grows by 36 or more
+            if (b + 4 > total) break;
+            const int bs = (int)bg_ld32(data + b);
+            if (bs < 32) break;
+            b += 4 + (long long)bs;
+        }
+        if (b < seg_end) break;                     // (not reached: BG_FAR says that the chain leaves the segment)
+        a = b;
+    }
+}
+
+template <bool WRITE>
+__global__ void __launch_bounds__(256) k_bg_walk(const uint8_t *__restrict__ data, long long total, int n_ref,
+                                                 const int *__restrict__ entry, int n_seg, int *__restrict__ cnt,
+                                                 const long long *__restrict__ seg_base, unsigned long long *stats,
+                                                 unsigned long long *err, int32_t *__restrict__ pos, uint8_t *__restrict__ mapq,
+                                                 uint16_t *__restrict__ flag, int32_t *__restrict__ mate, int32_t *__restrict__ refs) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= n_seg) return;
+    const int e = entry[t];
+    if (e < 0) {
+        if (!WRITE) cnt[t] = 0;
+        return;
+    }
+    long long a = (long long)t * BG_SEG + e;
+    const long long seg_end = min((long long)(t + 1) * BG_SEG, total);
+    long long idx = WRITE ? seg_base[t] : 0;
+    unsigned long long mapped = 0, unmapped = 0, nocoord = 0;
+    int placed = 0;
+    while (a < seg_end) {                           // a grows by 36 or more
+        int bad = -1;
+        int bs = 0;
+        if (a + 4 > total) bad = BG_R_TRUNC;
+        else {
+            bs = (int)bg_ld32(data + a);
+            if (bs < 32) bad = BG_R_BS;
+            else if (a + 4 + (long long)bs > total) bad = BG_R_TRUNC;
+        }
+        if (bad < 0) {
+            const uint8_t *r = data + a + 4;
+            const int ref = (int)bg_ld32(r), l_seq = (int)bg_ld32(r + 16);
+            const unsigned fl = bg_ld16(r + 14);
+            const long long need = 32 + (long long)r[8] + 4 * (long long)bg_ld16(r + 12) + ((long long)l_seq + 1) / 2 + (long long)l_seq;
+            if (l_seq < 0 || need > (long long)bs) bad = BG_R_FIELDS;
+            else if (ref >= n_ref) bad = BG_R_REF;
+            else {
+                if (fl & 4u) ++unmapped;
+                if (ref < 0) {
+                    ++nocoord;
+                } else {
+                    if (!(fl & 4u)) ++mapped;
+                    if (WRITE) {
+                        pos[idx] = (int32_t)bg_ld32(r + 4);
+                        mapq[idx] = r[9];
+                        flag[idx] = (uint16_t)fl;
+                        mate[idx] = (int32_t)bg_ld32(r + 24);
+                        refs[idx] = ref;
+                    }
+                    ++idx;
+                    ++placed;
+                }
+            }
+        }
+        if (bad >= 0) {
+            if (!WRITE) atomicMin(err, ((unsigned long long)a << 3) | (unsigned)bad);
+            break;
+        }
+        a += 4 + (long long)bs;
+    }
+    if (!WRITE) {
+        cnt[t] = placed;
+        if (mapped) atomicAdd(&stats[0], mapped);
+        if (unmapped) atomicAdd(&stats[1], unmapped);
+        if (nocoord) atomicAdd(&stats[2], nocoord);
+    }
+}
+
+// exclusive sums of cnt[0 .. n) into base[], the total into *sum; one workgroup
+__global__ void __launch_bounds__(256) k_bg_scan(const int *__restrict__ cnt, int n, long long *__restrict__ base,
+                                                 unsigned long long *sum) {
+    __shared__ long long part[256];
+    const int t = threadIdx.x, chunk = (n + 255) / 256;
+    const int lo = min(t * chunk, n), hi = min(lo + chunk, n);
+    long long s = 0;
+    for (int i = lo; i < hi; ++i) s += cnt[i];
+    part[t] = s;
+    wc_sync();
+    if (t == 0) {
+        long long run = 0;
+        for (int i = 0; i < 256; ++i) {
+            const long long v = part[i];
+            part[i] = run;
+            run += v;
+        }
+        *sum = (unsigned long long)run;
+    }
+    wc_sync();
+    s = part[t];
+    for (int i = lo; i < hi; ++i) {
+        base[i] = s;
+        s += cnt[i];
+    }
+}
+
+// err: the least (placed index << 2 | kind) with kind 1 a lower reference than the record before, 2 a lower position
+__global__ void __launch_bounds__(256) k_bg_order(const int32_t *__restrict__ refs, const int32_t *__restrict__ pos, long long n,
+                                                  unsigned long long *err) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x + 1;
+    if (i >= n) return;
+    const int a = refs[i - 1], b = refs[i];
+    const unsigned kind = b < a ? 1u : (b == a && pos[i] < pos[i - 1]) ? 2u : 0u;
+    if (kind) atomicMin(err, ((unsigned long long)i << 2) | kind);
+}
+
+// offsets[r] = the number of placed records of references below r (refs[] ascends)
+__global__ void __launch_bounds__(256) k_bg_offsets(const int32_t *__restrict__ refs, long long n, int n_ref,
+                                                    long long *__restrict__ offsets) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r > n_ref) return;
+    long long lo = 0, hi = n;
+    while (lo < hi) {
+        const long long mid = lo + (hi - lo) / 2;
+        if (refs[mid] < r) lo = mid + 1;
+        else hi = mid;
+    }
+    offsets[r] = lo;
+}
+
+struct DevMem {             // a device allocation of one call
+    void *p = nullptr;
+    DevMem() = default;
+    DevMem(const DevMem &) = delete;
+    DevMem &operator=(const DevMem &) = delete;
+    ~DevMem() { release(); }
+    int alloc(size_t bytes) {
+        hipError_t e = hipMalloc(&p, bytes ? bytes : 1);
+        if (e != hipSuccess) {
+            p = nullptr;
+            wc::set_error("hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
+            return WC_E_HIP;
+        }
+        return WC_OK;
+    }
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+    }
+    void *take() {
+        void *q = p;
+        p = nullptr;
+        return q;
+    }
+    template <class T> T *as() const { return reinterpret_cast<T *>(p); }
+};
+
+struct Events {
+    hipEvent_t ev[9] = {nullptr};
+    ~Events() {
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+};
+
+int first_bad_block(const std::vector<int> &status) {
+    for (size_t k = 0; k < status.size(); ++k)
+        if (status[k]) return (int)k;
+    return -1;
+}
+
+}  // namespace
+
+struct wc_bam_dev {
+    std::vector<std::string> names;
+    std::vector<int64_t> lengths, offsets;
+    void *pos = nullptr, *mapq = nullptr, *flag = nullptr, *mate = nullptr;
+    int64_t n = 0, mapped = 0, unmapped = 0, no_coordinate = 0, name_bytes = 0, need = 0, budget = 0;
+    double times[8] = {0};
+    ~wc_bam_dev() {
+        for (void *p : {pos, mapq, flag, mate})
+            if (p) (void)hipFree(p);
+    }
+};
+
+namespace {
+
+int open_dev(wc_ctx *ctx, hipStream_t stream, const wc_bamfile &f, int64_t budget, wc_bam_dev &h) {
+    const auto began = std::chrono::steady_clock::now();
+    h.names = f.names;
+    h.lengths = f.lengths;
+    h.name_bytes = f.name_bytes;
+    const int n_ref = (int)f.names.size();
+    h.offsets.assign((size_t)n_ref + 1, 0);
+    const int64_t total = f.total, n_blocks = (int64_t)f.blocks.size();
+    const int64_t n_seg = (total + BG_SEG - 1) / BG_SEG;
+    // the need, from the directory alone: compressed bytes, directory and status, the inflated bytes, the map (2 bytes per
+    // inflated byte), three words per segment, and the output of the most records the data can hold (36 bytes each;
+    // 15 bytes of fields per placed record, the reference numbers included)
+    const int64_t max_rec = total / BG_STEP + 1;
+    const int64_t need = (int64_t)f.size + WC_BGZF_PAD + n_blocks * (int64_t)(sizeof(wc::BgzfBlock) + 4) + total + 64 +
+                         2 * n_seg * BG_SEG + 16 * n_seg + 15 * max_rec + 8 * ((int64_t)n_ref + 1) + 4096;
+    if (budget <= 0) {
+        size_t free_b = 0, total_b = 0;
+        WC_HIP(hipMemGetInfo(&free_b, &total_b));
+        budget = (int64_t)(BG_BUDGET_FRACTION * (double)free_b);
+    }
+    h.need = need;
+    h.budget = budget;
+    WC_CHECK(need <= budget, WC_E_LIMIT, "bam: the device reader needs %lld bytes, budget %lld", (long long)need, (long long)budget);
+    WC_CHECK(n_seg < (int64_t)INT_MAX / 2 && n_blocks < (int64_t)INT_MAX, WC_E_LIMIT, "bam: %lld inflated bytes in one call",
+             (long long)total);
+    Events E;
+    for (hipEvent_t &e : E.ev) WC_HIP(hipEventCreate(&e));
+    DevMem comp, dir, status, plain, map, entry, cnt, base, misc;
+    int rc;
+    if ((rc = comp.alloc(f.size + WC_BGZF_PAD)) || (rc = dir.alloc(sizeof(wc::BgzfBlock) * (size_t)n_blocks)) ||
+        (rc = status.alloc(4 * (size_t)n_blocks)) || (rc = plain.alloc((size_t)total + 64)) ||
+        (rc = map.alloc(2 * (size_t)n_seg * BG_SEG)) || (rc = entry.alloc(4 * (size_t)n_seg)) ||
+        (rc = cnt.alloc(4 * (size_t)n_seg)) || (rc = base.alloc(8 * (size_t)n_seg)) || (rc = misc.alloc(64)))
+        return rc;
+    // misc: [0..2] mapped, unmapped, no_coordinate  [3] placed  [4] record error  [5] order error
+    unsigned long long *m = misc.as<unsigned long long>();
+    unsigned long long init[8] = {0, 0, 0, 0, ~0ull, ~0ull, 0, 0};
+    WC_HIP(hipEventRecord(E.ev[0], stream));
+    WC_HIP(hipMemcpyAsync(m, init, sizeof(init), hipMemcpyHostToDevice, stream));
+    WC_HIP(hipMemcpyAsync(comp.p, f.data, f.size + WC_BGZF_PAD, hipMemcpyHostToDevice, stream));
+    if (n_blocks) WC_HIP(hipMemcpyAsync(dir.p, f.blocks.data(), sizeof(wc::BgzfBlock) * (size_t)n_blocks, hipMemcpyHostToDevice, stream));
+    WC_HIP(hipEventRecord(E.ev[1], stream));
+    if (n_blocks)
+        hipLaunchKernelGGL(k_bg_inflate, dim3((unsigned)n_blocks), dim3(64), 0, stream, (const uint8_t *)comp.as<uint8_t>(),
+                           (const wc::BgzfBlock *)dir.as<wc::BgzfBlock>(), plain.as<uint8_t>(), status.as<int>());
+    WC_HIP(hipEventRecord(E.ev[2], stream));
+    if (n_seg)
+        hipLaunchKernelGGL(k_bg_chain, dim3((unsigned)n_seg), dim3(64), 0, stream, (const uint8_t *)plain.as<uint8_t>(),
+                           (long long)total, map.as<uint16_t>());
+    WC_HIP(hipEventRecord(E.ev[3], stream));
+    if (n_seg)
+        hipLaunchKernelGGL(k_bg_link, dim3(1), dim3(64), 0, stream, (const uint8_t *)plain.as<uint8_t>(), (long long)total,
+                           (long long)f.first_record, (const uint16_t *)map.as<uint16_t>(), (int)n_seg, entry.as<int>());
+    WC_HIP(hipEventRecord(E.ev[4], stream));
+    const unsigned walk_grid = (unsigned)((n_seg + 255) / 256);
+    if (n_seg) {
+        hipLaunchKernelGGL(k_bg_walk<false>, dim3(walk_grid), dim3(256), 0, stream, (const uint8_t *)plain.as<uint8_t>(),
+                           (long long)total, n_ref, (const int *)entry.as<int>(), (int)n_seg, cnt.as<int>(),
+                           (const long long *)nullptr, m, m + 4, (int32_t *)nullptr, (uint8_t *)nullptr, (uint16_t *)nullptr,
+                           (int32_t *)nullptr, (int32_t *)nullptr);
+        hipLaunchKernelGGL(k_bg_scan, dim3(1), dim3(256), 0, stream, (const int *)cnt.as<int>(), (int)n_seg,
+                           base.as<long long>(), m + 3);
+    }
+    WC_HIP(hipEventRecord(E.ev[5], stream));
+    WC_HIP(hipGetLastError());
+    std::vector<int> st((size_t)n_blocks, 0);
+    unsigned long long got[8];
+    if (n_blocks) WC_HIP(hipMemcpyAsync(st.data(), status.p, 4 * (size_t)n_blocks, hipMemcpyDeviceToHost, stream));
+    WC_HIP(hipMemcpyAsync(got, m, sizeof(got), hipMemcpyDeviceToHost, stream));
+    WC_HIP(hipStreamSynchronize(stream));
+    const int bad = first_bad_block(st);
+    WC_CHECK(bad < 0, WC_E_FORMAT, "bam: damaged BGZF block %d (%s)", bad,
+             st[(size_t)(bad < 0 ? 0 : bad)] == BG_E_CRC ? "CRC failed" : "inflate failed");
+    comp.release();
+    map.release();
+    if (got[4] != ~0ull) {
+        const long long at = (long long)(got[4] >> 3);
+        switch ((int)(got[4] & 7u)) {
+            case BG_R_BS: wc::set_error("bam: the record at inflated offset %lld has a block_size below its 32 fixed bytes", at); break;
+            case BG_R_FIELDS: wc::set_error("bam: the fields of the record at inflated offset %lld overrun its block_size", at); break;
+            case BG_R_REF: wc::set_error("bam: the record at inflated offset %lld names a reference beyond the %d of the header", at, n_ref); break;
+            default: wc::set_error("bam: truncated: the record at inflated offset %lld overruns the data (%lld bytes)", at, (long long)total);
+        }
+        return WC_E_FORMAT;
+    }
+    const unsigned long long n = got[3];
+    WC_CHECK(n <= (unsigned long long)INT32_MAX, WC_E_LIMIT, "bam: more than 2^31 - 1 placed records");
+    h.mapped = (int64_t)got[0];
+    h.unmapped = (int64_t)got[1];
+    h.no_coordinate = (int64_t)got[2];
+    h.n = (int64_t)n;
+    DevMem pos, mapq, flag, mate, refs, offs;
+    if ((rc = pos.alloc(4 * (size_t)n)) || (rc = mapq.alloc((size_t)n)) || (rc = flag.alloc(2 * (size_t)n)) ||
+        (rc = mate.alloc(4 * (size_t)n)) || (rc = refs.alloc(4 * (size_t)n)) || (rc = offs.alloc(8 * ((size_t)n_ref + 1))))
+        return rc;
+    WC_HIP(hipEventRecord(E.ev[6], stream));
+    if (n) {
+        hipLaunchKernelGGL(k_bg_walk<true>, dim3(walk_grid), dim3(256), 0, stream, (const uint8_t *)plain.as<uint8_t>(),
+                           (long long)total, n_ref, (const int *)entry.as<int>(), (int)n_seg, (int *)nullptr,
+                           (const long long *)base.as<long long>(), (unsigned long long *)nullptr, (unsigned long long *)nullptr,
+                           pos.as<int32_t>(), mapq.as<uint8_t>(), flag.as<uint16_t>(), mate.as<int32_t>(), refs.as<int32_t>());
+    }
+    WC_HIP(hipEventRecord(E.ev[7], stream));
+    if (n > 1)
+        hipLaunchKernelGGL(k_bg_order, dim3((unsigned)((n - 1 + 255) / 256)), dim3(256), 0, stream,
+                           (const int32_t *)refs.as<int32_t>(), (const int32_t *)pos.as<int32_t>(), (long long)n, m + 5);
+    hipLaunchKernelGGL(k_bg_offsets, dim3((unsigned)(n_ref / 256 + 1)), dim3(256), 0, stream, (const int32_t *)refs.as<int32_t>(),
+                       (long long)n, n_ref, offs.as<long long>());
+    WC_HIP(hipEventRecord(E.ev[8], stream));
+    WC_HIP(hipGetLastError());
+    WC_HIP(hipMemcpyAsync(got, m, sizeof(got), hipMemcpyDeviceToHost, stream));
+    WC_HIP(hipMemcpyAsync(h.offsets.data(), offs.p, 8 * ((size_t)n_ref + 1), hipMemcpyDeviceToHost, stream));
+    WC_HIP(hipStreamSynchronize(stream));
+    if (got[5] != ~0ull) {
+        const long long i = (long long)(got[5] >> 2);
+        int32_t two_ref[2] = {0, 0}, two_pos[2] = {0, 0};
+        WC_HIP(hipMemcpy(two_ref, refs.as<int32_t>() + i - 1, 8, hipMemcpyDeviceToHost));
+        WC_HIP(hipMemcpy(two_pos, pos.as<int32_t>() + i - 1, 8, hipMemcpyDeviceToHost));
+        if ((got[5] & 3u) == 1u)
+            wc::set_error("bam: not coordinate-sorted: placed record %lld of reference %d follows reference %d (the records of a "
+                          "reference must be contiguous, references in header order)", i, two_ref[1], two_ref[0]);
+        else
+            wc::set_error("bam: not coordinate-sorted: position %d follows %d in reference %d (placed record %lld)", two_pos[1],
+                          two_pos[0], two_ref[1], i);
+        return WC_E_ARG;
+    }
+    static const int pairs[7][2] = {{0, 1}, {1, 2}, {2, 3}, {3, 4}, {4, 5}, {6, 7}, {7, 8}};
+    for (int k = 0; k < 7; ++k) {
+        float ms = 0.f;
+        WC_HIP(hipEventElapsedTime(&ms, E.ev[pairs[k][0]], E.ev[pairs[k][1]]));
+        h.times[k] = ms;
+    }
+    h.times[7] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - began).count();
+    h.pos = pos.take();
+    h.mapq = mapq.take();
+    h.flag = flag.take();
+    h.mate = mate.take();
+    return WC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int wc_bam_chain_segment(void) { return BG_SEG; }
+
+int wc_bam_open_dev(wc_ctx *ctx, void *stream, const wc_bamfile *file, int64_t budget_bytes, wc_bam_dev **out) {
+    WC_CHECK(ctx && file && out, WC_E_ARG, "bam: NULL argument");
+    *out = nullptr;
+    WC_HIP(hipSetDevice(ctx->device));
+    wc_bam_dev *h = nullptr;
+    int rc;
+    try {
+        h = new wc_bam_dev();
+        rc = open_dev(ctx, (hipStream_t)stream, *file, budget_bytes, *h);
+    } catch (const std::exception &e) {
+        wc::set_error("bam: %s", e.what());
+        rc = WC_E_LIMIT;
+    }
+    if (rc != WC_OK) {
+        delete h;
+        return rc;
+    }
+    *out = h;
+    return WC_OK;
+}
+
+int wc_bam_dev_info(const wc_bam_dev *h, int64_t out[8]) {
+    WC_CHECK(h && out, WC_E_ARG, "bam: NULL argument");
+    out[0] = (int64_t)h->names.size();
+    out[1] = h->n;
+    out[2] = h->mapped;
+    out[3] = h->unmapped;
+    out[4] = h->no_coordinate;
+    out[5] = h->name_bytes;
+    out[6] = h->need;
+    out[7] = h->budget;
+    return WC_OK;
+}
+
+int wc_bam_dev_refs(const wc_bam_dev *h, char *names_out, int64_t names_cap, int64_t *lengths_out, int64_t *offsets_out) {
+    WC_CHECK(h && names_out && lengths_out && offsets_out, WC_E_ARG, "bam: NULL argument");
+    WC_CHECK(names_cap >= h->name_bytes, WC_E_ARG, "bam: %lld bytes of names, room for %lld", (long long)h->name_bytes,
+             (long long)names_cap);
+    char *w = names_out;
+    for (size_t r = 0; r < h->names.size(); ++r) {
+        memcpy(w, h->names[r].data(), h->names[r].size());
+        w += h->names[r].size();
+        *w++ = '\n';
+        lengths_out[r] = h->lengths[r];
+    }
+    for (size_t r = 0; r < h->offsets.size(); ++r) offsets_out[r] = h->offsets[r];
+    return WC_OK;
+}
+
+const int32_t *wc_bam_dev_pos(const wc_bam_dev *h) { return h ? (const int32_t *)h->pos : nullptr; }
+const uint8_t *wc_bam_dev_mapq(const wc_bam_dev *h) { return h ? (const uint8_t *)h->mapq : nullptr; }
+const uint16_t *wc_bam_dev_flag(const wc_bam_dev *h) { return h ? (const uint16_t *)h->flag : nullptr; }
+const int32_t *wc_bam_dev_mate_pos(const wc_bam_dev *h) { return h ? (const int32_t *)h->mate : nullptr; }
+
+int wc_bam_dev_times(const wc_bam_dev *h, double out[8]) {
+    WC_CHECK(h && out, WC_E_ARG, "bam: NULL argument");
+    for (int k = 0; k < 8; ++k) out[k] = h->times[k];
+    return WC_OK;
+}
+
+int wc_bam_dev_fetch(const wc_bam_dev *h, int32_t *pos_out, uint8_t *mapq_out, uint16_t *flag_out, int32_t *mate_pos_out) {
+    WC_CHECK(h, WC_E_ARG, "bam: NULL argument");
+    const size_t n = (size_t)h->n;
+    if (pos_out && n) WC_HIP(hipMemcpy(pos_out, h->pos, 4 * n, hipMemcpyDeviceToHost));
+    if (mapq_out && n) WC_HIP(hipMemcpy(mapq_out, h->mapq, n, hipMemcpyDeviceToHost));
+    if (flag_out && n) WC_HIP(hipMemcpy(flag_out, h->flag, 2 * n, hipMemcpyDeviceToHost));
+    if (mate_pos_out && n) WC_HIP(hipMemcpy(mate_pos_out, h->mate, 4 * n, hipMemcpyDeviceToHost));
+    return WC_OK;
+}
+
+void wc_bam_dev_close(wc_bam_dev *h) { delete h; }
+
+int wc_bgzf_inflate(wc_ctx *ctx, const unsigned char *bgzf_bytes, int64_t n, unsigned char *out, int64_t cap, int64_t *out_len) {
+    WC_CHECK(ctx && out_len && n >= 0 && cap >= 0 && (bgzf_bytes || n == 0) && (out || cap == 0), WC_E_ARG, "bgzf: unusable argument");
+    *out_len = 0;
+    std::vector<wc::BgzfBlock> blocks;
+    int64_t total = 0;
+    int rc = wc::bgzf_directory(bgzf_bytes, (size_t)n, blocks, total);
+    if (rc) return rc;
+    WC_CHECK(total <= cap, WC_E_ARG, "bgzf: %lld inflated bytes, room for %lld", (long long)total, (long long)cap);
+    WC_CHECK(blocks.size() < (size_t)INT_MAX, WC_E_LIMIT, "bgzf: %zu blocks in one call", blocks.size());
+    *out_len = total;
+    if (blocks.empty()) return WC_OK;
+    WC_HIP(hipSetDevice(ctx->device));
+    DevMem comp, dir, status, plain;
+    if ((rc = comp.alloc((size_t)n + WC_BGZF_PAD)) || (rc = dir.alloc(sizeof(wc::BgzfBlock) * blocks.size())) ||
+        (rc = status.alloc(4 * blocks.size())) || (rc = plain.alloc((size_t)total + 64)))
+        return rc;
+    WC_HIP(hipMemset(comp.as<uint8_t>() + n, 0, WC_BGZF_PAD));
+    WC_HIP(hipMemcpy(comp.p, bgzf_bytes, (size_t)n, hipMemcpyHostToDevice));
+    WC_HIP(hipMemcpy(dir.p, blocks.data(), sizeof(wc::BgzfBlock) * blocks.size(), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_bg_inflate, dim3((unsigned)blocks.size()), dim3(64), 0, (hipStream_t) nullptr,
+                       (const uint8_t *)comp.as<uint8_t>(), (const wc::BgzfBlock *)dir.as<wc::BgzfBlock>(), plain.as<uint8_t>(),
+                       status.as<int>());
+    WC_HIP(hipGetLastError());
+    std::vector<int> st(blocks.size(), 0);
+    WC_HIP(hipMemcpy(st.data(), status.p, 4 * blocks.size(), hipMemcpyDeviceToHost));
+    const int bad = first_bad_block(st);
+    WC_CHECK(bad < 0, WC_E_FORMAT, "bgzf: damaged BGZF block %d (%s)", bad,
+             st[(size_t)(bad < 0 ? 0 : bad)] == BG_E_CRC ? "CRC failed" : "inflate failed");
+    if (total) WC_HIP(hipMemcpy(out, plain.p, (size_t)total, hipMemcpyDeviceToHost));
+    return WC_OK;
+}
+
+int wc_convert_bam_dev(wc_ctx *ctx, void *stream_, const wc_bam_dev *h, const int32_t *refs, int n_chrom, double binsize,
+                       int min_shift, int threshold, int min_mapq, int demand_pair, const int64_t *bin_offsets,
+                       int32_t *counts_out, int64_t *stats_out) {
+    WC_CHECK(ctx && h && refs && bin_offsets && counts_out && stats_out, WC_E_ARG, "convert: NULL argument");
+    WC_CHECK(n_chrom >= 1 && n_chrom <= WC_CV_MAX_CHROM, WC_E_LIMIT, "convert: %d chromosomes (1..%d supported)", n_chrom,
+             WC_CV_MAX_CHROM);
+    const int64_t bins = bin_offsets[n_chrom];
+    WC_CHECK(bins >= 0 && bins <= (int64_t)INT_MAX, WC_E_LIMIT, "convert: %lld bins in one call", (long long)bins);
+    const int n_ref = (int)h->names.size();
+    std::vector<int64_t> ro((size_t)n_chrom + 1, 0);
+    bool contiguous = true;
+    for (int c = 0; c < n_chrom; ++c) {
+        WC_CHECK(refs[c] >= 0 && refs[c] < n_ref, WC_E_ARG, "convert: reference %d of %d", refs[c], n_ref);
+        ro[(size_t)c + 1] = ro[(size_t)c] + h->offsets[(size_t)refs[c] + 1] - h->offsets[(size_t)refs[c]];
+        if (c && h->offsets[(size_t)refs[c]] != h->offsets[(size_t)refs[c - 1] + 1]) contiguous = false;
+    }
+    const int64_t n = ro[(size_t)n_chrom];
+    const bool paired = demand_pair != 0;
+    WC_HIP(hipSetDevice(ctx->device));
+    hipStream_t stream = (hipStream_t)stream_;
+    int rc;
+    if ((rc = ctx->tmp_c.reserve(sizeof(int32_t) * (size_t)(bins + 1) + 64))) return rc;
+    int64_t *stats_dev = ctx->tmp_c.as<int64_t>();               // 8 words, then the counts
+    int32_t *counts_dev = reinterpret_cast<int32_t *>(stats_dev + 8);
+    const int64_t lo = h->offsets[(size_t)refs[0]];
+    const int32_t *pos = (const int32_t *)h->pos + lo, *mate = (const int32_t *)h->mate + lo;
+    const uint8_t *mapq = (const uint8_t *)h->mapq + lo;
+    const uint16_t *flag = (const uint16_t *)h->flag + lo;
+    if (!contiguous && n) {                                     // the picked references, gathered on the device
+        if ((rc = ctx->tmp_a.reserve(4 * (size_t)n)) || (rc = ctx->tmp_b.reserve((size_t)n)) ||
+            (paired && (rc = ctx->tmp_d.reserve(6 * (size_t)n + 8))))
+            return rc;
+        int32_t *mate_g = ctx->tmp_d.as<int32_t>();
+        uint16_t *flag_g = paired ? reinterpret_cast<uint16_t *>(mate_g + n) : nullptr;
+        for (int c = 0; c < n_chrom; ++c) {
+            const int64_t from = h->offsets[(size_t)refs[c]], k = ro[(size_t)c + 1] - ro[(size_t)c], to = ro[(size_t)c];
+            if (!k) continue;
+            WC_HIP(hipMemcpyAsync(ctx->tmp_a.as<int32_t>() + to, (const int32_t *)h->pos + from, 4 * (size_t)k, hipMemcpyDeviceToDevice, stream));
+            WC_HIP(hipMemcpyAsync(ctx->tmp_b.as<uint8_t>() + to, (const uint8_t *)h->mapq + from, (size_t)k, hipMemcpyDeviceToDevice, stream));
+            if (paired) {
+                WC_HIP(hipMemcpyAsync(mate_g + to, (const int32_t *)h->mate + from, 4 * (size_t)k, hipMemcpyDeviceToDevice, stream));
+                WC_HIP(hipMemcpyAsync(flag_g + to, (const uint16_t *)h->flag + from, 2 * (size_t)k, hipMemcpyDeviceToDevice, stream));
+            }
+        }
+        pos = ctx->tmp_a.as<int32_t>();
+        mapq = ctx->tmp_b.as<uint8_t>();
+        mate = mate_g;
+        flag = flag_g;
+    }
+    rc = wc_convert_reads_ex_dev(ctx, stream, pos, mapq, paired ? flag : nullptr, paired ? mate : nullptr, ro.data(), n_chrom,
+                                 binsize, min_shift, threshold, min_mapq, demand_pair, bin_offsets, counts_dev, stats_dev);
+    if (rc) return rc;
+    WC_HIP(hipMemcpyAsync(stats_out, stats_dev, sizeof(int64_t) * 8, hipMemcpyDeviceToHost, stream));
+    if (bins) WC_HIP(hipMemcpyAsync(counts_out, counts_dev, sizeof(int32_t) * (size_t)bins, hipMemcpyDeviceToHost, stream));
+    WC_HIP(hipStreamSynchronize(stream));
+    WC_CHECK(stats_out[4] == 0, WC_E_ARG,
+             "convert: %lld read(s) lie beyond their chromosome's last bin (a position past the header's length)",
+             (long long)stats_out[4]);
+    return WC_OK;
+}
+
+}  // extern "C"

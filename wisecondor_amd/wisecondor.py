@@ -99,8 +99,8 @@ def convert_output_names(paths, outdir):
 
 def toolConvertBatch(args):
     """`convertbatch infiles... outdir` (build-only): the same file per BAM as one `convert` each.  A reader thread
-    opens (reads, inflates, parses: native code, no GIL) file i + 1 and a writer thread stores file i - 1 while
-    file i is on the GPU."""
+    runs the host stage (file into pinned memory, block directory, header: native code, no GIL) of file i + 1 and a
+    writer thread stores file i - 1 while file i is on the GPU; the device stage of the reader runs on this thread."""
     import argparse
     import concurrent.futures
     outs = convert_output_names(args.infiles, args.outdir)
@@ -109,12 +109,27 @@ def toolConvertBatch(args):
     reader = concurrent.futures.ThreadPoolExecutor(max_workers=1)
     writer = concurrent.futures.ThreadPoolExecutor(max_workers=1)
     written = []
+    ahead = taken = None
     try:
-        ahead = reader.submit(wt.BamReads, args.infiles[0], args.io)
+        # the reader thread's share: the host stage of the device reader, or the whole host reader
+        if wt.CONVERT_READER == 'device':
+            def stage(path):
+                return wt.BamFile(path)
+        else:
+            def stage(path):
+                return wt.BamReads(path, args.io)
+        ahead = reader.submit(stage, args.infiles[0])
         for i, (path, out) in enumerate(zip(args.infiles, outs)):
             bam = ahead.result()
+            taken = ahead
             if i + 1 < len(args.infiles):
-                ahead = reader.submit(wt.BamReads, args.infiles[i + 1], args.io)
+                ahead = reader.submit(stage, args.infiles[i + 1])
+            if isinstance(bam, wt.BamFile):
+                bamfile = bam
+                try:
+                    bam = wt.openBamReads(bamfile, threads=args.io)     # the device stage, on this thread
+                finally:
+                    bamfile.close()
             try:
                 converted, qual_info = wt.convertBamReads(bam, args.binsize, args.retdist, args.retthres,
                                                           mapq=getattr(args, 'mapq', 1),
@@ -130,6 +145,9 @@ def toolConvertBatch(args):
     finally:
         reader.shutdown(wait=True)
         writer.shutdown(wait=True)
+        # a file the read-ahead thread opened and the loop never took (it left on an exception): release its buffers
+        if ahead is not None and ahead is not taken and ahead.exception() is None:
+            ahead.result().close()
     print('%d BAM files converted in %.2f s' % (len(outs), time.time() - began))
 
 

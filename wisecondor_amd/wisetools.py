@@ -539,6 +539,132 @@ class BamReads(object):
         self.close()
 
 
+class BamFile(object):
+    """The host stage of the device reader (csrc/bamfile.cpp, no GPU needed): the whole file in pinned host memory, its
+    BGZF block directory, and the BAM header from as many leading blocks as it needs: `names`, `lengths`, `n_blocks`,
+    `inflated_bytes` (the sum of ISIZE), `compressed_bytes`, `first_record` (offset of the first record in the inflated
+    stream).  Errors carry the codes BamReads raises for the same file."""
+
+    def __init__(self, path, device=0):
+        lib = _lib.load()
+        handle = ctypes.c_void_p()
+        _lib.check(lib.wc_bamfile_open(os.fsencode(path), int(device), ctypes.byref(handle)))
+        self._handle = handle
+        self.path = path
+        info = np.zeros(8, dtype=np.int64)
+        _lib.check(lib.wc_bamfile_info(handle, _lib.ptr(info)))
+        n_refs, self.n_blocks, self.inflated_bytes, self.compressed_bytes, self.first_record, name_bytes = (int(v) for v in info[:6])
+        self.pinned = bool(info[6])
+        self.pin_ms = float(info[7]) / 1e3          # of the pinned allocation, part of the open
+        names = ctypes.create_string_buffer(name_bytes + 1)
+        self.lengths = np.zeros(n_refs, dtype=np.int64)
+        _lib.check(lib.wc_bamfile_refs(handle, ctypes.cast(names, ctypes.c_void_p), name_bytes + 1, _lib.ptr(self.lengths)))
+        self.names = names.raw[:name_bytes].decode('latin1').split('\n')[:n_refs]
+
+    def close(self):
+        if self._handle is not None:
+            _lib.load().wc_bamfile_close(self._handle)
+            self._handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class DeviceArray(object):
+    """`n` elements of `dtype` at the device address `ptr`, owned by `reader` (a BamReadsDevice)."""
+
+    def __init__(self, reader, ptr, n, dtype):
+        self.reader, self.ptr, self.n, self.dtype = reader, ptr, n, np.dtype(dtype)
+
+    def __len__(self):
+        return self.n
+
+
+#: device bytes BamReadsDevice may take for one file; 0: the library's rule (0.8 of the free device memory).  A file
+#: that needs more takes the host reader (convertBam, convertbatch).
+BAM_DEVICE_BUDGET = 0
+
+
+class BamReadsDevice(object):
+    """BamReads with `pos` / `mapq` / `flag` / `mate_pos` born on the device (DeviceArray; csrc/bamgpu.hip: only the
+    compressed bytes cross to the device, BGZF inflate and the record walk are kernels).  `source` is a path or an
+    opened BamFile (which stays the caller's).  `budget`: device bytes the open may take (<= 0: BAM_DEVICE_BUDGET); a
+    file that needs more raises with code E_LIMIT.  `stage_ms`: the open's stage times (wc_bam_dev_times)."""
+
+    def __init__(self, source, device=0, budget=0):
+        lib = _lib.load()
+        own = not isinstance(source, BamFile)
+        bamfile = BamFile(source, device=device) if own else source
+        self._handle = None
+        try:
+            handle = ctypes.c_void_p()
+            _lib.check(lib.wc_bam_open_dev(_lib.context(device), None, bamfile._handle,
+                                           int(budget) if budget > 0 else int(BAM_DEVICE_BUDGET), ctypes.byref(handle)))
+        finally:
+            if own:
+                bamfile.close()
+        self._handle = handle
+        info = np.zeros(8, dtype=np.int64)
+        _lib.check(lib.wc_bam_dev_info(handle, _lib.ptr(info)))
+        n_refs, n_reads, self.mapped, self.unmapped, self.no_coordinate, name_bytes, self.device_bytes = (int(v) for v in info[:7])
+        names = ctypes.create_string_buffer(name_bytes + 1)
+        self.lengths = np.zeros(n_refs, dtype=np.int64)
+        self.offsets = np.zeros(n_refs + 1, dtype=np.int64)
+        _lib.check(lib.wc_bam_dev_refs(handle, ctypes.cast(names, ctypes.c_void_p), name_bytes + 1, _lib.ptr(self.lengths),
+                                       _lib.ptr(self.offsets)))
+        self.names = names.raw[:name_bytes].decode('latin1').split('\n')[:n_refs]
+        self.n_reads = n_reads
+        self.pos = DeviceArray(self, lib.wc_bam_dev_pos(handle), n_reads, np.int32)
+        self.mapq = DeviceArray(self, lib.wc_bam_dev_mapq(handle), n_reads, np.uint8)
+        self.flag = DeviceArray(self, lib.wc_bam_dev_flag(handle), n_reads, np.uint16)
+        self.mate_pos = DeviceArray(self, lib.wc_bam_dev_mate_pos(handle), n_reads, np.int32)
+        times = np.zeros(8, dtype=np.float64)
+        _lib.check(lib.wc_bam_dev_times(handle, _lib.ptr(times)))
+        self.stage_ms = dict(zip(('h2d', 'inflate', 'record_starts', 'link', 'checks', 'fields', 'order', 'call'),
+                                 (float(v) for v in times)))
+
+    def to_numpy(self):
+        """(pos, mapq, flag, mate_pos) copied to host arrays."""
+        out = (np.zeros(self.n_reads, dtype=np.int32), np.zeros(self.n_reads, dtype=np.uint8),
+               np.zeros(self.n_reads, dtype=np.uint16), np.zeros(self.n_reads, dtype=np.int32))
+        _lib.check(_lib.load().wc_bam_dev_fetch(self._handle, *[_lib.ptr(a) for a in out]))
+        return out
+
+    def close(self):
+        if self._handle is not None:
+            self.pos = self.mapq = self.flag = self.mate_pos = None
+            _lib.load().wc_bam_dev_close(self._handle)
+            self._handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+#: the reader convertBam and convertbatch open a file with: 'device' (BamReadsDevice; the host reader only for a file
+#: beyond the device budget) or 'host' (BamReads).  Set by the measurement in profiles/convert_times.json (DESIGN.md 6b):
+#: 5 million records, whole call 0.285 s through the device reader against 0.517 s (spread 0.024 s) through the host reader.
+CONVERT_READER = 'device'
+
+
+def openBamReads(source, threads=8, device=0):
+    """The reader convertBam uses for `source` (a path or an opened BamFile).  With CONVERT_READER == 'device': the device
+    reader, and the host reader where the file does not fit the device budget (E_LIMIT) -- the file's size decides, no
+    option.  With 'host': the host reader."""
+    if CONVERT_READER == 'device':
+        try:
+            return BamReadsDevice(source, device=device)
+        except _lib.WisecondorHipError as exc:
+            if getattr(exc, 'code', None) != _lib.E_LIMIT:
+                raise
+    return BamReads(source.path if isinstance(source, BamFile) else source, threads=threads)
+
+
 def convert_chromosome_key(name):
     """The sample-dict key of a BAM reference name (a leading 'chr' in any case dropped), None if it is skipped."""
     key = name[3:] if name[:3].lower() == 'chr' else name
@@ -550,8 +676,10 @@ def convertReads(names, lengths, offsets, pos, mapq, binsize=1000000, minShift=4
     """convertBam's filters and binning (wisetools.py:143-206) on reads that are already in arrays: references
     `names` / `lengths` in header order, reference r owning pos / mapq [offsets[r], offsets[r+1]).  One GPU call
     for all chromosomes (wc_convert_reads_ex).  `minMapq` is convertBam's `mapq` (the name is taken by the array);
-    `demandPair` needs `flag` (uint16 flag words) and `mate_pos` parallel to `pos`.  Returns (chromosomes dict, the
-    four filter counters + pair_fail)."""
+    `demandPair` needs `flag` (uint16 flag words) and `mate_pos` parallel to `pos`.  The arrays are numpy arrays, or the
+    DeviceArrays of a BamReadsDevice: those stay on the device (wc_convert_bam_dev hands their pointers to
+    wc_convert_reads_ex_dev and gathers there where the picked references are not contiguous).  Returns (chromosomes
+    dict, the four filter counters + pair_fail)."""
     lib = _lib.load()
     demandPair = bool(demandPair)
     if demandPair and (flag is None or mate_pos is None):
@@ -566,24 +694,38 @@ def convertReads(names, lengths, offsets, pos, mapq, binsize=1000000, minShift=4
         if verbose:
             for (r, _), bins in zip(picked, n_bins):
                 print(names[r], 'length:', int(lengths[r]), 'bins:', bins)
-        if all(spans[i][1] == spans[i + 1][0] for i in range(len(spans) - 1)):
-            def gather(a):
-                return a[spans[0][0]:spans[-1][1]]                              # no copy: the usual header order
-        else:
-            def gather(a):
-                return np.concatenate([a[lo:hi] for lo, hi in spans])
-        p = np.ascontiguousarray(gather(pos), dtype=np.int32)
-        q = np.ascontiguousarray(gather(mapq), dtype=np.uint8)
-        f = np.ascontiguousarray(gather(np.asarray(flag)), dtype=np.uint16) if demandPair else None
-        m = np.ascontiguousarray(gather(np.asarray(mate_pos)), dtype=np.int32) if demandPair else None
-        read_offsets = np.concatenate([[0], np.cumsum([b - a for a, b in spans])]).astype(np.int64)
         bin_offsets = np.concatenate([[0], np.cumsum(n_bins)]).astype(np.int64)
         counts = np.zeros(int(bin_offsets[-1]), dtype=np.int32)
-        _lib.check(lib.wc_convert_reads_ex(_lib.context(device), _lib.ptr(p), _lib.ptr(q),
-                                           _lib.ptr(f) if demandPair else None, _lib.ptr(m) if demandPair else None,
-                                           _lib.ptr(read_offsets), len(picked), float(binsize), int(minShift),
-                                           int(threshold), int(minMapq), int(demandPair), _lib.ptr(bin_offsets),
-                                           _lib.ptr(counts), _lib.ptr(stats)))
+        if isinstance(pos, DeviceArray):
+            # the call works on the reader's own arrays and offsets: anything else would be silently ignored
+            reader = pos.reader
+            if not (isinstance(mapq, DeviceArray) and mapq.reader is reader and pos is reader.pos and mapq is reader.mapq):
+                raise ValueError('convertReads: device arrays must be the pos / mapq of one BamReadsDevice')
+            if demandPair and not (flag is reader.flag and mate_pos is reader.mate_pos):
+                raise ValueError('convertReads: device flag / mate_pos must belong to the same BamReadsDevice')
+            if not np.array_equal(np.asarray(offsets, dtype=np.int64), reader.offsets):
+                raise ValueError('convertReads: with device arrays `offsets` must be the reader\'s own')
+            refs = np.asarray([r for r, _ in picked], dtype=np.int32)
+            _lib.check(lib.wc_convert_bam_dev(_lib.context(device), None, pos.reader._handle, _lib.ptr(refs), len(picked),
+                                              float(binsize), int(minShift), int(threshold), int(minMapq), int(demandPair),
+                                              _lib.ptr(bin_offsets), _lib.ptr(counts), _lib.ptr(stats)))
+        else:
+            if all(spans[i][1] == spans[i + 1][0] for i in range(len(spans) - 1)):
+                def gather(a):
+                    return a[spans[0][0]:spans[-1][1]]                              # no copy: the usual header order
+            else:
+                def gather(a):
+                    return np.concatenate([a[lo:hi] for lo, hi in spans])
+            p = np.ascontiguousarray(gather(pos), dtype=np.int32)
+            q = np.ascontiguousarray(gather(mapq), dtype=np.uint8)
+            f = np.ascontiguousarray(gather(np.asarray(flag)), dtype=np.uint16) if demandPair else None
+            m = np.ascontiguousarray(gather(np.asarray(mate_pos)), dtype=np.int32) if demandPair else None
+            read_offsets = np.concatenate([[0], np.cumsum([b - a for a, b in spans])]).astype(np.int64)
+            _lib.check(lib.wc_convert_reads_ex(_lib.context(device), _lib.ptr(p), _lib.ptr(q),
+                                               _lib.ptr(f) if demandPair else None, _lib.ptr(m) if demandPair else None,
+                                               _lib.ptr(read_offsets), len(picked), float(binsize), int(minShift),
+                                               int(threshold), int(minMapq), int(demandPair), _lib.ptr(bin_offsets),
+                                               _lib.ptr(counts), _lib.ptr(stats)))
         for i, (_, key) in enumerate(picked):
             chromosomes[key] = counts[bin_offsets[i]:bin_offsets[i + 1]].copy()
     return chromosomes, {'filter_rmdup': int(stats[0]), 'filter_mapq': int(stats[1]), 'pre_retro': int(stats[2]),
@@ -591,7 +733,7 @@ def convertReads(names, lengths, offsets, pos, mapq, binsize=1000000, minShift=4
 
 
 def convertBamReads(bam, binsize=1000000, minShift=4, threshold=4, device=0, verbose=False, mapq=1, demandPair=False):
-    """convertBam on an opened BamReads: (chromosomes, qual_info)."""
+    """convertBam on an opened BamReads or BamReadsDevice: (chromosomes, qual_info)."""
     chromosomes, counters = convertReads(bam.names, bam.lengths, bam.offsets, bam.pos, bam.mapq, binsize, minShift,
                                          threshold, device=device, verbose=verbose, flag=bam.flag, mate_pos=bam.mate_pos,
                                          minMapq=mapq, demandPair=demandPair)
@@ -604,7 +746,8 @@ def convertBam(bamfile, binsize=1000000, minShift=4, threshold=4, threads=8, dev
     """BAM file -> (dict chromosome -> int32[bins] or None, quality dict), wisetools.py:116-217: `mapq` the
     mapping-quality floor, `demandPair` the paired-end branch (only proper-pair first-in-pair reads take part, a
     duplicate has the previous such read's position and mate position, the rest is counted in pair_fail).  The file
-    is read by the native reader, the filters run on the GPU."""
-    with BamReads(bamfile, threads=threads) as bam:
+    is read by the device reader (BamReadsDevice; the host reader BamReads with `threads` threads where the file does
+    not fit the device budget), the filters run on the GPU."""
+    with openBamReads(bamfile, threads=threads, device=device) as bam:
         return convertBamReads(bam, binsize, minShift, threshold, device=device, verbose=True, mapq=mapq,
                                demandPair=demandPair)
