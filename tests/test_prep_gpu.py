@@ -25,7 +25,8 @@ def test_prep_matches_reference(golden):
 
 
 def test_prep_one_call_c_api(golden):
-    """The single-call C entry point (host Jacobi instead of LAPACK) on a few samples."""
+    """The single-call C entry point on nine samples (the GPU eigen-solver: the host Jacobi is for one or two
+    samples) against prepReference; against the oracle, and with two samples: test_prep_shapes_gpu.py."""
     import ctypes
     from wisecondor_amd import wisetools as wt, _lib
     g = golden("cfg1_pipeline.npz")
