@@ -29,7 +29,7 @@ namespace {
 constexpr int TB = 128;        // tile edge (rows and cols)
 constexpr int BK = 32;         // k-slab depth
 constexpr int LDA = 36;        // LDS row stride of a staged slab, floats (144 B keeps b128 reads conflict free)
-constexpr int LDT = 68;        // the 64 x 128 dot tile of the epilogues is column-major: stride of a column, floats
+constexpr int LDT = 68;        // the 64 x 128 dot tile of the threshold epilogue is column-major: stride of a column, floats
 constexpr int ROLE_ROWS = 1;   // targets are the tile's rows (P side)
 constexpr int ROLE_COLS = 2;   // targets are the tile's columns (Q side)
 constexpr int MAX_SAMPLE_COLS = 4096;
@@ -309,6 +309,24 @@ __device__ inline unsigned int run_mask(int a, int b) {
     return upto_b & ~((1u << a) - 1u);
 }
 
+// pack_entry for a key that has passed `key <= thr` (not a NaN: f32_ordered without its NaN case, same bits)
+__device__ inline unsigned long long pack_passed(float key, int j) {
+    const unsigned int b = __float_as_uint(key);
+    return ((unsigned long long)((b & 0x80000000u) ? ~b : (b | 0x80000000u)) << 32) | (unsigned int)j;
+}
+
+// mask = 2 mask + (key <= thr): the compare and an add-with-carry (the compiler makes three instructions of it)
+__device__ __forceinline__ void shift_in_le(unsigned int &mask, float key, float thr) {
+    asm("v_cmp_le_f32 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(mask) : "v"(key), "v"(thr) : "vcc");
+}
+
+// orders one wave's LDS writes before its other lanes' reads of them (no workgroup barrier)
+__device__ inline void wave_lds_fence() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 __device__ inline unsigned long long pack_entry(float key, int j) {
     return ((unsigned long long)wc::f32_ordered(key) << 32) | (unsigned int)j;
 }
@@ -319,137 +337,166 @@ __device__ inline unsigned long long pack_entry(float key, int j) {
 // of every row is known exactly (k_convert) and charged to that row's norm bounds: ONE matrix-core
 // product per multiply, rigorous lower bounds out.
 
-// The tile's epilogue (shared by the register-staged and the LDS-DMA tile kernels): dot products ->
-// lower-bound keys -> the few that pass a target's threshold appended to that target's list.
-__device__ __forceinline__ void gram_epilogue(const GramArgs &g, float *sm, float *D, const float *nbPs, const float *nbQs,
-                                              const float *thPs, const float *thQs, f32x16 (&acc)[2][2], const int I,
-                                              const int J, const int roles, const float m2, const int tid,
-                                              const int lane, const int w, const int wr, const int wc, const int li,
-                                              const int lh) {
-    // Epilogue in two halves (rows 0-63 from the waves with wr == 0, then rows 64-127):
-    // the 64 x 128 dot-product tile aliases the staging buffers, which keeps the
-    // workgroup at 39 KB of LDS -> four workgroups per CU cover each other's
-    // load / barrier / epilogue phases with MFMA work.
-    // ONE sweep evaluates every key of the half once (round 2 evaluated each twice, once per role):
-    // thread (x, q) owns column x and 32 of the half's rows.  Its keys against the column target's
-    // threshold give the column role's pass mask; the same keys against the ROW targets' thresholds --
-    // wave-uniform, the row is the loop variable -- are one v_cmp whose 64-bit result IS the row's
-    // pass mask over the wave's 64 columns (no ballot instruction, no second LDS read of the tile);
-    // lane 0 parks it in LDS.  After a barrier sixteen lanes per wave finish the rows: two masks per
-    // row, same-chromosome columns cleared as a run, ONE list reservation per row and half (round 2:
-    // four), keys of the few set bits rebuilt from the tile.
-    __builtin_amdgcn_s_setprio(0);
-    const int x = tid & 127, q = __builtin_amdgcn_readfirstlane(tid >> 7);   // column x, 32-row half q
-    const int2 rgq = g.range[(int64_t)J * TB + x];
-    unsigned long long *rowmask = reinterpret_cast<unsigned long long *>(sm + 128 * LDT);   // [64 rows][2 column halves]
-    const int rl = w * 16 + (lane & 15);                                   // the row this lane helps to finish (four lanes per row)
-    const int2 rgr0 = g.range[(int64_t)I * TB + rl], rgr1 = g.range[(int64_t)I * TB + 64 + rl];
-    for (int h = 0; h < 2; ++h) {
-        wc_sync();
-        if (wr == h) {
-#pragma unroll
-            for (int m = 0; m < 2; ++m)
-#pragma unroll
-                for (int n = 0; n < 2; ++n)
-#pragma unroll
-                    for (int r4 = 0; r4 < 4; ++r4) {
-                        // accumulators 4 r4 .. 4 r4 + 3 are four consecutive rows of one column: the
-                        // tile is stored column-major so that they go out as one 16-byte write
-                        // (and the column scan below comes back as 16-byte reads)
-                        const int row = m * 32 + 8 * r4 + 4 * lh;
-                        const int col = wc * 64 + n * 32 + li;
-                        f32x4 v4;
-                        v4[0] = acc[m][n][4 * r4]; v4[1] = acc[m][n][4 * r4 + 1];
-                        v4[2] = acc[m][n][4 * r4 + 2]; v4[3] = acc[m][n][4 * r4 + 3];
-                        *(f32x4 *)&D[col * LDT + row] = v4;
-                    }
-        }
-        wc_sync();
+// The tile's epilogue: dot products -> lower-bound keys -> the few that pass a target's threshold appended
+// to that target's list.  Every wave finishes its own 64 x 64 block; the workgroup meets once, before the
+// dot blocks overwrite the operand stages.
+//
+// 1. Sweep in the accumulator layout.  Element 4 r4 + e of acc[m][n] is row wr*64 + m*32 + 8 r4 + 4 lh + e,
+//    column wc*64 + n*32 + li: a lane holds two columns x 32 of the wave's 64 rows.  Each key is evaluated once.
+//    Against the column target's threshold it sets one bit of the lane's mask of that column (bit 16 m + 4 r4 + e:
+//    ascending in the row).  Against the ROW targets' thresholds -- the lane's four rows of a register group,
+//    one 16-byte read -- it is one v_cmp whose 64-bit result holds the 32-column masks of two rows (lh = 0, 1);
+//    it goes to the wave's mask table as one 8-byte write, word lh landing in its row's slot.
+// 2. Reservations, once per tile: the two lanes of a column add their counts (one cross-lane move each way),
+//    lane L finishes row L of the wave's 64 (two mask words, the row's own chromosome cleared as a run).  Both
+//    sets of atomics are issued back to back; their round trip is covered by the barrier and the staging.
+// 3. Appends, per 32-row half m: the wave writes its 32 x 64 dot block column-major into its own quarter of the
+//    operand stages (16-byte writes, the four-row chunks of a column XOR-swizzled by the column: an unpadded
+//    column is 128 bytes), and the two data-dependent append loops rebuild the keys of the set bits from it.
+constexpr int EP_LD = 32;                    // floats per column of a wave's dot block (32 rows, no padding)
+constexpr int EP_BLOCK = 64 * EP_LD;         // floats per wave
+constexpr int EP_MASKS = 128;                // 32-bit words of a wave's row-mask table: [n][m][r4][e][lh]
+static_assert(4 * EP_BLOCK <= 2 * GL_STAGE, "the four dot blocks alias the two operand stages");
 
-        unsigned int mask_c = 0u;
+__device__ __forceinline__ int ep_at(int col, int row) {      // float offset of (row 0..31, column 0..63) in a dot block
+    return col * EP_LD + ((((row >> 2) ^ col) & 7) << 2) + (row & 3);
+}
+
+__device__ __forceinline__ void gram_epilogue(const GramArgs &g, float *sm, const float *nbPs, const float *nbQs,
+                                              const float *thPs, const float *thQs, f32x16 (&acc)[2][2], const int I,
+                                              const int J, const int roles, const float m2, const int lane, const int w,
+                                              const int wr, const int wc, const int li, const int lh) {
+    __builtin_amdgcn_s_setprio(0);
+    const int row0 = I * TB + wr * 64, col0 = J * TB + wc * 64;           // the wave's block
+    const int2 rgq0 = g.range[(int64_t)col0 + li], rgq1 = g.range[(int64_t)col0 + 32 + li];
+    const int2 rgr = g.range[(int64_t)row0 + lane];
+    unsigned int *maskw = reinterpret_cast<unsigned int *>(sm + 2 * GL_STAGE) + w * EP_MASKS;
+    unsigned long long *mask2 = reinterpret_cast<unsigned long long *>(maskw);
+    const bool cols = (roles & ROLE_COLS) != 0, rows = (roles & ROLE_ROWS) != 0;
+    const float nbc0 = nbQs[wc * 64 + li], nbc1 = nbQs[wc * 64 + 32 + li];
+    const float thc0 = cols ? thQs[wc * 64 + li] : -INFINITY, thc1 = cols ? thQs[wc * 64 + 32 + li] : -INFINITY;
+    unsigned int mc0 = 0u, mc1 = 0u;
+    // (descending, so that the masks can take their bits by shifting them in: bit b is the key of step b)
+#pragma unroll
+    for (int m = 1; m >= 0; --m)
+#pragma unroll
+        for (int r4 = 3; r4 >= 0; --r4) {
+            const f32x4 nb4 = *(const f32x4 *)&nbPs[wr * 64 + m * 32 + 8 * r4 + 4 * lh];
+            const f32x4 th4 = *(const f32x4 *)&thPs[wr * 64 + m * 32 + 8 * r4 + 4 * lh];
+#pragma unroll
+            for (int e = 3; e >= 0; --e) {
+                const float key0 = fmaf(m2, acc[m][0][4 * r4 + e], nb4[e] + nbc0);
+                const float key1 = fmaf(m2, acc[m][1][4 * r4 + e], nb4[e] + nbc1);
+                shift_in_le(mc0, key0, thc0);
+                shift_in_le(mc1, key1, thc1);
+                // every lane stores the (uniform) pair of masks: one LDS write, no exec games
+                mask2[(m * 4 + r4) * 4 + e] = __ballot(key0 <= th4[e]);
+                mask2[32 + (m * 4 + r4) * 4 + e] = __ballot(key1 <= th4[e]);
+            }
+        }
+    // Column role: the own-chromosome rows leave as a run (the lane's 32 rows ascend with the bit number: of the
+    // rows below t, 4 per whole group of eight and the group's first or second four are this lane's)
+    auto below = [&](int t) {
+        t = t < 0 ? 0 : (t > 64 ? 64 : t);
+        const int part = (t & 7) - 4 * lh;
+        return 4 * (t >> 3) + (part < 0 ? 0 : (part > 4 ? 4 : part));
+    };
+    mc0 &= ~run_mask(below(rgq0.x - row0), below(rgq0.y - row0));
+    mc1 &= ~run_mask(below(rgq1.x - row0), below(rgq1.y - row0));
+    const int mine_c = __popc(mc0) | (__popc(mc1) << 16);
+    const int other_c = __shfl_xor(mine_c, 32);
+    // lane lh = 0 reserves for column li, lane lh = 1 for column 32 + li; the lh = 0 lane's entries go first
+    const int cnt_a = lh ? (other_c >> 16) : (mine_c & 0xFFFF), cnt_b = lh ? (mine_c >> 16) : (other_c & 0xFFFF);
+    const int64_t gq0 = (int64_t)col0 + li;
+    int res_c = 0;
+    if (cnt_a + cnt_b > 0) res_c = atomicAdd(&g.cnt[gq0 + 32 * lh], cnt_a + cnt_b);
+    // Row role: lane L owns row L of the wave's 64
+    unsigned int mr0 = 0u, mr1 = 0u;
+    int res_r = 0;
+    const int64_t gp = (int64_t)row0 + lane;
+    if (rows) {
+        wave_lds_fence();
+        const int at = (((lane >> 3) * 4 + (lane & 3)) << 1) + ((lane >> 2) & 1);
+        mr0 = maskw[at];
+        mr1 = maskw[64 + at];
+        mr0 &= ~run_mask(rgr.x - col0, rgr.y - col0);
+        mr1 &= ~run_mask(rgr.x - (col0 + 32), rgr.y - (col0 + 32));
+        const int n_r = __popc(mr0) + __popc(mr1);
+        if (n_r > 0) res_r = atomicAdd(&g.cnt[gp], n_r);
+    }
+    // The one workgroup barrier: every wave has its last fragment reads back (waited for before the epilogue) and
+    // its DMA landed; after it the operand stages are the waves' dot blocks.
+    // (as inline assembly: before the builtin barrier the compiler waits for EVERY counter, the reservations'
+    // round trip included; their first use is after the first half's staging)
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    float *D = sm + w * EP_BLOCK;
+    int base0 = 0, base1 = 0;                                // first free slot of this lane in its two columns' lists
+    unsigned long long *dstc0 = g.list + gq0 * g.cap, *dstc1 = g.list + (gq0 + 32) * g.cap;
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+        if (m) wave_lds_fence();                             // the first half's reads are done
+#pragma unroll
+        for (int n = 0; n < 2; ++n)
+#pragma unroll
+            for (int r4 = 0; r4 < 4; ++r4) {
+                f32x4 v4;
+                v4[0] = acc[m][n][4 * r4]; v4[1] = acc[m][n][4 * r4 + 1];
+                v4[2] = acc[m][n][4 * r4 + 2]; v4[3] = acc[m][n][4 * r4 + 3];
+                *(f32x4 *)&D[ep_at(n * 32 + li, 8 * r4 + 4 * lh)] = v4;
+            }
+        wave_lds_fence();
+        if (m == 0) {                                        // (the reservations have had the barrier and the staging to come back)
+            const int res_o = __shfl_xor(res_c, 32);
+            base0 = lh ? res_o + (other_c & 0xFFFF) : res_c;
+            base1 = lh ? res_c + (other_c >> 16) : res_o;
+        }
+        // Column role: bits 0-15 are column li, bits 16-31 column 32 + li, 16 rows each; two entries per trip
+        // (their LDS reads fly together)
         {
-            const float nbc = nbQs[x], thc = (roles & ROLE_COLS) ? thQs[x] : -INFINITY;
-            float dv[32];
-#pragma unroll
-            for (int g4 = 0; g4 < 8; ++g4) {
-                const f32x4 d4 = *(const f32x4 *)&D[x * LDT + q * 32 + 4 * g4];
-                dv[4 * g4] = d4[0]; dv[4 * g4 + 1] = d4[1]; dv[4 * g4 + 2] = d4[2]; dv[4 * g4 + 3] = d4[3];
+            const unsigned int h0 = (mc0 >> (16 * m)) & 0xFFFFu, h1 = (mc1 >> (16 * m)) & 0xFFFFu;
+            unsigned int mm = h0 | (h1 << 16);
+            const int c0 = __popc(h0);
+            const int off0 = base0, off1 = base1 - c0;       // the t-th set bit goes to slot off + t of its column
+            int t = 0;
+            while (mm) {
+                const int p0 = __ffs((int)mm) - 1;
+                mm &= mm - 1;
+                const bool two = mm != 0u;
+                const int p1 = two ? __ffs((int)mm) - 1 : p0;
+                mm &= mm - 1;                                   // (0 stays 0)
+                const int n0 = p0 >> 4, n1 = p1 >> 4;
+                const int l0 = 8 * ((p0 >> 2) & 3) + 4 * lh + (p0 & 3), l1 = 8 * ((p1 >> 2) & 3) + 4 * lh + (p1 & 3);
+                const float d0 = D[ep_at(n0 * 32 + li, l0)], d1 = D[ep_at(n1 * 32 + li, l1)];
+                const float q0 = nbPs[wr * 64 + m * 32 + l0], q1 = nbPs[wr * 64 + m * 32 + l1];
+                const float key0 = fmaf(m2, d0, q0 + (n0 ? nbc1 : nbc0)), key1 = fmaf(m2, d1, q1 + (n1 ? nbc1 : nbc0));
+                const int s0 = (n0 ? off1 : off0) + t, s1 = (n1 ? off1 : off0) + t + 1;
+                if (s0 < g.cap) (n0 ? dstc1 : dstc0)[s0] = pack_passed(key0, row0 + m * 32 + l0);
+                if (two && s1 < g.cap) (n1 ? dstc1 : dstc0)[s1] = pack_passed(key1, row0 + m * 32 + l1);
+                t += 2;
             }
-            const f32x4 *nbv = (const f32x4 *)&nbPs[h * 64 + q * 32];
-            const f32x4 *thv = (const f32x4 *)&thPs[h * 64 + q * 32];
-#pragma unroll
-            for (int g4 = 0; g4 < 8; ++g4) {
-                const f32x4 nb4 = nbv[g4], th4 = thv[g4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float key = fmaf(m2, dv[4 * g4 + e], nb4[e] + nbc);
-                    mask_c |= (key <= thc) ? (1u << (4 * g4 + e)) : 0u;
-                    const unsigned long long hit = __ballot(key <= th4[e]);      // a compare into a scalar pair
-                    // every lane stores the (uniform) mask to the row's slot: one LDS write, no exec games
-                    rowmask[(q * 32 + 4 * g4 + e) * 2 + (w & 1)] = hit;
-                }
-            }
-            mask_c &= ~run_mask(rgq.x - (I * TB + h * 64 + q * 32), rgq.y - (I * TB + h * 64 + q * 32));
+            base0 += c0;
+            base1 += __popc(h1);
         }
-        // the column role's reservation flies while the rows are finished
-        int base_c = 0;
-        const int64_t gq = (int64_t)J * TB + x;
-        if (mask_c) base_c = atomicAdd(&g.cnt[gq], __popc(mask_c));
-        wc_sync();
-        // Row role, first half: four lanes per row (lane = 16 part + row-in-wave), each takes a 32-column quarter of
-        // the row's 128-bit mask; part 0 reserves for all four.  The reservation's round trip is covered by the
-        // column role's appends; the row's own appends follow them.
-        const int part = lane >> 4;
-        unsigned int mm = 0u;
-        int base_r = 0, mine = 0, c1 = 0, c2 = 0, c3 = 0;
-        const int r_row = h * 64 + rl;
-        const int64_t gp = (int64_t)I * TB + r_row;
-        if (roles & ROLE_ROWS) {
-            const unsigned long long m64 = rowmask[rl * 2 + (part >> 1)];
-            mm = (unsigned int)(m64 >> (32 * (part & 1)));
-            const int2 rg = h ? rgr1 : rgr0;
-            mm &= ~run_mask(rg.x - (J * TB + 32 * part), rg.y - (J * TB + 32 * part));   // the row's own chromosome
-            mine = __popc(mm);
-            c1 = __shfl(mine, (lane & 15) + 16); c2 = __shfl(mine, (lane & 15) + 32); c3 = __shfl(mine, (lane & 15) + 48);
-            if (part == 0 && mine + c1 + c2 + c3 > 0) base_r = atomicAdd(&g.cnt[gp], mine + c1 + c2 + c3);
-        }
-        // Appends, two entries per trip (their LDS reads fly together)
-        if (mask_c) {
-            const float nbc = nbQs[x];
-            unsigned long long *dst = g.list + gq * g.cap;
-            while (mask_c) {
-                const int rr0 = __ffs((int)mask_c) - 1;
-                mask_c &= mask_c - 1;
-                const bool two = mask_c != 0u;
-                const int rr1 = two ? __ffs((int)mask_c) - 1 : rr0;
-                mask_c &= mask_c - 1;                                   // (0 stays 0)
-                const int l0 = q * 32 + rr0, l1 = q * 32 + rr1;
-                const float d0 = D[x * LDT + l0], d1 = D[x * LDT + l1];
-                const float n0 = nbPs[h * 64 + l0], n1 = nbPs[h * 64 + l1];
-                const float key0 = fmaf(m2, d0, n0 + nbc), key1 = fmaf(m2, d1, n1 + nbc);
-                if (base_c < g.cap) dst[base_c] = pack_entry(key0, I * TB + h * 64 + l0);
-                if (two && base_c + 1 < g.cap) dst[base_c + 1] = pack_entry(key1, I * TB + h * 64 + l1);
-                base_c += 2;
-            }
-        }
-        if (roles & ROLE_ROWS) {
-            base_r = __shfl(base_r, lane & 15);
-            const int c0 = __shfl(mine, lane & 15);
-            base_r += (part > 0 ? c0 : 0) + (part > 1 ? c1 : 0) + (part > 2 ? c2 : 0);
+        // Row role: two lanes per row of this half, one per 32-column word
+        if (rows) {
+            const int rr = lane & 31, own = m * 32 + rr;
+            const unsigned int w0 = (unsigned int)__shfl((int)mr0, own), w1 = (unsigned int)__shfl((int)mr1, own);
+            int base_r = __shfl(res_r, own) + (lh ? __popc(w0) : 0);
+            unsigned int mm = lh ? w1 : w0;
             if (mm) {
-                const float nbr = nbPs[r_row];
-                unsigned long long *dst = g.list + gp * g.cap;
+                const float nbr = nbPs[wr * 64 + own];
+                unsigned long long *dst = g.list + ((int64_t)row0 + own) * g.cap;
                 while (mm) {
-                    const int ca = 32 * part + (__ffs((int)mm) - 1);
+                    const int ca = 32 * lh + (__ffs((int)mm) - 1);
                     mm &= mm - 1;
                     const bool two = mm != 0u;
-                    const int cb = two ? 32 * part + (__ffs((int)mm) - 1) : ca;
+                    const int cb = two ? 32 * lh + (__ffs((int)mm) - 1) : ca;
                     mm &= mm - 1;
-                    const float d0 = D[ca * LDT + rl], d1 = D[cb * LDT + rl];
-                    const float n0 = nbQs[ca], n1 = nbQs[cb];
+                    const float d0 = D[ep_at(ca, rr)], d1 = D[ep_at(cb, rr)];
+                    const float n0 = nbQs[wc * 64 + ca], n1 = nbQs[wc * 64 + cb];
                     const float key0 = fmaf(m2, d0, nbr + n0), key1 = fmaf(m2, d1, nbr + n1);
-                    if (base_r < g.cap) dst[base_r] = pack_entry(key0, J * TB + ca);
-                    if (two && base_r + 1 < g.cap) dst[base_r + 1] = pack_entry(key1, J * TB + cb);
+                    if (base_r < g.cap) dst[base_r] = pack_passed(key0, col0 + ca);
+                    if (two && base_r + 1 < g.cap) dst[base_r + 1] = pack_passed(key1, col0 + cb);
                     base_r += 2;
                 }
             }
@@ -463,20 +510,18 @@ __device__ __forceinline__ void gram_epilogue(const GramArgs &g, float *sm, floa
 // a wave's DMA instruction fills 16 rows x 64 B = 1 KB lane-linearly, so the row padding of the
 // register-staged kernel is not available: the 16-byte chunk g of row r sits in slot g ^ ((r >> 2) & 3)
 // (swizzled on the SOURCE address and again on the fragment read), which keeps the sixteen rows a
-// ds_read_b128 group touches on distinct banks.  Two slabs of LDS (32 KB) + the dot tile's 35 KB aliasing
-// them: four workgroups per CU.  The loop is software pipelined: the fragments of k-step t + 1 are read from LDS
+// ds_read_b128 group touches on distinct banks.  Two slabs of LDS (32 KB), which the epilogue's four wave-private
+// dot blocks alias: four workgroups per CU.  The loop is software pipelined: the fragments of k-step t + 1 are read from LDS
 // while the matrix cores work on step t (two fragment sets), across the slab boundary as well; the ONE barrier per
 // slab sits between the two k-steps of a slab -- there every wave has its reads of the slab back and its DMA of the
 // next slab landed (waited for explicitly: a bare s_barrier, __syncthreads()'s fence would add nothing), after it
 // the freed stage is refilled with the slab after next.
 __global__ __launch_bounds__(256, 4) void k_gram_glds(GramArgs g) {
-    __shared__ __attribute__((aligned(16))) float sm[128 * LDT + 256 + 4 * TB];   // dot tile + row masks + bounds / thresholds
-    float *D = sm;
-    float *nbPs = sm + 128 * LDT + 256;
+    __shared__ __attribute__((aligned(16))) float sm[2 * GL_STAGE + 4 * EP_MASKS + 4 * TB];   // operand stages (then the waves' dot blocks) + row masks + bounds / thresholds
+    float *nbPs = sm + 2 * GL_STAGE + 4 * EP_MASKS;
     float *nbQs = nbPs + TB;
     float *thPs = nbQs + TB;
     float *thQs = thPs + TB;
-    static_assert(2 * GL_STAGE <= 128 * LDT, "the two operand stages alias the dot tile");
     const int chunk = (g.ntiles + 7) >> 3;
     const int t_id = (blockIdx.x & 7) * chunk + (blockIdx.x >> 3);
     if (t_id >= g.ntiles) return;
@@ -571,7 +616,7 @@ __global__ __launch_bounds__(256, 4) void k_gram_glds(GramArgs g) {
     mm(0);
     if (g.last_steps32 > 1) mm(1);
     __builtin_amdgcn_s_waitcnt(0x0070);   // nothing of this wave in flight into the LDS the dot tile is about to alias
-    gram_epilogue(g, sm, D, nbPs, nbQs, thPs, thQs, acc, I, J, roles, m2, tid, lane, w, wr, wc, li, lh);
+    gram_epilogue(g, sm, nbPs, nbQs, thPs, thQs, acc, I, J, roles, m2, lane, w, wr, wc, li, lh);
 }
 
 // ----------------------------------------------- threshold-estimate Gram (f16) ----
@@ -1443,12 +1488,6 @@ struct RowSum {
         return vs[0];
     }
 };
-
-__device__ inline void wave_lds_fence() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // One workgroup (ps threads = ps / 64 waves) per row; see the header of this section.
 // Xp is the padded float64 image (rows of Sp = 16 n samples, zero padded, 128-byte aligned): every
