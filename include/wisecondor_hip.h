@@ -327,6 +327,56 @@ int wc_convert_bam_dev(wc_ctx *ctx, void *stream, const wc_bam_dev *bam, const i
                        int32_t *counts_out, int64_t *stats_out);
 
 /*
+ * The streamed device reader: the same wc_bam_dev handle with host and device working memory bounded by a chunk size
+ * and the longest record, not by the file.  Only the four arrays (11 bytes per placed record) grow with the file.
+ *
+ * Host stage (no GPU needed): wc_bamchunks_open parses the BAM header from as many leading BGZF blocks as it needs (the
+ * checks, texts and codes of wc_bamfile_open) and starts a reader thread that fills two staging buffers of
+ * min(chunk_bytes, file size) + 65536 + 64 bytes in turn (pinned for `device`, ordinary memory where device < 0 or no
+ * device is present); the file is never held whole.  A chunk is the next run of WHOLE BGZF blocks whose compressed bytes
+ * total at most chunk_bytes, and at least one block (chunk_bytes = 1: one block per chunk; chunk_bytes <= 0: the default,
+ * wc_bam_stream_default_chunk).  The bytes of a block cut by the end of a read go in front of the next read.  A block
+ * header defect is reported by the wc_bamchunks_next call that meets it, with the file's block number: an incomplete
+ * block is WC_E_FORMAT "truncated" only at the true end of the file.
+ *   wc_bamchunks_info   as wc_bamfile_info, except [1] 0, [2] 0 (blocks and inflated bytes are known chunk by chunk) and
+ *                       [7] the bytes of the two staging buffers
+ *   wc_bamchunks_refs   as wc_bamfile_refs
+ *   wc_bamchunks_next   out[0] 1: a chunk, 0: the file is through (the other words are 0); [1] the file's number of the
+ *                       chunk's first block, [2] its blocks, [3] its compressed bytes, [4] the sum of its ISIZE fields,
+ *                       [5] its offset in the file, [6] 1 for the file's last chunk.  The chunk before is released.
+ *
+ * Device stage: wc_bam_stream_dev opens the chunk iterator itself and sends every chunk through the kernels of the
+ * whole-file reader: the compressed bytes are copied on a second stream while the chunk before is decoded on `stream`;
+ * the blocks are inflated behind the bytes carried over from the chunk before (the records that do not end inside their
+ * chunk, a cut block_size word included), the records of carry + chunk are walked and their fields appended to the four
+ * arrays at a running base kept on the device; the bytes from the first record that does not end inside the chunk are
+ * the next carry (a record longer than a chunk keeps accumulating: working memory is O(chunk + longest record)).
+ * The counters, the coordinate-order check (the last placed record of a chunk is the predecessor of the next chunk's
+ * first) and the per-reference counts accumulate on the device.  The arrays are reserved by the most records a chunk can
+ * hold and grow geometrically.  One small status read per chunk, after the copy of the next chunk has been enqueued.
+ * Errors carry the codes of wc_bam_open_dev, with block numbers and inflated offsets counted in the whole file; the first
+ * defect in file order is reported, so a file with a format defect behind an order defect is WC_E_ARG here and
+ * WC_E_FORMAT from wc_bam_open_dev (which checks every record before any order).  Leftover bytes behind the last chunk
+ * are the "truncated" error.  There is no budget: the need does not grow with the file.
+ *   wc_bam_dev_info          of a streamed handle: out[6] the peak device bytes INCLUDING the four arrays, [7] 0
+ *   wc_bam_dev_times         of a streamed handle: out[0] milliseconds the call waited for the reader thread, [1] for
+ *                            the device, [7] the whole call by the host clock; the others 0
+ *   wc_bam_dev_stream_info   out[0] chunks, [1] / [2] the largest chunk's compressed / inflated bytes, [3] the largest
+ *                            carry, [4] the peak device working bytes (everything except the four arrays), [5] the bytes
+ *                            of the host staging buffers, [6] times the arrays were regrown, [7] 1 when the staging
+ *                            buffers are pinned.  All 0 for a handle of wc_bam_open_dev.
+ */
+typedef struct wc_bamchunks wc_bamchunks;
+int wc_bamchunks_open(const char *path, int device, int64_t chunk_bytes, wc_bamchunks **out);
+int wc_bamchunks_info(const wc_bamchunks *chunks, int64_t out[8]);
+int wc_bamchunks_refs(const wc_bamchunks *chunks, char *names_out, int64_t names_cap, int64_t *lengths_out);
+int wc_bamchunks_next(wc_bamchunks *chunks, int64_t out[8]);
+void wc_bamchunks_close(wc_bamchunks *chunks);
+int64_t wc_bam_stream_default_chunk(void);
+int wc_bam_stream_dev(wc_ctx *ctx, void *stream, const char *path, int64_t chunk_bytes, wc_bam_dev **out);
+int wc_bam_dev_stream_info(const wc_bam_dev *bam, int64_t out[8]);
+
+/*
  * The numeric part of convertBam (wisetools.py:116-217) for all chromosomes of one file in one call: the paired-end
  * selection, duplicate removal, mapping-quality filter, the tower (RETRO) filter, binning.  wc_convert_reads[_dev] is
  * the function as toolConvert calls it (mapq 1, demandPair False); wc_convert_reads_ex[_dev] takes both parameters.

@@ -5,7 +5,8 @@ used before the device reader) against the device reader (BamReadsDevice), and t
 Two steps, each a process of its own, chained with && and each under its own time limit:
 
     timeout -k 10 600 python tools/gpu_convert_time.py make /tmp/wc_convert_time.bam --records 5000000 &&
-    timeout -k 10 600 python tools/gpu_convert_time.py time /tmp/wc_convert_time.bam --out profiles/convert_times.json
+    timeout -k 10 600 python tools/gpu_convert_time.py time /tmp/wc_convert_time.bam --out profiles/convert_times.json &&
+    timeout -k 10 600 python tools/gpu_convert_time.py stream /tmp/wc_convert_time.bam --out profiles/convert_stream_times.json
 
 `make` needs no GPU: a seeded BAM, coordinate-sorted over chr1..chr22, X, Y, records of 100 and 151 bases with names,
 CIGAR, 4-bit sequence, qualities and tags (about 230 and 310 bytes), compressed at zlib level 6 in BGZF blocks of 65 280
@@ -15,7 +16,12 @@ bytes by a pool of processes.  `time` writes the JSON:
   leg 2  the device reader's stages: the host stage by the host clock, the device stages between device events
          (wc_bam_dev_times), the convert kernels by the host clock around the synchronous call; inflated bytes per second
          of the inflate kernel
-The two readers' results are compared (dict and quality) before anything is written."""
+The two readers' results are compared (dict and quality) before anything is written.
+`stream` writes its own JSON: per chunk size (8, 32 and 256 MiB unless --chunks names others) the wall time of the whole
+call through the whole-file device reader and through the streamed reader (BamReadsStream), alternating, five times each
+after one warm-up of each, results compared first; the streamed reader's stream_info (chunks, peak device working bytes,
+host staging bytes) beside the whole-file reader's device_bytes; and whether the streamed reader beats the whole-file
+reader by more than that reader's own spread."""
 import argparse
 import json
 import os
@@ -166,6 +172,59 @@ def timing(args):
     print(json.dumps(result))
 
 
+def stream_timing(args):
+    from wisecondor_amd import _lib
+    from wisecondor_amd import wisetools as wt
+
+    seen = {}
+
+    def device_call():
+        with wt.BamReadsDevice(args.path) as bam:
+            seen["device_bytes"], seen["placed"] = bam.device_bytes, bam.n_reads
+            return wt.convertBamReads(bam, args.binsize)
+
+    def stream_call(chunk):
+        with wt.BamReadsStream(args.path, chunk=chunk) as bam:
+            seen["stream_info"], seen["stream_ms"], seen["stream_bytes"] = bam.stream_info, bam.stage_ms, bam.device_bytes
+            return wt.convertBamReads(bam, args.binsize)
+
+    def summary(ts):
+        return {"seconds": [round(t, 4) for t in ts], "median": round(float(np.median(ts)), 4), "spread": round(max(ts) - min(ts), 4)}
+
+    want = device_call()                                        # the warm-up of the whole-file reader
+    legs = []
+    for chunk in args.chunks:
+        if not _same(want, stream_call(chunk)):                 # the warm-up at this size, and the comparison
+            raise SystemExit("the two readers disagree at chunk %d: nothing is written" % chunk)
+        times = {"device_reader": [], "stream_reader": []}
+        for _ in range(args.repeats):
+            for name, call in (("device_reader", device_call), ("stream_reader", lambda: stream_call(chunk))):
+                t0 = time.perf_counter()
+                call()                                          # ends in a device synchronise (wc_convert_*)
+                times[name].append(time.perf_counter() - t0)
+        leg = {"chunk_bytes": chunk, "device_reader": summary(times["device_reader"]),
+               "stream_reader": summary(times["stream_reader"]), "stream_info": seen["stream_info"],
+               "stream_reader_wait_ms": {k: round(v, 3) for k, v in seen["stream_ms"].items()},
+               "stream_reader_peak_device_bytes_with_arrays": seen["stream_bytes"],
+               "device_reader_device_bytes": seen["device_bytes"]}
+        leg["stream_reader_beats_device_reader_by_more_than_its_spread"] = bool(
+            leg["device_reader"]["median"] - leg["stream_reader"]["median"] > leg["device_reader"]["spread"])
+        leg["device_reader_beats_stream_reader_by_more_than_its_spread"] = bool(
+            leg["stream_reader"]["median"] - leg["device_reader"]["median"] > leg["stream_reader"]["spread"])
+        legs.append(leg)
+    best = min(legs, key=lambda leg: leg["stream_reader"]["median"])
+    result = {"file": {"records_placed": seen["placed"], "compressed_bytes": os.path.getsize(args.path)},
+              "binsize": args.binsize, "repeats": args.repeats, "chunk_sizes": legs,
+              "fastest_chunk_bytes": best["chunk_bytes"],
+              "library_default_chunk_bytes": int(_lib.load().wc_bam_stream_default_chunk()),
+              "library": _lib.load().wc_version().decode()}
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(result, f, indent=1)
+        f.write("\n")
+    print(json.dumps(result))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     sub = ap.add_subparsers(dest="cmd", required=True)
@@ -182,6 +241,13 @@ def main():
     t.add_argument("--threads", type=int, default=16)
     t.add_argument("--binsize", type=int, default=1000000)
     t.set_defaults(func=timing)
+    st = sub.add_parser("stream")
+    st.add_argument("path")
+    st.add_argument("--out", default=os.path.join(ROOT, "profiles", "convert_stream_times.json"))
+    st.add_argument("--repeats", type=int, default=5)
+    st.add_argument("--binsize", type=int, default=1000000)
+    st.add_argument("--chunks", type=int, nargs="+", default=[8 << 20, 32 << 20, 256 << 20])
+    st.set_defaults(func=stream_timing)
     args = ap.parse_args()
     args.func(args)
 

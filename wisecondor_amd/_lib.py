@@ -72,6 +72,14 @@ SIGNATURES = {
     "wc_bam_chain_segment": (_i32, []),
     "wc_bgzf_inflate": (_i32, [_vp, _vp, _i64, _vp, _i64, _vp]),
     "wc_convert_bam_dev": (_i32, [_vp, _vp, _vp, _vp, _i32, _dbl, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "wc_bamchunks_open": (_i32, [_c.c_char_p, _i32, _i64, _vp]),
+    "wc_bamchunks_info": (_i32, [_vp, _vp]),
+    "wc_bamchunks_refs": (_i32, [_vp, _vp, _i64, _vp]),
+    "wc_bamchunks_next": (_i32, [_vp, _vp]),
+    "wc_bamchunks_close": (None, [_vp]),
+    "wc_bam_stream_default_chunk": (_i64, []),
+    "wc_bam_stream_dev": (_i32, [_vp, _vp, _c.c_char_p, _i64, _vp]),
+    "wc_bam_dev_stream_info": (_i32, [_vp, _vp]),
     "wc_convert_tile_reads": (_i32, []),
     "wc_convert_reads_dev": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _dbl, _i32, _i32, _vp, _vp, _vp]),
     "wc_convert_reads": (_i32, [_vp, _vp, _vp, _vp, _i32, _dbl, _i32, _i32, _vp, _vp, _vp]),

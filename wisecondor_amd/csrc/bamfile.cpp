@@ -3,15 +3,26 @@
 // blocks as the BAM header needs, the header itself (names, lengths, offset of the first record in the inflated
 // stream).  Nothing else is inflated here: the compressed bytes are what crosses to the device.  Errors carry the codes
 // wc_bam_open returns for the same file.  No GPU is needed: without one the buffer is ordinary memory.
+// The streamed reader's host stage (wc_bamchunks, below) shares the block and header code: the header from a prefix of
+// the file, then a reader thread that fills two staging buffers with runs of whole blocks; the file is never held whole.
 #include <hip/hip_runtime_api.h>
 #include <zlib.h>
 
+#include <fcntl.h>
+#include <sys/stat.h>
+#include <unistd.h>
+
+#include <algorithm>
+#include <cerrno>
 #include <chrono>
+#include <condition_variable>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <mutex>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "bamfile.h"
@@ -26,44 +37,55 @@ inline uint32_t rd32(const unsigned char *p) {
 }
 }  // namespace
 
+// One BGZF block header at p + at of n bytes, the checks of read_bam: WC_OK (b filled, in_off counted from p, out_off 0;
+// next: the offset behind the block), WC_E_FORMAT, or BGZF_CUT where the n bytes end inside the block (the text is set
+// all the same: at the end of a file that is the error).
+enum { BGZF_CUT = 1 };
+static int bgzf_block_at(const unsigned char *p, size_t n, size_t at, long long block_no, BgzfBlock &b, size_t &next) {
+    if (n - at < 12) { set_error("bam: truncated BGZF block %lld (header cut short)", block_no); return BGZF_CUT; }
+    const unsigned char *h = p + at;
+    if (h[0] != 31 || h[1] != 139 || h[2] != 8 || !(h[3] & 4)) {
+        set_error(block_no ? "bam: damaged BGZF block %lld (no gzip header with an extra field)"
+                           : "bam: bad magic: not a BGZF file (block %lld)", block_no);
+        return WC_E_FORMAT;
+    }
+    const size_t xlen = rd16(h + 10);
+    if (n - at - 12 < xlen) { set_error("bam: truncated BGZF block %lld (extra field cut short)", block_no); return BGZF_CUT; }
+    const unsigned char *x = h + 12;
+    long bsize = -1;
+    for (size_t q = 0; q + 4 <= xlen;) {
+        const size_t slen = rd16(x + q + 2);
+        if (x[q] == 'B' && x[q + 1] == 'C' && slen == 2 && q + 6 <= xlen) bsize = rd16(x + q + 4);
+        q += 4 + slen;
+    }
+    const long rest = bsize + 1 - 12 - (long)xlen;
+    if (bsize < 0 || rest < 8) { set_error("bam: damaged BGZF block %lld (no usable BC size field)", block_no); return WC_E_FORMAT; }
+    if (n - at - 12 - xlen < (size_t)rest) {
+        set_error("bam: truncated BGZF block %lld (%ld bytes announced)", block_no, rest);
+        return BGZF_CUT;
+    }
+    b.in_off = (int64_t)(at + 12 + xlen);
+    b.in_len = (int32_t)(rest - 8);
+    b.crc = rd32(p + b.in_off + rest - 8);
+    b.isize = rd32(p + b.in_off + rest - 4);
+    b.pad_ = 0;
+    if (b.isize > 65536) { set_error("bam: damaged BGZF block %lld (%u bytes of data announced)", block_no, b.isize); return WC_E_FORMAT; }
+    b.out_off = 0;
+    next = at + 12 + xlen + (size_t)rest;
+    return WC_OK;
+}
+
 int bgzf_directory(const unsigned char *p, size_t n, std::vector<BgzfBlock> &blocks, int64_t &total) {
     blocks.clear();
     total = 0;
     size_t at = 0;
     long long block_no = 0;
     while (at < n) {
-        if (n - at < 12) { set_error("bam: truncated BGZF block %lld (header cut short)", block_no); return WC_E_FORMAT; }
-        const unsigned char *h = p + at;
-        if (h[0] != 31 || h[1] != 139 || h[2] != 8 || !(h[3] & 4)) {
-            set_error(block_no ? "bam: damaged BGZF block %lld (no gzip header with an extra field)"
-                               : "bam: bad magic: not a BGZF file (block %lld)", block_no);
-            return WC_E_FORMAT;
-        }
-        const size_t xlen = rd16(h + 10);
-        if (n - at - 12 < xlen) { set_error("bam: truncated BGZF block %lld (extra field cut short)", block_no); return WC_E_FORMAT; }
-        const unsigned char *x = h + 12;
-        long bsize = -1;
-        for (size_t q = 0; q + 4 <= xlen;) {
-            const size_t slen = rd16(x + q + 2);
-            if (x[q] == 'B' && x[q + 1] == 'C' && slen == 2 && q + 6 <= xlen) bsize = rd16(x + q + 4);
-            q += 4 + slen;
-        }
-        const long rest = bsize + 1 - 12 - (long)xlen;
-        if (bsize < 0 || rest < 8) { set_error("bam: damaged BGZF block %lld (no usable BC size field)", block_no); return WC_E_FORMAT; }
-        if (n - at - 12 - xlen < (size_t)rest) {
-            set_error("bam: truncated BGZF block %lld (%ld bytes announced)", block_no, rest);
-            return WC_E_FORMAT;
-        }
         BgzfBlock b;
-        b.in_off = (int64_t)(at + 12 + xlen);
-        b.in_len = (int32_t)(rest - 8);
-        b.crc = rd32(p + b.in_off + rest - 8);
-        b.isize = rd32(p + b.in_off + rest - 4);
-        if (b.isize > 65536) { set_error("bam: damaged BGZF block %lld (%u bytes of data announced)", block_no, b.isize); return WC_E_FORMAT; }
+        if (bgzf_block_at(p, n, at, block_no, b, at)) return WC_E_FORMAT;
         b.out_off = total;
         total += b.isize;
         blocks.push_back(b);
-        at += 12 + xlen + (size_t)rest;
         ++block_no;
     }
     return WC_OK;
@@ -167,7 +189,270 @@ int open_file(const char *path, int device, wc_bamfile &f) {
     return WC_OK;
 }
 
+
+// ---- the streamed reader's host stage -------------------------------------------------------------------------------
+const int64_t STREAM_DEFAULT_CHUNK = 256ll << 20;   // the fastest size of profiles/convert_stream_times.json
+const size_t BGZF_MAX_BLOCK = 65536;                // BSIZE has 16 bits
+
+// The header from a prefix of the file: the leading blocks are read, checked and inflated one by one until the header is
+// whole -- what open_file does on the whole file's directory, with its texts.
+int read_header(int fd, wc_bamfile &h) {
+    std::vector<unsigned char> raw, plain;
+    size_t have = 0, at = 0;
+    bool eof = false;
+    long long block_no = 0, first = 0;
+    while (first == 0) {
+        wc::BgzfBlock b;
+        size_t next = 0;
+        int rc = wc::BGZF_CUT;
+        if (at < have) rc = wc::bgzf_block_at(raw.data(), have, at, block_no, b, next);
+        else if (eof) { wc::set_error("bam: truncated: the data ends inside the BAM header"); return WC_E_FORMAT; }
+        if (rc == wc::BGZF_CUT) {
+            if (eof) return WC_E_FORMAT;                        // the text of the cut block stands
+            raw.resize(have + 4 * BGZF_MAX_BLOCK);
+            const ssize_t got = pread(fd, raw.data() + have, raw.size() - have, (off_t)have);
+            if (got < 0) {
+                if (errno == EINTR) continue;
+                wc::set_error("bam: cannot read the file (%s)", strerror(errno));
+                return WC_E_IO;
+            }
+            if (got == 0) eof = true;
+            have += (size_t)got;
+            continue;
+        }
+        if (rc) return rc;
+        const size_t base = plain.size();
+        plain.resize(base + b.isize + 1);
+        if (!inflate_block(raw.data(), b, plain.data() + base)) {
+            wc::set_error("bam: damaged BGZF block %lld (inflate or CRC failed)", block_no);
+            return WC_E_FORMAT;
+        }
+        plain.resize(base + b.isize);
+        first = parse_header(plain.data(), plain.size(), h);
+        if (first < 0) return WC_E_FORMAT;
+        at = next;
+        ++block_no;
+    }
+    h.first_record = first;
+    h.name_bytes = 0;
+    for (const std::string &s : h.names) h.name_bytes += (int64_t)s.size() + 1;
+    return WC_OK;
+}
+
 }  // namespace
+
+struct wc_bamchunks {
+    struct Fill {                       // one staging buffer's chunk, or the reader thread's last word
+        std::vector<wc::BgzfBlock> blocks;
+        int64_t first_block = 0, bytes = 0, inflated = 0, file_offset = 0;
+        bool last = false, end = false;
+        int rc = WC_OK;
+        std::string error;
+    };
+    wc_bamfile hdr;                     // the header alone: no data
+    int fd = -1;
+    int64_t chunk_bytes = 0;
+    size_t room = 0;                    // data bytes of one staging buffer; WC_BGZF_PAD more are allocated
+    unsigned char *buf[2] = {nullptr, nullptr};
+    bool pinned = false;
+    Fill fill[2];
+    bool full[2] = {false, false};      // under mu: the buffer holds a chunk the caller has not released
+    bool stop = false;
+    std::mutex mu;
+    std::condition_variable cv;
+    std::thread reader;
+    int64_t taken = 0;                  // the caller's side: chunks handed out,
+    int held = -1;                      // the buffer it holds,
+    bool done = false;                  // nothing follows
+    wc_bamchunks() = default;
+    wc_bamchunks(const wc_bamchunks &) = delete;
+    wc_bamchunks &operator=(const wc_bamchunks &) = delete;
+    ~wc_bamchunks() {
+        if (reader.joinable()) {
+            {
+                std::lock_guard<std::mutex> lk(mu);
+                stop = true;
+            }
+            cv.notify_all();
+            reader.join();
+        }
+        for (unsigned char *b : buf) {
+            if (b && pinned) (void)hipHostFree(b);
+            else free(b);
+        }
+        if (fd >= 0) close(fd);
+    }
+};
+
+namespace {
+
+// The reader thread: fill k goes to buffer k & 1 once the caller has released it.  The bytes behind a fill's chunk (a
+// block cut by the end of the read, or whole blocks beyond chunk_bytes) are copied to the front of the next buffer before
+// the file is read on; the buffer they come from is not written before the fill after that.
+void read_chunks(wc_bamchunks *c) {
+    int64_t file_at = 0, chunk_off = 0, block_no = 0;
+    size_t left = 0;
+    const unsigned char *left_from = nullptr;
+    for (int64_t k = 0;; ++k) {
+        const int slot = (int)(k & 1);
+        {
+            std::unique_lock<std::mutex> lk(c->mu);
+            c->cv.wait(lk, [&] { return c->stop || !c->full[slot]; });
+            if (c->stop) return;
+        }
+        wc_bamchunks::Fill &f = c->fill[slot];
+        f = wc_bamchunks::Fill();
+        unsigned char *b = c->buf[slot];
+        if (left) memcpy(b, left_from, left);           // left < room: the chunk before took a block or more
+        size_t n = left;
+        bool eof = false;
+        while (n < c->room && !eof && !f.rc) {
+            const ssize_t got = pread(c->fd, b + n, c->room - n, (off_t)file_at);
+            if (got < 0) {
+                if (errno == EINTR) continue;
+                f.rc = WC_E_IO;
+                f.error = std::string("bam: cannot read the file (") + strerror(errno) + ")";
+            } else if (got == 0) {
+                eof = true;
+            } else {
+                n += (size_t)got;
+                file_at += got;
+            }
+        }
+        if (!f.rc && !eof) {                            // the buffer is full: does the file end here?
+            unsigned char probe;
+            ssize_t got;
+            do got = pread(c->fd, &probe, 1, (off_t)file_at);
+            while (got < 0 && errno == EINTR);
+            eof = got == 0;
+        }
+        memset(b + n, 0, WC_BGZF_PAD);
+        if (!f.rc && n == 0) f.end = true;
+        size_t at = 0;
+        int64_t total = 0;
+        while (!f.rc && at < n) {
+            // whole blocks while they fit chunk_bytes, and one block at the least
+            if (!f.blocks.empty() && (int64_t)at >= c->chunk_bytes) break;
+            wc::BgzfBlock blk;
+            size_t next = 0;
+            const int rc = wc::bgzf_block_at(b, n, at, block_no + (long long)f.blocks.size(), blk, next);
+            if (rc == wc::BGZF_CUT && !eof && !f.blocks.empty()) break;     // the next read completes it
+            if (rc) {
+                // a defect belongs to the chunk its block starts: the blocks before it go out first
+                if (!f.blocks.empty()) break;
+                f.rc = WC_E_FORMAT;
+                f.error = wc_last_error();
+                break;
+            }
+            if (!f.blocks.empty() && (int64_t)next > c->chunk_bytes) break;
+            blk.out_off = total;
+            total += blk.isize;
+            f.blocks.push_back(blk);
+            at = next;
+        }
+        f.bytes = (int64_t)at;
+        f.inflated = total;
+        f.first_block = block_no;
+        f.file_offset = chunk_off;
+        block_no += (int64_t)f.blocks.size();
+        chunk_off += (int64_t)at;
+        left = n - at;
+        left_from = b + at;
+        f.last = eof && left == 0;
+        const bool over = f.rc || f.end || f.last;
+        {
+            std::lock_guard<std::mutex> lk(c->mu);
+            c->full[slot] = true;
+        }
+        c->cv.notify_all();
+        if (over) return;
+    }
+}
+
+int open_chunks(const char *path, int device, int64_t chunk_bytes, wc_bamchunks &c) {
+    c.fd = open(path, O_RDONLY | O_CLOEXEC);
+    if (c.fd < 0) { wc::set_error("bam: cannot open %s", path); return WC_E_IO; }
+    struct stat st;
+    if (fstat(c.fd, &st) != 0 || !S_ISREG(st.st_mode)) { wc::set_error("bam: cannot seek in %s", path); return WC_E_IO; }
+    c.hdr.size = (size_t)st.st_size;
+    const int rc = read_header(c.fd, c.hdr);
+    if (rc) return rc;
+    c.chunk_bytes = chunk_bytes > 0 ? chunk_bytes : STREAM_DEFAULT_CHUNK;
+    // a read always holds the chunk's blocks and the whole of the block that no longer fits
+    c.room = (size_t)std::min<int64_t>(c.chunk_bytes, std::max<int64_t>((int64_t)c.hdr.size, 1)) + BGZF_MAX_BLOCK;
+    const size_t cap = c.room + WC_BGZF_PAD;
+    const auto t0 = std::chrono::steady_clock::now();
+    void *a = nullptr, *b = nullptr;
+    if (device >= 0 && hipSetDevice(device) == hipSuccess && hipHostMalloc(&a, cap, hipHostMallocDefault) == hipSuccess) {
+        if (hipHostMalloc(&b, cap, hipHostMallocDefault) != hipSuccess) {
+            (void)hipHostFree(a);
+            wc::set_error("bam: no pinned memory for two staging buffers of %zu bytes", cap);
+            return WC_E_LIMIT;
+        }
+        c.pinned = true;
+        c.hdr.pin_us = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
+    } else {
+        (void)hipGetLastError();
+        a = malloc(cap);
+        b = malloc(cap);
+        if (!a || !b) {
+            free(a);
+            free(b);
+            wc::set_error("bam: no memory for two staging buffers of %zu bytes", cap);
+            return WC_E_LIMIT;
+        }
+    }
+    c.buf[0] = static_cast<unsigned char *>(a);
+    c.buf[1] = static_cast<unsigned char *>(b);
+    c.reader = std::thread(read_chunks, &c);
+    return WC_OK;
+}
+
+}  // namespace
+
+namespace wc {
+
+int bamchunks_next(wc_bamchunks *it, wc_bamchunk &c) {
+    c = wc_bamchunk();
+    if (it->held >= 0) {
+        {
+            std::lock_guard<std::mutex> lk(it->mu);
+            it->full[it->held] = false;
+        }
+        it->cv.notify_all();
+        it->held = -1;
+    }
+    if (it->done) return WC_OK;
+    const int slot = (int)(it->taken & 1);
+    {
+        std::unique_lock<std::mutex> lk(it->mu);
+        it->cv.wait(lk, [&] { return it->full[slot]; });
+    }
+    const wc_bamchunks::Fill &f = it->fill[slot];
+    if (f.rc || f.end) {
+        it->done = true;
+        if (f.rc) set_error("%s", f.error.c_str());
+        return f.rc;
+    }
+    c.data = it->buf[slot];
+    c.blocks = f.blocks.data();
+    c.n_blocks = (int64_t)f.blocks.size();
+    c.first_block = f.first_block;
+    c.bytes = f.bytes;
+    c.inflated = f.inflated;
+    c.file_offset = f.file_offset;
+    c.last = f.last;
+    it->held = slot;
+    ++it->taken;
+    it->done = f.last;
+    return WC_OK;
+}
+
+const wc_bamfile &bamchunks_header(const wc_bamchunks *it) { return it->hdr; }
+int64_t bamchunks_host_bytes(const wc_bamchunks *it) { return 2 * (int64_t)(it->room + WC_BGZF_PAD); }
+bool bamchunks_pinned(const wc_bamchunks *it) { return it->pinned; }
+
+}  // namespace wc
 
 wc_bamfile::~wc_bamfile() {
     if (data && pinned) (void)hipHostFree(data);
@@ -220,5 +505,66 @@ int wc_bamfile_refs(const wc_bamfile *f, char *names_out, int64_t names_cap, int
 }
 
 void wc_bamfile_close(wc_bamfile *f) { delete f; }
+
+int wc_bamchunks_open(const char *path, int device, int64_t chunk_bytes, wc_bamchunks **out) {
+    if (!path || !out) { wc::set_error("bam: NULL argument"); return WC_E_ARG; }
+    *out = nullptr;
+    wc_bamchunks *c = nullptr;
+    int rc;
+    try {
+        c = new wc_bamchunks();
+        rc = open_chunks(path, device, chunk_bytes, *c);
+    } catch (const std::exception &e) {
+        wc::set_error("bam: %s", e.what());
+        rc = WC_E_LIMIT;
+    }
+    if (rc != WC_OK) { delete c; return rc; }
+    *out = c;
+    return WC_OK;
+}
+
+int wc_bamchunks_info(const wc_bamchunks *c, int64_t out[8]) {
+    if (!c || !out) { wc::set_error("bam: NULL argument"); return WC_E_ARG; }
+    out[0] = (int64_t)c->hdr.names.size();
+    out[1] = 0;
+    out[2] = 0;
+    out[3] = (int64_t)c->hdr.size;
+    out[4] = c->hdr.first_record;
+    out[5] = c->hdr.name_bytes;
+    out[6] = c->pinned ? 1 : 0;
+    out[7] = wc::bamchunks_host_bytes(c);
+    return WC_OK;
+}
+
+int wc_bamchunks_refs(const wc_bamchunks *c, char *names_out, int64_t names_cap, int64_t *lengths_out) {
+    if (!c) { wc::set_error("bam: NULL argument"); return WC_E_ARG; }
+    return wc_bamfile_refs(&c->hdr, names_out, names_cap, lengths_out);
+}
+
+int wc_bamchunks_next(wc_bamchunks *c, int64_t out[8]) {
+    if (!c || !out) { wc::set_error("bam: NULL argument"); return WC_E_ARG; }
+    for (int k = 0; k < 8; ++k) out[k] = 0;
+    wc_bamchunk ch;
+    int rc;
+    try {
+        rc = wc::bamchunks_next(c, ch);
+    } catch (const std::exception &e) {
+        wc::set_error("bam: %s", e.what());
+        rc = WC_E_LIMIT;
+    }
+    if (rc || !ch.data) return rc;
+    out[0] = 1;
+    out[1] = ch.first_block;
+    out[2] = ch.n_blocks;
+    out[3] = ch.bytes;
+    out[4] = ch.inflated;
+    out[5] = ch.file_offset;
+    out[6] = ch.last ? 1 : 0;
+    return WC_OK;
+}
+
+void wc_bamchunks_close(wc_bamchunks *c) { delete c; }
+
+int64_t wc_bam_stream_default_chunk(void) { return STREAM_DEFAULT_CHUNK; }
 
 }  // extern "C"

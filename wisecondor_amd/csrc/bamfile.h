@@ -38,3 +38,22 @@ struct wc_bamfile {
     wc_bamfile &operator=(const wc_bamfile &) = delete;
     ~wc_bamfile();
 };
+
+// One chunk of the streamed reader (wc_bamchunks_next): a run of whole BGZF blocks in a staging buffer.  The directory's
+// in_off counts from `data`, its out_off from the chunk's first inflated byte.  Valid until the next call of next().
+struct wc_bamchunk {
+    const unsigned char *data = nullptr;        // bytes + WC_BGZF_PAD readable, the pad zeroed
+    const wc::BgzfBlock *blocks = nullptr;
+    int64_t n_blocks = 0, first_block = 0;      // first_block: the file's number of blocks[0]
+    int64_t bytes = 0, inflated = 0;            // compressed bytes of the chunk (whole blocks), the sum of their ISIZE
+    int64_t file_offset = 0;
+    bool last = false;                          // the file ends with this chunk
+};
+
+namespace wc {
+// The C++ face of wc_bamchunks_next for the device stage: WC_OK and c.data == nullptr behind the last chunk.
+int bamchunks_next(wc_bamchunks *it, wc_bamchunk &c);
+const wc_bamfile &bamchunks_header(const wc_bamchunks *it);     // names, lengths, first_record, name_bytes (no data)
+int64_t bamchunks_host_bytes(const wc_bamchunks *it);           // of the two staging buffers
+bool bamchunks_pinned(const wc_bamchunks *it);
+}  // namespace wc

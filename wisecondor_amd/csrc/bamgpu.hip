@@ -10,11 +10,15 @@
 //                  bamio.cpp's Parser::feed; <false> counts the placed records, <true> (after k_bg_scan) writes their
 //                  fields in file order
 //   k_bg_order / k_bg_offsets   the coordinate-order check on neighbouring placed records, the per-reference offsets
+// The streamed reader (wc_bam_stream_dev, at the end) sends the file through the same kernels chunk by chunk; k_bs_walk is
+// k_bg_walk for data that may end inside a record (the carry), k_bs_order / k_bs_offsets / k_bs_advance keep the order
+// check, the per-reference counts and the running base of the output across chunks.
 // Every loop is bounded by the bytes that are there (see the comments at the loops); a violation sets a status and the
 // wave stops.  The inflate kernel's back-references read the global output it has written itself: its LDS holds the
 // Huffman tables only ("convert: the device reader").
 #include <limits.h>
 
+#include <algorithm>
 #include <chrono>
 
 #include "bamfile.h"
@@ -491,6 +495,133 @@ __global__ void __launch_bounds__(256) k_bg_offsets(const int32_t *__restrict__ 
     offsets[r] = lo;
 }
 
+// ---- the streamed reader: the words of its device state, and the kernels that differ from the whole-file ones --------
+// [0..2] mapped, unmapped, no_coordinate (all chunks)   [3] placed records of this chunk (k_bg_scan)
+// [4] record error, (file-absolute inflated offset << 3 | kind)   [5] order error, (placed index in the file << 2 | kind)
+// [6] placed records of the chunks before   [7] offset in carry + chunk of the first record that does not end inside
+// [8] reference of the last placed record so far
+enum { BS_PLACED = 3, BS_RECERR = 4, BS_ORDERR = 5, BS_BASE = 6, BS_TAIL = 7, BS_LASTREF = 8, BS_WORDS = 16 };
+
+__global__ void __launch_bounds__(64) k_bs_begin(unsigned long long *m, long long total) {
+    if (threadIdx.x == 0) {
+        m[BS_PLACED] = 0;
+        m[BS_TAIL] = (unsigned long long)total;
+    }
+}
+
+// k_bg_walk on carry + chunk (`total` bytes, the first of them at the file's inflated offset abs_base).  A record that
+// overruns `total`, its block_size word included, is the truncation error only in the file's last chunk; before that
+// it is where the next carry starts: its offset goes to m[BS_TAIL] (one lane at most meets it: the chain is one) and the
+// walk stops there.  <true> appends at m[BS_BASE]; refs[] holds this chunk's placed records alone.
+template <bool WRITE>
+__global__ void __launch_bounds__(256) k_bs_walk(const uint8_t *__restrict__ data, long long total, long long abs_base, int last,
+                                                 int n_ref, const int *__restrict__ entry, int n_seg, int *__restrict__ cnt,
+                                                 const long long *__restrict__ seg_base, unsigned long long *m,
+                                                 int32_t *__restrict__ pos, uint8_t *__restrict__ mapq,
+                                                 uint16_t *__restrict__ flag, int32_t *__restrict__ mate, int32_t *__restrict__ refs) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= n_seg) return;
+    const int e = entry[t];
+    if (e < 0) {
+        if (!WRITE) cnt[t] = 0;
+        return;
+    }
+    long long a = (long long)t * BG_SEG + e;
+    const long long seg_end = min((long long)(t + 1) * BG_SEG, total);
+    long long local = WRITE ? seg_base[t] : 0;
+    const long long out_base = WRITE ? (long long)m[BS_BASE] : 0;
+    unsigned long long mapped = 0, unmapped = 0, nocoord = 0;
+    int placed = 0;
+    while (a < seg_end) {                           // a grows by 36 or more
+        int bad = -1;
+        int bs = 0;
+        if (a + 4 > total) bad = BG_R_TRUNC;
+        else {
+            bs = (int)bg_ld32(data + a);
+            if (bs < 32) bad = BG_R_BS;
+            else if (a + 4 + (long long)bs > total) bad = BG_R_TRUNC;
+        }
+        if (bad == BG_R_TRUNC && !last) {
+            if (!WRITE) m[BS_TAIL] = (unsigned long long)a;
+            break;
+        }
+        if (bad < 0) {
+            const uint8_t *r = data + a + 4;
+            const int ref = (int)bg_ld32(r), l_seq = (int)bg_ld32(r + 16);
+            const unsigned fl = bg_ld16(r + 14);
+            const long long need = 32 + (long long)r[8] + 4 * (long long)bg_ld16(r + 12) + ((long long)l_seq + 1) / 2 + (long long)l_seq;
+            if (l_seq < 0 || need > (long long)bs) bad = BG_R_FIELDS;
+            else if (ref >= n_ref) bad = BG_R_REF;
+            else {
+                if (fl & 4u) ++unmapped;
+                if (ref < 0) {
+                    ++nocoord;
+                } else {
+                    if (!(fl & 4u)) ++mapped;
+                    if (WRITE) {
+                        const long long idx = out_base + local;
+                        pos[idx] = (int32_t)bg_ld32(r + 4);
+                        mapq[idx] = r[9];
+                        flag[idx] = (uint16_t)fl;
+                        mate[idx] = (int32_t)bg_ld32(r + 24);
+                        refs[local] = ref;
+                    }
+                    ++local;
+                    ++placed;
+                }
+            }
+        }
+        if (bad >= 0) {
+            if (!WRITE) atomicMin(&m[BS_RECERR], ((unsigned long long)(abs_base + a) << 3) | (unsigned)bad);
+            break;
+        }
+        a += 4 + (long long)bs;
+    }
+    if (!WRITE) {
+        cnt[t] = placed;
+        if (mapped) atomicAdd(&m[0], mapped);
+        if (unmapped) atomicAdd(&m[1], unmapped);
+        if (nocoord) atomicAdd(&m[2], nocoord);
+    }
+}
+
+// k_bg_order on this chunk's placed records: the predecessor of the first is the last placed record of the chunks
+// before (its reference in m[BS_LASTREF], its position in the output).  The grid covers the most records the chunk can hold.
+__global__ void __launch_bounds__(256) k_bs_order(const int32_t *__restrict__ refs, const int32_t *__restrict__ pos,
+                                                  unsigned long long *m) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)m[BS_PLACED]) return;
+    const long long base = (long long)m[BS_BASE], g = base + i;
+    if (g == 0) return;
+    const int a = i ? refs[i - 1] : (int)(long long)m[BS_LASTREF], b = refs[i];
+    const unsigned kind = b < a ? 1u : (b == a && pos[g] < pos[g - 1]) ? 2u : 0u;
+    if (kind) atomicMin(&m[BS_ORDERR], ((unsigned long long)g << 2) | kind);
+}
+
+// acc[r] += the number of this chunk's placed records of references below r (refs[] ascends, or the order check fails):
+// behind the last chunk acc[] is k_bg_offsets' result
+__global__ void __launch_bounds__(256) k_bs_offsets(const int32_t *__restrict__ refs, const unsigned long long *__restrict__ m,
+                                                    int n_ref, long long *__restrict__ acc) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r > n_ref) return;
+    long long lo = 0, hi = (long long)m[BS_PLACED];
+    while (lo < hi) {
+        const long long mid = lo + (hi - lo) / 2;
+        if (refs[mid] < r) lo = mid + 1;
+        else hi = mid;
+    }
+    acc[r] += lo;
+}
+
+__global__ void __launch_bounds__(64) k_bs_advance(const int32_t *__restrict__ refs, unsigned long long *m) {
+    if (threadIdx.x) return;
+    const long long n = (long long)m[BS_PLACED];
+    if (n) {
+        m[BS_LASTREF] = (unsigned long long)(long long)refs[n - 1];
+        m[BS_BASE] += (unsigned long long)n;
+    }
+}
+
 struct DevMem {             // a device allocation of one call
     void *p = nullptr;
     DevMem() = default;
@@ -540,6 +671,7 @@ struct wc_bam_dev {
     void *pos = nullptr, *mapq = nullptr, *flag = nullptr, *mate = nullptr;
     int64_t n = 0, mapped = 0, unmapped = 0, no_coordinate = 0, name_bytes = 0, need = 0, budget = 0;
     double times[8] = {0};
+    int64_t stream_info[8] = {0};       // wc_bam_dev_stream_info (a streamed open)
     ~wc_bam_dev() {
         for (void *p : {pos, mapq, flag, mate})
             if (p) (void)hipFree(p);
@@ -688,6 +820,239 @@ int open_dev(wc_ctx *ctx, hipStream_t stream, const wc_bamfile &f, int64_t budge
     return WC_OK;
 }
 
+// ---- the streamed open ------------------------------------------------------------------------------------------------
+struct ChunkCloser {
+    wc_bamchunks *it = nullptr;
+    ~ChunkCloser() { wc_bamchunks_close(it); }
+};
+struct CopyStream {
+    hipStream_t s = nullptr;
+    hipEvent_t done[2] = {nullptr, nullptr};
+    ~CopyStream() {
+        if (s) (void)hipStreamSynchronize(s);           // no copy may outlive the staging buffers
+        for (hipEvent_t e : done)
+            if (e) (void)hipEventDestroy(e);
+        if (s) (void)hipStreamDestroy(s);
+    }
+};
+struct Sized {              // a working buffer that grows to the largest need seen (its old content is not kept)
+    DevMem mem;
+    size_t cap = 0;
+    int reserve(size_t want) {
+        if (want <= cap) return WC_OK;
+        mem.release();
+        cap = 0;
+        const int rc = mem.alloc(want);
+        if (rc == WC_OK) cap = want;
+        return rc;
+    }
+};
+
+int stream_dev(wc_ctx *ctx, hipStream_t stream, const char *path, int64_t chunk_bytes, wc_bam_dev &h) {
+    const auto began = std::chrono::steady_clock::now();
+    auto ms_since = [](std::chrono::steady_clock::time_point t) {
+        return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
+    };
+    ChunkCloser chunks;
+    int rc = wc_bamchunks_open(path, ctx->device, chunk_bytes, &chunks.it);
+    if (rc) return rc;
+    const wc_bamfile &hdr = wc::bamchunks_header(chunks.it);
+    h.names = hdr.names;
+    h.lengths = hdr.lengths;
+    h.name_bytes = hdr.name_bytes;
+    const int n_ref = (int)hdr.names.size();
+    h.offsets.assign((size_t)n_ref + 1, 0);
+    const long long first_record = hdr.first_record;
+
+    CopyStream copy;
+    WC_HIP(hipStreamCreateWithFlags(&copy.s, hipStreamNonBlocking));
+    for (hipEvent_t &e : copy.done) WC_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    // comp, dir: one per chunk in flight (the copy of chunk i + 1 runs beside the decode of chunk i); plain: the carry
+    // moves from one to the other
+    Sized comp[2], dir[2], plain[2], status, map, entry, cnt, base, refs;
+    DevMem acc, misc, out[4];
+    static const size_t width[4] = {4, 1, 2, 4};        // pos, mapq, flag, mate_pos
+    int64_t out_cap = 0, peak_work = 0, peak_all = 0, regrows = 0;
+    auto account = [&]() {
+        int64_t w = 8 * ((int64_t)n_ref + 1) + 8 * BS_WORDS;
+        for (const Sized *b : {&comp[0], &comp[1], &dir[0], &dir[1], &plain[0], &plain[1], &status, &map, &entry, &cnt, &base, &refs})
+            w += (int64_t)b->cap;
+        peak_work = std::max(peak_work, w);
+        peak_all = std::max(peak_all, w + 11 * out_cap);
+    };
+    if ((rc = acc.alloc(8 * ((size_t)n_ref + 1))) || (rc = misc.alloc(8 * BS_WORDS))) return rc;
+    unsigned long long *m = misc.as<unsigned long long>();
+    unsigned long long got[BS_WORDS] = {0};
+    got[BS_RECERR] = got[BS_ORDERR] = ~0ull;
+    got[BS_LASTREF] = (unsigned long long)-1ll;
+    WC_HIP(hipMemcpyAsync(m, got, sizeof(got), hipMemcpyHostToDevice, stream));
+    WC_HIP(hipMemsetAsync(acc.p, 0, 8 * ((size_t)n_ref + 1), stream));
+
+    double wait_reader = 0., wait_device = 0.;
+    auto next_chunk = [&](wc_bamchunk &c) {
+        const auto t0 = std::chrono::steady_clock::now();
+        const int r = wc::bamchunks_next(chunks.it, c);
+        wait_reader += ms_since(t0);
+        return r;
+    };
+    auto upload = [&](const wc_bamchunk &c, int slot) {
+        int r;
+        if ((r = comp[slot].reserve((size_t)c.bytes + WC_BGZF_PAD)) || (r = dir[slot].reserve(sizeof(wc::BgzfBlock) * (size_t)c.n_blocks)))
+            return r;
+        account();
+        WC_HIP(hipMemcpyAsync(comp[slot].mem.p, c.data, (size_t)c.bytes + WC_BGZF_PAD, hipMemcpyHostToDevice, copy.s));
+        WC_HIP(hipMemcpyAsync(dir[slot].mem.p, c.blocks, sizeof(wc::BgzfBlock) * (size_t)c.n_blocks, hipMemcpyHostToDevice, copy.s));
+        WC_HIP(hipEventRecord(copy.done[slot], copy.s));
+        return (int)WC_OK;
+    };
+
+    wc_bamchunk cur, nxt;
+    if ((rc = next_chunk(cur))) return rc;
+    if (cur.data && (rc = upload(cur, 0))) return rc;
+    long long carry = 0, tail = 0, abs_next = 0, placed = 0, prev_last_ref = -1;
+    int64_t n_chunks = 0, max_comp = 0, max_infl = 0, max_carry = 0;
+    std::vector<int> st;
+    for (int64_t i = 0; cur.data; ++i) {
+        const int s = (int)(i & 1);
+        const long long total = carry + cur.inflated, abs_base = abs_next - carry;
+        const int64_t n_seg = (total + BG_SEG - 1) / BG_SEG, n_blocks = cur.n_blocks;
+        const int64_t max_rec = total / BG_STEP + 1;
+        WC_CHECK(n_seg < (int64_t)INT_MAX / 2 && n_blocks < (int64_t)INT_MAX, WC_E_LIMIT, "bam: %lld inflated bytes in one chunk",
+                 (long long)total);
+        if ((rc = plain[s].reserve((size_t)n_seg * BG_SEG + 64)) || (rc = map.reserve(2 * (size_t)n_seg * BG_SEG)) ||
+            (rc = entry.reserve(4 * (size_t)n_seg)) || (rc = cnt.reserve(4 * (size_t)n_seg)) || (rc = base.reserve(8 * (size_t)n_seg)) ||
+            (rc = refs.reserve(4 * (size_t)((n_seg * BG_SEG) / BG_STEP + 1))) || (rc = status.reserve(4 * (size_t)n_blocks)))
+            return rc;
+        if (placed + max_rec > out_cap) {               // the arrays: room for the most records this chunk can hold
+            const int64_t want = std::max<int64_t>(placed + max_rec, 2 * out_cap);
+            DevMem grown[4];
+            for (int k = 0; k < 4; ++k)
+                if ((rc = grown[k].alloc(width[k] * (size_t)want))) return rc;
+            peak_all = std::max(peak_all, peak_work + 11 * (out_cap + want));
+            for (int k = 0; k < 4 && placed; ++k)
+                WC_HIP(hipMemcpyAsync(grown[k].p, out[k].p, width[k] * (size_t)placed, hipMemcpyDeviceToDevice, stream));
+            WC_HIP(hipStreamSynchronize(stream));
+            for (int k = 0; k < 4; ++k) {
+                out[k].release();
+                out[k].p = grown[k].take();
+            }
+            if (out_cap) ++regrows;
+            out_cap = want;
+        }
+        account();
+        uint8_t *data = plain[s].mem.as<uint8_t>();
+        if (carry)
+            WC_HIP(hipMemcpyAsync(data, plain[s ^ 1].mem.as<uint8_t>() + tail, (size_t)carry, hipMemcpyDeviceToDevice, stream));
+        WC_HIP(hipStreamWaitEvent(stream, copy.done[s], 0));
+        hipLaunchKernelGGL(k_bs_begin, dim3(1), dim3(64), 0, stream, m, total);
+        if (n_blocks)
+            hipLaunchKernelGGL(k_bg_inflate, dim3((unsigned)n_blocks), dim3(64), 0, stream, (const uint8_t *)comp[s].mem.as<uint8_t>(),
+                               (const wc::BgzfBlock *)dir[s].mem.as<wc::BgzfBlock>(), data + carry, status.mem.as<int>());
+        // the records: from the carry's first byte, or from the end of the header in the chunk that holds it
+        const long long first = std::max(first_record - abs_base, 0ll);
+        if (first < total) {
+            const unsigned walk_grid = (unsigned)((n_seg + 255) / 256);
+            const int last = cur.last ? 1 : 0;
+            hipLaunchKernelGGL(k_bg_chain, dim3((unsigned)n_seg), dim3(64), 0, stream, (const uint8_t *)data, total, map.mem.as<uint16_t>());
+            hipLaunchKernelGGL(k_bg_link, dim3(1), dim3(64), 0, stream, (const uint8_t *)data, total, first,
+                               (const uint16_t *)map.mem.as<uint16_t>(), (int)n_seg, entry.mem.as<int>());
+            hipLaunchKernelGGL(k_bs_walk<false>, dim3(walk_grid), dim3(256), 0, stream, (const uint8_t *)data, total, abs_base, last,
+                               n_ref, (const int *)entry.mem.as<int>(), (int)n_seg, cnt.mem.as<int>(), (const long long *)nullptr, m,
+                               (int32_t *)nullptr, (uint8_t *)nullptr, (uint16_t *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr);
+            hipLaunchKernelGGL(k_bg_scan, dim3(1), dim3(256), 0, stream, (const int *)cnt.mem.as<int>(), (int)n_seg,
+                               base.mem.as<long long>(), m + BS_PLACED);
+            hipLaunchKernelGGL(k_bs_walk<true>, dim3(walk_grid), dim3(256), 0, stream, (const uint8_t *)data, total, abs_base, last,
+                               n_ref, (const int *)entry.mem.as<int>(), (int)n_seg, (int *)nullptr,
+                               (const long long *)base.mem.as<long long>(), m, out[0].as<int32_t>(), out[1].as<uint8_t>(),
+                               out[2].as<uint16_t>(), out[3].as<int32_t>(), refs.mem.as<int32_t>());
+            hipLaunchKernelGGL(k_bs_order, dim3((unsigned)((max_rec + 255) / 256)), dim3(256), 0, stream,
+                               (const int32_t *)refs.mem.as<int32_t>(), (const int32_t *)out[0].as<int32_t>(), m);
+            hipLaunchKernelGGL(k_bs_offsets, dim3((unsigned)(n_ref / 256 + 1)), dim3(256), 0, stream,
+                               (const int32_t *)refs.mem.as<int32_t>(), (const unsigned long long *)m, n_ref, acc.as<long long>());
+            hipLaunchKernelGGL(k_bs_advance, dim3(1), dim3(64), 0, stream, (const int32_t *)refs.mem.as<int32_t>(), m);
+        }
+        WC_HIP(hipGetLastError());
+        // the staging buffer of this chunk is free once its copy has run: the reader thread may fill it with chunk i + 2,
+        // and the copy of chunk i + 1 runs beside this chunk's kernels
+        const auto t0 = std::chrono::steady_clock::now();
+        WC_HIP(hipEventSynchronize(copy.done[s]));
+        wait_device += ms_since(t0);
+        const long long first_block = cur.first_block;
+        const bool was_last = cur.last;
+        ++n_chunks;
+        max_comp = std::max<int64_t>(max_comp, cur.bytes);
+        max_infl = std::max<int64_t>(max_infl, cur.inflated);
+        abs_next += cur.inflated;
+        const int rc_next = next_chunk(nxt);            // a defect of the next chunk waits for this chunk's status: file order
+        char next_error[1024];
+        if (rc_next) snprintf(next_error, sizeof(next_error), "%s", wc_last_error());
+        else if (nxt.data && (rc = upload(nxt, s ^ 1))) return rc;
+        st.assign((size_t)n_blocks, 0);
+        if (n_blocks) WC_HIP(hipMemcpyAsync(st.data(), status.mem.p, 4 * (size_t)n_blocks, hipMemcpyDeviceToHost, stream));
+        WC_HIP(hipMemcpyAsync(got, m, sizeof(got), hipMemcpyDeviceToHost, stream));
+        const auto t1 = std::chrono::steady_clock::now();
+        WC_HIP(hipStreamSynchronize(stream));
+        wait_device += ms_since(t1);
+        const int bad = first_bad_block(st);
+        WC_CHECK(bad < 0, WC_E_FORMAT, "bam: damaged BGZF block %lld (%s)", first_block + bad,
+                 st[(size_t)(bad < 0 ? 0 : bad)] == BG_E_CRC ? "CRC failed" : "inflate failed");
+        if (got[BS_RECERR] != ~0ull) {
+            const long long at = (long long)(got[BS_RECERR] >> 3);
+            switch ((int)(got[BS_RECERR] & 7u)) {
+                case BG_R_BS: wc::set_error("bam: the record at inflated offset %lld has a block_size below its 32 fixed bytes", at); break;
+                case BG_R_FIELDS: wc::set_error("bam: the fields of the record at inflated offset %lld overrun its block_size", at); break;
+                case BG_R_REF: wc::set_error("bam: the record at inflated offset %lld names a reference beyond the %d of the header", at, n_ref); break;
+                default: wc::set_error("bam: truncated: the record at inflated offset %lld overruns the data (%lld bytes)", at, abs_base + total);
+            }
+            return WC_E_FORMAT;
+        }
+        if (got[BS_ORDERR] != ~0ull) {
+            const long long g = (long long)(got[BS_ORDERR] >> 2), local = g - placed;
+            int32_t two_ref[2] = {(int32_t)prev_last_ref, 0}, two_pos[2] = {0, 0};
+            if (local > 0) WC_HIP(hipMemcpy(two_ref, refs.mem.as<int32_t>() + local - 1, 8, hipMemcpyDeviceToHost));
+            else WC_HIP(hipMemcpy(two_ref + 1, refs.mem.as<int32_t>(), 4, hipMemcpyDeviceToHost));
+            WC_HIP(hipMemcpy(two_pos, out[0].as<int32_t>() + g - 1, 8, hipMemcpyDeviceToHost));
+            if ((got[BS_ORDERR] & 3u) == 1u)
+                wc::set_error("bam: not coordinate-sorted: placed record %lld of reference %d follows reference %d (the records of a "
+                              "reference must be contiguous, references in header order)", g, two_ref[1], two_ref[0]);
+            else
+                wc::set_error("bam: not coordinate-sorted: position %d follows %d in reference %d (placed record %lld)", two_pos[1],
+                              two_pos[0], two_ref[1], g);
+            return WC_E_ARG;
+        }
+        placed = (long long)got[BS_BASE];
+        WC_CHECK(placed <= (long long)INT32_MAX, WC_E_LIMIT, "bam: more than 2^31 - 1 placed records");
+        prev_last_ref = (long long)got[BS_LASTREF];
+        tail = (long long)got[BS_TAIL];
+        carry = was_last ? 0 : total - tail;
+        max_carry = std::max<int64_t>(max_carry, carry);
+        if (rc_next) {
+            wc::set_error("%s", next_error);
+            return rc_next;
+        }
+        cur = nxt;
+    }
+    h.mapped = (int64_t)got[0];
+    h.unmapped = (int64_t)got[1];
+    h.no_coordinate = (int64_t)got[2];
+    h.n = placed;
+    WC_HIP(hipMemcpyAsync(h.offsets.data(), acc.p, 8 * ((size_t)n_ref + 1), hipMemcpyDeviceToHost, stream));
+    WC_HIP(hipStreamSynchronize(stream));
+    h.need = peak_all;
+    h.budget = 0;
+    const int64_t info[8] = {n_chunks, max_comp, max_infl, max_carry, peak_work, wc::bamchunks_host_bytes(chunks.it), regrows,
+                             wc::bamchunks_pinned(chunks.it) ? 1 : 0};
+    for (int k = 0; k < 8; ++k) h.stream_info[k] = info[k];
+    h.times[0] = wait_reader;
+    h.times[1] = wait_device;
+    h.times[7] = ms_since(began);
+    h.pos = out[0].take();
+    h.mapq = out[1].take();
+    h.flag = out[2].take();
+    h.mate = out[3].take();
+    return WC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -712,6 +1077,33 @@ int wc_bam_open_dev(wc_ctx *ctx, void *stream, const wc_bamfile *file, int64_t b
         return rc;
     }
     *out = h;
+    return WC_OK;
+}
+
+int wc_bam_stream_dev(wc_ctx *ctx, void *stream, const char *path, int64_t chunk_bytes, wc_bam_dev **out) {
+    WC_CHECK(ctx && path && out, WC_E_ARG, "bam: NULL argument");
+    *out = nullptr;
+    WC_HIP(hipSetDevice(ctx->device));
+    wc_bam_dev *h = nullptr;
+    int rc;
+    try {
+        h = new wc_bam_dev();
+        rc = stream_dev(ctx, (hipStream_t)stream, path, chunk_bytes, *h);
+    } catch (const std::exception &e) {
+        wc::set_error("bam: %s", e.what());
+        rc = WC_E_LIMIT;
+    }
+    if (rc != WC_OK) {
+        delete h;
+        return rc;
+    }
+    *out = h;
+    return WC_OK;
+}
+
+int wc_bam_dev_stream_info(const wc_bam_dev *h, int64_t out[8]) {
+    WC_CHECK(h && out, WC_E_ARG, "bam: NULL argument");
+    for (int k = 0; k < 8; ++k) out[k] = h->stream_info[k];
     return WC_OK;
 }
 

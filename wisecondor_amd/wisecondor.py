@@ -74,11 +74,27 @@ def writeConvertOutput(outfile, args, converted, qual_info):
     write_npz(outfile, arguments=vars(args), runtime=getRuntime(), sample=converted, quality=qual_info)
 
 
+def _convert_streamed(args):
+    """True where `convert` / `convertbatch` read through the streamed reader.  `-chunk` is that reader's option: without
+    it the option is an error, not something to ignore and then record in the output file's `arguments`."""
+    streamed = getattr(args, 'stream', False) or wt.CONVERT_READER == 'stream'
+    if hasattr(args, 'chunk') and not streamed:
+        raise ValueError('-chunk sets the chunk size of the streamed reader: give -stream as well')
+    return streamed
+
+
 def toolConvert(args):
     """`convert infile outfile`: BAM -> binned, filtered sample (wisecondor.py:20-27)."""
-    converted, qual_info = wt.convertBam(args.infile, binsize=args.binsize, minShift=args.retdist,
-                                         threshold=args.retthres, mapq=getattr(args, 'mapq', 1),
-                                         demandPair=getattr(args, 'paired', False))
+    if _convert_streamed(args):
+        # build-only: the streamed device reader (memory bounded by the chunk); the same filters and binning behind it
+        with wt.openBamReads(args.infile, stream=True, chunk=getattr(args, 'chunk', 0)) as bam:
+            converted, qual_info = wt.convertBamReads(bam, args.binsize, args.retdist, args.retthres, verbose=True,
+                                                      mapq=getattr(args, 'mapq', 1),
+                                                      demandPair=getattr(args, 'paired', False))
+    else:
+        converted, qual_info = wt.convertBam(args.infile, binsize=args.binsize, minShift=args.retdist,
+                                             threshold=args.retthres, mapq=getattr(args, 'mapq', 1),
+                                             demandPair=getattr(args, 'paired', False))
     writeConvertOutput(args.outfile, args, converted, qual_info)
     print('Conversion finished')
 
@@ -111,19 +127,27 @@ def toolConvertBatch(args):
     written = []
     ahead = taken = None
     try:
-        # the reader thread's share: the host stage of the device reader, or the whole host reader
-        if wt.CONVERT_READER == 'device':
+        # the reader thread's share: the host stage of the device reader, or the whole host reader; nothing for the
+        # streamed reader, which has a reader thread of its own and holds no file whole
+        streamed = _convert_streamed(args)
+        if streamed:
+            stage = None
+        elif wt.CONVERT_READER == 'device':
             def stage(path):
                 return wt.BamFile(path)
         else:
             def stage(path):
                 return wt.BamReads(path, args.io)
-        ahead = reader.submit(stage, args.infiles[0])
+        if stage:
+            ahead = reader.submit(stage, args.infiles[0])
         for i, (path, out) in enumerate(zip(args.infiles, outs)):
-            bam = ahead.result()
-            taken = ahead
-            if i + 1 < len(args.infiles):
-                ahead = reader.submit(stage, args.infiles[i + 1])
+            if streamed:
+                bam = wt.openBamReads(path, stream=True, chunk=getattr(args, 'chunk', 0))
+            else:
+                bam = ahead.result()
+                taken = ahead
+                if i + 1 < len(args.infiles):
+                    ahead = reader.submit(stage, args.infiles[i + 1])
             if isinstance(bam, wt.BamFile):
                 bamfile = bam
                 try:
@@ -551,6 +575,10 @@ def buildParser():
         ('-paired', dict(action='store_true', default=argparse.SUPPRESS,
                          help='Paired-end mode: count proper-pair first-in-pair reads only, a duplicate repeats the '
                               'previous read\'s position and mate position')),
+        ('-stream', dict(action='store_true', default=argparse.SUPPRESS,
+                         help='Read the BAM through the GPU in chunks (memory bounded by the chunk, not the file)')),
+        ('-chunk', dict(type=int, default=argparse.SUPPRESS,
+                        help='Compressed bytes per chunk of -stream (default: the library\'s)')),
     )
     p = sub.add_parser('convert', description='Convert and filter a bam file to an npz')
     p.add_argument('infile', type=str, help='Bam input file for conversion')

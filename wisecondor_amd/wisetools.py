@@ -606,6 +606,11 @@ class BamReadsDevice(object):
         finally:
             if own:
                 bamfile.close()
+        self._adopt(handle)
+
+    def _adopt(self, handle):
+        """The attributes of an opened wc_bam_dev handle."""
+        lib = _lib.load()
         self._handle = handle
         info = np.zeros(8, dtype=np.int64)
         _lib.check(lib.wc_bam_dev_info(handle, _lib.ptr(info)))
@@ -646,16 +651,91 @@ class BamReadsDevice(object):
         self.close()
 
 
+#: compressed bytes per chunk of BamReadsStream; 0: the library's default (wc_bam_stream_default_chunk)
+BAM_STREAM_CHUNK = 0
+
+STREAM_INFO_KEYS = ('chunks', 'largest_chunk_compressed_bytes', 'largest_chunk_inflated_bytes', 'largest_carry_bytes',
+                    'peak_device_working_bytes', 'host_staging_bytes', 'output_regrows', 'pinned')
+
+
+class BamReadsStream(BamReadsDevice):
+    """BamReadsDevice by the streamed reader (wc_bam_stream_dev): the file goes through the GPU in chunks of whole BGZF
+    blocks of at most `chunk` compressed bytes (<= 0: BAM_STREAM_CHUNK), records that straddle a chunk boundary are carried
+    over, and host and device working memory are bounded by the chunk and the longest record.  The same attributes;
+    `device_bytes` is the peak of the device memory, the four arrays included; `stage_ms` has 'reader_wait' (the call
+    waiting for the file), 'device_wait' and 'call'; `stream_info` is wc_bam_dev_stream_info as a dict."""
+
+    def __init__(self, path, device=0, chunk=0):
+        lib = _lib.load()
+        self._handle = None
+        handle = ctypes.c_void_p()
+        _lib.check(lib.wc_bam_stream_dev(_lib.context(device), None, os.fsencode(path),
+                                         int(chunk) if chunk > 0 else int(BAM_STREAM_CHUNK), ctypes.byref(handle)))
+        self._adopt(handle)
+        times = np.zeros(8, dtype=np.float64)           # wc_bam_dev_times of a streamed handle: [0], [1] and [7] are set
+        _lib.check(lib.wc_bam_dev_times(handle, _lib.ptr(times)))
+        self.stage_ms = {'reader_wait': float(times[0]), 'device_wait': float(times[1]), 'call': float(times[7])}
+        info = np.zeros(8, dtype=np.int64)
+        _lib.check(lib.wc_bam_dev_stream_info(handle, _lib.ptr(info)))
+        self.stream_info = dict(zip(STREAM_INFO_KEYS, (int(v) for v in info)))
+
+
+class BamChunks(object):
+    """The host stage of the streamed reader (csrc/bamfile.cpp, no GPU needed): the header (`names`, `lengths`,
+    `first_record`), then iteration over the chunks as dicts (first_block, blocks, compressed_bytes, inflated_bytes,
+    file_offset, last).  Errors carry the codes of BamFile; a defect of a block is raised when its chunk is reached."""
+
+    def __init__(self, path, device=0, chunk=0):
+        lib = _lib.load()
+        handle = ctypes.c_void_p()
+        _lib.check(lib.wc_bamchunks_open(os.fsencode(path), int(device), int(chunk), ctypes.byref(handle)))
+        self._handle = handle
+        info = np.zeros(8, dtype=np.int64)
+        _lib.check(lib.wc_bamchunks_info(handle, _lib.ptr(info)))
+        n_refs, _, _, self.compressed_bytes, self.first_record, name_bytes = (int(v) for v in info[:6])
+        self.pinned, self.host_bytes = bool(info[6]), int(info[7])
+        names = ctypes.create_string_buffer(name_bytes + 1)
+        self.lengths = np.zeros(n_refs, dtype=np.int64)
+        _lib.check(lib.wc_bamchunks_refs(handle, ctypes.cast(names, ctypes.c_void_p), name_bytes + 1, _lib.ptr(self.lengths)))
+        self.names = names.raw[:name_bytes].decode('latin1').split('\n')[:n_refs]
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        out = np.zeros(8, dtype=np.int64)
+        _lib.check(_lib.load().wc_bamchunks_next(self._handle, _lib.ptr(out)))
+        if not out[0]:
+            raise StopIteration
+        return {'first_block': int(out[1]), 'blocks': int(out[2]), 'compressed_bytes': int(out[3]),
+                'inflated_bytes': int(out[4]), 'file_offset': int(out[5]), 'last': bool(out[6])}
+
+    def close(self):
+        if self._handle is not None:
+            _lib.load().wc_bamchunks_close(self._handle)
+            self._handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 #: the reader convertBam and convertbatch open a file with: 'device' (BamReadsDevice; the host reader only for a file
-#: beyond the device budget) or 'host' (BamReads).  Set by the measurement in profiles/convert_times.json:
+#: beyond the device budget), 'stream' (BamReadsStream: memory bounded by BAM_STREAM_CHUNK, no budget) or 'host' (BamReads).
+#: Set by the measurement in profiles/convert_times.json (DESIGN.md 6b):
 #: 5 million records, whole call 0.285 s through the device reader against 0.517 s (spread 0.024 s) through the host reader.
 CONVERT_READER = 'device'
 
 
-def openBamReads(source, threads=8, device=0):
-    """The reader convertBam uses for `source` (a path or an opened BamFile).  With CONVERT_READER == 'device': the device
-    reader, and the host reader where the file does not fit the device budget (E_LIMIT) -- the file's size decides, no
-    option.  With 'host': the host reader."""
+def openBamReads(source, threads=8, device=0, stream=None, chunk=0):
+    """The reader convertBam uses for `source` (a path or an opened BamFile).  With `stream` true, or None and
+    CONVERT_READER == 'stream': the streamed device reader with chunks of `chunk` bytes (<= 0: BAM_STREAM_CHUNK).  Else with
+    CONVERT_READER == 'device': the device reader, and the host reader where the file does not fit the device budget
+    (E_LIMIT) -- the file's size decides, no option.  With 'host': the host reader."""
+    if stream or (stream is None and CONVERT_READER == 'stream'):
+        return BamReadsStream(source.path if isinstance(source, BamFile) else source, device=device, chunk=chunk)
     if CONVERT_READER == 'device':
         try:
             return BamReadsDevice(source, device=device)
@@ -747,7 +827,8 @@ def convertBam(bamfile, binsize=1000000, minShift=4, threshold=4, threads=8, dev
     mapping-quality floor, `demandPair` the paired-end branch (only proper-pair first-in-pair reads take part, a
     duplicate has the previous such read's position and mate position, the rest is counted in pair_fail).  The file
     is read by the device reader (BamReadsDevice; the host reader BamReads with `threads` threads where the file does
-    not fit the device budget), the filters run on the GPU."""
+    not fit the device budget; the streamed reader where CONVERT_READER says so: openBamReads), the filters run on the
+    GPU."""
     with openBamReads(bamfile, threads=threads, device=device) as bam:
         return convertBamReads(bam, binsize, minShift, threshold, device=device, verbose=True, mapq=mapq,
                                demandPair=demandPair)
