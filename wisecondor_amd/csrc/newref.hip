@@ -161,19 +161,53 @@ __global__ __launch_bounds__(256) void k_convert(const double *__restrict__ X, i
     if (blockIdx.x == 0)
         for (int i = threadIdx.x; i < n_fb_zero; i += 256) fb_zero[i] = 0;
     if (row >= Bpad) return;                   // (Bpad is a multiple of 128: whole waves)
-    // float64 image with rows padded to whole 16-sample chunks (128-byte aligned rows, zero
-    // padding): the re-score gathers read it with aligned 16-byte loads and no tail cases
-    if (X64 && row < B)
-        for (int64_t s = hl; s < Sp; s += 32) X64[row * Sp + s] = s < S ? X[row * S + s] : 0.0;
-    const int slot = row < B ? sample_slot[row] : -1;   // >= 0: this row is one of the sampled rows
+    // The half wave reads its row ONCE, samples hl + 32 i in blocks of CB: every load of a block -- the row's values,
+    // mean[s] and the scale terms mean[S + s] -- is an unconditional load of a selected index (element 0 always exists)
+    // issued before the block's first use, so a block is one memory round trip.  (One load and one wait per iteration
+    // of three loops, two of which read again what the first had read, were twelve dependent trips at 100 samples.)
+    constexpr int CB = 4;
+    const int64_t xrow = (row < B ? row : 0) * S;
+    auto load_x = [&](int64_t s0, double (&xv)[CB], double (&mv)[CB]) {
+#pragma unroll
+        for (int j = 0; j < CB; ++j) {
+            const int64_t s = s0 + 32 * j, sc = s < S ? s : 0;
+            xv[j] = X[xrow + sc];
+            mv[j] = mean[sc];
+        }
+    };
+    // (the empty statements pin a batch behind its loads: a load whose only use is under a lane condition is
+    // otherwise sunk into that block, with a wait of its own)
+    auto pin = [&](double (&v)[CB]) {
+#pragma unroll
+        for (int j = 0; j < CB; ++j) asm volatile("" : "+v"(v[j]));
+    };
+    auto load_scale = [&](int64_t s0, double (&sv)[CB]) {
+#pragma unroll
+        for (int j = 0; j < CB; ++j) {
+            const int64_t s = s0 + 32 * j;
+            sv[j] = mean[S + (s < S ? s : 0)];
+        }
+    };
+    // the first block of the row and of the centre rides with the first block of the scale terms, the row's sample
+    // slot and the chromosome ends: at up to 128 samples that is everything this half wave reads, in one trip
+    // (up to WC_MAX_CHROM = 64 chromosomes: two ends per lane of the half)
+    double xv[CB], mv[CB], sv[CB];
+    load_scale(hl, sv);
+    load_x(hl, xv, mv);
+    int slot_w = sample_slot[row < B ? row : 0];
+    int64_t end0_w = chrom_off[hl < n_chrom ? hl + 1 : 0], end1_w = chrom_off[hl + 32 < n_chrom ? hl + 33 : 0];
+    asm volatile("" : "+v"(slot_w), "+v"(end0_w), "+v"(end1_w));
+    pin(sv);
+    pin(xv);
+    pin(mv);
+    const int slot = row < B ? slot_w : -1;    // >= 0: this row is one of the sampled rows
     // chromosome of the row: lane c of the half holds the end of chromosome c (at most 32 of them), the row's
     // chromosome is the number of ends at or below it (the serial search was up to 22 dependent loads on lane 0)
     int ch_w = -1;
     int2 range_w = make_int2(0, 0);
     {
-        // (up to WC_MAX_CHROM = 64 chromosomes: two ends per lane of the half)
         const int64_t none = (int64_t)0x7FFFFFFFFFFFFFFFll;
-        const int64_t end0 = hl < n_chrom ? chrom_off[hl + 1] : none, end1 = hl + 32 < n_chrom ? chrom_off[hl + 33] : none;
+        const int64_t end0 = hl < n_chrom ? end0_w : none, end1 = hl + 32 < n_chrom ? end1_w : none;
         const unsigned long long b0 = __ballot(row < B && hl < n_chrom - 1 && row >= end0);
         const unsigned long long b1 = __ballot(row < B && hl + 32 < n_chrom - 1 && row >= end1);
         const int c = __popc((unsigned int)(b0 >> (32 * half))) + __popc((unsigned int)(b1 >> (32 * half)));
@@ -192,9 +226,13 @@ __global__ __launch_bounds__(256) void k_convert(const double *__restrict__ X, i
         // every half wave derives the same scale: typical |a| * gam lands in [4, 8) (float16 keeps
         // 2^13 above that and 2^16 below it in its normal range)
         double t = 0.0, c = 0.0;
-        for (int64_t s = hl; s < S; s += 32) {
-            const double m = mean[S + s];
-            if (isfinite(m) && m > 0.0) { t += m; c += 1.0; }
+        for (int64_t s0 = hl; s0 < S; s0 += 32 * CB) {
+            if (s0 != hl) { load_scale(s0, sv); pin(sv); }
+#pragma unroll
+            for (int j = 0; j < CB; ++j) {
+                const double m = sv[j];
+                if (s0 + 32 * j < S && isfinite(m) && m > 0.0) { t += m; c += 1.0; }
+            }
         }
         for (int o = 16; o > 0; o >>= 1) { t += __shfl_xor(t, o); c += __shfl_xor(c, o); }
         if (c > 0.0 && isfinite(t)) {
@@ -207,17 +245,29 @@ __global__ __launch_bounds__(256) void k_convert(const double *__restrict__ X, i
     }
     double acc = 0.0, e2 = 0.0, hn = 0.0;
     bool clamped = false;
-    for (int64_t s = hl; s < Kpad16; s += 32) {
-        float a = 0.f;
-        if (row < B && s < S) a = (float)(X[row * S + s] - mean[s]);
-        double back;
-        const unsigned short h = f32_to_f16_scaled(a, gam, inv_gam, back, clamped);
-        const double err = (double)a - back;
-        e2 += err * err;
-        hn += back * back;
-        A16[a16_index(row, s, Kpad16)] = h;
-        if (slot >= 0) S16[(int64_t)slot * Kpad16 + s] = h;
-        acc += (double)a * (double)a;
+    // (Kpad16 is a multiple of 64 and the padded float64 row is no longer: a block of four may run past Kpad16, never
+    // an iteration inside it that is used)
+    for (int64_t s0 = hl; s0 < Kpad16; s0 += 32 * CB) {
+        if (s0 != hl) { load_x(s0, xv, mv); pin(xv); pin(mv); }
+#pragma unroll
+        for (int j = 0; j < CB; ++j) {
+            const int64_t s = s0 + 32 * j;
+            if (s < Kpad16) {
+                // float64 image with rows padded to whole 16-sample chunks (128-byte aligned rows, zero
+                // padding): the re-score gathers read it with aligned 16-byte loads and no tail cases
+                if (X64 && row < B && s < Sp) X64[row * Sp + s] = s < S ? xv[j] : 0.0;
+                float a = 0.f;
+                if (row < B && s < S) a = (float)(xv[j] - mv[j]);
+                double back;
+                const unsigned short h = f32_to_f16_scaled(a, gam, inv_gam, back, clamped);
+                const double err = (double)a - back;
+                e2 += err * err;
+                hn += back * back;
+                A16[a16_index(row, s, Kpad16)] = h;
+                if (slot >= 0) S16[(int64_t)slot * Kpad16 + s] = h;
+                acc += (double)a * (double)a;
+            }
+        }
     }
     for (int o = 16; o > 0; o >>= 1) {
         acc += __shfl_xor(acc, o);
@@ -1246,24 +1296,41 @@ struct PickArgs {
     int ps;                       // threads per k_rescore workgroup: k + margin rounded up to whole waves
 };
 
+// Element `i` of a wave-uniform table through a 32-bit byte offset: the load takes its base from scalar registers and
+// one address register instead of two; every table here is far below 4 GB.  The offset is made opaque, or a selected
+// index is widened before the selection and the address is a 64-bit sum in vector registers again.
+template <class T>
+__device__ __forceinline__ T at_u32(const T *base, uint32_t i) {
+    uint32_t off = i * (uint32_t)sizeof(T);
+    asm volatile("" : "+v"(off));
+    return *(const T *)((const char *)base + off);
+}
+
 // Selection for one row by one wave; NE list entries per lane.  Returns the number of pairs, -1
 // when the row has no certificate (exact path).
-// LEAN (the lists beyond 512 entries, a few rows at most): only the KEYS stay in registers through the bisection; the
-// candidate numbers and the candidates' slacks are read again where they are needed (the list is L2-hot) -- the full
-// form of sixteen entries per lane took 77 registers and with them the whole kernel's occupancy (six waves per SIMD).
+// LEAN (the lists beyond 512 entries): only the KEYS stay in registers through the bisection; the candidate numbers
+// are read again behind it (the list is L2-hot) and the candidates' slacks after them -- the full form of sixteen
+// entries per lane took 77 registers and with them the whole kernel's occupancy (six waves per SIMD).
+// Every gather here is an UNCONDITIONAL load of a selected index (slot 0 of the list and entry 0 of norm_hi always
+// exist): a load under a lane condition is compiled into an exec-masked block with a wait of its own, one memory
+// round trip per entry where a batch in front of one wait pays a single trip.
 template <int NE, bool LEAN>
 __device__ inline int pick_row(const PickArgs &p, int64_t row, int lane, int n, bool admit_all, float thr_f,
-                               float nhi_f, const unsigned long long (&spec)[8]) {
+                               float nhi_f, float nlo_f, float bad, const unsigned long long (&spec)[8]) {
     const FinishArgs &a = p.f;
     const unsigned long long *lst = a.list + row * a.cap;
     unsigned long long ent[LEAN ? 1 : NE];
     float nh[LEAN ? 1 : NE];
     uint32_t key[LEAN ? NE : 1];
+    uint32_t cand[LEAN ? NE - 8 : 1];         // candidate words of the entries beyond `spec`
     if constexpr (LEAN) {
+        unsigned long long far[NE - 8];
+#pragma unroll
+        for (int e = 8; e < NE; ++e) far[e - 8] = at_u32(lst, e * 64 + lane < n ? (uint32_t)(e * 64 + lane) : 0u);
 #pragma unroll
         for (int e = 0; e < NE; ++e) {
             const int t = e * 64 + lane;
-            key[e] = t < n ? (uint32_t)((e < 8 ? spec[e] : lst[t]) >> 32) : 0xFFFFFFFFu;
+            key[e] = t < n ? (uint32_t)((e < 8 ? spec[e] : far[e < 8 ? 0 : e - 8]) >> 32) : 0xFFFFFFFFu;
         }
     } else {
 #pragma unroll
@@ -1271,14 +1338,15 @@ __device__ inline int pick_row(const PickArgs &p, int64_t row, int lane, int n, 
             const int t = e * 64 + lane;
             ent[e] = t < n ? (e < 8 ? spec[e] : lst[t]) : ~0ull;
         }
+        // the candidates' slacks, one batch: they stay floats until the U step (entries beyond n read entry 0
+        // and are never used)
 #pragma unroll
-        for (int e = 0; e < NE; ++e) {
-            const int t = e * 64 + lane;
-            nh[e] = t < n ? a.norm_hi[(int)(uint32_t)ent[e]] : 0.f;
-        }
+        for (int e = 0; e < NE; ++e) nh[e] = at_u32(a.norm_hi, e * 64 + lane < n ? (uint32_t)ent[e] : 0u);
+#pragma unroll
+        for (int e = 0; e < NE; ++e) asm volatile("" : "+v"(nh[e]));
     }
     auto KU = [&](int e) -> uint32_t { if constexpr (LEAN) return key[e]; else return (uint32_t)(ent[e] >> 32); };
-    auto IDX = [&](int e) -> uint32_t { if constexpr (LEAN) return (uint32_t)lst[e * 64 + lane]; else return (uint32_t)ent[e]; };
+    auto IDX = [&](int e) -> uint32_t { if constexpr (LEAN) return e < 8 ? (uint32_t)spec[e] : cand[e < 8 ? 0 : e - 8]; else return (uint32_t)ent[e]; };
     double U = INFINITY;   // admit-all rows with fewer than k candidates re-score everything
     if (n < a.k) {
         if (!admit_all) return -1;
@@ -1317,14 +1385,42 @@ __device__ inline int pick_row(const PickArgs &p, int64_t row, int lane, int n, 
         // upper bound of the k-th true distance: the largest upper bound among those entries
         const double nhi = (double)nhi_f;
         double my = -INFINITY;
+        if constexpr (LEAN) {
+            // the candidate words beyond `spec` (whose own ride in its registers) in one batch, kept for the output
+            // step, then the slacks of the entries at or below the separator in halves of eight (sixteen more live
+            // values would cost a wave).  (The lane number is made opaque here: with the key loads' own addresses
+            // these loads are merged into them, and the candidate words -- or their addresses -- live through the
+            // bisection in registers the kernel does not have.)
+            int ln = lane;
+            asm volatile("" : "+v"(ln));
 #pragma unroll
-        for (int e = 0; e < NE; ++e) {
-            const uint32_t ku = KU(e);
-            if (e * 64 + lane < n && ku <= res) {
-                float slack;
-                if constexpr (LEAN) slack = a.norm_hi[(int)IDX(e)]; else slack = nh[e];
-                const double ub = (double)wc::f32_from_ordered(ku) + (nhi + (double)slack) + 1e-36;
-                my = fmax(my, ub);
+            for (int e = 8; e < NE; ++e) cand[e - 8] = (uint32_t)at_u32(lst, e * 64 + ln < n ? (uint32_t)(e * 64 + ln) : 0u);
+#pragma unroll
+            for (int e = 8; e < NE; ++e) asm volatile("" : "+v"(cand[e - 8]));
+#pragma unroll
+            for (int h = 0; h < NE; h += 8) {
+                __builtin_amdgcn_sched_barrier(0);    // (one half's addresses at a time: hoisted, they spill)
+                float sl[8];
+#pragma unroll
+                for (int e = 0; e < 8; ++e)
+                    sl[e] = at_u32(a.norm_hi, ((h + e) * 64 + lane < n && key[h + e] <= res) ? IDX(h + e) : 0u);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) asm volatile("" : "+v"(sl[e]));
+#pragma unroll
+                for (int e = 0; e < 8; ++e)
+                    if ((h + e) * 64 + lane < n && key[h + e] <= res) {
+                        const double ub = (double)wc::f32_from_ordered(key[h + e]) + (nhi + (double)sl[e]) + 1e-36;
+                        my = fmax(my, ub);
+                    }
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < NE; ++e) {
+                const uint32_t ku = KU(e);
+                if (e * 64 + lane < n && ku <= res) {
+                    const double ub = (double)wc::f32_from_ordered(ku) + (nhi + (double)nh[e]) + 1e-36;
+                    my = fmax(my, ub);
+                }
             }
         }
         for (int o = 32; o > 0; o >>= 1) my = fmax(my, __shfl_xor(my, o));
@@ -1336,9 +1432,8 @@ __device__ inline int pick_row(const PickArgs &p, int64_t row, int lane, int n, 
         // rows with clamped values are never listed (k_convert): their distance to this row is at least
         // (|a_bad| - |a_i|)^2, which must stay above U (|a_i|^2 <= lo_i + slack_i); an admit-all row with
         // fewer than k candidates (U infinite) cannot tell and takes the exact path
-        const float bad = *a.bad_norm;
         if (bad < INFINITY) {
-            const double ni = sqrt(fmax((double)a.norm_lo[row] + (double)nhi_f, 0.0));
+            const double ni = sqrt(fmax((double)nlo_f + (double)nhi_f, 0.0));
             if (!((sqrt(fmax(U, 0.0)) + ni) * (1.0 + 1e-3) < (double)bad * (1.0 - 1e-3))) return -1;
         }
     }
@@ -1358,22 +1453,35 @@ __device__ inline int pick_row(const PickArgs &p, int64_t row, int lane, int n, 
 __global__ __launch_bounds__(256, 7) void k_pick(PickArgs p) {   // (seven waves per SIMD, 72 registers: the 11 087 rows of cfg2 are 1.55 rounds of the chip instead of 1.8; eight would spill)
     const FinishArgs &a = p.f;
     const int lane = threadIdx.x & 63;
-    const int64_t row = a.row_begin + (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    // (the wave's number through readfirstlane: the row and every address derived from it are wave-uniform, which
+    // the compiler cannot see in threadIdx.x >> 6 -- the row's list, its output and its scalars then take scalar
+    // registers and the gathers one address register each)
+    const int64_t row = a.row_begin + (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if (row >= a.row_end) return;
-    // the first 512 list slots (the expected length is 384) are requested together with the count:
-    // one round trip less before the row's work can start (slots beyond the count are never used)
+    // The row's scalars -- with the two that the clamped-row test behind the bisection reads, norm_lo and bad_norm --
+    // and the first 512 list slots (the expected length is 384; slots beyond the count are never used) are requested
+    // together: one round trip before the row's work can start.  The scalars go through VECTOR loads (an opaque zero
+    // in the index) and readfirstlane: as scalar loads each is waited for together with the next kernel argument,
+    // a chain of trips in front of the list.
+    int zl = 0;
+    asm volatile("" : "+v"(zl));
+    const int c_w = a.cnt[row + zl];
+    const float thr_w = a.thr[row + zl], nhi_w = a.norm_hi[row + zl], nlo_w = a.norm_lo[row + zl], bad_w = a.bad_norm[zl];
+    const int ch_w = a.chrom_of_row[row + zl];
     unsigned long long spec[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) spec[e] = a.list[row * a.cap + e * 64 + lane];
-    const int c = a.cnt[row];
-    const float thr_f = a.thr[row];
-    const float nhi_f = a.norm_hi[row];
-    const int ch = a.chrom_of_row[row];
+    // (pinned here: the list loads are otherwise sunk behind the wave-uniform branch on the count, a second trip)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) asm volatile("" : "+v"(spec[e]));
+    auto uniform_f = [](float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); };
+    const int c = __builtin_amdgcn_readfirstlane(c_w), ch = __builtin_amdgcn_readfirstlane(ch_w);
+    const float thr_f = uniform_f(thr_w), nhi_f = uniform_f(nhi_w), nlo_f = uniform_f(nlo_w), bad = uniform_f(bad_w);
     const bool admit_all = (thr_f == WC_ADMIT_ALL);
     const bool exact = c > a.cap || ((a.lone_mask >> ch) & 1ull);   // lost entries / C-ordered chromData: exact path
     int R = -1;
-    if (!exact) R = c <= 512 ? pick_row<8, false>(p, row, lane, c, admit_all, thr_f, nhi_f, spec)
-                             : pick_row<LIST_CAP / 64, true>(p, row, lane, c, admit_all, thr_f, nhi_f, spec);
+    if (!exact) R = c <= 512 ? pick_row<8, false>(p, row, lane, c, admit_all, thr_f, nhi_f, nlo_f, bad, spec)
+                             : pick_row<LIST_CAP / 64, true>(p, row, lane, c, admit_all, thr_f, nhi_f, nlo_f, bad, spec);
     if (lane != 0) return;
     if (R < 0 || R > RMAX) {
         const int at = atomicAdd(a.fb_count, 1);
