@@ -26,8 +26,8 @@ def test_bamgpu_listing_has_guarded_barriers_and_no_scratch(tmp_path):
     meta = text[text.index("amdhsa.kernels:"):]
     kernels = meta.split("  - .agpr_count:")[1:]
     names = [re.search(r"\.name:\s+(\S+)", k).group(1) for k in kernels]
-    for want in ("k_bg_inflate", "k_bg_chain", "k_bg_link", "k_bg_walkILb0", "k_bg_walkILb1", "k_bg_scan", "k_bg_order",
-                 "k_bg_offsets"):
+    for want in ("k_bg_inflate", "k_bg_chain", "k_bg_link", "k_bg_begin", "k_bg_walkILb0", "k_bg_walkILb1", "k_bg_scan",
+                 "k_bg_order", "k_bg_offsets", "k_bg_advance"):
         assert any(want in n for n in names), (want, names)
     for name, k in zip(names, kernels):
         assert re.search(r"\.private_segment_fixed_size:\s+(\d+)", k).group(1) == "0", name

@@ -1,8 +1,12 @@
-// A stand-alone check of the streamed reader's host stage (csrc/bamfile.cpp) for a sanitizer build, no GPU and no Python:
+// A stand-alone check of the BAM readers' host code (csrc/bamfile.cpp, csrc/bamio.cpp) for a sanitizer build, no GPU and
+// no Python:
 //
 //   hipcc -std=c++17 -g -O1 -Xarch_host -fsanitize=address,undefined tools/bamchunks_check.cpp \
-//         wisecondor_amd/csrc/bamfile.cpp -lz -o bamchunks_check && ./bamchunks_check FILE.bam CHUNK_BYTES [CHUNK_BYTES ...]
+//         wisecondor_amd/csrc/bamfile.cpp wisecondor_amd/csrc/bamio.cpp -lz -o bamchunks_check &&
+//   ./bamchunks_check FILE.bam CHUNK_BYTES [CHUNK_BYTES ...]
 //
+// First the host reader (wc_bam_open), which shares its block, inflate, header and record rules with the other two,
+// reads the whole file: its names and lengths must be those of the whole-file host stage.
 // For every chunk size it walks the chunk iterator to the end and compares each chunk, block by block, with the directory
 // of the whole-file host stage (wc_bamfile_open): the same raw-deflate bytes in the staging buffer (so the bytes carried
 // from one staging buffer to the next are the file's), the same CRC and ISIZE words, running output offsets, the chunk
@@ -12,6 +16,8 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <string>
+#include <vector>
 
 #include "../wisecondor_amd/csrc/bamfile.h"
 
@@ -84,6 +90,27 @@ static int check(const char *path, const wc_bamfile &whole, long long chunk_byte
     return 0;
 }
 
+// the host reader's header against the whole-file host stage's; every record of the file goes through the record rule
+static int check_host_reader(const char *path, const wc_bamfile &whole) {
+    wc_bam *bam = nullptr;
+    if (wc_bam_open(path, 4, &bam)) {
+        fprintf(stderr, "wc_bam_open: %s\n", wc_last_error());
+        return 1;
+    }
+    int64_t info[8];
+    REQUIRE(wc_bam_info(bam, info) == WC_OK);
+    REQUIRE(info[0] == (int64_t)whole.names.size() && info[5] == whole.name_bytes);
+    std::string names((size_t)info[5], '\0'), want;
+    std::vector<int64_t> lengths(whole.names.size()), offsets(whole.names.size() + 1);
+    REQUIRE(wc_bam_refs(bam, &names[0], info[5], lengths.data(), offsets.data()) == WC_OK);
+    for (const std::string &n : whole.names) want += n + "\n";
+    REQUIRE(names == want && lengths == whole.lengths);
+    REQUIRE(offsets.back() == info[1] && info[1] > 0);
+    printf("ok: host reader, %lld references, %lld placed records\n", (long long)info[0], (long long)info[1]);
+    wc_bam_close(bam);
+    return 0;
+}
+
 int main(int argc, char **argv) {
     if (argc < 3) {
         fprintf(stderr, "usage: %s FILE.bam CHUNK_BYTES [CHUNK_BYTES ...]\n", argv[0]);
@@ -94,7 +121,7 @@ int main(int argc, char **argv) {
         fprintf(stderr, "%s\n", wc_last_error());
         return 1;
     }
-    int rc = 0;
+    int rc = check_host_reader(argv[1], *whole);
     for (int a = 2; a < argc && !rc; ++a) rc = check(argv[1], *whole, atoll(argv[a]));
     wc_bamfile_close(whole);
     return rc;

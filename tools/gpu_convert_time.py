@@ -15,7 +15,7 @@ bytes by a pool of processes.  `time` writes the JSON:
          alternating, after one warm-up of each: every time, median, spread (max - min)
   leg 2  the device reader's stages: the host stage by the host clock, the device stages between device events
          (wc_bam_dev_times), the convert kernels by the host clock around the synchronous call; inflated bytes per second
-         of the inflate kernel
+         of the inflate kernel; the sum of the walk's stages (checks, fields, order) per run, its median and spread
 The two readers' results are compared (dict and quality) before anything is written.
 `stream` writes its own JSON: per chunk size (8, 32 and 256 MiB unless --chunks names others) the wall time of the whole
 call through the whole-file device reader and through the streamed reader (BamReadsStream), alternating, five times each
@@ -151,6 +151,7 @@ def timing(args):
     keys = ["host_stage", "host_stage_pinning", "h2d", "inflate", "record_starts", "link", "checks", "fields", "order", "device_open_call",
             "convert_kernels_call"]
     med = {k: round(float(np.median([r[k] for r in stages])), 3) for k in keys}
+    walk = [r["checks"] + r["fields"] + r["order"] for r in stages]         # both walk passes and what follows them
     last = stages[-1]
     result = {
         "file": {"records_placed": last["placed_records"], "bgzf_blocks": last["blocks"], "inflated_bytes": last["inflated_bytes"],
@@ -161,6 +162,8 @@ def timing(args):
         "device_reader_beats_host_reader_by_more_than_its_spread":
             bool(leg1["host_reader"]["median"] - leg1["device_reader"]["median"] > leg1["host_reader"]["spread"]),
         "leg2_stage_milliseconds_median": med,
+        "leg2_walk_stages_sum_milliseconds": {"runs": [round(w, 3) for w in walk], "median": round(float(np.median(walk)), 3),
+                                              "spread": round(max(walk) - min(walk), 3)},
         "leg2_inflate_gigabytes_per_second": round(last["inflated_bytes"] / (med["inflate"] * 1e-3) / 1e9, 3),
         "leg2_h2d_gigabytes_per_second": round(last["compressed_bytes"] / (med["h2d"] * 1e-3) / 1e9, 3),
         "library": _lib.load().wc_version().decode(),

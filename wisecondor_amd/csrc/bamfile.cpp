@@ -1,10 +1,11 @@
 // Host stage of the device BAM reader (bamgpu.hip): the whole file into pinned host memory, the BGZF block directory
-// (the header checks of bamio.cpp's read_bam: gzip magic, BC field, BSIZE, ISIZE <= 65536), zlib on as many leading
-// blocks as the BAM header needs, the header itself (names, lengths, offset of the first record in the inflated
-// stream).  Nothing else is inflated here: the compressed bytes are what crosses to the device.  Errors carry the codes
-// wc_bam_open returns for the same file.  No GPU is needed: without one the buffer is ordinary memory.
-// The streamed reader's host stage (wc_bamchunks, below) shares the block and header code: the header from a prefix of
-// the file, then a reader thread that fills two staging buffers with runs of whole blocks; the file is never held whole.
+// (gzip magic, BC field, BSIZE, ISIZE <= 65536), zlib on as many leading blocks as the BAM header needs, the header
+// itself (names, lengths, offset of the first record in the inflated stream).  Nothing else is inflated here: the
+// compressed bytes are what crosses to the device.  No GPU is needed: without one the buffer is ordinary memory.
+// The streamed reader's host stage (wc_bamchunks, below) takes the header from a prefix of the file, then a reader thread
+// fills two staging buffers with runs of whole blocks; the file is never held whole.
+// The block header rules, the inflate of one block and the BAM header parser are the only ones of the library: the host
+// reader (bamio.cpp) uses them through bamfile.h, so the same file gives the same text and code from every reader.
 #include <hip/hip_runtime_api.h>
 #include <zlib.h>
 
@@ -37,11 +38,7 @@ inline uint32_t rd32(const unsigned char *p) {
 }
 }  // namespace
 
-// One BGZF block header at p + at of n bytes, the checks of read_bam: WC_OK (b filled, in_off counted from p, out_off 0;
-// next: the offset behind the block), WC_E_FORMAT, or BGZF_CUT where the n bytes end inside the block (the text is set
-// all the same: at the end of a file that is the error).
-enum { BGZF_CUT = 1 };
-static int bgzf_block_at(const unsigned char *p, size_t n, size_t at, long long block_no, BgzfBlock &b, size_t &next) {
+int bgzf_block_at(const unsigned char *p, size_t n, size_t at, long long block_no, BgzfBlock &b, size_t &next) {
     if (n - at < 12) { set_error("bam: truncated BGZF block %lld (header cut short)", block_no); return BGZF_CUT; }
     const unsigned char *h = p + at;
     if (h[0] != 31 || h[1] != 139 || h[2] != 8 || !(h[3] & 4)) {
@@ -91,12 +88,6 @@ int bgzf_directory(const unsigned char *p, size_t n, std::vector<BgzfBlock> &blo
     return WC_OK;
 }
 
-}  // namespace wc
-
-namespace {
-
-using wc::rd32;
-
 bool inflate_block(const unsigned char *in, const wc::BgzfBlock &b, unsigned char *out) {
     unsigned char dummy = 0;
     z_stream zs;
@@ -113,33 +104,85 @@ bool inflate_block(const unsigned char *in, const wc::BgzfBlock &b, unsigned cha
     return (uint32_t)crc32(crc32(0L, Z_NULL, 0), out, b.isize) == b.crc || (b.isize == 0 && b.crc == 0);
 }
 
-// The BAM header from the first n inflated bytes: > 0 the offset of the first record, 0 more bytes are needed,
-// < 0 an error (text set).  The checks and texts of bamio.cpp's Parser::feed.
-long long parse_header(const unsigned char *p, size_t n, wc_bamfile &f) {
+int inflate_failed(long long block_no) {
+    set_error("bam: damaged BGZF block %lld (inflate or CRC failed)", block_no);
+    return WC_E_FORMAT;
+}
+
+int header_cut() {
+    set_error("bam: truncated: the data ends inside the BAM header");
+    return WC_E_FORMAT;
+}
+
+long long parse_header(const unsigned char *p, size_t n, std::vector<std::string> &names, std::vector<int64_t> &lengths) {
     if (n >= 4 && memcmp(p, "BAM\1", 4) != 0) {
-        wc::set_error("bam: bad magic (the inflated data does not start with BAM\\1)");
+        set_error("bam: bad magic (the inflated data does not start with BAM\\1)");
         return -1;
     }
     if (n < 12) return 0;
     const int32_t l_text = (int32_t)rd32(p + 4);
-    if (l_text < 0) { wc::set_error("bam: negative header text length"); return -1; }
+    if (l_text < 0) { set_error("bam: negative header text length"); return -1; }
     size_t at = 8 + (size_t)l_text;
     if (n < at + 4) return 0;
     const int32_t n_ref = (int32_t)rd32(p + at);
     at += 4;
-    if (n_ref < 0) { wc::set_error("bam: negative reference count"); return -1; }
-    f.names.clear();
-    f.lengths.clear();
+    if (n_ref < 0) { set_error("bam: negative reference count"); return -1; }
+    names.clear();
+    lengths.clear();
     for (int32_t r = 0; r < n_ref; ++r) {
         if (n < at + 4) return 0;
         const int32_t l_name = (int32_t)rd32(p + at);
-        if (l_name < 1) { wc::set_error("bam: reference %d has a name of %d bytes", r, l_name); return -1; }
+        if (l_name < 1) { set_error("bam: reference %d has a name of %d bytes", r, l_name); return -1; }
         if (n < at + 4 + (size_t)l_name + 4) return 0;
-        f.names.emplace_back(reinterpret_cast<const char *>(p + at + 4), strnlen(reinterpret_cast<const char *>(p + at + 4), (size_t)l_name));
-        f.lengths.push_back((int64_t)(int32_t)rd32(p + at + 4 + l_name));
+        names.emplace_back(reinterpret_cast<const char *>(p + at + 4), strnlen(reinterpret_cast<const char *>(p + at + 4), (size_t)l_name));
+        lengths.push_back((int64_t)(int32_t)rd32(p + at + 4 + l_name));
         at += 8 + (size_t)l_name;
     }
     return (long long)at;
+}
+
+}  // namespace wc
+
+namespace {
+
+const size_t BGZF_MAX_BLOCK = 65536;                // BSIZE has 16 bits
+
+// The header from the file's leading blocks, which are checked and inflated one by one until the header is whole.
+// more(raw, have) makes more of the file's leading bytes readable at raw[0 .. have): 1 it did, 0 the file ends at
+// `have`, WC_E_IO with a text.
+template <class More> int read_header(More more, wc_bamfile &h) {
+    std::vector<unsigned char> plain;
+    const unsigned char *raw = nullptr;
+    size_t have = 0, at = 0;
+    bool eof = false;
+    long long block_no = 0, first = 0;
+    while (first == 0) {
+        wc::BgzfBlock b;
+        size_t next = 0;
+        int rc = wc::BGZF_CUT;
+        if (at < have) rc = wc::bgzf_block_at(raw, have, at, block_no, b, next);
+        else if (eof) return wc::header_cut();
+        if (rc == wc::BGZF_CUT) {
+            if (eof) return WC_E_FORMAT;                        // the text of the cut block stands
+            const int got = more(raw, have);
+            if (got < 0) return got;
+            eof = got == 0;
+            continue;
+        }
+        if (rc) return rc;
+        const size_t base = plain.size();
+        plain.resize(base + b.isize + 1);
+        if (!wc::inflate_block(raw, b, plain.data() + base)) return wc::inflate_failed(block_no);
+        plain.resize(base + b.isize);
+        first = wc::parse_header(plain.data(), plain.size(), h.names, h.lengths);
+        if (first < 0) return WC_E_FORMAT;
+        at = next;
+        ++block_no;
+    }
+    h.first_record = first;
+    h.name_bytes = 0;
+    for (const std::string &s : h.names) h.name_bytes += (int64_t)s.size() + 1;
+    return WC_OK;
 }
 
 int open_file(const char *path, int device, wc_bamfile &f) {
@@ -167,76 +210,34 @@ int open_file(const char *path, int device, wc_bamfile &f) {
     memset(f.data + f.size, 0, WC_BGZF_PAD);
     int rc = wc::bgzf_directory(f.data, f.size, f.blocks, f.total);
     if (rc) return rc;
-    // the header: leading blocks only
-    std::vector<unsigned char> plain;
-    long long first = 0;
-    for (size_t k = 0; k < f.blocks.size() && first == 0; ++k) {
-        const wc::BgzfBlock &b = f.blocks[k];
-        const size_t base = plain.size();
-        plain.resize(base + b.isize + 1);
-        if (!inflate_block(f.data, b, plain.data() + base)) {
-            wc::set_error("bam: damaged BGZF block %lld (inflate or CRC failed)", (long long)k);
-            return WC_E_FORMAT;
-        }
-        plain.resize(base + b.isize);
-        first = parse_header(plain.data(), plain.size(), f);
-        if (first < 0) return WC_E_FORMAT;
-    }
-    if (first == 0) { wc::set_error("bam: truncated: the data ends inside the BAM header"); return WC_E_FORMAT; }
-    f.first_record = first;
-    f.name_bytes = 0;
-    for (const std::string &s : f.names) f.name_bytes += (int64_t)s.size() + 1;
-    return WC_OK;
+    // the header: the whole file is there, and the directory has passed every block header
+    return read_header([&](const unsigned char *&raw, size_t &have) {
+        if (raw) return 0;
+        raw = f.data;
+        have = f.size;
+        return 1;
+    }, f);
 }
-
 
 // ---- the streamed reader's host stage -------------------------------------------------------------------------------
 const int64_t STREAM_DEFAULT_CHUNK = 256ll << 20;   // the fastest size of profiles/convert_stream_times.json
-const size_t BGZF_MAX_BLOCK = 65536;                // BSIZE has 16 bits
 
-// The header from a prefix of the file: the leading blocks are read, checked and inflated one by one until the header is
-// whole -- what open_file does on the whole file's directory, with its texts.
-int read_header(int fd, wc_bamfile &h) {
-    std::vector<unsigned char> raw, plain;
-    size_t have = 0, at = 0;
-    bool eof = false;
-    long long block_no = 0, first = 0;
-    while (first == 0) {
-        wc::BgzfBlock b;
-        size_t next = 0;
-        int rc = wc::BGZF_CUT;
-        if (at < have) rc = wc::bgzf_block_at(raw.data(), have, at, block_no, b, next);
-        else if (eof) { wc::set_error("bam: truncated: the data ends inside the BAM header"); return WC_E_FORMAT; }
-        if (rc == wc::BGZF_CUT) {
-            if (eof) return WC_E_FORMAT;                        // the text of the cut block stands
-            raw.resize(have + 4 * BGZF_MAX_BLOCK);
-            const ssize_t got = pread(fd, raw.data() + have, raw.size() - have, (off_t)have);
-            if (got < 0) {
-                if (errno == EINTR) continue;
-                wc::set_error("bam: cannot read the file (%s)", strerror(errno));
-                return WC_E_IO;
-            }
-            if (got == 0) eof = true;
-            have += (size_t)got;
-            continue;
+// The header from a prefix of the file, read on in steps of four blocks' room.
+int read_header_fd(int fd, wc_bamfile &h) {
+    std::vector<unsigned char> buf;
+    return read_header([&](const unsigned char *&raw, size_t &have) {
+        buf.resize(have + 4 * BGZF_MAX_BLOCK);
+        raw = buf.data();
+        ssize_t got;
+        do got = pread(fd, buf.data() + have, buf.size() - have, (off_t)have);
+        while (got < 0 && errno == EINTR);
+        if (got < 0) {
+            wc::set_error("bam: cannot read the file (%s)", strerror(errno));
+            return (int)WC_E_IO;
         }
-        if (rc) return rc;
-        const size_t base = plain.size();
-        plain.resize(base + b.isize + 1);
-        if (!inflate_block(raw.data(), b, plain.data() + base)) {
-            wc::set_error("bam: damaged BGZF block %lld (inflate or CRC failed)", block_no);
-            return WC_E_FORMAT;
-        }
-        plain.resize(base + b.isize);
-        first = parse_header(plain.data(), plain.size(), h);
-        if (first < 0) return WC_E_FORMAT;
-        at = next;
-        ++block_no;
-    }
-    h.first_record = first;
-    h.name_bytes = 0;
-    for (const std::string &s : h.names) h.name_bytes += (int64_t)s.size() + 1;
-    return WC_OK;
+        have += (size_t)got;
+        return got ? 1 : 0;
+    }, h);
 }
 
 }  // namespace
@@ -375,7 +376,7 @@ int open_chunks(const char *path, int device, int64_t chunk_bytes, wc_bamchunks 
     struct stat st;
     if (fstat(c.fd, &st) != 0 || !S_ISREG(st.st_mode)) { wc::set_error("bam: cannot seek in %s", path); return WC_E_IO; }
     c.hdr.size = (size_t)st.st_size;
-    const int rc = read_header(c.fd, c.hdr);
+    const int rc = read_header_fd(c.fd, c.hdr);
     if (rc) return rc;
     c.chunk_bytes = chunk_bytes > 0 ? chunk_bytes : STREAM_DEFAULT_CHUNK;
     // a read always holds the chunk's blocks and the whole of the block that no longer fits

@@ -6,13 +6,14 @@
 //                  its start (a record is at least 36 bytes, so 36 consecutive offsets depend only on higher ones: 36
 //                  offsets per wave step), the map  entry offset -> where that chain leaves the segment
 //   k_bg_link      one wave walks the segments from the first record: the entry offset of every segment on the real chain
-//   k_bg_walk      one lane per segment follows the real chain through its segment: the format checks and counters of
-//                  bamio.cpp's Parser::feed; <false> counts the placed records, <true> (after k_bg_scan) writes their
-//                  fields in file order
+//   k_bg_walk      one lane per segment follows the real chain through its segment: the record rule of bamfile.h and the
+//                  counters of bamio.cpp's Parser::feed; <false> counts the placed records, <true> (after k_bg_scan)
+//                  writes their fields in file order
 //   k_bg_order / k_bg_offsets   the coordinate-order check on neighbouring placed records, the per-reference offsets
-// The streamed reader (wc_bam_stream_dev, at the end) sends the file through the same kernels chunk by chunk; k_bs_walk is
-// k_bg_walk for data that may end inside a record (the carry), k_bs_order / k_bs_offsets / k_bs_advance keep the order
-// check, the per-reference counts and the running base of the output across chunks.
+// The streamed reader (wc_bam_stream_dev, at the end) sends the file through the same kernels chunk by chunk: the walk
+// takes a `last` flag (data that is not the file's end may end inside a record: the carry), and the order check, the
+// per-reference counts and the running base of the output live in device words (BG_*) that k_bg_begin / k_bg_advance
+// keep across chunks.  To these kernels the whole file is one chunk, the last, with nothing before it.
 // Every loop is bounded by the bytes that are there (see the comments at the loops); a violation sets a status and the
 // wave stops.  The inflate kernel's back-references read the global output it has written itself: its LDS holds the
 // Huffman tables only ("convert: the device reader").
@@ -34,7 +35,13 @@ const int BG_LIT_BITS = 10, BG_DIST_BITS = 9, BG_CL_BITS = 7;
 const double BG_BUDGET_FRACTION = 0.8;      // of the free device memory, when the caller names no budget
 
 enum { BG_E_DEFLATE = 1, BG_E_CRC = 2 };
-enum { BG_R_TRUNC = 0, BG_R_BS = 1, BG_R_FIELDS = 2, BG_R_REF = 3 };
+
+// The walk's device words, kept across the chunks of a streamed open:
+// [0..2] mapped, unmapped, no_coordinate (all chunks)   [3] placed records of this chunk (k_bg_scan)
+// [4] record error, (file-absolute inflated offset << 3 | wc::BAM_R_* kind)
+// [5] order error, (placed index in the file << 2 | kind)   [6] placed records of the chunks before
+// [7] offset in carry + chunk of the first record that does not end inside   [8] reference of the last placed record so far
+enum { BG_PLACED = 3, BG_RECERR = 4, BG_ORDERR = 5, BG_BASE = 6, BG_TAIL = 7, BG_LASTREF = 8, BG_WORDS = 16 };
 
 struct InflLds {
     uint32_t crc_tab[256];
@@ -324,7 +331,6 @@ __global__ void __launch_bounds__(64) k_bg_inflate(const uint8_t *__restrict__ c
 __device__ __forceinline__ uint32_t bg_ld32(const uint8_t *p) {
     return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
 }
-__device__ __forceinline__ uint32_t bg_ld16(const uint8_t *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8); }
 
 // map[a], a an absolute inflated offset of segment s = a / BG_SEG ending at e = min((s + 1) BG_SEG, total): the chain
 // that starts at a leaves the segment at e + map[a] (BG_FAR: further than 16 bits say; BG_BAD: it does not leave it).
@@ -378,11 +384,23 @@ __global__ void __launch_bounds__(64) k_bg_link(const uint8_t *__restrict__ data
     }
 }
 
+__global__ void __launch_bounds__(64) k_bg_begin(unsigned long long *m, long long total) {
+    if (threadIdx.x == 0) {
+        m[BG_PLACED] = 0;
+        m[BG_TAIL] = (unsigned long long)total;
+    }
+}
+
+// The walk of `total` bytes (a whole file, or carry + chunk), the first of them at the file's inflated offset abs_base.
+// A record that overruns `total`, its block_size word included, is the truncation error only where the file ends with
+// these bytes (`last`); before that it is where the next carry starts: its offset goes to m[BG_TAIL] (one lane at most
+// meets it: the chain is one) and the walk stops there.  <true> appends at m[BG_BASE]; refs[] holds the placed records
+// of these bytes alone.
 template <bool WRITE>
-__global__ void __launch_bounds__(256) k_bg_walk(const uint8_t *__restrict__ data, long long total, int n_ref,
-                                                 const int *__restrict__ entry, int n_seg, int *__restrict__ cnt,
-                                                 const long long *__restrict__ seg_base, unsigned long long *stats,
-                                                 unsigned long long *err, int32_t *__restrict__ pos, uint8_t *__restrict__ mapq,
+__global__ void __launch_bounds__(256) k_bg_walk(const uint8_t *__restrict__ data, long long total, long long abs_base, int last,
+                                                 int n_ref, const int *__restrict__ entry, int n_seg, int *__restrict__ cnt,
+                                                 const long long *__restrict__ seg_base, unsigned long long *m,
+                                                 int32_t *__restrict__ pos, uint8_t *__restrict__ mapq,
                                                  uint16_t *__restrict__ flag, int32_t *__restrict__ mate, int32_t *__restrict__ refs) {
     const int t = blockIdx.x * 256 + threadIdx.x;
     if (t >= n_seg) return;
@@ -393,54 +411,44 @@ __global__ void __launch_bounds__(256) k_bg_walk(const uint8_t *__restrict__ dat
     }
     long long a = (long long)t * BG_SEG + e;
     const long long seg_end = min((long long)(t + 1) * BG_SEG, total);
-    long long idx = WRITE ? seg_base[t] : 0;
+    long long local = WRITE ? seg_base[t] : 0;
+    const long long out_base = WRITE ? (long long)m[BG_BASE] : 0;
     unsigned long long mapped = 0, unmapped = 0, nocoord = 0;
     int placed = 0;
     while (a < seg_end) {                           // a grows by 36 or more
-        int bad = -1;
-        int bs = 0;
-        if (a + 4 > total) bad = BG_R_TRUNC;
-        else {
-            bs = (int)bg_ld32(data + a);
-            if (bs < 32) bad = BG_R_BS;
-            else if (a + 4 + (long long)bs > total) bad = BG_R_TRUNC;
-        }
-        if (bad < 0) {
-            const uint8_t *r = data + a + 4;
-            const int ref = (int)bg_ld32(r), l_seq = (int)bg_ld32(r + 16);
-            const unsigned fl = bg_ld16(r + 14);
-            const long long need = 32 + (long long)r[8] + 4 * (long long)bg_ld16(r + 12) + ((long long)l_seq + 1) / 2 + (long long)l_seq;
-            if (l_seq < 0 || need > (long long)bs) bad = BG_R_FIELDS;
-            else if (ref >= n_ref) bad = BG_R_REF;
-            else {
-                if (fl & 4u) ++unmapped;
-                if (ref < 0) {
-                    ++nocoord;
-                } else {
-                    if (!(fl & 4u)) ++mapped;
-                    if (WRITE) {
-                        pos[idx] = (int32_t)bg_ld32(r + 4);
-                        mapq[idx] = r[9];
-                        flag[idx] = (uint16_t)fl;
-                        mate[idx] = (int32_t)bg_ld32(r + 24);
-                        refs[idx] = ref;
-                    }
-                    ++idx;
-                    ++placed;
-                }
-            }
-        }
-        if (bad >= 0) {
-            if (!WRITE) atomicMin(err, ((unsigned long long)a << 3) | (unsigned)bad);
+        wc::BamRecord rec;
+        const int bad = wc::bam_record(data + a, total - a, n_ref, rec);
+        if (bad == wc::BAM_R_TRUNC && !last) {
+            if (!WRITE) m[BG_TAIL] = (unsigned long long)a;
             break;
         }
-        a += 4 + (long long)bs;
+        if (bad != wc::BAM_R_OK) {
+            if (!WRITE) atomicMin(&m[BG_RECERR], ((unsigned long long)(abs_base + a) << 3) | (unsigned)bad);
+            break;
+        }
+        if (rec.flag & 4u) ++unmapped;
+        if (rec.ref < 0) {
+            ++nocoord;
+        } else {
+            if (!(rec.flag & 4u)) ++mapped;
+            if (WRITE) {
+                const long long idx = out_base + local;
+                pos[idx] = rec.pos;
+                mapq[idx] = rec.mapq;
+                flag[idx] = (uint16_t)rec.flag;
+                mate[idx] = rec.mate_pos;
+                refs[local] = rec.ref;
+            }
+            ++local;
+            ++placed;
+        }
+        a += 4 + (long long)rec.block_size;
     }
     if (!WRITE) {
         cnt[t] = placed;
-        if (mapped) atomicAdd(&stats[0], mapped);
-        if (unmapped) atomicAdd(&stats[1], unmapped);
-        if (nocoord) atomicAdd(&stats[2], nocoord);
+        if (mapped) atomicAdd(&m[0], mapped);
+        if (unmapped) atomicAdd(&m[1], unmapped);
+        if (nocoord) atomicAdd(&m[2], nocoord);
     }
 }
 
@@ -471,140 +479,28 @@ __global__ void __launch_bounds__(256) k_bg_scan(const int *__restrict__ cnt, in
     }
 }
 
-// err: the least (placed index << 2 | kind) with kind 1 a lower reference than the record before, 2 a lower position
-__global__ void __launch_bounds__(256) k_bg_order(const int32_t *__restrict__ refs, const int32_t *__restrict__ pos, long long n,
-                                                  unsigned long long *err) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x + 1;
-    if (i >= n) return;
-    const int a = refs[i - 1], b = refs[i];
-    const unsigned kind = b < a ? 1u : (b == a && pos[i] < pos[i - 1]) ? 2u : 0u;
-    if (kind) atomicMin(err, ((unsigned long long)i << 2) | kind);
-}
-
-// offsets[r] = the number of placed records of references below r (refs[] ascends)
-__global__ void __launch_bounds__(256) k_bg_offsets(const int32_t *__restrict__ refs, long long n, int n_ref,
-                                                    long long *__restrict__ offsets) {
-    const int r = blockIdx.x * 256 + threadIdx.x;
-    if (r > n_ref) return;
-    long long lo = 0, hi = n;
-    while (lo < hi) {
-        const long long mid = lo + (hi - lo) / 2;
-        if (refs[mid] < r) lo = mid + 1;
-        else hi = mid;
-    }
-    offsets[r] = lo;
-}
-
-// ---- the streamed reader: the words of its device state, and the kernels that differ from the whole-file ones --------
-// [0..2] mapped, unmapped, no_coordinate (all chunks)   [3] placed records of this chunk (k_bg_scan)
-// [4] record error, (file-absolute inflated offset << 3 | kind)   [5] order error, (placed index in the file << 2 | kind)
-// [6] placed records of the chunks before   [7] offset in carry + chunk of the first record that does not end inside
-// [8] reference of the last placed record so far
-enum { BS_PLACED = 3, BS_RECERR = 4, BS_ORDERR = 5, BS_BASE = 6, BS_TAIL = 7, BS_LASTREF = 8, BS_WORDS = 16 };
-
-__global__ void __launch_bounds__(64) k_bs_begin(unsigned long long *m, long long total) {
-    if (threadIdx.x == 0) {
-        m[BS_PLACED] = 0;
-        m[BS_TAIL] = (unsigned long long)total;
-    }
-}
-
-// k_bg_walk on carry + chunk (`total` bytes, the first of them at the file's inflated offset abs_base).  A record that
-// overruns `total`, its block_size word included, is the truncation error only in the file's last chunk; before that
-// it is where the next carry starts: its offset goes to m[BS_TAIL] (one lane at most meets it: the chain is one) and the
-// walk stops there.  <true> appends at m[BS_BASE]; refs[] holds this chunk's placed records alone.
-template <bool WRITE>
-__global__ void __launch_bounds__(256) k_bs_walk(const uint8_t *__restrict__ data, long long total, long long abs_base, int last,
-                                                 int n_ref, const int *__restrict__ entry, int n_seg, int *__restrict__ cnt,
-                                                 const long long *__restrict__ seg_base, unsigned long long *m,
-                                                 int32_t *__restrict__ pos, uint8_t *__restrict__ mapq,
-                                                 uint16_t *__restrict__ flag, int32_t *__restrict__ mate, int32_t *__restrict__ refs) {
-    const int t = blockIdx.x * 256 + threadIdx.x;
-    if (t >= n_seg) return;
-    const int e = entry[t];
-    if (e < 0) {
-        if (!WRITE) cnt[t] = 0;
-        return;
-    }
-    long long a = (long long)t * BG_SEG + e;
-    const long long seg_end = min((long long)(t + 1) * BG_SEG, total);
-    long long local = WRITE ? seg_base[t] : 0;
-    const long long out_base = WRITE ? (long long)m[BS_BASE] : 0;
-    unsigned long long mapped = 0, unmapped = 0, nocoord = 0;
-    int placed = 0;
-    while (a < seg_end) {                           // a grows by 36 or more
-        int bad = -1;
-        int bs = 0;
-        if (a + 4 > total) bad = BG_R_TRUNC;
-        else {
-            bs = (int)bg_ld32(data + a);
-            if (bs < 32) bad = BG_R_BS;
-            else if (a + 4 + (long long)bs > total) bad = BG_R_TRUNC;
-        }
-        if (bad == BG_R_TRUNC && !last) {
-            if (!WRITE) m[BS_TAIL] = (unsigned long long)a;
-            break;
-        }
-        if (bad < 0) {
-            const uint8_t *r = data + a + 4;
-            const int ref = (int)bg_ld32(r), l_seq = (int)bg_ld32(r + 16);
-            const unsigned fl = bg_ld16(r + 14);
-            const long long need = 32 + (long long)r[8] + 4 * (long long)bg_ld16(r + 12) + ((long long)l_seq + 1) / 2 + (long long)l_seq;
-            if (l_seq < 0 || need > (long long)bs) bad = BG_R_FIELDS;
-            else if (ref >= n_ref) bad = BG_R_REF;
-            else {
-                if (fl & 4u) ++unmapped;
-                if (ref < 0) {
-                    ++nocoord;
-                } else {
-                    if (!(fl & 4u)) ++mapped;
-                    if (WRITE) {
-                        const long long idx = out_base + local;
-                        pos[idx] = (int32_t)bg_ld32(r + 4);
-                        mapq[idx] = r[9];
-                        flag[idx] = (uint16_t)fl;
-                        mate[idx] = (int32_t)bg_ld32(r + 24);
-                        refs[local] = ref;
-                    }
-                    ++local;
-                    ++placed;
-                }
-            }
-        }
-        if (bad >= 0) {
-            if (!WRITE) atomicMin(&m[BS_RECERR], ((unsigned long long)(abs_base + a) << 3) | (unsigned)bad);
-            break;
-        }
-        a += 4 + (long long)bs;
-    }
-    if (!WRITE) {
-        cnt[t] = placed;
-        if (mapped) atomicAdd(&m[0], mapped);
-        if (unmapped) atomicAdd(&m[1], unmapped);
-        if (nocoord) atomicAdd(&m[2], nocoord);
-    }
-}
-
-// k_bg_order on this chunk's placed records: the predecessor of the first is the last placed record of the chunks
-// before (its reference in m[BS_LASTREF], its position in the output).  The grid covers the most records the chunk can hold.
-__global__ void __launch_bounds__(256) k_bs_order(const int32_t *__restrict__ refs, const int32_t *__restrict__ pos,
+// The order check on the placed records of these bytes: m[BG_ORDERR] is the least (placed index in the file << 2 | kind)
+// with kind 1 a lower reference than the record before, 2 a lower position.  The predecessor of the first is the last
+// placed record of the chunks before (its reference in m[BG_LASTREF], its position in the output).  The grid covers
+// m[BG_PLACED] records or more.
+__global__ void __launch_bounds__(256) k_bg_order(const int32_t *__restrict__ refs, const int32_t *__restrict__ pos,
                                                   unsigned long long *m) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (long long)m[BS_PLACED]) return;
-    const long long base = (long long)m[BS_BASE], g = base + i;
+    if (i >= (long long)m[BG_PLACED]) return;
+    const long long base = (long long)m[BG_BASE], g = base + i;
     if (g == 0) return;
-    const int a = i ? refs[i - 1] : (int)(long long)m[BS_LASTREF], b = refs[i];
+    const int a = i ? refs[i - 1] : (int)(long long)m[BG_LASTREF], b = refs[i];
     const unsigned kind = b < a ? 1u : (b == a && pos[g] < pos[g - 1]) ? 2u : 0u;
-    if (kind) atomicMin(&m[BS_ORDERR], ((unsigned long long)g << 2) | kind);
+    if (kind) atomicMin(&m[BG_ORDERR], ((unsigned long long)g << 2) | kind);
 }
 
-// acc[r] += the number of this chunk's placed records of references below r (refs[] ascends, or the order check fails):
-// behind the last chunk acc[] is k_bg_offsets' result
-__global__ void __launch_bounds__(256) k_bs_offsets(const int32_t *__restrict__ refs, const unsigned long long *__restrict__ m,
+// acc[r] += the number of these bytes' placed records of references below r (refs[] ascends, or the order check fails):
+// behind the last chunk acc[r] is the number of the file's placed records of references below r
+__global__ void __launch_bounds__(256) k_bg_offsets(const int32_t *__restrict__ refs, const unsigned long long *__restrict__ m,
                                                     int n_ref, long long *__restrict__ acc) {
     const int r = blockIdx.x * 256 + threadIdx.x;
     if (r > n_ref) return;
-    long long lo = 0, hi = (long long)m[BS_PLACED];
+    long long lo = 0, hi = (long long)m[BG_PLACED];
     while (lo < hi) {
         const long long mid = lo + (hi - lo) / 2;
         if (refs[mid] < r) lo = mid + 1;
@@ -613,12 +509,12 @@ __global__ void __launch_bounds__(256) k_bs_offsets(const int32_t *__restrict__ 
     acc[r] += lo;
 }
 
-__global__ void __launch_bounds__(64) k_bs_advance(const int32_t *__restrict__ refs, unsigned long long *m) {
+__global__ void __launch_bounds__(64) k_bg_advance(const int32_t *__restrict__ refs, unsigned long long *m) {
     if (threadIdx.x) return;
-    const long long n = (long long)m[BS_PLACED];
+    const long long n = (long long)m[BG_PLACED];
     if (n) {
-        m[BS_LASTREF] = (unsigned long long)(long long)refs[n - 1];
-        m[BS_BASE] += (unsigned long long)n;
+        m[BG_LASTREF] = (unsigned long long)(long long)refs[n - 1];
+        m[BG_BASE] += (unsigned long long)n;
     }
 }
 
@@ -661,6 +557,88 @@ int first_bad_block(const std::vector<int> &status) {
     for (size_t k = 0; k < status.size(); ++k)
         if (status[k]) return (int)k;
     return -1;
+}
+
+// One walk: `total` inflated bytes at `data` (a whole file, or carry + chunk), the first of them at the file's inflated
+// offset abs_base, the records from offset `first`; `last`: the file ends with them.  The working arrays hold n_seg
+// segments, m the BG_WORDS device words.
+struct Walk {
+    const uint8_t *data;
+    long long total, abs_base, first;
+    int last, n_ref, n_seg;
+    uint16_t *map;
+    int *entry, *cnt;
+    long long *seg_base;
+    unsigned long long *m;
+};
+
+// chain -> link -> count -> scan: behind them m[BG_PLACED], m[BG_RECERR], m[BG_TAIL] and the counters are these bytes'.
+// ev (optional): three events, recorded behind the chain maps, the link, and the count with its scan.
+int launch_count(hipStream_t stream, const Walk &w, hipEvent_t *ev) {
+    hipLaunchKernelGGL(k_bg_chain, dim3((unsigned)w.n_seg), dim3(64), 0, stream, w.data, w.total, w.map);
+    if (ev) WC_HIP(hipEventRecord(ev[0], stream));
+    hipLaunchKernelGGL(k_bg_link, dim3(1), dim3(64), 0, stream, w.data, w.total, w.first, (const uint16_t *)w.map, w.n_seg, w.entry);
+    if (ev) WC_HIP(hipEventRecord(ev[1], stream));
+    hipLaunchKernelGGL(k_bg_walk<false>, dim3((unsigned)((w.n_seg + 255) / 256)), dim3(256), 0, stream, w.data, w.total, w.abs_base,
+                       w.last, w.n_ref, (const int *)w.entry, w.n_seg, w.cnt, (const long long *)nullptr, w.m, (int32_t *)nullptr,
+                       (uint8_t *)nullptr, (uint16_t *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr);
+    hipLaunchKernelGGL(k_bg_scan, dim3(1), dim3(256), 0, stream, (const int *)w.cnt, w.n_seg, w.seg_base, w.m + BG_PLACED);
+    if (ev) WC_HIP(hipEventRecord(ev[2], stream));
+    return WC_OK;
+}
+
+// fields -> order -> offsets, behind launch_count: the placed records' fields appended to the four arrays at m[BG_BASE],
+// their references to refs[] (from 0), the order check, acc[] advanced.  order_room: m[BG_PLACED] or any number above it.
+// ev (optional): two events, recorded behind the fields, and the order check with the offsets.
+int launch_fields(hipStream_t stream, const Walk &w, int32_t *pos, uint8_t *mapq, uint16_t *flag, int32_t *mate, int32_t *refs,
+                  long long *acc, long long order_room, hipEvent_t *ev) {
+    hipLaunchKernelGGL(k_bg_walk<true>, dim3((unsigned)((w.n_seg + 255) / 256)), dim3(256), 0, stream, w.data, w.total, w.abs_base,
+                       w.last, w.n_ref, (const int *)w.entry, w.n_seg, (int *)nullptr, (const long long *)w.seg_base, w.m, pos, mapq,
+                       flag, mate, refs);
+    if (ev) WC_HIP(hipEventRecord(ev[0], stream));
+    hipLaunchKernelGGL(k_bg_order, dim3((unsigned)((order_room + 255) / 256)), dim3(256), 0, stream, (const int32_t *)refs,
+                       (const int32_t *)pos, w.m);
+    hipLaunchKernelGGL(k_bg_offsets, dim3((unsigned)(w.n_ref / 256 + 1)), dim3(256), 0, stream, (const int32_t *)refs,
+                       (const unsigned long long *)w.m, w.n_ref, acc);
+    if (ev) WC_HIP(hipEventRecord(ev[1], stream));
+    return WC_OK;
+}
+
+// What one status read says, the first kind of defect first: a damaged block (st: the statuses of the blocks from the
+// file's block first_block on), a record defect, an order defect.  got: the BG_WORDS device words; data_end: the file's
+// inflated offset behind the bytes walked.  For the pair of an order defect: refs (device) holds the references of the
+// placed records from the file's index placed_before on, prev_last_ref that of the one before them, pos (device) the
+// positions of all.  WC_OK where nothing is wrong.
+int check_status(const unsigned long long *got, const std::vector<int> &st, long long first_block, long long data_end, int n_ref,
+                 const int32_t *refs, const int32_t *pos, long long placed_before, long long prev_last_ref) {
+    const int bad = first_bad_block(st);
+    WC_CHECK(bad < 0, WC_E_FORMAT, "bam: damaged BGZF block %lld (%s)", first_block + bad,
+             st[(size_t)(bad < 0 ? 0 : bad)] == BG_E_CRC ? "CRC failed" : "inflate failed");
+    if (got[BG_RECERR] != ~0ull) {
+        const long long at = (long long)(got[BG_RECERR] >> 3);
+        switch ((int)(got[BG_RECERR] & 7u)) {
+            case wc::BAM_R_BS: wc::set_error("bam: the record at inflated offset %lld has a block_size below its 32 fixed bytes", at); break;
+            case wc::BAM_R_FIELDS: wc::set_error("bam: the fields of the record at inflated offset %lld overrun its block_size", at); break;
+            case wc::BAM_R_REF: wc::set_error("bam: the record at inflated offset %lld names a reference beyond the %d of the header", at, n_ref); break;
+            default: wc::set_error("bam: truncated: the record at inflated offset %lld overruns the data (%lld bytes)", at, data_end);
+        }
+        return WC_E_FORMAT;
+    }
+    if (got[BG_ORDERR] != ~0ull) {
+        const long long g = (long long)(got[BG_ORDERR] >> 2), local = g - placed_before;
+        int32_t two_ref[2] = {(int32_t)prev_last_ref, 0}, two_pos[2] = {0, 0};
+        if (local > 0) WC_HIP(hipMemcpy(two_ref, refs + local - 1, 8, hipMemcpyDeviceToHost));
+        else WC_HIP(hipMemcpy(two_ref + 1, refs, 4, hipMemcpyDeviceToHost));
+        WC_HIP(hipMemcpy(two_pos, pos + g - 1, 8, hipMemcpyDeviceToHost));
+        if ((got[BG_ORDERR] & 3u) == 1u)
+            wc::set_error("bam: not coordinate-sorted: placed record %lld of reference %d follows reference %d (the records of a "
+                          "reference must be contiguous, references in header order)", g, two_ref[1], two_ref[0]);
+        else
+            wc::set_error("bam: not coordinate-sorted: position %d follows %d in reference %d (placed record %lld)", two_pos[1],
+                          two_pos[0], two_ref[1], g);
+        return WC_E_ARG;
+    }
+    return WC_OK;
 }
 
 }  // namespace
@@ -712,13 +690,17 @@ int open_dev(wc_ctx *ctx, hipStream_t stream, const wc_bamfile &f, int64_t budge
     if ((rc = comp.alloc(f.size + WC_BGZF_PAD)) || (rc = dir.alloc(sizeof(wc::BgzfBlock) * (size_t)n_blocks)) ||
         (rc = status.alloc(4 * (size_t)n_blocks)) || (rc = plain.alloc((size_t)total + 64)) ||
         (rc = map.alloc(2 * (size_t)n_seg * BG_SEG)) || (rc = entry.alloc(4 * (size_t)n_seg)) ||
-        (rc = cnt.alloc(4 * (size_t)n_seg)) || (rc = base.alloc(8 * (size_t)n_seg)) || (rc = misc.alloc(64)))
+        (rc = cnt.alloc(4 * (size_t)n_seg)) || (rc = base.alloc(8 * (size_t)n_seg)) || (rc = misc.alloc(8 * BG_WORDS)))
         return rc;
-    // misc: [0..2] mapped, unmapped, no_coordinate  [3] placed  [4] record error  [5] order error
+    // to the walk the file is one chunk, the last, with nothing before it
     unsigned long long *m = misc.as<unsigned long long>();
-    unsigned long long init[8] = {0, 0, 0, 0, ~0ull, ~0ull, 0, 0};
+    unsigned long long got[BG_WORDS] = {0};
+    got[BG_RECERR] = got[BG_ORDERR] = ~0ull;
+    got[BG_LASTREF] = (unsigned long long)-1ll;
+    const Walk walk = {plain.as<uint8_t>(), (long long)total, 0, (long long)f.first_record, 1, n_ref, (int)n_seg,
+                       map.as<uint16_t>(), entry.as<int>(), cnt.as<int>(), base.as<long long>(), m};
     WC_HIP(hipEventRecord(E.ev[0], stream));
-    WC_HIP(hipMemcpyAsync(m, init, sizeof(init), hipMemcpyHostToDevice, stream));
+    WC_HIP(hipMemcpyAsync(m, got, sizeof(got), hipMemcpyHostToDevice, stream));
     WC_HIP(hipMemcpyAsync(comp.p, f.data, f.size + WC_BGZF_PAD, hipMemcpyHostToDevice, stream));
     if (n_blocks) WC_HIP(hipMemcpyAsync(dir.p, f.blocks.data(), sizeof(wc::BgzfBlock) * (size_t)n_blocks, hipMemcpyHostToDevice, stream));
     WC_HIP(hipEventRecord(E.ev[1], stream));
@@ -726,46 +708,17 @@ int open_dev(wc_ctx *ctx, hipStream_t stream, const wc_bamfile &f, int64_t budge
         hipLaunchKernelGGL(k_bg_inflate, dim3((unsigned)n_blocks), dim3(64), 0, stream, (const uint8_t *)comp.as<uint8_t>(),
                            (const wc::BgzfBlock *)dir.as<wc::BgzfBlock>(), plain.as<uint8_t>(), status.as<int>());
     WC_HIP(hipEventRecord(E.ev[2], stream));
-    if (n_seg)
-        hipLaunchKernelGGL(k_bg_chain, dim3((unsigned)n_seg), dim3(64), 0, stream, (const uint8_t *)plain.as<uint8_t>(),
-                           (long long)total, map.as<uint16_t>());
-    WC_HIP(hipEventRecord(E.ev[3], stream));
-    if (n_seg)
-        hipLaunchKernelGGL(k_bg_link, dim3(1), dim3(64), 0, stream, (const uint8_t *)plain.as<uint8_t>(), (long long)total,
-                           (long long)f.first_record, (const uint16_t *)map.as<uint16_t>(), (int)n_seg, entry.as<int>());
-    WC_HIP(hipEventRecord(E.ev[4], stream));
-    const unsigned walk_grid = (unsigned)((n_seg + 255) / 256);
-    if (n_seg) {
-        hipLaunchKernelGGL(k_bg_walk<false>, dim3(walk_grid), dim3(256), 0, stream, (const uint8_t *)plain.as<uint8_t>(),
-                           (long long)total, n_ref, (const int *)entry.as<int>(), (int)n_seg, cnt.as<int>(),
-                           (const long long *)nullptr, m, m + 4, (int32_t *)nullptr, (uint8_t *)nullptr, (uint16_t *)nullptr,
-                           (int32_t *)nullptr, (int32_t *)nullptr);
-        hipLaunchKernelGGL(k_bg_scan, dim3(1), dim3(256), 0, stream, (const int *)cnt.as<int>(), (int)n_seg,
-                           base.as<long long>(), m + 3);
-    }
-    WC_HIP(hipEventRecord(E.ev[5], stream));
+    if ((rc = launch_count(stream, walk, E.ev + 3))) return rc;     // n_seg >= 1: the header lies in the data
     WC_HIP(hipGetLastError());
     std::vector<int> st((size_t)n_blocks, 0);
-    unsigned long long got[8];
     if (n_blocks) WC_HIP(hipMemcpyAsync(st.data(), status.p, 4 * (size_t)n_blocks, hipMemcpyDeviceToHost, stream));
     WC_HIP(hipMemcpyAsync(got, m, sizeof(got), hipMemcpyDeviceToHost, stream));
     WC_HIP(hipStreamSynchronize(stream));
-    const int bad = first_bad_block(st);
-    WC_CHECK(bad < 0, WC_E_FORMAT, "bam: damaged BGZF block %d (%s)", bad,
-             st[(size_t)(bad < 0 ? 0 : bad)] == BG_E_CRC ? "CRC failed" : "inflate failed");
+    // every block and record defect here, before the arrays are sized and any order is looked at
+    if ((rc = check_status(got, st, 0, total, n_ref, nullptr, nullptr, 0, -1))) return rc;
     comp.release();
     map.release();
-    if (got[4] != ~0ull) {
-        const long long at = (long long)(got[4] >> 3);
-        switch ((int)(got[4] & 7u)) {
-            case BG_R_BS: wc::set_error("bam: the record at inflated offset %lld has a block_size below its 32 fixed bytes", at); break;
-            case BG_R_FIELDS: wc::set_error("bam: the fields of the record at inflated offset %lld overrun its block_size", at); break;
-            case BG_R_REF: wc::set_error("bam: the record at inflated offset %lld names a reference beyond the %d of the header", at, n_ref); break;
-            default: wc::set_error("bam: truncated: the record at inflated offset %lld overruns the data (%lld bytes)", at, (long long)total);
-        }
-        return WC_E_FORMAT;
-    }
-    const unsigned long long n = got[3];
+    const unsigned long long n = got[BG_PLACED];
     WC_CHECK(n <= (unsigned long long)INT32_MAX, WC_E_LIMIT, "bam: more than 2^31 - 1 placed records");
     h.mapped = (int64_t)got[0];
     h.unmapped = (int64_t)got[1];
@@ -775,37 +728,17 @@ int open_dev(wc_ctx *ctx, hipStream_t stream, const wc_bamfile &f, int64_t budge
     if ((rc = pos.alloc(4 * (size_t)n)) || (rc = mapq.alloc((size_t)n)) || (rc = flag.alloc(2 * (size_t)n)) ||
         (rc = mate.alloc(4 * (size_t)n)) || (rc = refs.alloc(4 * (size_t)n)) || (rc = offs.alloc(8 * ((size_t)n_ref + 1))))
         return rc;
+    WC_HIP(hipMemsetAsync(offs.p, 0, 8 * ((size_t)n_ref + 1), stream));
     WC_HIP(hipEventRecord(E.ev[6], stream));
-    if (n) {
-        hipLaunchKernelGGL(k_bg_walk<true>, dim3(walk_grid), dim3(256), 0, stream, (const uint8_t *)plain.as<uint8_t>(),
-                           (long long)total, n_ref, (const int *)entry.as<int>(), (int)n_seg, (int *)nullptr,
-                           (const long long *)base.as<long long>(), (unsigned long long *)nullptr, (unsigned long long *)nullptr,
-                           pos.as<int32_t>(), mapq.as<uint8_t>(), flag.as<uint16_t>(), mate.as<int32_t>(), refs.as<int32_t>());
-    }
-    WC_HIP(hipEventRecord(E.ev[7], stream));
-    if (n > 1)
-        hipLaunchKernelGGL(k_bg_order, dim3((unsigned)((n - 1 + 255) / 256)), dim3(256), 0, stream,
-                           (const int32_t *)refs.as<int32_t>(), (const int32_t *)pos.as<int32_t>(), (long long)n, m + 5);
-    hipLaunchKernelGGL(k_bg_offsets, dim3((unsigned)(n_ref / 256 + 1)), dim3(256), 0, stream, (const int32_t *)refs.as<int32_t>(),
-                       (long long)n, n_ref, offs.as<long long>());
-    WC_HIP(hipEventRecord(E.ev[8], stream));
+    // the order grid by n, which the host knows here (a file without placed records: one workgroup that finds none)
+    if ((rc = launch_fields(stream, walk, pos.as<int32_t>(), mapq.as<uint8_t>(), flag.as<uint16_t>(), mate.as<int32_t>(),
+                            refs.as<int32_t>(), offs.as<long long>(), std::max<long long>((long long)n, 1), E.ev + 7)))
+        return rc;
     WC_HIP(hipGetLastError());
     WC_HIP(hipMemcpyAsync(got, m, sizeof(got), hipMemcpyDeviceToHost, stream));
     WC_HIP(hipMemcpyAsync(h.offsets.data(), offs.p, 8 * ((size_t)n_ref + 1), hipMemcpyDeviceToHost, stream));
     WC_HIP(hipStreamSynchronize(stream));
-    if (got[5] != ~0ull) {
-        const long long i = (long long)(got[5] >> 2);
-        int32_t two_ref[2] = {0, 0}, two_pos[2] = {0, 0};
-        WC_HIP(hipMemcpy(two_ref, refs.as<int32_t>() + i - 1, 8, hipMemcpyDeviceToHost));
-        WC_HIP(hipMemcpy(two_pos, pos.as<int32_t>() + i - 1, 8, hipMemcpyDeviceToHost));
-        if ((got[5] & 3u) == 1u)
-            wc::set_error("bam: not coordinate-sorted: placed record %lld of reference %d follows reference %d (the records of a "
-                          "reference must be contiguous, references in header order)", i, two_ref[1], two_ref[0]);
-        else
-            wc::set_error("bam: not coordinate-sorted: position %d follows %d in reference %d (placed record %lld)", two_pos[1],
-                          two_pos[0], two_ref[1], i);
-        return WC_E_ARG;
-    }
+    if ((rc = check_status(got, st, 0, total, n_ref, refs.as<int32_t>(), pos.as<int32_t>(), 0, -1))) return rc;
     static const int pairs[7][2] = {{0, 1}, {1, 2}, {2, 3}, {3, 4}, {4, 5}, {6, 7}, {7, 8}};
     for (int k = 0; k < 7; ++k) {
         float ms = 0.f;
@@ -874,17 +807,17 @@ int stream_dev(wc_ctx *ctx, hipStream_t stream, const char *path, int64_t chunk_
     static const size_t width[4] = {4, 1, 2, 4};        // pos, mapq, flag, mate_pos
     int64_t out_cap = 0, peak_work = 0, peak_all = 0, regrows = 0;
     auto account = [&]() {
-        int64_t w = 8 * ((int64_t)n_ref + 1) + 8 * BS_WORDS;
+        int64_t w = 8 * ((int64_t)n_ref + 1) + 8 * BG_WORDS;
         for (const Sized *b : {&comp[0], &comp[1], &dir[0], &dir[1], &plain[0], &plain[1], &status, &map, &entry, &cnt, &base, &refs})
             w += (int64_t)b->cap;
         peak_work = std::max(peak_work, w);
         peak_all = std::max(peak_all, w + 11 * out_cap);
     };
-    if ((rc = acc.alloc(8 * ((size_t)n_ref + 1))) || (rc = misc.alloc(8 * BS_WORDS))) return rc;
+    if ((rc = acc.alloc(8 * ((size_t)n_ref + 1))) || (rc = misc.alloc(8 * BG_WORDS))) return rc;
     unsigned long long *m = misc.as<unsigned long long>();
-    unsigned long long got[BS_WORDS] = {0};
-    got[BS_RECERR] = got[BS_ORDERR] = ~0ull;
-    got[BS_LASTREF] = (unsigned long long)-1ll;
+    unsigned long long got[BG_WORDS] = {0};
+    got[BG_RECERR] = got[BG_ORDERR] = ~0ull;
+    got[BG_LASTREF] = (unsigned long long)-1ll;
     WC_HIP(hipMemcpyAsync(m, got, sizeof(got), hipMemcpyHostToDevice, stream));
     WC_HIP(hipMemsetAsync(acc.p, 0, 8 * ((size_t)n_ref + 1), stream));
 
@@ -944,32 +877,21 @@ int stream_dev(wc_ctx *ctx, hipStream_t stream, const char *path, int64_t chunk_
         if (carry)
             WC_HIP(hipMemcpyAsync(data, plain[s ^ 1].mem.as<uint8_t>() + tail, (size_t)carry, hipMemcpyDeviceToDevice, stream));
         WC_HIP(hipStreamWaitEvent(stream, copy.done[s], 0));
-        hipLaunchKernelGGL(k_bs_begin, dim3(1), dim3(64), 0, stream, m, total);
+        hipLaunchKernelGGL(k_bg_begin, dim3(1), dim3(64), 0, stream, m, total);
         if (n_blocks)
             hipLaunchKernelGGL(k_bg_inflate, dim3((unsigned)n_blocks), dim3(64), 0, stream, (const uint8_t *)comp[s].mem.as<uint8_t>(),
                                (const wc::BgzfBlock *)dir[s].mem.as<wc::BgzfBlock>(), data + carry, status.mem.as<int>());
         // the records: from the carry's first byte, or from the end of the header in the chunk that holds it
         const long long first = std::max(first_record - abs_base, 0ll);
         if (first < total) {
-            const unsigned walk_grid = (unsigned)((n_seg + 255) / 256);
-            const int last = cur.last ? 1 : 0;
-            hipLaunchKernelGGL(k_bg_chain, dim3((unsigned)n_seg), dim3(64), 0, stream, (const uint8_t *)data, total, map.mem.as<uint16_t>());
-            hipLaunchKernelGGL(k_bg_link, dim3(1), dim3(64), 0, stream, (const uint8_t *)data, total, first,
-                               (const uint16_t *)map.mem.as<uint16_t>(), (int)n_seg, entry.mem.as<int>());
-            hipLaunchKernelGGL(k_bs_walk<false>, dim3(walk_grid), dim3(256), 0, stream, (const uint8_t *)data, total, abs_base, last,
-                               n_ref, (const int *)entry.mem.as<int>(), (int)n_seg, cnt.mem.as<int>(), (const long long *)nullptr, m,
-                               (int32_t *)nullptr, (uint8_t *)nullptr, (uint16_t *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr);
-            hipLaunchKernelGGL(k_bg_scan, dim3(1), dim3(256), 0, stream, (const int *)cnt.mem.as<int>(), (int)n_seg,
-                               base.mem.as<long long>(), m + BS_PLACED);
-            hipLaunchKernelGGL(k_bs_walk<true>, dim3(walk_grid), dim3(256), 0, stream, (const uint8_t *)data, total, abs_base, last,
-                               n_ref, (const int *)entry.mem.as<int>(), (int)n_seg, (int *)nullptr,
-                               (const long long *)base.mem.as<long long>(), m, out[0].as<int32_t>(), out[1].as<uint8_t>(),
-                               out[2].as<uint16_t>(), out[3].as<int32_t>(), refs.mem.as<int32_t>());
-            hipLaunchKernelGGL(k_bs_order, dim3((unsigned)((max_rec + 255) / 256)), dim3(256), 0, stream,
-                               (const int32_t *)refs.mem.as<int32_t>(), (const int32_t *)out[0].as<int32_t>(), m);
-            hipLaunchKernelGGL(k_bs_offsets, dim3((unsigned)(n_ref / 256 + 1)), dim3(256), 0, stream,
-                               (const int32_t *)refs.mem.as<int32_t>(), (const unsigned long long *)m, n_ref, acc.as<long long>());
-            hipLaunchKernelGGL(k_bs_advance, dim3(1), dim3(64), 0, stream, (const int32_t *)refs.mem.as<int32_t>(), m);
+            const Walk walk = {data, total, abs_base, first, cur.last ? 1 : 0, n_ref, (int)n_seg, map.mem.as<uint16_t>(),
+                               entry.mem.as<int>(), cnt.mem.as<int>(), base.mem.as<long long>(), m};
+            // no host synchronise between the two: the order grid covers the most records the chunk can hold
+            if ((rc = launch_count(stream, walk, nullptr)) ||
+                (rc = launch_fields(stream, walk, out[0].as<int32_t>(), out[1].as<uint8_t>(), out[2].as<uint16_t>(), out[3].as<int32_t>(),
+                                    refs.mem.as<int32_t>(), acc.as<long long>(), (long long)max_rec, nullptr)))
+                return rc;
+            hipLaunchKernelGGL(k_bg_advance, dim3(1), dim3(64), 0, stream, (const int32_t *)refs.mem.as<int32_t>(), m);
         }
         WC_HIP(hipGetLastError());
         // the staging buffer of this chunk is free once its copy has run: the reader thread may fill it with chunk i + 2,
@@ -993,37 +915,13 @@ int stream_dev(wc_ctx *ctx, hipStream_t stream, const char *path, int64_t chunk_
         const auto t1 = std::chrono::steady_clock::now();
         WC_HIP(hipStreamSynchronize(stream));
         wait_device += ms_since(t1);
-        const int bad = first_bad_block(st);
-        WC_CHECK(bad < 0, WC_E_FORMAT, "bam: damaged BGZF block %lld (%s)", first_block + bad,
-                 st[(size_t)(bad < 0 ? 0 : bad)] == BG_E_CRC ? "CRC failed" : "inflate failed");
-        if (got[BS_RECERR] != ~0ull) {
-            const long long at = (long long)(got[BS_RECERR] >> 3);
-            switch ((int)(got[BS_RECERR] & 7u)) {
-                case BG_R_BS: wc::set_error("bam: the record at inflated offset %lld has a block_size below its 32 fixed bytes", at); break;
-                case BG_R_FIELDS: wc::set_error("bam: the fields of the record at inflated offset %lld overrun its block_size", at); break;
-                case BG_R_REF: wc::set_error("bam: the record at inflated offset %lld names a reference beyond the %d of the header", at, n_ref); break;
-                default: wc::set_error("bam: truncated: the record at inflated offset %lld overruns the data (%lld bytes)", at, abs_base + total);
-            }
-            return WC_E_FORMAT;
-        }
-        if (got[BS_ORDERR] != ~0ull) {
-            const long long g = (long long)(got[BS_ORDERR] >> 2), local = g - placed;
-            int32_t two_ref[2] = {(int32_t)prev_last_ref, 0}, two_pos[2] = {0, 0};
-            if (local > 0) WC_HIP(hipMemcpy(two_ref, refs.mem.as<int32_t>() + local - 1, 8, hipMemcpyDeviceToHost));
-            else WC_HIP(hipMemcpy(two_ref + 1, refs.mem.as<int32_t>(), 4, hipMemcpyDeviceToHost));
-            WC_HIP(hipMemcpy(two_pos, out[0].as<int32_t>() + g - 1, 8, hipMemcpyDeviceToHost));
-            if ((got[BS_ORDERR] & 3u) == 1u)
-                wc::set_error("bam: not coordinate-sorted: placed record %lld of reference %d follows reference %d (the records of a "
-                              "reference must be contiguous, references in header order)", g, two_ref[1], two_ref[0]);
-            else
-                wc::set_error("bam: not coordinate-sorted: position %d follows %d in reference %d (placed record %lld)", two_pos[1],
-                              two_pos[0], two_ref[1], g);
-            return WC_E_ARG;
-        }
-        placed = (long long)got[BS_BASE];
+        if ((rc = check_status(got, st, first_block, abs_base + total, n_ref, refs.mem.as<int32_t>(), out[0].as<int32_t>(), placed,
+                               prev_last_ref)))
+            return rc;
+        placed = (long long)got[BG_BASE];
         WC_CHECK(placed <= (long long)INT32_MAX, WC_E_LIMIT, "bam: more than 2^31 - 1 placed records");
-        prev_last_ref = (long long)got[BS_LASTREF];
-        tail = (long long)got[BS_TAIL];
+        prev_last_ref = (long long)got[BG_LASTREF];
+        tail = (long long)got[BG_TAIL];
         carry = was_last ? 0 : total - tail;
         max_carry = std::max<int64_t>(max_carry, carry);
         if (rc_next) {
@@ -1053,21 +951,15 @@ int stream_dev(wc_ctx *ctx, hipStream_t stream, const char *path, int64_t chunk_
     return WC_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int wc_bam_chain_segment(void) { return BG_SEG; }
-
-int wc_bam_open_dev(wc_ctx *ctx, void *stream, const wc_bamfile *file, int64_t budget_bytes, wc_bam_dev **out) {
-    WC_CHECK(ctx && file && out, WC_E_ARG, "bam: NULL argument");
+// a handle filled by `open` on the context's device, or none and open's code
+template <class Open> int new_handle(wc_ctx *ctx, wc_bam_dev **out, Open open) {
     *out = nullptr;
     WC_HIP(hipSetDevice(ctx->device));
     wc_bam_dev *h = nullptr;
     int rc;
     try {
         h = new wc_bam_dev();
-        rc = open_dev(ctx, (hipStream_t)stream, *file, budget_bytes, *h);
+        rc = open(*h);
     } catch (const std::exception &e) {
         wc::set_error("bam: %s", e.what());
         rc = WC_E_LIMIT;
@@ -1080,25 +972,20 @@ int wc_bam_open_dev(wc_ctx *ctx, void *stream, const wc_bamfile *file, int64_t b
     return WC_OK;
 }
 
+}  // namespace
+
+extern "C" {
+
+int wc_bam_chain_segment(void) { return BG_SEG; }
+
+int wc_bam_open_dev(wc_ctx *ctx, void *stream, const wc_bamfile *file, int64_t budget_bytes, wc_bam_dev **out) {
+    WC_CHECK(ctx && file && out, WC_E_ARG, "bam: NULL argument");
+    return new_handle(ctx, out, [&](wc_bam_dev &h) { return open_dev(ctx, (hipStream_t)stream, *file, budget_bytes, h); });
+}
+
 int wc_bam_stream_dev(wc_ctx *ctx, void *stream, const char *path, int64_t chunk_bytes, wc_bam_dev **out) {
     WC_CHECK(ctx && path && out, WC_E_ARG, "bam: NULL argument");
-    *out = nullptr;
-    WC_HIP(hipSetDevice(ctx->device));
-    wc_bam_dev *h = nullptr;
-    int rc;
-    try {
-        h = new wc_bam_dev();
-        rc = stream_dev(ctx, (hipStream_t)stream, path, chunk_bytes, *h);
-    } catch (const std::exception &e) {
-        wc::set_error("bam: %s", e.what());
-        rc = WC_E_LIMIT;
-    }
-    if (rc != WC_OK) {
-        delete h;
-        return rc;
-    }
-    *out = h;
-    return WC_OK;
+    return new_handle(ctx, out, [&](wc_bam_dev &h) { return stream_dev(ctx, (hipStream_t)stream, path, chunk_bytes, h); });
 }
 
 int wc_bam_dev_stream_info(const wc_bam_dev *h, int64_t out[8]) {
