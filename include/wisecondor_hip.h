@@ -377,6 +377,28 @@ int wc_bam_stream_dev(wc_ctx *ctx, void *stream, const char *path, int64_t chunk
 int wc_bam_dev_stream_info(const wc_bam_dev *bam, int64_t out[8]);
 
 /*
+ * The bounded route of `convert`: the loop of wc_bam_stream_dev with another sink.  A chunk's placed records go to a buffer
+ * of the chunk's own (reserved by the most records a chunk plus carry can hold, reused by the next chunk), and once the
+ * chunk's status read has found it sound, its records of the references refs[n_chrom] (indices into the header,
+ * ascending: the rest is skipped) are set side by side and fed to a resumable convert (wc_convert_begin below) on
+ * `stream`; the slice's table is made on the device from the chunk's references, so the route adds no host
+ * synchronisation to the reader's one status read per chunk.  Device memory does not grow with the read count and the
+ * number of placed records is not limited; one chunk is limited as one wc_convert_reads_ex_dev call is.  Errors keep the
+ * codes, texts, block numbers and the first-defect-in-file-order rule of wc_bam_stream_dev; a damaged or unsorted chunk
+ * is never fed.  counts_out (int32 [bin_offsets[n_chrom]]) and stats_out (int64 [8]) are HOST memory and what
+ * wc_convert_bam_dev gives for the same file; on any error counts_out is not written (a read beyond its chromosome's
+ * bins: WC_E_ARG, stats_out written).
+ *   info_out   int64 [16]: [0] chunks, [1] the largest chunk's compressed bytes, [2] the largest carry of bytes from chunk
+ *              to chunk, [3] the most positions the convert carried from slice to slice, [4] the peak device bytes,
+ *              everything included, [5] the bytes of the host staging buffers, [6] placed records, [7] the largest
+ *              chunk's inflated bytes, [8] / [9] / [10] mapped / unmapped / no_coordinate as wc_bam_dev_info [2..4],
+ *              [11] of [4]: the bytes of the convert's own working memory; the others 0
+ */
+int wc_convert_bam_stream_dev(wc_ctx *ctx, void *stream, const char *path, int64_t chunk_bytes, const int32_t *refs, int n_chrom,
+                              double binsize, int min_shift, int threshold, int min_mapq, int demand_pair,
+                              const int64_t *bin_offsets, int32_t *counts_out, int64_t *stats_out, int64_t info_out[16]);
+
+/*
  * The numeric part of convertBam (wisetools.py:116-217) for all chromosomes of one file in one call: the paired-end
  * selection, duplicate removal, mapping-quality filter, the tower (RETRO) filter, binning.  wc_convert_reads[_dev] is
  * the function as toolConvert calls it (mapq 1, demandPair False); wc_convert_reads_ex[_dev] takes both parameters.
@@ -418,6 +440,40 @@ int wc_convert_reads_ex_dev(wc_ctx *ctx, void *stream, const int32_t *pos, const
 int wc_convert_reads_ex(wc_ctx *ctx, const int32_t *pos, const uint8_t *mapq, const uint16_t *flag, const int32_t *mate_pos,
                         const int64_t *read_offsets, int n_chrom, double binsize, int min_shift, int threshold, int min_mapq,
                         int demand_pair, const int64_t *bin_offsets, int32_t *counts_out, int64_t *stats_out);
+
+/*
+ * The same computation in resumable form: the reads arrive in slices, in file order, and every slice is filtered and
+ * binned as it arrives; only a small carry stays on the device between slices (csrc/convert.hip), so the
+ * working memory follows the largest slice and not the read count, and the total number of reads is not limited.
+ *   wc_convert_begin       the parameters of wc_convert_reads_ex that do not depend on the reads; zeroes the counts
+ *   wc_convert_feed_dev    one slice: DEVICE arrays (flag / mate_pos may be NULL unless demand_pair) and slice_offsets,
+ *                          HOST int64 [n_chrom + 1], slice_offsets[0] == 0: chromosome c owns [slice_offsets[c], [c+1]) of
+ *                          THIS slice's arrays.  A slice may be empty, hold parts of several chromosomes and end anywhere:
+ *                          on a chromosome's consumed first read, inside a tower.  Reads for a chromosome in front of one
+ *                          that has had reads already are WC_E_ARG.  One slice is limited as one wc_convert_reads_ex_dev
+ *                          call is.  The call enqueues kernels on `stream` and returns without waiting; the arrays must
+ *                          stay valid until they have run.  Slices of one run go to one stream (or the caller orders them).
+ *   wc_convert_feed        the same from HOST arrays; it waits for the slice and returns WC_E_ARG as soon as the status
+ *                          word (stats [4]) is not 0
+ *   wc_convert_finish_dev  closes the open run and copies the counts (int32 [bin_offsets[n_chrom]]) and stats (int64 [8],
+ *                          as stats_out above, every word 64-bit over all slices) to DEVICE memory on `stream`
+ *   wc_convert_finish      the same to HOST memory; status word not 0: WC_E_ARG, stats_out written, counts_out untouched
+ *   wc_convert_run_info    out[0] slices that ran, [1] device bytes the run holds, [2] an upper bound of the positions carried
+ *   wc_convert_end         frees the run (finished or not)
+ * After any sequence of slices whose concatenation is the input of wc_convert_reads_ex, counts and stats [0..6] are that
+ * call's, bit for bit.  The carry holds at most min(longest open run, max(threshold, 0)) positions.
+ */
+typedef struct wc_convert_run wc_convert_run;
+int wc_convert_begin(wc_ctx *ctx, int n_chrom, double binsize, int min_shift, int threshold, int min_mapq, int demand_pair,
+                     const int64_t *bin_offsets, wc_convert_run **out);
+int wc_convert_feed_dev(wc_convert_run *run, void *stream, const int32_t *pos, const uint8_t *mapq, const uint16_t *flag,
+                        const int32_t *mate_pos, const int64_t *slice_offsets);
+int wc_convert_feed(wc_convert_run *run, const int32_t *pos, const uint8_t *mapq, const uint16_t *flag,
+                    const int32_t *mate_pos, const int64_t *slice_offsets);
+int wc_convert_finish_dev(wc_convert_run *run, void *stream, int32_t *counts_out, int64_t *stats_out);
+int wc_convert_finish(wc_convert_run *run, int32_t *counts_out, int64_t *stats_out);
+int wc_convert_run_info(const wc_convert_run *run, int64_t out[8]);
+void wc_convert_end(wc_convert_run *run);
 
 /* ---- test: per-reference state -------------------------------------------- */
 typedef struct wc_reference wc_reference;

@@ -80,11 +80,20 @@ SIGNATURES = {
     "wc_bam_stream_default_chunk": (_i64, []),
     "wc_bam_stream_dev": (_i32, [_vp, _vp, _c.c_char_p, _i64, _vp]),
     "wc_bam_dev_stream_info": (_i32, [_vp, _vp]),
+    "wc_convert_bam_stream_dev": (_i32, [_vp, _vp, _c.c_char_p, _i64, _vp, _i32, _dbl, _i32, _i32, _i32, _i32, _vp, _vp, _vp,
+                                         _vp]),
     "wc_convert_tile_reads": (_i32, []),
     "wc_convert_reads_dev": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _dbl, _i32, _i32, _vp, _vp, _vp]),
     "wc_convert_reads": (_i32, [_vp, _vp, _vp, _vp, _i32, _dbl, _i32, _i32, _vp, _vp, _vp]),
     "wc_convert_reads_ex_dev": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _dbl, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "wc_convert_reads_ex": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _dbl, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "wc_convert_begin": (_i32, [_vp, _i32, _dbl, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "wc_convert_feed_dev": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "wc_convert_feed": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "wc_convert_finish_dev": (_i32, [_vp, _vp, _vp, _vp]),
+    "wc_convert_finish": (_i32, [_vp, _vp, _vp]),
+    "wc_convert_run_info": (_i32, [_vp, _vp]),
+    "wc_convert_end": (None, [_vp]),
     "wc_newref_prep_gram": (_i32, [_vp, _vp, _i64, _i64, _vp, _i32, _vp, _vp, _vp, _vp]),
     "wc_newref_prep_eig": (_i32, [_vp, _i32, _vp, _vp]),
     "wc_sym_eigh_leading_dev": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp]),

@@ -518,6 +518,86 @@ __global__ void __launch_bounds__(64) k_bg_advance(const int32_t *__restrict__ r
     }
 }
 
+// ---- the bounded route (wc_convert_bam_stream_dev): a chunk's placed records go to a buffer of the chunk's own, records
+// from element 1 on; element 0 of the positions keeps the last position of the chunks before for the order check
+__global__ void __launch_bounds__(64) k_bg_keep_last(int32_t *pos_buf, const unsigned long long *__restrict__ m) {
+    if (threadIdx.x) return;
+    const long long n = (long long)m[BG_PLACED];
+    if (n) pos_buf[0] = pos_buf[n];
+}
+
+// The slice table of the chunk for the picked references picked[n_chrom] (ascending): so[c] = the chunk's placed records
+// of picked references in front of picked[c], from[c] = the chunk's placed records of references below picked[c].
+// refs[] ascends (the order check has passed).  One workgroup, n_chrom <= 256.
+__global__ void __launch_bounds__(256) k_bg_slice(const int32_t *__restrict__ refs, const unsigned long long *__restrict__ m,
+                                                  const int32_t *__restrict__ picked, int n_chrom, int *__restrict__ so,
+                                                  int *__restrict__ from) {
+    __shared__ int s_cnt[256];
+    const int c = (int)threadIdx.x;
+    const long long n = (long long)m[BG_PLACED];
+    int here = 0;
+    if (c < n_chrom) {
+        const int r = picked[c];
+        long long lo = 0, hi = n;
+        while (lo < hi) {
+            const long long mid = lo + (hi - lo) / 2;
+            if (refs[mid] < r) lo = mid + 1;
+            else hi = mid;
+        }
+        const long long begin = lo;
+        hi = n;
+        while (lo < hi) {
+            const long long mid = lo + (hi - lo) / 2;
+            if (refs[mid] <= r) lo = mid + 1;
+            else hi = mid;
+        }
+        from[c] = (int)begin;
+        here = (int)(lo - begin);
+    }
+    s_cnt[c] = here;
+    wc_sync();
+    if (c == 0) {
+        int run = 0;
+        for (int k = 0; k < n_chrom; ++k) {
+            so[k] = run;
+            run += s_cnt[k];
+        }
+        so[n_chrom] = run;
+    }
+}
+
+// the chunk's records of the picked references side by side: record i of picked[c] goes to so[c] + (i - from[c])
+__global__ void __launch_bounds__(256) k_bg_gather(const int32_t *__restrict__ refs, const unsigned long long *__restrict__ m,
+                                                   const int32_t *__restrict__ picked, int n_chrom, const int *__restrict__ so,
+                                                   const int *__restrict__ from, const int32_t *__restrict__ pos,
+                                                   const uint8_t *__restrict__ mapq, const uint16_t *__restrict__ flag,
+                                                   const int32_t *__restrict__ mate, int32_t *__restrict__ pos_out,
+                                                   uint8_t *__restrict__ mapq_out, uint16_t *__restrict__ flag_out,
+                                                   int32_t *__restrict__ mate_out) {
+    __shared__ int s_picked[256], s_so[256], s_from[256];
+    if ((int)threadIdx.x < n_chrom) {
+        s_picked[threadIdx.x] = picked[threadIdx.x];
+        s_so[threadIdx.x] = so[threadIdx.x];
+        s_from[threadIdx.x] = from[threadIdx.x];
+    }
+    wc_sync();
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)m[BG_PLACED]) return;
+    const int r = refs[i];
+    int lo = 0, hi = n_chrom;                           // the first picked reference that is not below r
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (s_picked[mid] < r) lo = mid + 1;
+        else hi = mid;
+    }
+    if (lo >= n_chrom || s_picked[lo] != r) return;     // a reference the conversion skips
+    const long long d = (long long)s_so[lo] + (i - (long long)s_from[lo]);
+    pos_out[d] = pos[i];
+    mapq_out[d] = mapq[i];
+    flag_out[d] = flag[i];
+    mate_out[d] = mate[i];
+}
+
 struct DevMem {             // a device allocation of one call
     void *p = nullptr;
     DevMem() = default;
@@ -781,7 +861,17 @@ struct Sized {              // a working buffer that grows to the largest need s
     }
 };
 
-int stream_dev(wc_ctx *ctx, hipStream_t stream, const char *path, int64_t chunk_bytes, wc_bam_dev &h) {
+// The sink of the bounded route: every chunk's records are fed to `run` (the references picked[n_chrom] of the file,
+// ascending) and dropped; no arrays are kept.
+struct Bounded {
+    wc_convert_run *run = nullptr;
+    const int32_t *picked = nullptr;
+    int n_chrom = 0;
+    bool paired = false;
+    int64_t peak_all = 0;           // peak device bytes, everything
+};
+
+int stream_dev(wc_ctx *ctx, hipStream_t stream, const char *path, int64_t chunk_bytes, wc_bam_dev &h, Bounded *bd = nullptr) {
     const auto began = std::chrono::steady_clock::now();
     auto ms_since = [](std::chrono::steady_clock::time_point t) {
         return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
@@ -803,16 +893,33 @@ int stream_dev(wc_ctx *ctx, hipStream_t stream, const char *path, int64_t chunk_
     // comp, dir: one per chunk in flight (the copy of chunk i + 1 runs beside the decode of chunk i); plain: the carry
     // moves from one to the other
     Sized comp[2], dir[2], plain[2], status, map, entry, cnt, base, refs;
-    DevMem acc, misc, out[4];
+    Sized rec[4], gat[4];                               // bounded route: the chunk's records, and those of the picked references
+    DevMem acc, misc, out[4], pick;                     // pick: picked[], so[], from[] of the bounded route
     static const size_t width[4] = {4, 1, 2, 4};        // pos, mapq, flag, mate_pos
-    int64_t out_cap = 0, peak_work = 0, peak_all = 0, regrows = 0;
+    int64_t out_cap = 0, peak_work = 0, peak_all = 0, regrows = 0, run_bytes = 0;
     auto account = [&]() {
         int64_t w = 8 * ((int64_t)n_ref + 1) + 8 * BG_WORDS;
         for (const Sized *b : {&comp[0], &comp[1], &dir[0], &dir[1], &plain[0], &plain[1], &status, &map, &entry, &cnt, &base, &refs})
             w += (int64_t)b->cap;
         peak_work = std::max(peak_work, w);
         peak_all = std::max(peak_all, w + 11 * out_cap);
+        if (bd) {
+            for (int k = 0; k < 4; ++k) w += (int64_t)(rec[k].cap + gat[k].cap);
+            bd->peak_all = std::max(bd->peak_all, w + run_bytes + 12 * ((int64_t)bd->n_chrom + 1));
+        }
     };
+    if (bd) {
+        for (int c = 0; c < bd->n_chrom; ++c)
+            WC_CHECK(bd->picked[c] >= 0 && bd->picked[c] < n_ref && (!c || bd->picked[c] > bd->picked[c - 1]), WC_E_ARG,
+                     "convert: reference %d of %d (the picked references ascend)", bd->picked[c], n_ref);
+        if ((rc = pick.alloc(12 * ((size_t)bd->n_chrom + 1)))) return rc;
+        WC_HIP(hipMemcpyAsync(pick.p, bd->picked, 4 * (size_t)bd->n_chrom, hipMemcpyHostToDevice, stream));
+        int64_t info[8];
+        if ((rc = wc_convert_run_info(bd->run, info))) return rc;
+        run_bytes = info[1];
+    }
+    const int32_t *picked_dev = pick.as<int32_t>();
+    int *so_dev = bd ? pick.as<int>() + bd->n_chrom + 1 : nullptr, *from_dev = bd ? so_dev + bd->n_chrom + 1 : nullptr;
     if ((rc = acc.alloc(8 * ((size_t)n_ref + 1))) || (rc = misc.alloc(8 * BG_WORDS))) return rc;
     unsigned long long *m = misc.as<unsigned long long>();
     unsigned long long got[BG_WORDS] = {0};
@@ -856,7 +963,18 @@ int stream_dev(wc_ctx *ctx, hipStream_t stream, const char *path, int64_t chunk_
             (rc = entry.reserve(4 * (size_t)n_seg)) || (rc = cnt.reserve(4 * (size_t)n_seg)) || (rc = base.reserve(8 * (size_t)n_seg)) ||
             (rc = refs.reserve(4 * (size_t)((n_seg * BG_SEG) / BG_STEP + 1))) || (rc = status.reserve(4 * (size_t)n_blocks)))
             return rc;
-        if (placed + max_rec > out_cap) {               // the arrays: room for the most records this chunk can hold
+        if (bd) {                                       // room for the most records this chunk can hold, behind element 0
+            const size_t room = (size_t)max_rec + 1;
+            if (4 * room > rec[0].cap && rec[0].cap) {  // the positions grow: element 0 moves along
+                int32_t lead = 0;
+                WC_HIP(hipStreamSynchronize(stream));
+                WC_HIP(hipMemcpy(&lead, rec[0].mem.p, 4, hipMemcpyDeviceToHost));
+                if ((rc = rec[0].reserve(4 * room))) return rc;
+                WC_HIP(hipMemcpy(rec[0].mem.p, &lead, 4, hipMemcpyHostToDevice));
+            }
+            for (int k = 0; k < 4; ++k)
+                if ((rc = rec[k].reserve(width[k] * room)) || (rc = gat[k].reserve(width[k] * room))) return rc;
+        } else if (placed + max_rec > out_cap) {        // the arrays: room for the most records this chunk can hold
             const int64_t want = std::max<int64_t>(placed + max_rec, 2 * out_cap);
             DevMem grown[4];
             for (int k = 0; k < 4; ++k)
@@ -881,6 +999,12 @@ int stream_dev(wc_ctx *ctx, hipStream_t stream, const char *path, int64_t chunk_
         if (n_blocks)
             hipLaunchKernelGGL(k_bg_inflate, dim3((unsigned)n_blocks), dim3(64), 0, stream, (const uint8_t *)comp[s].mem.as<uint8_t>(),
                                (const wc::BgzfBlock *)dir[s].mem.as<wc::BgzfBlock>(), data + carry, status.mem.as<int>());
+        // where the walk writes: the growing arrays; bounded route: the chunk's buffers, addressed so that the file's
+        // placed record number `placed` (the running base on the device) lands on element 1
+        auto sink = [&](int k) -> void * {
+            if (!bd) return out[k].p;
+            return (void *)((uintptr_t)rec[k].mem.p + width[k] - width[k] * (size_t)placed);
+        };
         // the records: from the carry's first byte, or from the end of the header in the chunk that holds it
         const long long first = std::max(first_record - abs_base, 0ll);
         if (first < total) {
@@ -888,7 +1012,7 @@ int stream_dev(wc_ctx *ctx, hipStream_t stream, const char *path, int64_t chunk_
                                entry.mem.as<int>(), cnt.mem.as<int>(), base.mem.as<long long>(), m};
             // no host synchronise between the two: the order grid covers the most records the chunk can hold
             if ((rc = launch_count(stream, walk, nullptr)) ||
-                (rc = launch_fields(stream, walk, out[0].as<int32_t>(), out[1].as<uint8_t>(), out[2].as<uint16_t>(), out[3].as<int32_t>(),
+                (rc = launch_fields(stream, walk, (int32_t *)sink(0), (uint8_t *)sink(1), (uint16_t *)sink(2), (int32_t *)sink(3),
                                     refs.mem.as<int32_t>(), acc.as<long long>(), (long long)max_rec, nullptr)))
                 return rc;
             hipLaunchKernelGGL(k_bg_advance, dim3(1), dim3(64), 0, stream, (const int32_t *)refs.mem.as<int32_t>(), m);
@@ -915,11 +1039,33 @@ int stream_dev(wc_ctx *ctx, hipStream_t stream, const char *path, int64_t chunk_
         const auto t1 = std::chrono::steady_clock::now();
         WC_HIP(hipStreamSynchronize(stream));
         wait_device += ms_since(t1);
-        if ((rc = check_status(got, st, first_block, abs_base + total, n_ref, refs.mem.as<int32_t>(), out[0].as<int32_t>(), placed,
+        if ((rc = check_status(got, st, first_block, abs_base + total, n_ref, refs.mem.as<int32_t>(), (const int32_t *)sink(0), placed,
                                prev_last_ref)))
             return rc;
+        if (bd && got[BG_PLACED]) {                     // the chunk is sound: its picked records to the run, behind the walk
+            const long long here = (long long)got[BG_PLACED];
+            // (behind the status read: an order defect's text shows the position the check compared with)
+            hipLaunchKernelGGL(k_bg_keep_last, dim3(1), dim3(64), 0, stream, rec[0].mem.as<int32_t>(), (const unsigned long long *)m);
+            hipLaunchKernelGGL(k_bg_slice, dim3(1), dim3(256), 0, stream, (const int32_t *)refs.mem.as<int32_t>(),
+                               (const unsigned long long *)m, picked_dev, bd->n_chrom, so_dev, from_dev);
+            hipLaunchKernelGGL(k_bg_gather, dim3((unsigned)((here + 255) / 256)), dim3(256), 0, stream,
+                               (const int32_t *)refs.mem.as<int32_t>(), (const unsigned long long *)m, picked_dev, bd->n_chrom,
+                               (const int *)so_dev, (const int *)from_dev, (const int32_t *)rec[0].mem.as<int32_t>() + 1,
+                               (const uint8_t *)rec[1].mem.as<uint8_t>() + 1, (const uint16_t *)rec[2].mem.as<uint16_t>() + 1,
+                               (const int32_t *)rec[3].mem.as<int32_t>() + 1, gat[0].mem.as<int32_t>(), gat[1].mem.as<uint8_t>(),
+                               gat[2].mem.as<uint16_t>(), gat[3].mem.as<int32_t>());
+            WC_HIP(hipGetLastError());
+            if ((rc = wc::convert_feed_table_dev(bd->run, stream, gat[0].mem.as<int32_t>(), gat[1].mem.as<uint8_t>(),
+                                                 bd->paired ? gat[2].mem.as<uint16_t>() : nullptr,
+                                                 bd->paired ? gat[3].mem.as<int32_t>() : nullptr, so_dev, here)))
+                return rc;
+            int64_t info[8];
+            if ((rc = wc_convert_run_info(bd->run, info))) return rc;
+            run_bytes = info[1];
+            account();
+        }
         placed = (long long)got[BG_BASE];
-        WC_CHECK(placed <= (long long)INT32_MAX, WC_E_LIMIT, "bam: more than 2^31 - 1 placed records");
+        WC_CHECK(bd || placed <= (long long)INT32_MAX, WC_E_LIMIT, "bam: more than 2^31 - 1 placed records");
         prev_last_ref = (long long)got[BG_LASTREF];
         tail = (long long)got[BG_TAIL];
         carry = was_last ? 0 : total - tail;
@@ -1074,6 +1220,52 @@ int wc_bgzf_inflate(wc_ctx *ctx, const unsigned char *bgzf_bytes, int64_t n, uns
     WC_CHECK(bad < 0, WC_E_FORMAT, "bgzf: damaged BGZF block %d (%s)", bad,
              st[(size_t)(bad < 0 ? 0 : bad)] == BG_E_CRC ? "CRC failed" : "inflate failed");
     if (total) WC_HIP(hipMemcpy(out, plain.p, (size_t)total, hipMemcpyDeviceToHost));
+    return WC_OK;
+}
+
+int wc_convert_bam_stream_dev(wc_ctx *ctx, void *stream_, const char *path, int64_t chunk_bytes, const int32_t *refs, int n_chrom,
+                              double binsize, int min_shift, int threshold, int min_mapq, int demand_pair,
+                              const int64_t *bin_offsets, int32_t *counts_out, int64_t *stats_out, int64_t info_out[16]) {
+    WC_CHECK(ctx && path && refs && bin_offsets && counts_out && stats_out && info_out, WC_E_ARG, "convert: NULL argument");
+    WC_HIP(hipSetDevice(ctx->device));
+    hipStream_t stream = (hipStream_t)stream_;
+    struct RunCloser {
+        wc_convert_run *run = nullptr;
+        ~RunCloser() { wc_convert_end(run); }
+    } closer;
+    int rc = wc_convert_begin(ctx, n_chrom, binsize, min_shift, threshold, min_mapq, demand_pair, bin_offsets, &closer.run);
+    if (rc) return rc;
+    Bounded bd;
+    bd.run = closer.run;
+    bd.picked = refs;
+    bd.n_chrom = n_chrom;
+    bd.paired = demand_pair != 0;
+    wc_bam_dev h;                                       // the header and the counters only: it gets no arrays
+    try {
+        rc = stream_dev(ctx, stream, path, chunk_bytes, h, &bd);
+    } catch (const std::exception &e) {
+        wc::set_error("bam: %s", e.what());
+        rc = WC_E_LIMIT;
+    }
+    if (rc) return rc;
+    int64_t max_pending = 0;
+    if ((rc = wc::convert_run_max_pending(closer.run, stream, &max_pending))) return rc;      // (waits for the last slice)
+    if ((rc = wc_convert_finish(closer.run, counts_out, stats_out))) return rc;
+    int64_t run_info[8];
+    if ((rc = wc_convert_run_info(closer.run, run_info))) return rc;
+    for (int k = 0; k < 16; ++k) info_out[k] = 0;
+    info_out[0] = h.stream_info[0];                     // chunks
+    info_out[1] = h.stream_info[1];                     // the largest chunk's compressed bytes
+    info_out[2] = h.stream_info[3];                     // the largest byte carry
+    info_out[3] = max_pending;                          // the largest run carry (positions)
+    info_out[4] = bd.peak_all;                          // peak device bytes, everything
+    info_out[5] = h.stream_info[5];                     // host staging bytes
+    info_out[6] = h.n;                                  // placed records
+    info_out[7] = h.stream_info[2];                     // the largest chunk's inflated bytes
+    info_out[8] = h.mapped;
+    info_out[9] = h.unmapped;
+    info_out[10] = h.no_coordinate;
+    info_out[11] = run_info[1];                         // of the peak: the run's own bytes (tables, kpos, counts, carry)
     return WC_OK;
 }
 

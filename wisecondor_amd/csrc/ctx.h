@@ -148,4 +148,12 @@ namespace wc {
 // eigh.hip: leading eigenpairs of a device-resident symmetric matrix (host outputs)
 int sym_eigh_leading(wc_ctx *ctx, const double *matrix_dev, int64_t n, int n_pairs, double *eigvals_out,
                      double *eigvecs_out);
+
+// convert.hip, for the streamed BAM route (bamgpu.hip): one slice of a run whose offsets table is born on the device
+// (DEVICE int [n_chrom + 1]); `most`: a bound of its last entry, by which the grids and the working memory are sized.
+// The order of the chromosomes is the caller's to keep (the reader's order check does).  convert_run_max_pending: the
+// most positions the run has carried from one slice to the next (waits for the stream).
+int convert_feed_table_dev(wc_convert_run *run, hipStream_t stream, const int32_t *pos, const uint8_t *mapq,
+                           const uint16_t *flag, const int32_t *mate_pos, const int *slice_offsets_dev, int64_t most);
+int convert_run_max_pending(const wc_convert_run *run, hipStream_t stream, int64_t *out);
 }  // namespace wc

@@ -74,18 +74,38 @@ def writeConvertOutput(outfile, args, converted, qual_info):
     write_npz(outfile, arguments=vars(args), runtime=getRuntime(), sample=converted, quality=qual_info)
 
 
+def _convert_route(args):
+    """The route `convert` / `convertbatch` take: 'bounded' (-bounded: chunk by chunk through the reader AND the filters),
+    'stream' (-stream: the streamed reader, the filters on the whole arrays) or 'whole'.  `-chunk` is the option of the
+    two chunked routes: without one of them it is an error, not something to ignore and then record in the output
+    file's `arguments`."""
+    bounded, streamed = getattr(args, 'bounded', False), getattr(args, 'stream', False)
+    if bounded and streamed:
+        raise ValueError('-stream and -bounded are two routes: give one of them')
+    route = 'bounded' if bounded else 'stream' if streamed else \
+        wt.CONVERT_READER if wt.CONVERT_READER in ('stream', 'bounded') else 'whole'
+    if hasattr(args, 'chunk') and route == 'whole':
+        raise ValueError('-chunk sets the chunk size of the streamed reader: give -stream (or -bounded) as well')
+    return route
+
+
 def _convert_streamed(args):
-    """True where `convert` / `convertbatch` read through the streamed reader.  `-chunk` is that reader's option: without
-    it the option is an error, not something to ignore and then record in the output file's `arguments`."""
-    streamed = getattr(args, 'stream', False) or wt.CONVERT_READER == 'stream'
-    if hasattr(args, 'chunk') and not streamed:
-        raise ValueError('-chunk sets the chunk size of the streamed reader: give -stream as well')
-    return streamed
+    """True where `convert` / `convertbatch` read through the streamed reader (_convert_route: 'stream')."""
+    return _convert_route(args) == 'stream'
+
+
+def _convert_bounded(args, path, verbose):
+    return wt.convertBamBounded(path, args.binsize, args.retdist, args.retthres, mapq=getattr(args, 'mapq', 1),
+                                demandPair=getattr(args, 'paired', False), chunk=getattr(args, 'chunk', 0), verbose=verbose)
 
 
 def toolConvert(args):
     """`convert infile outfile`: BAM -> binned, filtered sample (wisecondor.py:20-27)."""
-    if _convert_streamed(args):
+    route = _convert_route(args)
+    if route == 'bounded':
+        # build-only: reader and filters chunk by chunk, no per-read arrays (memory does not grow with the read count)
+        converted, qual_info = _convert_bounded(args, args.infile, True)
+    elif route == 'stream':
         # build-only: the streamed device reader (memory bounded by the chunk); the same filters and binning behind it
         with wt.openBamReads(args.infile, stream=True, chunk=getattr(args, 'chunk', 0)) as bam:
             converted, qual_info = wt.convertBamReads(bam, args.binsize, args.retdist, args.retthres, verbose=True,
@@ -129,8 +149,9 @@ def toolConvertBatch(args):
     try:
         # the reader thread's share: the host stage of the device reader, or the whole host reader; nothing for the
         # streamed reader, which has a reader thread of its own and holds no file whole
-        streamed = _convert_streamed(args)
-        if streamed:
+        route = _convert_route(args)
+        streamed = route == 'stream'
+        if route != 'whole':
             stage = None
         elif wt.CONVERT_READER == 'device':
             def stage(path):
@@ -141,7 +162,9 @@ def toolConvertBatch(args):
         if stage:
             ahead = reader.submit(stage, args.infiles[0])
         for i, (path, out) in enumerate(zip(args.infiles, outs)):
-            if streamed:
+            if route == 'bounded':
+                bam = None
+            elif streamed:
                 bam = wt.openBamReads(path, stream=True, chunk=getattr(args, 'chunk', 0))
             else:
                 bam = ahead.result()
@@ -155,11 +178,15 @@ def toolConvertBatch(args):
                 finally:
                     bamfile.close()
             try:
-                converted, qual_info = wt.convertBamReads(bam, args.binsize, args.retdist, args.retthres,
-                                                          mapq=getattr(args, 'mapq', 1),
-                                                          demandPair=getattr(args, 'paired', False))
+                if bam is None:
+                    converted, qual_info = _convert_bounded(args, path, False)
+                else:
+                    converted, qual_info = wt.convertBamReads(bam, args.binsize, args.retdist, args.retthres,
+                                                              mapq=getattr(args, 'mapq', 1),
+                                                              demandPair=getattr(args, 'paired', False))
             finally:
-                bam.close()
+                if bam is not None:
+                    bam.close()
             # what one `convert` call would record: its own infile / outfile, not the batch's list
             one = argparse.Namespace(**{k: v for k, v in vars(args).items() if k not in ('infiles', 'outdir', 'io', 'func')})
             one.infile, one.outfile, one.func = path, out, toolConvert
@@ -577,8 +604,11 @@ def buildParser():
                               'previous read\'s position and mate position')),
         ('-stream', dict(action='store_true', default=argparse.SUPPRESS,
                          help='Read the BAM through the GPU in chunks (memory bounded by the chunk, not the file)')),
+        ('-bounded', dict(action='store_true', default=argparse.SUPPRESS,
+                          help='Read AND filter the BAM chunk by chunk: no per-read arrays, device memory independent of '
+                               'the read count, no limit on the number of reads')),
         ('-chunk', dict(type=int, default=argparse.SUPPRESS,
-                        help='Compressed bytes per chunk of -stream (default: the library\'s)')),
+                        help='Compressed bytes per chunk of -stream / -bounded (default: the library\'s)')),
     )
     p = sub.add_parser('convert', description='Convert and filter a bam file to an npz')
     p.add_argument('infile', type=str, help='Bam input file for conversion')

@@ -723,7 +723,8 @@ class BamChunks(object):
 
 
 #: the reader convertBam and convertbatch open a file with: 'device' (BamReadsDevice; the host reader only for a file
-#: beyond the device budget), 'stream' (BamReadsStream: memory bounded by BAM_STREAM_CHUNK, no budget) or 'host' (BamReads).
+#: beyond the device budget), 'stream' (BamReadsStream: memory bounded by BAM_STREAM_CHUNK, no budget) or 'host' (BamReads);
+#: 'bounded': no reader object at all, convertBam goes through convertBamBounded (openBamReads then opens the streamed reader).
 #: Set by the measurement in profiles/convert_times.json:
 #: 5 million records, whole call 0.285 s through the device reader against 0.517 s (spread 0.024 s) through the host reader.
 CONVERT_READER = 'device'
@@ -734,7 +735,7 @@ def openBamReads(source, threads=8, device=0, stream=None, chunk=0):
     CONVERT_READER == 'stream': the streamed device reader with chunks of `chunk` bytes (<= 0: BAM_STREAM_CHUNK).  Else with
     CONVERT_READER == 'device': the device reader, and the host reader where the file does not fit the device budget
     (E_LIMIT) -- the file's size decides, no option.  With 'host': the host reader."""
-    if stream or (stream is None and CONVERT_READER == 'stream'):
+    if stream or (stream is None and CONVERT_READER in ('stream', 'bounded')):
         return BamReadsStream(source.path if isinstance(source, BamFile) else source, device=device, chunk=chunk)
     if CONVERT_READER == 'device':
         try:
@@ -812,6 +813,86 @@ def convertReads(names, lengths, offsets, pos, mapq, binsize=1000000, minShift=4
                          'post_retro': int(stats[3]), 'pair_fail': int(stats[6])}
 
 
+class ConvertRun(object):
+    """convertReads in resumable form (wc_convert_begin / feed / finish): the reads of the references `names` /
+    `lengths` (header order) arrive in slices, in file order; every slice is filtered and binned as it arrives and only
+    a small carry stays on the device, so the working memory follows the largest slice, not the read count.
+    `feed(offsets, pos, mapq, flag, mate_pos)`: reference r owns [offsets[r], offsets[r+1]) of this slice's numpy arrays
+    (references that are not processed are skipped); with `device_arrays` true the four are device addresses (ints)
+    and the call returns as soon as the slice's kernels are enqueued on `stream`.  `finish()` returns what
+    convertReads returns for the concatenation of the slices."""
+
+    def __init__(self, names, lengths, binsize=1000000, minShift=4, threshold=4, device=0, minMapq=1, demandPair=False):
+        lib = _lib.load()
+        self._handle = None
+        self.demandPair = bool(demandPair)
+        picked = [(r, convert_chromosome_key(name)) for r, name in enumerate(names)]
+        self.picked = [(r, key) for r, key in picked if key is not None]
+        if not self.picked:
+            raise ValueError('ConvertRun: none of the references is a processed chromosome')
+        n_bins = [int(int(lengths[r]) / float(binsize) + 1) for r, _ in self.picked]
+        self.bin_offsets = np.concatenate([[0], np.cumsum(n_bins)]).astype(np.int64)
+        handle = ctypes.c_void_p()
+        _lib.check(lib.wc_convert_begin(_lib.context(device), len(self.picked), float(binsize), int(minShift), int(threshold),
+                                        int(minMapq), int(self.demandPair), _lib.ptr(self.bin_offsets), ctypes.byref(handle)))
+        self._handle = handle
+
+    def feed(self, offsets, pos, mapq, flag=None, mate_pos=None, device_arrays=False, stream=None):
+        lib = _lib.load()
+        if self.demandPair and (flag is None or mate_pos is None):
+            raise ValueError('ConvertRun.feed: demandPair needs the flag and mate_pos arrays')
+        spans = [(int(offsets[r]), int(offsets[r + 1])) for r, _ in self.picked]
+        slice_offsets = np.concatenate([[0], np.cumsum([b - a for a, b in spans])]).astype(np.int64)
+        contiguous = all(spans[i][1] == spans[i + 1][0] for i in range(len(spans) - 1))
+        if device_arrays:
+            if not contiguous:
+                raise ValueError('ConvertRun.feed: device arrays must hold the processed references side by side')
+            lo = spans[0][0]
+            args = [ctypes.c_void_p(int(pos) + 4 * lo), ctypes.c_void_p(int(mapq) + lo),
+                    ctypes.c_void_p(int(flag) + 2 * lo) if self.demandPair else None,
+                    ctypes.c_void_p(int(mate_pos) + 4 * lo) if self.demandPair else None]
+            _lib.check(lib.wc_convert_feed_dev(self._handle, ctypes.c_void_p(stream) if stream else None, *args,
+                                               _lib.ptr(slice_offsets)))
+            return
+
+        def gather(a, dtype):
+            a = np.asarray(a)
+            a = a[spans[0][0]:spans[-1][1]] if contiguous else np.concatenate([a[lo:hi] for lo, hi in spans])
+            return np.ascontiguousarray(a, dtype=dtype)
+        p, q = gather(pos, np.int32), gather(mapq, np.uint8)
+        f = gather(flag, np.uint16) if self.demandPair else None
+        m = gather(mate_pos, np.int32) if self.demandPair else None
+        _lib.check(lib.wc_convert_feed(self._handle, _lib.ptr(p), _lib.ptr(q), _lib.ptr(f), _lib.ptr(m),
+                                       _lib.ptr(slice_offsets)))
+
+    def info(self):
+        """wc_convert_run_info: slices that ran, device bytes held, the bound of the carried positions."""
+        out = np.zeros(8, dtype=np.int64)
+        _lib.check(_lib.load().wc_convert_run_info(self._handle, _lib.ptr(out)))
+        return {'slices': int(out[0]), 'device_bytes': int(out[1]), 'carry_bound': int(out[2])}
+
+    def finish(self):
+        counts = np.zeros(int(self.bin_offsets[-1]), dtype=np.int32)
+        stats = np.zeros(8, dtype=np.int64)
+        _lib.check(_lib.load().wc_convert_finish(self._handle, _lib.ptr(counts), _lib.ptr(stats)))
+        chromosomes = dict((key, None) for key in CONVERT_KEYS)
+        for i, (_, key) in enumerate(self.picked):
+            chromosomes[key] = counts[self.bin_offsets[i]:self.bin_offsets[i + 1]].copy()
+        return chromosomes, {'filter_rmdup': int(stats[0]), 'filter_mapq': int(stats[1]), 'pre_retro': int(stats[2]),
+                             'post_retro': int(stats[3]), 'pair_fail': int(stats[6])}
+
+    def close(self):
+        if self._handle is not None:
+            _lib.load().wc_convert_end(self._handle)
+            self._handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 def convertBamReads(bam, binsize=1000000, minShift=4, threshold=4, device=0, verbose=False, mapq=1, demandPair=False):
     """convertBam on an opened BamReads or BamReadsDevice: (chromosomes, qual_info)."""
     chromosomes, counters = convertReads(bam.names, bam.lengths, bam.offsets, bam.pos, bam.mapq, binsize, minShift,
@@ -822,13 +903,58 @@ def convertBamReads(bam, binsize=1000000, minShift=4, threshold=4, device=0, ver
     return chromosomes, qual_info
 
 
+BOUNDED_INFO_KEYS = ('chunks', 'largest_chunk_compressed_bytes', 'largest_carry_bytes', 'largest_carry_positions',
+                     'peak_device_bytes', 'host_staging_bytes', 'placed_records', 'largest_chunk_inflated_bytes')
+
+
+def convertBamBounded(bamfile, binsize=1000000, minShift=4, threshold=4, device=0, mapq=1, demandPair=False, chunk=0,
+                      verbose=False, info=None):
+    """convertBam by the bounded route (wc_convert_bam_stream_dev): the file goes through the GPU in chunks of at most
+    `chunk` compressed bytes (<= 0: BAM_STREAM_CHUNK) as BamReadsStream reads it, and every chunk's reads are filtered
+    and binned at once (ConvertRun's kernels) and dropped: device memory does not grow with the read count and the
+    number of reads is not limited.  The same (chromosomes, qual_info).  `info`: a dict that receives BOUNDED_INFO_KEYS."""
+    lib = _lib.load()
+    with BamChunks(bamfile, device=-1, chunk=65536) as header:      # the header alone (host stage, ordinary memory)
+        names, lengths = header.names, header.lengths
+    chromosomes = dict((key, None) for key in CONVERT_KEYS)
+    picked = [(r, convert_chromosome_key(name)) for r, name in enumerate(names)]
+    picked = [(r, key) for r, key in picked if key is not None]
+    if not picked:
+        # nothing to bin: the reader alone gives the record counts (and the file's errors)
+        with BamReadsStream(bamfile, device=device, chunk=chunk) as bam:
+            return convertBamReads(bam, binsize, minShift, threshold, device=device, mapq=mapq, demandPair=demandPair)
+    n_bins = [int(int(lengths[r]) / float(binsize) + 1) for r, _ in picked]
+    if verbose:
+        for (r, _), bins in zip(picked, n_bins):
+            print(names[r], 'length:', int(lengths[r]), 'bins:', bins)
+    bin_offsets = np.concatenate([[0], np.cumsum(n_bins)]).astype(np.int64)
+    counts = np.zeros(int(bin_offsets[-1]), dtype=np.int32)
+    stats = np.zeros(8, dtype=np.int64)
+    out = np.zeros(16, dtype=np.int64)
+    refs = np.asarray([r for r, _ in picked], dtype=np.int32)
+    _lib.check(lib.wc_convert_bam_stream_dev(_lib.context(device), None, os.fsencode(bamfile),
+                                             int(chunk) if chunk > 0 else int(BAM_STREAM_CHUNK), _lib.ptr(refs), len(picked),
+                                             float(binsize), int(minShift), int(threshold), int(mapq), int(bool(demandPair)),
+                                             _lib.ptr(bin_offsets), _lib.ptr(counts), _lib.ptr(stats), _lib.ptr(out)))
+    for i, (_, key) in enumerate(picked):
+        chromosomes[key] = counts[bin_offsets[i]:bin_offsets[i + 1]].copy()
+    if info is not None:
+        info.update(zip(BOUNDED_INFO_KEYS, (int(v) for v in out[:8])))
+    return chromosomes, {'mapped': int(out[8]), 'unmapped': int(out[9]), 'no_coordinate': int(out[10]),
+                         'filter_rmdup': int(stats[0]), 'filter_mapq': int(stats[1]), 'pre_retro': int(stats[2]),
+                         'post_retro': int(stats[3]), 'pair_fail': int(stats[6])}
+
+
 def convertBam(bamfile, binsize=1000000, minShift=4, threshold=4, threads=8, device=0, mapq=1, demandPair=False):
     """BAM file -> (dict chromosome -> int32[bins] or None, quality dict), wisetools.py:116-217: `mapq` the
     mapping-quality floor, `demandPair` the paired-end branch (only proper-pair first-in-pair reads take part, a
     duplicate has the previous such read's position and mate position, the rest is counted in pair_fail).  The file
     is read by the device reader (BamReadsDevice; the host reader BamReads with `threads` threads where the file does
     not fit the device budget; the streamed reader where CONVERT_READER says so: openBamReads), the filters run on the
-    GPU."""
+    GPU.  With CONVERT_READER == 'bounded': convertBamBounded (chunks of BAM_STREAM_CHUNK bytes), no reader object."""
+    if CONVERT_READER == 'bounded':
+        return convertBamBounded(bamfile, binsize, minShift, threshold, device=device, mapq=mapq, demandPair=demandPair,
+                                 verbose=True)
     with openBamReads(bamfile, threads=threads, device=device) as bam:
         return convertBamReads(bam, binsize, minShift, threshold, device=device, verbose=True, mapq=mapq,
                                demandPair=demandPair)
