@@ -902,6 +902,7 @@ struct FinishArgs {
     double beta;
     const int *chrom_of_row;
     const int64_t *chrom_off;
+    const int2 *chrom_range;   // per row: [first, end) rows of its chromosome
     int64_t row_begin, row_end;
     int32_t *idx_out;
     double *dist_out;
@@ -1599,9 +1600,12 @@ struct RowSum {
 
 // One workgroup (ps threads = ps / 64 waves) per row; see the header of this section.
 // Xp is the padded float64 image (rows of Sp = 16 n samples, zero padded, 128-byte aligned): every
-// chunk of every candidate row is one aligned cache line, fetched by eight lanes with 16-byte loads
-// (scalar chunk base + 32-bit lane offset: no per-load address arithmetic), and there are no tail
-// cases -- the zero padding adds +0.0 to sums that are >= +0 (or NaN), which is exact.
+// chunk of every candidate row is one aligned cache line, fetched by eight lanes with 16-byte loads,
+// and there are no tail cases -- the zero padding adds +0.0 to sums that are >= +0 (or NaN), which is exact.
+// Addresses of the gathers: the chunk's base is wave uniform and lives in scalar registers, a lane's part is one
+// 32-bit byte offset per load (the image is below 4 GB), made opaque in front of every load: left alone the compiler
+// hoists base + offset out of the chunk loop as eight 64-bit lane addresses and advances each of them per chunk
+// (eight v_lshl_add_u64 per chunk and eight more registers).
 // Wave slab: 64 candidate rows x 128 bytes, the 16-byte pieces of a row XOR-swizzled by
 // f(row) = bits {1, 2, 4} of the row number, which makes the transposing writes (eight lanes
 // fill one row) and the per-candidate reads (sixteen lanes, sixteen rows) conflict free without
@@ -1619,11 +1623,13 @@ __global__ __launch_bounds__(PS_MAX, (SEQ && !GLDS) ? 4 : (SEQ ? 5 : 3)) void k_
     extern __shared__ __attribute__((aligned(16))) double rs_dyn[];
     const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int64_t row = a.row_begin + blockIdx.x;
-    // the row's state, its own values and the first trip's pairs are requested together: three
-    // dependent round trips were a third of a row's life at 100 samples (the pair slots beyond the
-    // row's count hold stale indexes; they are replaced below before anything is gathered)
+    // the row's state, its own values, the first trip's pairs and -- for the output -- the rows of its
+    // chromosome are requested together: one round trip where there were three in front of the chunks and
+    // two more (chrom_of_row -> chrom_off) behind the order (the pair slots beyond the row's count hold
+    // stale indexes; they are replaced below before anything is gathered)
     const int cj_first = p.pairs[row * RMAX + tid];      // tid < ps <= RMAX
     const int R = a.row_stat[row];
+    const int2 own = a.chrom_range[row];                 // [first, end) rows of the row's chromosome
     double *xs = rs_dyn;
     char *slab = reinterpret_cast<char *>(rs_dyn + Sp + w * SLAB_DOUBLES);
     {
@@ -1706,7 +1712,10 @@ __global__ __launch_bounds__(PS_MAX, (SEQ && !GLDS) ? 4 : (SEQ ? 5 : 3)) void k_
             src[q] = ((unsigned int)__shfl(cj, r0 + 8 * q) * (unsigned int)Sp + 2u * (unsigned int)l8) * 8u;
         f64x2 pre[NP];
 #pragma unroll
-        for (int q = 0; q < NP; ++q) pre[q] = *(const f64x2 *)(base + src[q]);
+        for (int q = 0; q < NP; ++q) {
+            asm volatile("" : "+v"(src[q]));                 // (see the header: the base stays in scalar registers)
+            pre[q] = *(const f64x2 *)(base + src[q]);
+        }
         for (int c = 0; c < nchunk; ++c) {
             const f64x2 x2 = *(const f64x2 *)&xs[c * ST_CH + 2 * l8];
             wave_lds_fence();                            // the previous chunk's reads are done
@@ -1722,7 +1731,10 @@ __global__ __launch_bounds__(PS_MAX, (SEQ && !GLDS) ? 4 : (SEQ ? 5 : 3)) void k_
             if (c + 1 < nchunk) {
                 const char *cb = base + (size_t)(c + 1) * (ST_CH * 8);      // wave-uniform chunk base
 #pragma unroll
-                for (int q = 0; q < NP; ++q) pre[q] = *(const f64x2 *)(cb + src[q]);
+                for (int q = 0; q < NP; ++q) {
+                    asm volatile("" : "+v"(src[q]));
+                    pre[q] = *(const f64x2 *)(cb + src[q]);
+                }
             }
             double v[ST_CH];
 #pragma unroll
@@ -1786,8 +1798,7 @@ __global__ __launch_bounds__(PS_MAX, (SEQ && !GLDS) ? 4 : (SEQ ? 5 : 3)) void k_
         }
         wc_sync();
     }
-    const int ch = a.chrom_of_row[row];
-    const int64_t cs = a.chrom_off[ch], ce = a.chrom_off[ch + 1];
+    const int cs = own.x, ce = own.y;
     const int64_t orow = row - a.row_begin;
     for (int t = tid; t < a.k; t += p.ps) {
         int32_t oi = -1;                                 // fewer candidates than k: sentinels (wisetools.py:305-306)
@@ -2615,6 +2626,7 @@ static void finish_args(NewrefState &st, int64_t row_begin, int64_t row_end, int
     a.beta = (double)st.beta;
     a.chrom_of_row = st.chrom_of_row.as<int>();
     a.chrom_off = st.chrom_off_dev.as<int64_t>();
+    a.chrom_range = st.chrom_range.as<int2>();
     a.row_begin = row_begin;
     a.row_end = row_end;
     a.idx_out = idx_out;
