@@ -170,3 +170,8 @@ def test_routes_agree_and_match_oracle(wt, layouts, monkeypatch, layout_id, n_co
         assert np.allclose(np.concatenate(out["results_r"]), np.concatenate(want["results_r"]),
                            rtol=1e-8, atol=1e-10, equal_nan=True)
         assert np.allclose(out["results_cwz"], want["results_cwz"], rtol=1e-8, atol=1e-9, equal_nan=True)
+        if n_comp == 0:                                   # no projection: data = x / mean, every later step is bit-exact
+            assert same_bits(gc_, wc_), (gc_, wc_)
+            assert same_bits(np.concatenate(out["results_z"]), np.concatenate(want["results_z"]))
+            assert same_bits(np.concatenate(out["results_r"]), np.concatenate(want["results_r"]))
+            assert same_bits(out["results_cwz"], want["results_cwz"])
