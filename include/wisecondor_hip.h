@@ -603,6 +603,53 @@ int wc_test_profile(wc_ctx *ctx, int enable);
 int wc_debug_times(wc_ctx *ctx, int block_plus_one, unsigned long long *out64);
 int wc_test_profile_read(wc_ctx *ctx, double out[8]);
 
+/* ---- result files: raw deflate and CRC-32 on the device (testbatch -encoder gpu) ------------
+ * Every row of `src` (n_rows rows of row_bytes bytes, src_stride bytes apart) becomes one complete raw deflate
+ * stream (zlib.decompress(x, -15) reads it): out_len[i] bytes at out + i * out_stride, out_stride >=
+ * wc_deflate_bound(row_bytes); crc[i] is the CRC-32 of the row's input bytes, as zlib.crc32 gives it.  The bytes of
+ * `out` behind a stream are not written.
+ * A row is cut into blocks of wc_deflate_block_bytes() input bytes that are coded independently: a run of equal
+ * bytes is one literal and distance-1 matches of 3 .. 258 bytes (zlib's Z_RLE strategy; matches do not cross a
+ * block cut), the block's own Huffman code (dynamic header; code lengths limited to 15 bits, those of the
+ * code-length alphabet to 7), or a stored block where that is not smaller.  Behind every coded block but the last an
+ * empty stored block pads to a byte boundary.  wc_deflate_bound(n) = n + 10 * (ceil(n / B) + 1).
+ * The streams depend on the input bytes alone.  wc_deflate_rows_dev enqueues on `stream` without synchronising
+ * (scratch memory of `ctx`: one call in flight per context).                                              */
+int wc_deflate_block_bytes(void);
+int64_t wc_deflate_bound(int64_t row_bytes);
+int wc_deflate_rows_dev(wc_ctx *ctx, void *stream, const unsigned char *src, int64_t n_rows, int64_t row_bytes,
+                        int64_t src_stride, unsigned char *out, int64_t out_stride, int64_t *out_len, uint32_t *crc);
+int wc_deflate_rows(wc_ctx *ctx, const unsigned char *src, int64_t n_rows, int64_t row_bytes, int64_t src_stride,
+                    unsigned char *out, int64_t out_stride, int64_t *out_len, uint32_t *crc);
+/* The encoder's Huffman construction, host only (no GPU needed): len_out[s] = code length of symbol s, 0 where
+ * freq[s] == 0, at most `limit` (1 .. 15) bits; n <= 288; a single used symbol gets length 1; with two or more the
+ * Kraft sum is exactly 1; sum(freq * len) is the unlimited Huffman cost wherever that tree fits the limit.     */
+int wc_huffman_lengths(const uint32_t *freq, int n, int limit, uint8_t *len_out);
+
+/* The members results_r.npy / results_z.npy of a result file are a 1-d object array of n_chrom float64 arrays
+ * (protocol 3 pickle, what np.save writes); everything but the values depends on chrom_sizes alone.
+ * wc_results_member_bytes: the member's size (-1: unusable argument).  wc_results_member_template: the member with
+ * zeros for values into tmpl (cap >= that size), and table [3, n_chrom] int64 = the byte offset of every
+ * chromosome's values in the member, its first element in a dense row, its number of elements.  Host only.
+ * wc_results_members_dev: image[row, :member_bytes] = the member of rows[row, :] (DEVICE float64, row_stride
+ * elements apart); tmpl and table are DEVICE copies of the above; image rows are image_stride bytes apart (a
+ * multiple of 4, >= member_bytes, padded with zeros).  Enqueues on `stream`.                               */
+int64_t wc_results_member_bytes(const int64_t *chrom_sizes, int n_chrom);
+int wc_results_member_template(const int64_t *chrom_sizes, int n_chrom, unsigned char *tmpl, int64_t cap, int64_t *table);
+int wc_results_members_dev(wc_ctx *ctx, void *stream, const unsigned char *tmpl, int64_t member_bytes, const int64_t *table,
+                           int n_gaps, const double *rows, int64_t row_stride, int64_t n_rows, unsigned char *image,
+                           int64_t image_stride);
+/* wc_write_test_results with results_z / results_r given as ready-made raw deflate streams (z_len[i] bytes at
+ * z_streams + i * z_stride, CRC-32 z_crc[i] of the member_bytes uncompressed bytes; likewise r): stored with
+ * method 8 as they are.  The other members are encoded as wc_write_test_results encodes them.               */
+int wc_write_test_results_packed(int n_files, int n_threads, const char *const *out_paths, const unsigned char *const *args_npy,
+                                 const int64_t *args_len, const unsigned char *runtime_npy, int64_t runtime_len, double binsize,
+                                 int binsize_is_int, double threshold_z, const unsigned char *z_streams, int64_t z_stride,
+                                 const int64_t *z_len, const uint32_t *z_crc, const unsigned char *r_streams, int64_t r_stride,
+                                 const int64_t *r_len, const uint32_t *r_crc, int64_t member_bytes, const double *cwz, int n_sel,
+                                 const double *calls, const int32_t *n_calls, int max_calls, const double *asdef, int level,
+                                 int *status);
+
 #ifdef __cplusplus
 }
 #endif

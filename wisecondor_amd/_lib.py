@@ -47,6 +47,16 @@ SIGNATURES = {
     "wc_read_sample_lengths": (_i32, [_vp, _i32, _i32, _i32, _dbl, _vp, _vp, _vp]),
     "wc_write_test_results": (_i32, [_i32, _i32, _vp, _vp, _vp, _vp, _i64, _dbl, _i32, _dbl, _vp, _i32, _vp, _vp, _i64, _vp,
                                      _i32, _vp, _vp, _i32, _vp, _i32, _vp]),
+    "wc_write_test_results_packed": (_i32, [_i32, _i32, _vp, _vp, _vp, _vp, _i64, _dbl, _i32, _dbl, _vp, _i64, _vp, _vp, _vp, _i64,
+                                            _vp, _vp, _i64, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _vp]),
+    "wc_results_member_bytes": (_i64, [_vp, _i32]),
+    "wc_results_member_template": (_i32, [_vp, _i32, _vp, _i64, _vp]),
+    "wc_results_members_dev": (_i32, [_vp, _vp, _vp, _i64, _vp, _i32, _vp, _i64, _i64, _vp, _i64]),
+    "wc_deflate_block_bytes": (_i32, []),
+    "wc_deflate_bound": (_i64, [_i64]),
+    "wc_deflate_rows_dev": (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp]),
+    "wc_deflate_rows": (_i32, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp]),
+    "wc_huffman_lengths": (_i32, [_vp, _i32, _i32, _vp]),
     "wc_bam_open": (_i32, [_c.c_char_p, _i32, _vp]),
     "wc_bam_info": (_i32, [_vp, _vp]),
     "wc_bam_refs": (_i32, [_vp, _vp, _i64, _vp, _vp]),

@@ -91,6 +91,7 @@ struct wc_ctx {
     NewrefState nr;
     TestState ts;
     wc::DevBuf tmp_a, tmp_b, tmp_c, tmp_d;  // host-pointer API staging
+    wc::DevBuf df_scratch, df_meta;         // deflate.hip: the blocks' slots before they are gathered; their lengths and CRC shares
     void *pinned = nullptr;
     size_t pinned_bytes = 0;
     int64_t last_stats[8] = {0};
@@ -140,7 +141,7 @@ struct wc_ctx {
                 &ts.reg_flag, &ts.rs, &ts.jobs_a, &ts.jobs_b, &ts.job_cnt, &ts.partial, &ts.cbound, &ts.cuts, &ts.job_res, &ts.hot,
                 &ts.cand, &ts.cand_cnt, &ts.seg, &ts.out_val, &ts.out_x, &ts.out_y, &ts.out_n,
                 &ts.whole, &ts.effect, &ts.misc, &ts.misc2, &ts.reduce_tmp, &ts.win_bits, &ts.bit_off, &ts.pairs_a, &ts.pairs_b, &ts.cut_vals, &ts.prof_work, &ts.sd_fail, &ts.walk_hot, &prep.eig_ws,
-                &cv.tab, &cv.tiles, &cv.kpos, &cv.cls};
+                &cv.tab, &cv.tiles, &cv.kpos, &cv.cls, &df_scratch, &df_meta};
     }
 };
 

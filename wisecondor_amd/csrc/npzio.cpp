@@ -496,7 +496,9 @@ void pk_reconstruct(std::string &s) {
     s.push_back('C'); s.push_back(1); s.push_back('b');         // b'b'
     s.push_back((char)0x87); s.push_back('R');
 }
-std::string npy_object_of_f64(const double *row, const int64_t *sizes, int n) {
+// row == nullptr: zeros in place of the values (the members' framing, wc_results_member_template); gaps_at, when given,
+// receives the member offset of every chromosome's values
+std::string npy_object_of_f64(const double *row, const int64_t *sizes, int n, std::vector<int64_t> *gaps_at = nullptr) {
     std::string p;
     p.push_back((char)0x80); p.push_back(3);
     pk_reconstruct(p);
@@ -515,14 +517,20 @@ std::string npy_object_of_f64(const double *row, const int64_t *sizes, int n) {
         pk_int(p, sizes[c]); p.push_back((char)0x85);
         pk_dtype(p, "f8", "<", 0);
         p.push_back((char)0x89);
-        p.push_back('B'); put32(p, (uint32_t)(sizes[c] * 8)); p.append((const char *)(row + at), (size_t)sizes[c] * 8);
+        p.push_back('B'); put32(p, (uint32_t)(sizes[c] * 8));
+        if (gaps_at) gaps_at->push_back((int64_t)p.size());
+        if (row) p.append((const char *)(row + at), (size_t)sizes[c] * 8);
+        else p.append((size_t)sizes[c] * 8, '\0');
         p.push_back('t'); p.push_back('b');
         at += sizes[c];
     }
     p.push_back('e');
     p.push_back('t'); p.push_back('b');
     p.push_back('.');
-    return npy_header("|O", "(" + std::to_string(n) + ",)") + p;
+    const std::string head = npy_header("|O", "(" + std::to_string(n) + ",)");
+    if (gaps_at)
+        for (int64_t &g : *gaps_at) g += (int64_t)head.size();
+    return head + p;
 }
 
 struct ZipWriter {
@@ -553,22 +561,29 @@ struct ZipWriter {
             method = 8;
         }
         const std::string &body = method ? comp : data;
+        emit(name, method, crc, body.data(), body.size(), data.size());
+        return true;
+    }
+    // a member whose deflate stream and CRC-32 were made elsewhere (the GPU encoder)
+    void add_packed(const std::string &name, const unsigned char *stream, size_t csize, uint32_t crc, size_t usize) {
+        emit(name, 8, crc, (const char *)stream, csize, usize);
+    }
+    void emit(const std::string &name, int method, uint32_t crc, const char *body, size_t csize, size_t usize) {
         const uint32_t offset = (uint32_t)out.size();
         put32(out, 0x04034b50u); put16(out, 20); put16(out, 0); put16(out, (uint16_t)method);
         put16(out, 0); put16(out, 0x21);               // time 00:00:00, date 1980-01-01
-        put32(out, crc); put32(out, (uint32_t)body.size()); put32(out, (uint32_t)data.size());
+        put32(out, crc); put32(out, (uint32_t)csize); put32(out, (uint32_t)usize);
         put16(out, (uint16_t)name.size()); put16(out, 0);
         out += name;
-        out += body;
+        out.append(body, csize);
         put32(central, 0x02014b50u); put16(central, 20); put16(central, 20); put16(central, 0); put16(central, (uint16_t)method);
         put16(central, 0); put16(central, 0x21);
-        put32(central, crc); put32(central, (uint32_t)body.size()); put32(central, (uint32_t)data.size());
+        put32(central, crc); put32(central, (uint32_t)csize); put32(central, (uint32_t)usize);
         put16(central, (uint16_t)name.size()); put16(central, 0); put16(central, 0); put16(central, 0); put16(central, 0);
         put32(central, 0x01800000u);                    // external attributes: a regular file, rw-------
         put32(central, offset);
         central += name;
         ++count;
-        return true;
     }
     bool finish(const char *path) {
         const uint32_t cd_off = (uint32_t)out.size(), cd_len = (uint32_t)central.size();
@@ -592,6 +607,54 @@ void run_pool(int n, int threads, F work) {
     for (int t = 1; t < threads; ++t) pool.emplace_back(loop);
     loop();
     for (std::thread &t : pool) t.join();
+}
+
+// One `test` output file.  The small members are encoded here; `big(zw)` adds results_r.npy and results_z.npy at their
+// place in the reference's key order: from the float64 rows (wc_write_test_results) or from ready-made deflate streams
+// (wc_write_test_results_packed).
+struct ResultSmall {
+    const unsigned char *args_npy;
+    int64_t args_len;
+    const unsigned char *runtime_npy;
+    int64_t runtime_len;
+    double binsize;
+    int binsize_is_int;
+    double threshold_z;
+    const double *cwz;
+    int n_sel;
+    const double *calls;    // this file's rows
+    int n_calls;
+    double asdef;
+};
+template <class Big>
+int write_result_file(const char *path, int level, const ResultSmall &s, Big big) {
+    try {
+        ZipWriter zw(level);
+        const std::vector<int64_t> none;
+        bool ok = zw.add("arguments.npy", std::string((const char *)s.args_npy, (size_t)s.args_len));
+        ok = ok && zw.add("runtime.npy", std::string((const char *)s.runtime_npy, (size_t)s.runtime_len));
+        if (s.binsize_is_int) {
+            // the reference stores referenceFile['binsize'].item() unchanged: a Python int becomes an int64 array
+            const int64_t bi = (int64_t)s.binsize;
+            std::string m = npy_header("<i8", "()");
+            m.append((const char *)&bi, 8);
+            ok = ok && zw.add("binsize.npy", m);
+        } else {
+            ok = ok && zw.add("binsize.npy", npy_f64(&s.binsize, none));
+        }
+        ok = ok && big(zw);
+        ok = ok && zw.add("results_cwz.npy", npy_f64(s.cwz, {(int64_t)s.n_sel}));
+        // no calls: the reference stores np.array([]) -- float64, shape (0,)
+        if (s.n_calls > 0) ok = ok && zw.add("results_calls.npy", npy_f64(s.calls, {(int64_t)s.n_calls, 5}));
+        else ok = ok && zw.add("results_calls.npy", npy_f64(s.calls, {0}));
+        ok = ok && zw.add("threshold_z.npy", npy_f64(&s.threshold_z, none));
+        ok = ok && zw.add("asdef.npy", npy_f64(&s.asdef, none));
+        const double aasdef = s.asdef * s.threshold_z;
+        ok = ok && zw.add("aasdef.npy", npy_f64(&aasdef, none));
+        return ok && zw.finish(path) ? WC_OK : WC_NPZ_IO;
+    } catch (...) {
+        return WC_NPZ_IO;
+    }
 }
 
 }  // namespace
@@ -643,37 +706,71 @@ int wc_write_test_results(int n_files, int n_threads, const char *const *out_pat
         !cwz || !calls || !n_calls || !asdef || !status)
         return WC_E_ARG;
     run_pool(n_files, n_threads, [&](int i) {
-        int rc = WC_OK;
-        try {
-            ZipWriter zw(level);
-            const std::vector<int64_t> none;
-            bool ok = zw.add("arguments.npy", std::string((const char *)args_npy[i], (size_t)args_len[i]));
-            ok = ok && zw.add("runtime.npy", std::string((const char *)runtime_npy, (size_t)runtime_len));
-            if (binsize_is_int) {
-                // the reference stores referenceFile['binsize'].item() unchanged: a Python int becomes an int64 array
-                const int64_t bi = (int64_t)binsize;
-                std::string m = npy_header("<i8", "()");
-                m.append((const char *)&bi, 8);
-                ok = ok && zw.add("binsize.npy", m);
-            } else {
-                ok = ok && zw.add("binsize.npy", npy_f64(&binsize, none));
-            }
-            ok = ok && zw.add("results_r.npy", npy_object_of_f64(r + (int64_t)i * row_stride, chrom_sizes, n_chrom), true);
-            ok = ok && zw.add("results_z.npy", npy_object_of_f64(z + (int64_t)i * row_stride, chrom_sizes, n_chrom), true);
-            ok = ok && zw.add("results_cwz.npy", npy_f64(cwz + (int64_t)i * n_sel, {(int64_t)n_sel}));
-            const int nc = n_calls[i] < max_calls ? n_calls[i] : max_calls;
-            // no calls: the reference stores np.array([]) -- float64, shape (0,)
-            if (nc > 0) ok = ok && zw.add("results_calls.npy", npy_f64(calls + (int64_t)i * max_calls * 5, {(int64_t)nc, 5}));
-            else ok = ok && zw.add("results_calls.npy", npy_f64(calls, {0}));
-            ok = ok && zw.add("threshold_z.npy", npy_f64(&threshold_z, none));
-            ok = ok && zw.add("asdef.npy", npy_f64(&asdef[i], none));
-            const double aasdef = asdef[i] * threshold_z;
-            ok = ok && zw.add("aasdef.npy", npy_f64(&aasdef, none));
-            if (!ok || !zw.finish(out_paths[i])) rc = WC_NPZ_IO;
-        } catch (...) {
-            rc = WC_NPZ_IO;
+        const ResultSmall small = {args_npy[i], args_len[i], runtime_npy, runtime_len, binsize, binsize_is_int, threshold_z,
+                                   cwz + (int64_t)i * n_sel, n_sel, calls + (int64_t)i * max_calls * 5,
+                                   n_calls[i] < max_calls ? n_calls[i] : max_calls, asdef[i]};
+        status[i] = write_result_file(out_paths[i], level, small, [&](ZipWriter &zw) {
+            return zw.add("results_r.npy", npy_object_of_f64(r + (int64_t)i * row_stride, chrom_sizes, n_chrom), true) &&
+                   zw.add("results_z.npy", npy_object_of_f64(z + (int64_t)i * row_stride, chrom_sizes, n_chrom), true);
+        });
+    });
+    return WC_OK;
+}
+
+int64_t wc_results_member_bytes(const int64_t *chrom_sizes, int n_chrom) {
+    if (!chrom_sizes || n_chrom <= 0) return -1;
+    for (int c = 0; c < n_chrom; ++c)
+        if (chrom_sizes[c] < 0) return -1;
+    try {
+        return (int64_t)npy_object_of_f64(nullptr, chrom_sizes, n_chrom).size();
+    } catch (...) {
+        return -1;
+    }
+}
+
+int wc_results_member_template(const int64_t *chrom_sizes, int n_chrom, unsigned char *tmpl, int64_t cap, int64_t *table) {
+    if (!chrom_sizes || n_chrom <= 0 || !tmpl || !table) return WC_E_ARG;
+    for (int c = 0; c < n_chrom; ++c)
+        if (chrom_sizes[c] < 0) return WC_E_ARG;
+    try {
+        std::vector<int64_t> gaps;
+        const std::string m = npy_object_of_f64(nullptr, chrom_sizes, n_chrom, &gaps);
+        if ((int64_t)m.size() > cap || (int)gaps.size() != n_chrom) return WC_E_ARG;
+        memcpy(tmpl, m.data(), m.size());
+        int64_t at = 0;
+        for (int c = 0; c < n_chrom; ++c) {
+            table[c] = gaps[(size_t)c];
+            table[n_chrom + c] = at;
+            table[2 * n_chrom + c] = chrom_sizes[c];
+            at += chrom_sizes[c];
         }
-        status[i] = rc;
+    } catch (...) {
+        return WC_E_INTERNAL;
+    }
+    return WC_OK;
+}
+
+int wc_write_test_results_packed(int n_files, int n_threads, const char *const *out_paths, const unsigned char *const *args_npy,
+                                 const int64_t *args_len, const unsigned char *runtime_npy, int64_t runtime_len, double binsize,
+                                 int binsize_is_int, double threshold_z, const unsigned char *z_streams, int64_t z_stride,
+                                 const int64_t *z_len, const uint32_t *z_crc, const unsigned char *r_streams, int64_t r_stride,
+                                 const int64_t *r_len, const uint32_t *r_crc, int64_t member_bytes, const double *cwz, int n_sel,
+                                 const double *calls, const int32_t *n_calls, int max_calls, const double *asdef, int level,
+                                 int *status) {
+    if (!out_paths || n_files < 0 || !args_npy || !args_len || !runtime_npy || !z_streams || !z_len || !z_crc || !r_streams ||
+        !r_len || !r_crc || member_bytes < 0 || member_bytes > 0xFFFFFFFFll || !cwz || !calls || !n_calls || !asdef || !status)
+        return WC_E_ARG;
+    for (int i = 0; i < n_files; ++i)
+        if (z_len[i] < 0 || z_len[i] > z_stride || r_len[i] < 0 || r_len[i] > r_stride) return WC_E_ARG;
+    run_pool(n_files, n_threads, [&](int i) {
+        const ResultSmall small = {args_npy[i], args_len[i], runtime_npy, runtime_len, binsize, binsize_is_int, threshold_z,
+                                   cwz + (int64_t)i * n_sel, n_sel, calls + (int64_t)i * max_calls * 5,
+                                   n_calls[i] < max_calls ? n_calls[i] : max_calls, asdef[i]};
+        status[i] = write_result_file(out_paths[i], level, small, [&](ZipWriter &zw) {
+            zw.add_packed("results_r.npy", r_streams + (int64_t)i * r_stride, (size_t)r_len[i], r_crc[i], (size_t)member_bytes);
+            zw.add_packed("results_z.npy", z_streams + (int64_t)i * z_stride, (size_t)z_len[i], z_crc[i], (size_t)member_bytes);
+            return true;
+        });
     });
     return WC_OK;
 }

@@ -118,41 +118,107 @@ def _object_npy(obj):
     return b'\x93NUMPY\x01\x00' + len(header).to_bytes(2, 'little') + header + body
 
 
-def write_results(out_paths, per_file_args, runtime, binsize, threshold_z, chrom_sizes, z, r, cwz, calls, n_calls,
-                  asdef, threads=8, level=1):
-    """One `test` output file per row through the library's C++ thread pool (wc_write_test_results):
-    the keys, dtypes and shapes of writeTestOutput's files (SURVEY.md App. B).  z, r: float64
-    [n, sum(chrom_sizes)]; cwz [n, n_sel]; calls [n, max_calls, 5]; n_calls int32 [n]; asdef [n]."""
+def check_encoder(encoder, level):
+    """'host' or 'gpu'; the GPU encoder is one strategy (run-length matches, a Huffman code per block: what the host
+    writer does at level 1), not a zlib level, so it goes with -ziplevel 1 only."""
+    if encoder not in ('host', 'gpu'):
+        raise ValueError("encoder: 'host' or 'gpu', not %r" % (encoder,))
+    if encoder == 'gpu' and int(level) != 1:
+        raise ValueError('-encoder gpu writes run-length deflate, which is -ziplevel 1; -ziplevel %d (%s) is the host '
+                         "encoder's" % (int(level), 'stored' if int(level) == 0 else 'zlib\'s string search'))
+    return encoder
+
+
+def pack_results(members, z, r, ctx=None):
+    """results_z / results_r of a batch as ready-made zip members, on the device: the .npy images of the rows of the
+    device tensors z and r (wt.ResultMembers), deflated row by row (wt.deflateRows).  Returns the six device tensors
+    (z streams, lengths, crcs, r streams, lengths, crcs)."""
+    return wt.deflateRows(members.image(z, ctx=ctx), ctx=ctx) + wt.deflateRows(members.image(r, ctx=ctx), ctx=ctx)
+
+
+def _host_array(a):
+    return a if isinstance(a, np.ndarray) else np.ascontiguousarray(a.detach().cpu().numpy())
+
+
+def _native_write(entry, out_paths, per_file_args, runtime, binsize, threshold_z, big, cwz, calls, n_calls, asdef, threads,
+                  level):
+    """wc_write_test_results / wc_write_test_results_packed: `big` is what the entry takes for results_z / results_r."""
     n = len(out_paths)
-    if n == 0:
-        return
-    sizes = np.ascontiguousarray(chrom_sizes, dtype=np.int64)
     blobs = [_object_npy(vars(a) if not isinstance(a, dict) else a) for a in per_file_args]
     blob_ptrs = (ctypes.c_char_p * n)()
     blob_ptrs[:] = blobs
     lens = np.array([len(b) for b in blobs], dtype=np.int64)
     rt = _object_npy(runtime)
     status = np.zeros(n, dtype=np.int32)
-    for a in (z, r, cwz, calls, asdef):
+    for a in (cwz, calls, asdef):
         assert a.dtype == np.float64 and a.flags['C_CONTIGUOUS']
-    assert n_calls.dtype == np.int32 and z.shape[1] == int(sizes.sum())
-    _lib.check(_lib.load().wc_write_test_results(
+    assert n_calls.dtype == np.int32
+    _lib.check(entry(
         n, int(threads), _c_strings(out_paths), blob_ptrs, _lib.ptr(lens), rt, len(rt), float(binsize),
-        int(isinstance(binsize, (int, np.integer)) and not isinstance(binsize, bool)), float(threshold_z), _lib.ptr(sizes), len(sizes), _lib.ptr(z), _lib.ptr(r), z.shape[1], _lib.ptr(cwz),
+        int(isinstance(binsize, (int, np.integer)) and not isinstance(binsize, bool)), float(threshold_z), *big, _lib.ptr(cwz),
         cwz.shape[1], _lib.ptr(calls), _lib.ptr(n_calls), calls.shape[1], _lib.ptr(asdef), int(level), _lib.ptr(status)))
     bad = np.nonzero(status)[0]
     if len(bad):
         raise IOError('could not write %d result file(s), first: %s' % (len(bad), out_paths[bad[0]]))
 
 
+def write_packed(out_paths, per_file_args, runtime, binsize, threshold_z, member_bytes, packed, cwz, calls, n_calls, asdef,
+                 threads=8, level=1):
+    """write_results with results_z / results_r as the host copies of pack_results' output (uint8 [n, stride] streams,
+    int64 lengths, CRCs): wc_write_test_results_packed stores them as they are."""
+    n = len(out_paths)
+    if n == 0:
+        return
+    zs, zl, zc, rs, rl, rc = packed
+    for s, l, c in ((zs, zl, zc), (rs, rl, rc)):
+        assert s.dtype == np.uint8 and s.ndim == 2 and s.flags['C_CONTIGUOUS'] and s.shape[0] >= n
+        assert l.dtype == np.int64 and len(l) >= n and c.dtype.itemsize == 4 and len(c) >= n
+    big = (_lib.ptr(zs), zs.shape[1], _lib.ptr(zl), _lib.ptr(zc), _lib.ptr(rs), rs.shape[1], _lib.ptr(rl), _lib.ptr(rc),
+           int(member_bytes))
+    _native_write(_lib.load().wc_write_test_results_packed, out_paths, per_file_args, runtime, binsize, threshold_z, big,
+                  cwz, calls, n_calls, asdef, threads, level)
+
+
+def write_results(out_paths, per_file_args, runtime, binsize, threshold_z, chrom_sizes, z, r, cwz, calls, n_calls,
+                  asdef, threads=8, level=1, encoder='host'):
+    """One `test` output file per row through the library's C++ thread pool (wc_write_test_results):
+    the keys, dtypes and shapes of writeTestOutput's files (SURVEY.md App. B).  z, r: float64
+    [n, sum(chrom_sizes)]; cwz [n, n_sel]; calls [n, max_calls, 5]; n_calls int32 [n]; asdef [n].
+    encoder='gpu': z and r are tensors on the GPU and are deflated there (pack_results); only the streams come to the
+    host.  The files load identical; their results_z / results_r members are coded differently."""
+    n = len(out_paths)
+    if n == 0:
+        return
+    if check_encoder(encoder, level) == 'gpu':
+        members = wt.ResultMembers(chrom_sizes, z.device)
+        packed = tuple(_host_array(t) for t in pack_results(members, z, r))
+        write_packed(out_paths, per_file_args, runtime, binsize, threshold_z, members.member_bytes, packed,
+                     _host_array(cwz), _host_array(calls), _host_array(n_calls), _host_array(asdef), threads, level)
+        return
+    sizes = np.ascontiguousarray(chrom_sizes, dtype=np.int64)
+    for a in (z, r):
+        assert a.dtype == np.float64 and a.flags['C_CONTIGUOUS']
+    assert z.shape[1] == int(sizes.sum())
+    big = (_lib.ptr(sizes), len(sizes), _lib.ptr(z), _lib.ptr(r), z.shape[1])
+    _native_write(_lib.load().wc_write_test_results, out_paths, per_file_args, runtime, binsize, threshold_z, big, cwz, calls,
+                  n_calls, asdef, threads, level)
+
+
 class _Staging(object):
     """Pinned host buffers of one in-flight batch."""
 
-    def __init__(self, torch, batch, n_total, n_sel, max_calls):
+    def __init__(self, torch, batch, n_total, n_sel, max_calls, packed_stride=0):
         pin = dict(pin_memory=True)
         self.counts = torch.zeros((batch, n_total), dtype=torch.int32, **pin)
-        self.z = torch.empty((batch, n_total), dtype=torch.float64, **pin)
-        self.r = torch.empty((batch, n_total), dtype=torch.float64, **pin)
+        if packed_stride:
+            # the GPU encoder's route: the deflate streams of the two big members, their lengths and CRCs -- no z, no r
+            self.streams = [torch.empty((batch * packed_stride,), dtype=torch.uint8, **pin) for _ in range(2)]
+            self.lengths = [torch.empty((batch,), dtype=torch.int64, **pin) for _ in range(2)]
+            self.crcs = [torch.empty((batch,), dtype=torch.int32, **pin) for _ in range(2)]
+            self.packed = None
+        else:
+            self.z = torch.empty((batch, n_total), dtype=torch.float64, **pin)
+            self.r = torch.empty((batch, n_total), dtype=torch.float64, **pin)
         self.cwz = torch.empty((batch, n_sel), dtype=torch.float64, **pin)
         self.calls = torch.empty((batch, max_calls, 5), dtype=torch.float64, **pin)
         self.n_calls = torch.empty((batch,), dtype=torch.int32, **pin)
@@ -179,7 +245,9 @@ def run_testbatch(reference, paths, outdir, threshold, args, writer=None, max_ca
     """`test` for every file of `paths` in GPU batches of args.batch samples.
 
     Pipeline per batch: decode (C++ thread pool) -> pinned counts -> H2D -> wc_test_batch_dev ->
-    D2H into pinned results -> encode + write (C++ thread pool).  The decode of batch i+1 and the
+    D2H into pinned results -> encode + write (C++ thread pool).  With args.encoder == 'gpu' the two big members
+    (results_z, results_r) are assembled, deflated and CRC-summed on the device (pack_results) and only their streams
+    come to the host; the thread pool then encodes the small members and writes.  The decode of batch i+1 and the
     writes of batch i-1 overlap the GPU work of batch i (two Python helper threads that only wait on
     the native calls, which release the GIL).  Returns timing figures (files, wall_s, files_per_s,
     gpu_s).  `writer(path, per_sample_args, result)`, when given, stores each result file in Python
@@ -199,8 +267,13 @@ def run_testbatch(reference, paths, outdir, threshold, args, writer=None, max_ca
     batch = max(1, min(int(args.batch), n, 60000 // max(1, len(sel))))
     io_threads = max(1, int(getattr(args, 'io', 8)))
     level = int(getattr(args, 'ziplevel', 1))
+    on_gpu = check_encoder(getattr(args, 'encoder', 'host'), level) == 'gpu'
+    if on_gpu and writer is not None:
+        raise ValueError('the GPU encoder writes through the native writer: no `writer`')
     outs = output_names(paths, outdir)
-    stage = [_Staging(torch, batch, reference.n_total, len(sel), max_calls) for _ in range(2)]
+    members = wt.ResultMembers(sizes, dev) if on_gpu else None
+    packed_stride = wt.deflateBound(members.member_bytes) if on_gpu else 0
+    stage = [_Staging(torch, batch, reference.n_total, len(sel), max_calls, packed_stride) for _ in range(2)]
     dev_counts = torch.zeros((batch, reference.n_total), dtype=torch.int32, device=dev)
 
     def new_batch(counts, calls_cap):
@@ -227,6 +300,13 @@ def run_testbatch(reference, paths, outdir, threshold, args, writer=None, max_ca
             one.infile = name
             one.outfile = outs[at + i]
             per_file.append(one)
+        if on_gpu:
+            st.write_done = helpers.submit(
+                write_packed, outs[at:at + ns], per_file, runtime, reference.binsize, threshold, members.member_bytes,
+                st.packed, st.cwz.numpy()[:ns], st.calls.numpy()[:ns], st.n_calls.numpy()[:ns], st.asdef.numpy()[:ns],
+                io_threads, level)
+            pending.append(st.write_done)
+            return
         if writer is None:
             st.write_done = helpers.submit(
                 write_results, outs[at:at + ns], per_file, runtime, reference.binsize, threshold, sizes,
@@ -282,8 +362,23 @@ def run_testbatch(reference, paths, outdir, threshold, args, writer=None, max_ca
             torch.cuda.synchronize()
             run_s += time.time() - t1
             t2 = time.time()
-            st.z[:ns].copy_(run.results_z, non_blocking=True)
-            st.r[:ns].copy_(run.results_r, non_blocking=True)
+            if on_gpu:
+                # encode on the device; the lengths first (how much of every stream there is to copy), then the streams
+                # cut to the longest, the rows packed
+                dev_packed = pack_results(members, run.results_z, run.results_r, ctx=reference.ctx)
+                for m in (0, 1):
+                    st.lengths[m][:ns].copy_(dev_packed[3 * m + 1], non_blocking=True)
+                    st.crcs[m][:ns].copy_(dev_packed[3 * m + 2], non_blocking=True)
+                torch.cuda.synchronize()
+                st.packed = ()
+                for m in (0, 1):
+                    longest = max(1, int(st.lengths[m][:ns].max()))
+                    host = st.streams[m][:ns * longest].view(ns, longest)
+                    host.copy_(dev_packed[3 * m][:, :longest], non_blocking=True)
+                    st.packed += (host.numpy(), st.lengths[m].numpy()[:ns], st.crcs[m].numpy()[:ns])
+            else:
+                st.z[:ns].copy_(run.results_z, non_blocking=True)
+                st.r[:ns].copy_(run.results_r, non_blocking=True)
             st.cwz[:ns].copy_(run.cwz, non_blocking=True)
             st.calls[:ns].copy_(run.calls, non_blocking=True)
             st.n_calls[:ns].copy_(run.n_calls, non_blocking=True)

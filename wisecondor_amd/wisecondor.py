@@ -529,7 +529,10 @@ def toolTest(args):
 def toolTestBatch(args):
     """`testbatch samples... outdir reference` (build-only): the same numbers and the same
     per-sample files as one `test` per sample, in GPU batches with pooled file decode / encode.
-    `-gpus N` (or a torchrun environment) shards the sample list over N processes."""
+    `-gpus N` (or a torchrun environment) shards the sample list over N processes.  `-encoder gpu` deflates the two
+    large members of every result file on the GPU (ingest.pack_results); it is refused with any -ziplevel but 1."""
+    from . import ingest
+    ingest.check_encoder(getattr(args, 'encoder', 'host'), getattr(args, 'ziplevel', 1))
     world_env = int(os.environ.get('WORLD_SIZE', '1'))
     if world_env == 1 and _rank_count(args) > 1:
         from . import ranks as rk
@@ -684,6 +687,10 @@ def buildParser():
     p.add_argument('-ziplevel', type=int, default=1,
                    help='zlib level of the result files (0 = stored, 1 = run-length deflate: the same size at a third of '
                         'the time on these arrays, 6 = what np.savez_compressed uses)')
+    # build-only; SUPPRESS keeps it out of the namespace (and the `arguments` of the result files) unless it is given
+    p.add_argument('-encoder', choices=('host', 'gpu'), default=argparse.SUPPRESS,
+                   help='who deflates results_z / results_r: the I/O threads (host, the default) or the GPU, from which '
+                        'then only the compressed streams are copied (gpu; goes with -ziplevel 1 only)')
     for flag, settings in _TEST_OPTIONS:
         p.add_argument(flag, **settings)
     p.set_defaults(func=toolTestBatch)

@@ -958,3 +958,90 @@ def convertBam(bamfile, binsize=1000000, minShift=4, threshold=4, threads=8, dev
     with openBamReads(bamfile, threads=threads, device=device) as bam:
         return convertBamReads(bam, binsize, minShift, threshold, device=device, verbose=True, mapq=mapq,
                                demandPair=demandPair)
+
+
+# ------------------------------------------------------- result files: deflate on the GPU ----
+def deflateBound(row_bytes):
+    """Most bytes one row of `row_bytes` bytes takes as a stream of deflateRows (wc_deflate_bound)."""
+    return int(_lib.load().wc_deflate_bound(int(row_bytes)))
+
+
+def deflateRows(rows, device=0, ctx=None, out_stride=None):
+    """Every row of `rows` as one raw deflate stream (zlib.decompress(x, -15) reads it) and its CRC-32, made on the
+    GPU (wc_deflate_rows: run-length matches and a Huffman code per block of wc_deflate_block_bytes() bytes).
+    rows: 2-d, a numpy array (any dtype; the rows' bytes in memory order, rows may be strided) or a torch tensor on the
+    GPU.  Returns (streams uint8 [n, out_stride], lengths int64 [n], crcs uint32 [n]) of the same kind: numpy arrays, or
+    tensors that stay on the device (crcs then int32: the same 32 bits).  Row i is streams[i, :lengths[i]]; the bytes
+    behind it mean nothing.  out_stride defaults to deflateBound(bytes per row)."""
+    lib = _lib.load()
+    if isinstance(rows, np.ndarray):
+        assert rows.ndim == 2 and (rows.shape[1] == 0 or rows.strides[1] == rows.itemsize) and rows.strides[0] >= 0
+        n, row_bytes = rows.shape[0], rows.shape[1] * rows.itemsize
+        src_stride = rows.strides[0] if n > 1 else row_bytes
+        assert src_stride >= row_bytes
+        stride = int(out_stride or deflateBound(row_bytes))
+        streams = np.zeros((n, stride), dtype=np.uint8)
+        lengths = np.zeros(n, dtype=np.int64)
+        crcs = np.zeros(n, dtype=np.uint32)
+        if n:
+            _lib.check(lib.wc_deflate_rows(ctx or _lib.context(device), ctypes.c_void_p(rows.ctypes.data), n, row_bytes,
+                                           src_stride, _lib.ptr(streams), stride, _lib.ptr(lengths), _lib.ptr(crcs)))
+        return streams, lengths, crcs
+    import torch
+    assert rows.is_cuda and rows.dim() == 2 and (rows.shape[1] == 0 or rows.stride(1) == 1)
+    item = rows.element_size()
+    n, row_bytes = int(rows.shape[0]), int(rows.shape[1]) * item
+    src_stride = int(rows.stride(0)) * item if n > 1 else row_bytes
+    assert src_stride >= row_bytes
+    stride = int(out_stride or deflateBound(row_bytes))
+    dev = rows.device
+    streams = torch.empty((n, stride), dtype=torch.uint8, device=dev)
+    lengths = torch.empty((n,), dtype=torch.int64, device=dev)
+    crcs = torch.empty((n,), dtype=torch.int32, device=dev)
+    if n:
+        with torch.cuda.device(dev):
+            _lib.check(lib.wc_deflate_rows_dev(ctx or _lib.context(dev.index or 0), torch.cuda.current_stream().cuda_stream,
+                                               rows.data_ptr(), n, row_bytes, src_stride, streams.data_ptr(), stride,
+                                               lengths.data_ptr(), crcs.data_ptr()))
+    return streams, lengths, crcs
+
+
+class ResultMembers(object):
+    """The framing of the members results_r.npy / results_z.npy for one set of chromosome sizes, on the device: the
+    member with gaps for the values (wc_results_member_template), uploaded once.  image(rows) writes the members of a
+    batch of dense float64 rows [n, sum(chrom_sizes)] that live on the device (wc_results_members_dev)."""
+
+    def __init__(self, chrom_sizes, device):
+        import torch
+        lib = _lib.load()
+        sizes = np.ascontiguousarray(chrom_sizes, dtype=np.int64)
+        self.n_total = int(sizes.sum())
+        self.n_gaps = len(sizes)
+        self.member_bytes = int(lib.wc_results_member_bytes(_lib.ptr(sizes), len(sizes)))
+        if self.member_bytes < 0 or self.n_gaps > 64:
+            raise ValueError('result members: unusable chromosome sizes')
+        tmpl = np.zeros(self.member_bytes, dtype=np.uint8)
+        table = np.zeros(3 * len(sizes), dtype=np.int64)
+        _lib.check(lib.wc_results_member_template(_lib.ptr(sizes), len(sizes), _lib.ptr(tmpl), len(tmpl), _lib.ptr(table)))
+        self.device = torch.device(device)
+        self.template = torch.from_numpy(tmpl).to(self.device)
+        self.table = torch.from_numpy(table).to(self.device)
+        self.stride = (self.member_bytes + 15) // 16 * 16
+
+    def image(self, rows, ctx=None):
+        """uint8 tensor [n, member_bytes] (rows `stride` bytes apart): the member of every row of `rows`."""
+        import torch
+        assert rows.is_cuda and rows.dtype == torch.float64 and rows.dim() == 2 and rows.shape[1] == self.n_total
+        assert rows.shape[1] == 0 or rows.stride(1) == 1
+        n = int(rows.shape[0])
+        out = torch.empty((n, self.stride), dtype=torch.uint8, device=rows.device)
+        done = 0
+        while done < n:                                 # (the kernel's grid takes 65 535 rows)
+            part = min(n - done, 65535)
+            with torch.cuda.device(rows.device):
+                _lib.check(_lib.load().wc_results_members_dev(
+                    ctx or _lib.context(rows.device.index or 0), torch.cuda.current_stream().cuda_stream,
+                    self.template.data_ptr(), self.member_bytes, self.table.data_ptr(), self.n_gaps, rows[done:].data_ptr(),
+                    int(rows.stride(0)) if n > 1 else self.n_total, part, out[done:].data_ptr(), self.stride))
+            done += part
+        return out[:, :self.member_bytes]
