@@ -115,7 +115,9 @@ def test_batch_of_125_samples(wt, g, case):
             assert row[4] == np.median(rs[c - 1][int(x):int(y) + 1]) - 1, c
     planted = [row for row in calls0 if row[0] in (1.0, 2.0) and row[2] - row[1] > 300]
     assert len(planted) >= 2
-    # the batch's z-scores against the CPU oracle's repeat_test, all bins, three samples
+    # three samples' z-scores against the CPU oracle's repeat_test, all bins: cleaned_regions runs wt.repeatTest on ONE
+    # sample, the lone-sample route (k_zscore_pairs, bin-major outputs), not the batch's -- the batch route
+    # (k_zscore_tiled with sample-major outputs and what follows it) is held to numpy's bits by test_zscore_batch_gpu.py
     ref = case["reference"]
     ms = [int(v) for v in case["masked_bins"]]
     msum = [int(v) for v in np.cumsum(ms)]
