@@ -118,6 +118,21 @@ int wc_newref_export_lists_dev(wc_ctx *ctx, void *stream, int64_t row_begin, int
                                int64_t dst_cap, int32_t *dst_cnt, uint64_t *dst_list);
 int wc_newref_import_lists_dev(wc_ctx *ctx, void *stream, int64_t row_begin, int64_t row_end,
                                int64_t src_cap, const int32_t *src_cnt, const uint64_t *src_list);
+/* Inside a context a list entry's low word is (row | slack code << index bits): the candidate's slack
+ * (wc_newref_get_bounds_dev), rounded UP to a code of 32 - index bits bits, rides above its row number, so that
+ * stage D needs no gather per candidate.  The exchange format above stays (ordered key << 32 | plain row):
+ * the export clears the code, the import puts the importing context's own code back.  For tests:
+ *   wc_newref_export_raw_dev   the export without the clearing
+ *   wc_newref_index_bits       the width of the prepared job (0: not prepared)
+ *   wc_newref_set_index_bits   0 = automatic (max(17, bits of the padded row count - 1)); otherwise 1..24 and at
+ *                              least what the problem needs (checked by the next prepare, where it takes effect)
+ *   wc_slack_code_host         the code itself on the host: code_out[i] = code of slack[i] >= 0 in code_bits
+ *                              (1..31) bits, decoded_out[i] = the slack it stands for (>= slack[i])            */
+int wc_newref_export_raw_dev(wc_ctx *ctx, void *stream, int64_t row_begin, int64_t row_end,
+                             int64_t dst_cap, int32_t *dst_cnt, uint64_t *dst_list);
+int wc_newref_index_bits(wc_ctx *ctx);
+int wc_newref_set_index_bits(wc_ctx *ctx, int bits);
+int wc_slack_code_host(const float *slack, int64_t n, int code_bits, uint32_t *code_out, float *decoded_out);
 int wc_newref_finish_dev(wc_ctx *ctx, void *stream, int64_t row_begin, int64_t row_end,
                          int32_t *idx_out, double *dist_out);
 /* stage D in its two halves, for callers that time them apart: the per-row fast path, then

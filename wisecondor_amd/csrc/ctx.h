@@ -27,6 +27,9 @@ struct NewrefState {
     bool fb_dirty = true;       // fb_count holds a finished pass's counts (k_convert zeroes it for the next job)
     int64_t s_pad = 0;      // samples padded to whole 16-sample chunks (x64 row stride)
     bool exact_only = false; // refsize beyond the candidate lists' design size: every row takes the exact path
+    wc::DevBuf cand_word;    // per row: row | slack code << index_bits, the low word of the row's entries in other rows' lists
+    int index_bits = 17;     // bits of the row number in a candidate word (prepare: max(17, what bins_pad needs))
+    int index_bits_req = 0;  // wc_newref_set_index_bits: 0 = automatic
     bool x64_pad = false;   // the padded float64 image exists (pair engine usable)
     int pw_leaves = 0;
     int64_t pw_for = -1;
@@ -131,7 +134,7 @@ struct wc_ctx {
     }
 
     std::vector<wc::DevBuf *> all_buffers() {
-        return {&nr.col_partial, &nr.col_mean, &nr.norm_lo, &nr.norm_hi, &nr.chrom_of_row, &nr.chrom_range,
+        return {&nr.col_partial, &nr.col_mean, &nr.norm_lo, &nr.norm_hi, &nr.cand_word, &nr.chrom_of_row, &nr.chrom_range,
                 &nr.chrom_off_dev, &nr.sample_rows, &nr.sample_slot, &nr.s32, &nr.s_norm_lo, &nr.s_chrom, &nr.s_range, &nr.keys1,
                 &nr.thr, &nr.cnt, &nr.list, &nr.tiles, &nr.fb_rows, &nr.fb_count, &nr.fb_scratch,
                 &nr.stats, &nr.tiles0, &nr.pw_prog, &nr.pairs, &nr.x64, &nr.m2, &nr.a16, &nr.s16, &tmp_a, &tmp_b, &tmp_c, &tmp_d,

@@ -124,6 +124,30 @@ __device__ inline unsigned short f32_to_f16_scaled(float a, double gam, double i
     return bits;
 }
 
+// A row's slack as a short code in the free high bits of a list entry's candidate word (row | code << index_bits,
+// cb = 32 - index_bits code bits): the top cb of the float's 31 non-sign bits, rounded UP, so that the decoded
+// slack is never below the true one -- a larger slack only raises k_pick's U (a few more re-scores, a marginally
+// stricter certificate; every delivered index and distance is decided in float64).  A carry into the exponent is
+// the next power of two, +inf stays +inf (its dropped bits are zero), a NaN counts as +inf.  With eight exponent
+// bits and cb - 8 mantissa bits the decoded value is at most 1 + 2^-(cb - 8) times the slack.
+__host__ __device__ inline unsigned int slack_encode(float slack, int cb) {
+    unsigned int u;
+    __builtin_memcpy(&u, &slack, 4);
+    u = u > 0x7F800000u ? 0x7F800000u : u;        // (negative values do not occur: a slack is a rounded-up norm gap)
+    const int sh = 31 - cb;
+    return (u + ((1u << sh) - 1u)) >> sh;
+}
+__host__ __device__ inline float slack_decode(unsigned int code, int cb) {
+    const unsigned int u = code << (31 - cb);
+    float f;
+    __builtin_memcpy(&f, &u, 4);
+    return f;
+}
+// the slack of a candidate word: its code sits one bit left of where the float's bits belong
+__device__ __forceinline__ float slack_of_word(unsigned int word, unsigned int index_mask) {
+    return __uint_as_float((word >> 1) & ~(index_mask >> 1));
+}
+
 // Half a wave per row: centred operand image, norm interval, chromosome id.
 // ONE float16 image (A16; values scaled by the power of two gam) serves the threshold estimate and
 // the distance tiles.  The row's representation error e = |a - h| and |h|^2 are accumulated in
@@ -150,7 +174,8 @@ __global__ __launch_bounds__(256) void k_convert(const double *__restrict__ X, i
                                                  float *__restrict__ thr, int *__restrict__ cnt,
                                                  int *__restrict__ row_stat,
                                                  double *__restrict__ X64, int64_t Sp, float *__restrict__ m2_out,
-                                                 int *__restrict__ bad_norm, int *__restrict__ fb_zero, int n_fb_zero) {
+                                                 int *__restrict__ bad_norm, int *__restrict__ fb_zero, int n_fb_zero,
+                                                 unsigned int *__restrict__ cand_word, int index_bits) {
     // Half a wave per row (lane hl of 32, `half` picks the row): a row's life here is a few dependent round trips,
     // and with a wave per row the 11 087 rows of a 250 kb problem were 1.35 rounds of what fits the chip -- two rounds
     // of ~5 us.  Two rows per wave make it one.
@@ -295,6 +320,9 @@ __global__ __launch_bounds__(256) void k_convert(const double *__restrict__ X, i
         chrom_range[row] = range;
         norm_lo[row] = lo;
         norm_hi[row] = hi;
+        // the row as a listed candidate: its number with its slack's code above it (k_gram_glds copies the word into
+        // the entry, k_pick needs no gather of norm_hi)
+        cand_word[row] = (unsigned int)row | (slack_encode(hi, 32 - index_bits) << index_bits);
         chrom_of_row[row] = ch;
         if (slot >= 0) {
             s_norm_lo[slot] = lo;
@@ -330,6 +358,7 @@ struct GramArgs {
     const float *m2;             // -2 / gam^2 (the operand image is scaled by gam)
     int nslab32, last_steps32;   // 32-sample slabs, 16-sample MFMA steps of the last one that hold samples (1..2)
     const float *nbP, *nbQ;      // lower norm bounds
+    const unsigned int *cwP, *cwQ;   // candidate words: row | slack code << index_bits (k_convert)
     const int2 *range;           // per row: [first, last+1) row of its chromosome (never candidates)
     const int4 *tiles;           // {I, J, roles, 0}
     int ntiles;
@@ -360,9 +389,10 @@ __device__ inline unsigned int run_mask(int a, int b) {
 }
 
 // pack_entry for a key that has passed `key <= thr` (not a NaN: f32_ordered without its NaN case, same bits)
-__device__ inline unsigned long long pack_passed(float key, int j) {
+// (the low word is the candidate's word: its row number under its slack's code)
+__device__ inline unsigned long long pack_passed(float key, unsigned int word) {
     const unsigned int b = __float_as_uint(key);
-    return ((unsigned long long)((b & 0x80000000u) ? ~b : (b | 0x80000000u)) << 32) | (unsigned int)j;
+    return ((unsigned long long)((b & 0x80000000u) ? ~b : (b | 0x80000000u)) << 32) | word;
 }
 
 // mask = 2 mask + (key <= thr): the compare and an add-with-carry (the compiler makes three instructions of it)
@@ -413,7 +443,8 @@ __device__ __forceinline__ int ep_at(int col, int row) {      // float offset of
 }
 
 __device__ __forceinline__ void gram_epilogue(const GramArgs &g, float *sm, const float *nbPs, const float *nbQs,
-                                              const float *thPs, const float *thQs, f32x16 (&acc)[2][2], const int I,
+                                              const float *thPs, const float *thQs, const unsigned int *cwPs,
+                                              const unsigned int *cwQs, f32x16 (&acc)[2][2], const int I,
                                               const int J, const int roles, const float m2, const int lane, const int w,
                                               const int wr, const int wc, const int li, const int lh) {
     __builtin_amdgcn_s_setprio(0);
@@ -520,8 +551,9 @@ __device__ __forceinline__ void gram_epilogue(const GramArgs &g, float *sm, cons
                 const float q0 = nbPs[wr * 64 + m * 32 + l0], q1 = nbPs[wr * 64 + m * 32 + l1];
                 const float key0 = fmaf(m2, d0, q0 + (n0 ? nbc1 : nbc0)), key1 = fmaf(m2, d1, q1 + (n1 ? nbc1 : nbc0));
                 const int s0 = (n0 ? off1 : off0) + t, s1 = (n1 ? off1 : off0) + t + 1;
-                if (s0 < g.cap) (n0 ? dstc1 : dstc0)[s0] = pack_passed(key0, row0 + m * 32 + l0);
-                if (two && s1 < g.cap) (n1 ? dstc1 : dstc0)[s1] = pack_passed(key1, row0 + m * 32 + l1);
+                const unsigned int cw0 = cwPs[wr * 64 + m * 32 + l0], cw1 = cwPs[wr * 64 + m * 32 + l1];
+                if (s0 < g.cap) (n0 ? dstc1 : dstc0)[s0] = pack_passed(key0, cw0);
+                if (two && s1 < g.cap) (n1 ? dstc1 : dstc0)[s1] = pack_passed(key1, cw1);
                 t += 2;
             }
             base0 += c0;
@@ -545,8 +577,9 @@ __device__ __forceinline__ void gram_epilogue(const GramArgs &g, float *sm, cons
                     const float d0 = D[ep_at(ca, rr)], d1 = D[ep_at(cb, rr)];
                     const float n0 = nbQs[wc * 64 + ca], n1 = nbQs[wc * 64 + cb];
                     const float key0 = fmaf(m2, d0, nbr + n0), key1 = fmaf(m2, d1, nbr + n1);
-                    if (base_r < g.cap) dst[base_r] = pack_passed(key0, col0 + ca);
-                    if (two && base_r + 1 < g.cap) dst[base_r + 1] = pack_passed(key1, col0 + cb);
+                    const unsigned int cw0 = cwQs[wc * 64 + ca], cw1 = cwQs[wc * 64 + cb];
+                    if (base_r < g.cap) dst[base_r] = pack_passed(key0, cw0);
+                    if (two && base_r + 1 < g.cap) dst[base_r + 1] = pack_passed(key1, cw1);
                     base_r += 2;
                 }
             }
@@ -567,11 +600,13 @@ __device__ __forceinline__ void gram_epilogue(const GramArgs &g, float *sm, cons
 // next slab landed (waited for explicitly: a bare s_barrier, __syncthreads()'s fence would add nothing), after it
 // the freed stage is refilled with the slab after next.
 __global__ __launch_bounds__(256, 4) void k_gram_glds(GramArgs g) {
-    __shared__ __attribute__((aligned(16))) float sm[2 * GL_STAGE + 4 * EP_MASKS + 4 * TB];   // operand stages (then the waves' dot blocks) + row masks + bounds / thresholds
+    __shared__ __attribute__((aligned(16))) float sm[2 * GL_STAGE + 4 * EP_MASKS + 6 * TB];   // operand stages (then the waves' dot blocks) + row masks + bounds / thresholds / candidate words
     float *nbPs = sm + 2 * GL_STAGE + 4 * EP_MASKS;
     float *nbQs = nbPs + TB;
     float *thPs = nbQs + TB;
     float *thQs = thPs + TB;
+    unsigned int *cwPs = reinterpret_cast<unsigned int *>(thQs + TB);
+    unsigned int *cwQs = cwPs + TB;
     const int chunk = (g.ntiles + 7) >> 3;
     const int t_id = (blockIdx.x & 7) * chunk + (blockIdx.x >> 3);
     if (t_id >= g.ntiles) return;
@@ -632,16 +667,18 @@ __global__ __launch_bounds__(256, 4) void k_gram_glds(GramArgs g) {
         acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[t][1], fb[t][1], acc[1][1], 0, 0, 0);
     };
     dma(0, 0);
-    // (the bounds and thresholds of the tile's rows and columns: their loads fly with the first slab)
+    // (the bounds, thresholds and candidate words of the tile's rows and columns: their loads fly with the first slab)
     if (tid < TB) {
         int64_t gp = (int64_t)I * TB + tid;
         nbPs[tid] = g.nbP[gp];
         thPs[tid] = g.thr[gp];
+        cwPs[tid] = g.cwP[gp];
     } else {
         int c = tid - TB;
         int64_t gq = (int64_t)J * TB + c;
         nbQs[c] = g.nbQ[gq];
         thQs[c] = g.thr[gq];
+        cwQs[c] = g.cwQ[gq];
     }
     __builtin_amdgcn_s_waitcnt(0x0070);
     __builtin_amdgcn_s_barrier();
@@ -666,7 +703,7 @@ __global__ __launch_bounds__(256, 4) void k_gram_glds(GramArgs g) {
     mm(0);
     if (g.last_steps32 > 1) mm(1);
     __builtin_amdgcn_s_waitcnt(0x0070);   // nothing of this wave in flight into the LDS the dot tile is about to alias
-    gram_epilogue(g, sm, nbPs, nbQs, thPs, thQs, acc, I, J, roles, m2, lane, w, wr, wc, li, lh);
+    gram_epilogue(g, sm, nbPs, nbQs, thPs, thQs, cwPs, cwQs, acc, I, J, roles, m2, lane, w, wr, wc, li, lh);
 }
 
 // ----------------------------------------------- threshold-estimate Gram (f16) ----
@@ -897,7 +934,8 @@ struct FinishArgs {
     int64_t B, S;
     const float *norm_lo, *norm_hi, *thr;
     const int *cnt;
-    const unsigned long long *list;
+    const unsigned long long *list;   // entries: ordered key << 32 | candidate word (row | slack code << index bits)
+    unsigned int index_mask;          // the row number's bits of a candidate word
     int cap, k;
     double beta;
     const int *chrom_of_row;
@@ -1017,7 +1055,7 @@ __global__ __launch_bounds__(NT, 4) void k_finish(FinishArgs a) {
         if (t < n) {
             const unsigned long long en = e < SPEC ? spec[e] : a.list[row * a.cap + t];
             ent[t] = en;
-            nh[e] = a.norm_hi[(int)(uint32_t)en];
+            nh[e] = a.norm_hi[(int)((uint32_t)en & a.index_mask)];
         }
     }
     const double *xi = a.X + row * a.S;
@@ -1073,7 +1111,7 @@ __global__ __launch_bounds__(NT, 4) void k_finish(FinishArgs a) {
                 bool keep = false;
                 int j = 0;
                 if (t < n) {
-                    j = (int)(uint32_t)ent[t];
+                    j = (int)((uint32_t)ent[t] & a.index_mask);
                     keep = (double)wc::f32_from_ordered((uint32_t)(ent[t] >> 32)) <= U;
                 }
                 unsigned long long m = __ballot(keep);
@@ -1309,19 +1347,20 @@ __device__ __forceinline__ T at_u32(const T *base, uint32_t i) {
 
 // Selection for one row by one wave; NE list entries per lane.  Returns the number of pairs, -1
 // when the row has no certificate (exact path).
-// LEAN (the lists beyond 512 entries): only the KEYS stay in registers through the bisection; the candidate numbers
-// are read again behind it (the list is L2-hot) and the candidates' slacks after them -- the full form of sixteen
-// entries per lane took 77 registers and with them the whole kernel's occupancy (six waves per SIMD).
-// Every gather here is an UNCONDITIONAL load of a selected index (slot 0 of the list and entry 0 of norm_hi always
-// exist): a load under a lane condition is compiled into an exec-masked block with a wait of its own, one memory
-// round trip per entry where a batch in front of one wait pays a single trip.
+// A candidate's slack rides in its entry (the code above the row number, slack_of_word): nothing is gathered per
+// candidate, the wave's first trip is all it needs on the short form.
+// LEAN (the lists beyond 512 entries): only the KEYS stay in registers through the bisection; the candidate words
+// are read again behind it (the list is L2-hot) -- the full form of sixteen entries per lane took 77 registers and
+// with them the whole kernel's occupancy (six waves per SIMD).
+// Every gather here is an UNCONDITIONAL load of a selected index (slot 0 of the list always exists): a load under a
+// lane condition is compiled into an exec-masked block with a wait of its own, one memory round trip per entry where
+// a batch in front of one wait pays a single trip.
 template <int NE, bool LEAN>
 __device__ inline int pick_row(const PickArgs &p, int64_t row, int lane, int n, bool admit_all, float thr_f,
                                float nhi_f, float nlo_f, float bad, const unsigned long long (&spec)[8]) {
     const FinishArgs &a = p.f;
     const unsigned long long *lst = a.list + row * a.cap;
     unsigned long long ent[LEAN ? 1 : NE];
-    float nh[LEAN ? 1 : NE];
     uint32_t key[LEAN ? NE : 1];
     uint32_t cand[LEAN ? NE - 8 : 1];         // candidate words of the entries beyond `spec`
     if constexpr (LEAN) {
@@ -1339,12 +1378,6 @@ __device__ inline int pick_row(const PickArgs &p, int64_t row, int lane, int n, 
             const int t = e * 64 + lane;
             ent[e] = t < n ? (e < 8 ? spec[e] : lst[t]) : ~0ull;
         }
-        // the candidates' slacks, one batch: they stay floats until the U step (entries beyond n read entry 0
-        // and are never used)
-#pragma unroll
-        for (int e = 0; e < NE; ++e) nh[e] = at_u32(a.norm_hi, e * 64 + lane < n ? (uint32_t)ent[e] : 0u);
-#pragma unroll
-        for (int e = 0; e < NE; ++e) asm volatile("" : "+v"(nh[e]));
     }
     auto KU = [&](int e) -> uint32_t { if constexpr (LEAN) return key[e]; else return (uint32_t)(ent[e] >> 32); };
     auto IDX = [&](int e) -> uint32_t { if constexpr (LEAN) return e < 8 ? (uint32_t)spec[e] : cand[e < 8 ? 0 : e - 8]; else return (uint32_t)ent[e]; };
@@ -1388,40 +1421,23 @@ __device__ inline int pick_row(const PickArgs &p, int64_t row, int lane, int n, 
         double my = -INFINITY;
         if constexpr (LEAN) {
             // the candidate words beyond `spec` (whose own ride in its registers) in one batch, kept for the output
-            // step, then the slacks of the entries at or below the separator in halves of eight (sixteen more live
-            // values would cost a wave).  (The lane number is made opaque here: with the key loads' own addresses
-            // these loads are merged into them, and the candidate words -- or their addresses -- live through the
-            // bisection in registers the kernel does not have.)
+            // step; they carry the slacks of the entries at or below the separator.  (The lane number is made opaque
+            // here: with the key loads' own addresses these loads are merged into them, and the candidate words -- or
+            // their addresses -- live through the bisection in registers the kernel does not have.)
             int ln = lane;
             asm volatile("" : "+v"(ln));
 #pragma unroll
             for (int e = 8; e < NE; ++e) cand[e - 8] = (uint32_t)at_u32(lst, e * 64 + ln < n ? (uint32_t)(e * 64 + ln) : 0u);
 #pragma unroll
             for (int e = 8; e < NE; ++e) asm volatile("" : "+v"(cand[e - 8]));
+        }
 #pragma unroll
-            for (int h = 0; h < NE; h += 8) {
-                __builtin_amdgcn_sched_barrier(0);    // (one half's addresses at a time: hoisted, they spill)
-                float sl[8];
-#pragma unroll
-                for (int e = 0; e < 8; ++e)
-                    sl[e] = at_u32(a.norm_hi, ((h + e) * 64 + lane < n && key[h + e] <= res) ? IDX(h + e) : 0u);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) asm volatile("" : "+v"(sl[e]));
-#pragma unroll
-                for (int e = 0; e < 8; ++e)
-                    if ((h + e) * 64 + lane < n && key[h + e] <= res) {
-                        const double ub = (double)wc::f32_from_ordered(key[h + e]) + (nhi + (double)sl[e]) + 1e-36;
-                        my = fmax(my, ub);
-                    }
-            }
-        } else {
-#pragma unroll
-            for (int e = 0; e < NE; ++e) {
-                const uint32_t ku = KU(e);
-                if (e * 64 + lane < n && ku <= res) {
-                    const double ub = (double)wc::f32_from_ordered(ku) + (nhi + (double)nh[e]) + 1e-36;
-                    my = fmax(my, ub);
-                }
+        for (int e = 0; e < NE; ++e) {
+            const uint32_t ku = KU(e);
+            if (e * 64 + lane < n && ku <= res) {
+                const double sl = (double)slack_of_word(IDX(e), a.index_mask);
+                const double ub = (double)wc::f32_from_ordered(ku) + (nhi + sl) + 1e-36;
+                my = fmax(my, ub);
             }
         }
         for (int o = 32; o > 0; o >>= 1) my = fmax(my, __shfl_xor(my, o));
@@ -1445,13 +1461,13 @@ __device__ inline int pick_row(const PickArgs &p, int64_t row, int lane, int n, 
         const bool keep = e * 64 + lane < n && (double)wc::f32_from_ordered(KU(e)) <= U;
         const unsigned long long m = __ballot(keep);
         const int at = base + __popcll(m & ((1ull << lane) - 1ull));
-        if (keep && at < RMAX) out[at] = (int)IDX(e);
+        if (keep && at < RMAX) out[at] = (int)(IDX(e) & a.index_mask);
         base += __popcll(m);
     }
     return base;
 }
 
-__global__ __launch_bounds__(256, 7) void k_pick(PickArgs p) {   // (seven waves per SIMD, 72 registers: the 11 087 rows of cfg2 are 1.55 rounds of the chip instead of 1.8; eight would spill)
+__global__ __launch_bounds__(256, 7) void k_pick(PickArgs p) {   // (seven waves per SIMD, 66 registers: the 11 087 rows of cfg2 are 1.55 rounds of the chip instead of 1.8; held to 64 for eight waves one register spills -- 8 bytes of scratch, no faster: EXPERIMENTS.md)
     const FinishArgs &a = p.f;
     const int lane = threadIdx.x & 63;
     // (the wave's number through readfirstlane: the row and every address derived from it are wave-uniform, which
@@ -2216,22 +2232,28 @@ __global__ void k_all_exact(FinishArgs a) {
     if (row == a.row_begin) *a.fb_count = (int)(a.row_end - a.row_begin);
 }
 
-// Multi-GPU exchange helpers: pack / merge per-row candidate lists.
+// Multi-GPU exchange helpers: pack / merge per-row candidate lists.  The exchange format is (ordered key << 32 |
+// plain row number): the export clears the slack code above the row number (`keep` = the row number's bits; all
+// ones: the entries as they are), the import puts the importing context's own word of that row back -- every rank
+// prepares the whole matrix and so holds the whole table.
 __global__ __launch_bounds__(64) void k_export_lists(const int *__restrict__ cnt,
                                                      const unsigned long long *__restrict__ list, int cap,
                                                      int64_t row_begin, int dst_cap, int *__restrict__ dst_cnt,
-                                                     unsigned long long *__restrict__ dst_list) {
+                                                     unsigned long long *__restrict__ dst_list, unsigned int keep) {
     const int64_t r = blockIdx.x, row = row_begin + r;
     const int c = cnt[row];
     const int n = c < dst_cap ? c : dst_cap;
-    for (int t = threadIdx.x; t < n; t += 64) dst_list[r * dst_cap + t] = list[row * cap + t];
+    const unsigned long long keep64 = 0xFFFFFFFF00000000ull | keep;
+    for (int t = threadIdx.x; t < n; t += 64) dst_list[r * dst_cap + t] = list[row * cap + t] & keep64;
     if (threadIdx.x == 0) dst_cnt[r] = c;  // the true count: > dst_cap tells the owner entries were lost
 }
 
 __global__ __launch_bounds__(64) void k_import_lists(int *__restrict__ cnt, unsigned long long *__restrict__ list,
                                                      int cap, int64_t row_begin, int src_cap,
                                                      const int *__restrict__ src_cnt,
-                                                     const unsigned long long *__restrict__ src_list) {
+                                                     const unsigned long long *__restrict__ src_list,
+                                                     const unsigned int *__restrict__ cand_word,
+                                                     unsigned int index_mask, unsigned int n_words) {
     const int64_t r = blockIdx.x, row = row_begin + r;
     const int c = src_cnt[r];
     const int base = cnt[row];
@@ -2241,7 +2263,11 @@ __global__ __launch_bounds__(64) void k_import_lists(int *__restrict__ cnt, unsi
         return;
     }
     for (int t = threadIdx.x; t < c; t += 64)
-        if (base + t < cap) list[row * cap + base + t] = src_list[r * src_cap + t];
+        if (base + t < cap) {
+            const unsigned long long e = src_list[r * src_cap + t];
+            const unsigned int j = (unsigned int)e & index_mask;
+            list[row * cap + base + t] = (e & 0xFFFFFFFF00000000ull) | cand_word[j < n_words ? j : 0u];
+        }
     wc_sync();
     if (threadIdx.x == 0) cnt[row] = base + c;
 }
@@ -2340,6 +2366,19 @@ int wc_newref_prepare_dev(wc_ctx *ctx, void *stream_, const double *corrected, i
     WC_CHECK(st.chrom_off[n_chrom] == n_bins, WC_E_ARG, "newref: chromosome sizes sum to %lld, expected %lld",
              (long long)st.chrom_off[n_chrom], (long long)n_bins);
     st.bins_pad = round_up(n_bins, TB);
+    {
+        // a list entry's candidate word: the row number in its low index_bits bits, the candidate's slack as a
+        // code of 32 - index_bits bits above it (slack_encode).  At least 17 index bits: 8 exponent + 7 mantissa
+        // bits of slack up to 131 072 padded rows, fewer mantissa bits beyond, exponent only at 2^24 rows; more
+        // rows than that (lists of 137 GB) have no fast path.
+        int need = 1;
+        while (need < 31 && ((st.bins_pad - 1) >> need) != 0) ++need;
+        if (need > 24) st.exact_only = true;
+        WC_CHECK(st.index_bits_req == 0 || st.exact_only || st.index_bits_req >= need, WC_E_ARG,
+                 "newref: %d index bits requested, %lld padded rows need %d", st.index_bits_req,
+                 (long long)st.bins_pad, need);
+        st.index_bits = st.index_bits_req ? st.index_bits_req : std::min(24, std::max(17, need));
+    }
     st.k_pad16 = round_up(n_samples, 64);
     st.cap = LIST_CAP;
     st.expect = LIST_CAP * 3 / 8;     // 384: k = 100 is 4 sigma of the sampled order statistic away, the cap 6
@@ -2365,6 +2404,7 @@ int wc_newref_prepare_dev(wc_ctx *ctx, void *stream_, const double *corrected, i
     if ((rc = st.m2.reserve(sizeof(float) * 4))) return rc;
     if ((rc = st.norm_lo.reserve(sizeof(float) * st.bins_pad))) return rc;
     if ((rc = st.norm_hi.reserve(sizeof(float) * st.bins_pad))) return rc;
+    if ((rc = st.cand_word.reserve(sizeof(unsigned int) * st.bins_pad))) return rc;
     if ((rc = st.chrom_of_row.reserve(sizeof(int) * st.bins_pad))) return rc;
     if ((rc = st.chrom_range.reserve(sizeof(int2) * st.bins_pad))) return rc;
     if ((rc = st.chrom_off_dev.reserve(sizeof(int64_t) * (WC_MAX_CHROM + 1)))) return rc;
@@ -2443,7 +2483,7 @@ int wc_newref_prepare_dev(wc_ctx *ctx, void *stream_, const double *corrected, i
                        st.s16.as<unsigned short>(), st.s_norm_lo.as<float>(), st.s_chrom.as<int>(),
                        st.s_range.as<int2>(), st.thr.as<float>(), st.cnt.as<int>(), st.stats.as<int>(),
                        st.x64_pad ? st.x64.as<double>() : (double *)nullptr, st.s_pad, st.m2.as<float>(),
-                       st.m2.as<int>() + 1, st.fb_count.as<int>(), 4);
+                       st.m2.as<int>() + 1, st.fb_count.as<int>(), 4, st.cand_word.as<unsigned int>(), st.index_bits);
     st.fb_dirty = false;
     if (M > n_bins)
         hipLaunchKernelGGL(k_pad_samples, dim3((unsigned)(M - n_bins)), dim3(256), 0, stream, st.k_pad16, n_bins,
@@ -2538,16 +2578,47 @@ int wc_newref_set_thresholds_dev(wc_ctx *ctx, void *stream, int64_t row_begin, i
     return WC_OK;
 }
 
-int wc_newref_export_lists_dev(wc_ctx *ctx, void *stream, int64_t row_begin, int64_t row_end, int64_t dst_cap,
-                               int32_t *dst_cnt, uint64_t *dst_list) {
+static int newref_export(wc_ctx *ctx, void *stream, int64_t row_begin, int64_t row_end, int64_t dst_cap,
+                         int32_t *dst_cnt, uint64_t *dst_list, bool raw) {
     WC_CHECK(ctx && ctx->nr.prepared && dst_cnt && dst_list && dst_cap > 0, WC_E_ARG, "newref: bad argument");
     WC_CHECK(row_begin >= 0 && row_begin <= row_end && row_end <= ctx->nr.n_bins, WC_E_ARG, "newref: bad row range");
     if (row_end == row_begin) return WC_OK;
     NewrefState &st = ctx->nr;
     hipLaunchKernelGGL(k_export_lists, dim3((unsigned)(row_end - row_begin)), dim3(64), 0, (hipStream_t)stream,
                        (const int *)st.cnt.as<int>(), (const unsigned long long *)st.list.as<unsigned long long>(),
-                       (int)st.cap, row_begin, (int)dst_cap, dst_cnt, (unsigned long long *)dst_list);
+                       (int)st.cap, row_begin, (int)dst_cap, dst_cnt, (unsigned long long *)dst_list,
+                       raw ? ~0u : (1u << st.index_bits) - 1u);
     WC_HIP(hipGetLastError());
+    return WC_OK;
+}
+
+int wc_newref_export_lists_dev(wc_ctx *ctx, void *stream, int64_t row_begin, int64_t row_end, int64_t dst_cap,
+                               int32_t *dst_cnt, uint64_t *dst_list) {
+    return newref_export(ctx, stream, row_begin, row_end, dst_cap, dst_cnt, dst_list, false);
+}
+
+int wc_newref_export_raw_dev(wc_ctx *ctx, void *stream, int64_t row_begin, int64_t row_end, int64_t dst_cap,
+                             int32_t *dst_cnt, uint64_t *dst_list) {
+    return newref_export(ctx, stream, row_begin, row_end, dst_cap, dst_cnt, dst_list, true);
+}
+
+int wc_newref_index_bits(wc_ctx *ctx) { return ctx && ctx->nr.prepared ? ctx->nr.index_bits : 0; }
+
+int wc_newref_set_index_bits(wc_ctx *ctx, int bits) {
+    WC_CHECK(ctx, WC_E_ARG, "newref: NULL context");
+    WC_CHECK(bits == 0 || (bits >= 1 && bits <= 24), WC_E_ARG, "newref: index bits must be 0 (automatic) or 1..24");
+    ctx->nr.index_bits_req = bits;      // the next prepare checks it against the problem's rows
+    return WC_OK;
+}
+
+int wc_slack_code_host(const float *slack, int64_t n, int code_bits, uint32_t *code_out, float *decoded_out) {
+    WC_CHECK(slack && code_out && decoded_out && n >= 0, WC_E_ARG, "slack code: bad argument");
+    WC_CHECK(code_bits >= 1 && code_bits <= 31, WC_E_ARG, "slack code: 1..31 code bits");
+    for (int64_t i = 0; i < n; ++i) {
+        WC_CHECK(!(slack[i] < 0.f), WC_E_ARG, "slack code: negative value at %lld", (long long)i);
+        code_out[i] = slack_encode(slack[i], code_bits);
+        decoded_out[i] = slack_decode(code_out[i], code_bits);
+    }
     return WC_OK;
 }
 
@@ -2559,7 +2630,9 @@ int wc_newref_import_lists_dev(wc_ctx *ctx, void *stream, int64_t row_begin, int
     NewrefState &st = ctx->nr;
     hipLaunchKernelGGL(k_import_lists, dim3((unsigned)(row_end - row_begin)), dim3(64), 0, (hipStream_t)stream,
                        st.cnt.as<int>(), st.list.as<unsigned long long>(), (int)st.cap, row_begin, (int)src_cap,
-                       src_cnt, (const unsigned long long *)src_list);
+                       src_cnt, (const unsigned long long *)src_list,
+                       (const unsigned int *)st.cand_word.as<unsigned int>(), (1u << st.index_bits) - 1u,
+                       (unsigned int)st.bins_pad);
     WC_HIP(hipGetLastError());
     return WC_OK;
 }
@@ -2597,6 +2670,7 @@ int wc_newref_collect_dev(wc_ctx *ctx, void *stream_, int64_t row_begin, int64_t
     g.nslab32 = (int)((st.n_samples + 31) / 32);
     g.last_steps32 = (int)(((st.n_samples - (int64_t)(g.nslab32 - 1) * 32) + 15) / 16);
     g.nbP = g.nbQ = st.norm_lo.as<float>();
+    g.cwP = g.cwQ = st.cand_word.as<unsigned int>();
     g.range = st.chrom_range.as<int2>();
     g.tiles = st.tiles.as<int4>();
     g.ntiles = (int)st.tiles1_n;
@@ -2621,6 +2695,7 @@ static void finish_args(NewrefState &st, int64_t row_begin, int64_t row_end, int
     a.thr = st.thr.as<float>();
     a.cnt = st.cnt.as<int>();
     a.list = st.list.as<unsigned long long>();
+    a.index_mask = (1u << st.index_bits) - 1u;
     a.cap = (int)st.cap;
     a.k = st.k;
     a.beta = (double)st.beta;

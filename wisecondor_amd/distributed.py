@@ -78,6 +78,18 @@ class HipStages(object):
         _lib.check(self.lib.wc_newref_export_lists_dev(self.ctx, self._stream(), rb, re, cap, cnt.data_ptr(),
                                                        lst.data_ptr()))
 
+    def export_raw(self, rb, re, cap, cnt, lst):
+        """The entries as the context holds them: the candidates' slack codes above the row numbers (tests)."""
+        _lib.check(self.lib.wc_newref_export_raw_dev(self.ctx, self._stream(), rb, re, cap, cnt.data_ptr(),
+                                                     lst.data_ptr()))
+
+    def set_index_bits(self, bits):
+        """Width of the row number in a list entry's low word from the next prepare on (0: automatic; tests)."""
+        _lib.check(self.lib.wc_newref_set_index_bits(self.ctx, int(bits)))
+
+    def index_bits(self):
+        return int(self.lib.wc_newref_index_bits(self.ctx))
+
     def import_(self, rb, re, cap, cnt, lst):
         _lib.check(self.lib.wc_newref_import_lists_dev(self.ctx, self._stream(), rb, re, cap, cnt.data_ptr(),
                                                        lst.data_ptr()))
