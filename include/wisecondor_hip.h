@@ -665,6 +665,65 @@ int wc_write_test_results_packed(int n_files, int n_threads, const char *const *
                                  const double *calls, const int32_t *n_calls, int max_calls, const double *asdef, int level,
                                  int *status);
 
+/* ---- plotbatch: result files -> z-score panel PNGs (upstream plotLines, wisetools.py:527-662) -----------
+ * What is drawn follows the reference; how it is drawn is this library's own rasteriser ("plotbatch":
+ * integer blending, half-open rectangles, a column-wise polyline, a bitmap font), so that the bytes are reproducible.
+ *
+ * wc_plot_layout (host): the pixel boxes [x0, y0, x1, y1) of n_panels panels in `rows` rows of `columns`, int32
+ *   [n_panels, 4], inside the reference's figure margins.  A box may be empty in a very small image.
+ * wc_plot_list: the display list a kernel makes of dense z-score rows and calls in the layout wc_test_batch_dev leaves
+ *   them in (results_z [n_samples, row_stride], chromosome c at the sum of chrom_sizes before it; calls [n_samples,
+ *   max_calls, 5]; n_calls [n_samples]) for the panels panel_chrom[n_panels] (1-based chromosome numbers).  HOST pointers.
+ *   entries_out float64 [n_samples, n_panels, capacity, 9], rows (kind, panel, x0, x1, y0, y1, colour id, alpha, value)
+ *   in data coordinates, counts_out int32 [n_samples, n_panels] the entries every panel NEEDS.  Per panel: one kind 0
+ *   entry (x1 = bins, y0 / y1 = min / max of the finite z-scores, +inf / -inf when there is none, value = the number of
+ *   kind 2 entries), one kind 2 entry per stretch of bins whose z == 0 ([first - 0.5, last + 0.5] x [-thr, thr],
+ *   colour 7, alpha 0.5), one kind 3 entry per call of the chromosome with abs(effect) * 100 >= mineffect ([start - 0.5,
+ *   end + 0.5] x [0, thr], -thr when z < 0; colour 1 below abs(effect) 0.2, else 3; alpha min(1, abs(effect) * 10); value
+ *   z).  A panel that needs more than `capacity` entries keeps the first `capacity` and sets bit 0 of *status_out (the
+ *   call still returns WC_OK); wc_plot_batch sizes its lists for the worst case, 1 + ceil(bins / 2) + max_calls.
+ * wc_plot_batch_dev: list, raster, Adler-32 and deflate for n_samples images of width x height pixels, enqueued on
+ *   `stream` without synchronising.  results_z / calls / n_calls are DEVICE pointers, the tables are HOST memory:
+ *   bands_host [n_bands, 4] rows (x0, x1, alpha, hatch 0 / 1 '//' / 2 '\' / -1: a band of the table that gets no
+ *   rectangle) in bins with band_off_host int32 [n_panels + 1] (NULL: no cytoband file); a panel with any row, drawn or
+ *   not, gets the grey line at -1.5 threshold, as the reference draws it once per band of the table; names_host [n_samples, name_cap] NUL-padded sample names.  Outputs, all
+ *   DEVICE memory: streams (the raw deflate stream of image i at i * out_stride, out_stride >= wc_deflate_bound(
+ *   wc_plot_image_bytes(width, height))), out_len, adler, *status (as wc_plot_list's), and, unless NULL, scanlines: image
+ *   i in PNG scanline layout (per row a filter byte 0 and 3 * width bytes) at i * scan_stride, scan_stride a multiple
+ *   of 16.  It uses wc_deflate_rows_dev and shares its rule: one call in flight per context.  WC_E_LIMIT: more images
+ *   or larger ones than that call accepts, or more than 65535 images.  threshold must be positive and finite.
+ *   The tables are copied from pinned memory of the context; the next call waits for that copy (not for the kernels)
+ *   before it writes the block again.
+ * wc_plot_batch: the same from HOST pointers, synchronising (the bytes of streams_out behind a stream are not
+ *   written); scanlines_out (may be NULL) is [n_samples,
+ *   wc_plot_image_bytes]; times_ms (may be NULL) double [8]: milliseconds of [0] copy in [1] list [2] raster
+ *   [3] Adler-32 [4] deflate [5] copy out.  A list beyond its capacity is WC_E_INTERNAL here.
+ * wc_adler32_rows_dev: adler[i] = zlib.adler32 of row i (n_rows <= 65535 rows of row_bytes bytes, src_stride apart),
+ *   as blockwise sums modulo 65521 combined in order.  DEVICE pointers, enqueues on `stream`.
+ * wc_png_bytes / wc_png_assemble (host): the file of one image: signature, IHDR (8-bit RGB), one IDAT chunk = 78 01 +
+ *   the raw deflate stream + the big-endian Adler-32, IEND; wc_png_bytes(deflate_len) is its size.                  */
+int wc_plot_layout(int width, int height, int rows, int columns, int n_panels, int32_t *boxes_out);
+int64_t wc_plot_image_bytes(int width, int height);
+int wc_plot_list(wc_ctx *ctx, const double *results_z, int64_t row_stride, int64_t n_samples, const int64_t *chrom_sizes, int n_chrom,
+                 const double *calls, const int32_t *n_calls, int max_calls, double threshold, double mineffect,
+                 const int32_t *panel_chrom, int n_panels, int capacity, double *entries_out, int32_t *counts_out, int32_t *status_out);
+int wc_plot_batch_dev(wc_ctx *ctx, void *stream, const double *results_z, int64_t row_stride, int64_t n_samples,
+                      const int64_t *chrom_sizes_host, int n_chrom, const double *calls, const int32_t *n_calls, int max_calls,
+                      double threshold, double mineffect, const int32_t *panel_chrom_host, int n_panels, int columns,
+                      const double *bands_host, const int32_t *band_off_host, const char *names_host, int name_cap, int width, int height,
+                      int dpi, unsigned char *scanlines, int64_t scan_stride, unsigned char *streams, int64_t out_stride, int64_t *out_len,
+                      uint32_t *adler, int32_t *status);
+int wc_plot_batch(wc_ctx *ctx, const double *results_z, int64_t row_stride, int64_t n_samples, const int64_t *chrom_sizes, int n_chrom,
+                  const double *calls, const int32_t *n_calls, int max_calls, double threshold, double mineffect,
+                  const int32_t *panel_chrom, int n_panels, int columns, const double *bands, const int32_t *band_off, const char *names,
+                  int name_cap, int width, int height, int dpi, unsigned char *scanlines_out, unsigned char *streams_out,
+                  int64_t out_stride, int64_t *out_len, uint32_t *adler_out, double *times_ms);
+int wc_adler32_rows_dev(wc_ctx *ctx, void *stream, const unsigned char *src, int64_t n_rows, int64_t row_bytes, int64_t src_stride,
+                        uint32_t *adler);
+int64_t wc_png_bytes(int64_t deflate_len);
+int wc_png_assemble(int width, int height, const unsigned char *deflate, int64_t deflate_len, uint32_t adler, unsigned char *out,
+                    int64_t cap, int64_t *out_len);
+
 #ifdef __cplusplus
 }
 #endif

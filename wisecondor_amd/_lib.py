@@ -61,6 +61,16 @@ SIGNATURES = {
     "wc_deflate_rows_dev": (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp]),
     "wc_deflate_rows": (_i32, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp]),
     "wc_huffman_lengths": (_i32, [_vp, _i32, _i32, _vp]),
+    "wc_plot_layout": (_i32, [_i32, _i32, _i32, _i32, _i32, _vp]),
+    "wc_plot_image_bytes": (_i64, [_i32, _i32]),
+    "wc_plot_list": (_i32, [_vp, _vp, _i64, _i64, _vp, _i32, _vp, _vp, _i32, _dbl, _dbl, _vp, _i32, _i32, _vp, _vp, _vp]),
+    "wc_plot_batch_dev": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _i32, _vp, _vp, _i32, _dbl, _dbl, _vp, _i32, _i32, _vp, _vp, _vp,
+                                 _i32, _i32, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _vp]),
+    "wc_plot_batch": (_i32, [_vp, _vp, _i64, _i64, _vp, _i32, _vp, _vp, _i32, _dbl, _dbl, _vp, _i32, _i32, _vp, _vp, _vp,
+                             _i32, _i32, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "wc_adler32_rows_dev": (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _vp]),
+    "wc_png_bytes": (_i64, [_i64]),
+    "wc_png_assemble": (_i32, [_i32, _i32, _vp, _i64, _c.c_uint32, _vp, _i64, _vp]),
     "wc_bam_open": (_i32, [_c.c_char_p, _i32, _vp]),
     "wc_bam_info": (_i32, [_vp, _vp]),
     "wc_bam_refs": (_i32, [_vp, _vp, _i64, _vp, _vp]),

@@ -95,6 +95,26 @@ struct wc_ctx {
     TestState ts;
     wc::DevBuf tmp_a, tmp_b, tmp_c, tmp_d;  // host-pointer API staging
     wc::DevBuf df_scratch, df_meta;         // deflate.hip: the blocks' slots before they are gathered; their lengths and CRC shares
+    // plot.hip: display lists and their counts, the small tables of a call (and the host block they are copied from),
+    // the scanline images, the Adler-32 block sums, the status word
+    wc::DevBuf pl_list, pl_counts, pl_tab, pl_img, pl_part, pl_status;
+    // the tables' host block is pinned, so its copy is truly asynchronous; pl_sent is recorded behind that copy and
+    // waited for before the block is written again (it waits for the small copy only, not for the call's kernels)
+    unsigned char *pl_host = nullptr;
+    size_t pl_host_bytes = 0;
+    hipEvent_t pl_sent = nullptr;
+    int pl_host_reserve(size_t bytes) {
+        if (!pl_sent) WC_HIP(hipEventCreateWithFlags(&pl_sent, hipEventDisableTiming));
+        else WC_HIP(hipEventSynchronize(pl_sent));
+        if (bytes <= pl_host_bytes) return WC_OK;
+        if (pl_host) (void)hipHostFree(pl_host);
+        pl_host = nullptr;
+        pl_host_bytes = 0;
+        const size_t ask = bytes + (bytes >> 1) + 256;
+        WC_HIP(hipHostMalloc((void **)&pl_host, ask, hipHostMallocDefault));
+        pl_host_bytes = ask;
+        return WC_OK;
+    }
     void *pinned = nullptr;
     size_t pinned_bytes = 0;
     int64_t last_stats[8] = {0};
@@ -144,7 +164,7 @@ struct wc_ctx {
                 &ts.reg_flag, &ts.rs, &ts.jobs_a, &ts.jobs_b, &ts.job_cnt, &ts.partial, &ts.cbound, &ts.cuts, &ts.job_res, &ts.hot,
                 &ts.cand, &ts.cand_cnt, &ts.seg, &ts.out_val, &ts.out_x, &ts.out_y, &ts.out_n,
                 &ts.whole, &ts.effect, &ts.misc, &ts.misc2, &ts.reduce_tmp, &ts.win_bits, &ts.bit_off, &ts.pairs_a, &ts.pairs_b, &ts.cut_vals, &ts.prof_work, &ts.sd_fail, &ts.walk_hot, &prep.eig_ws,
-                &cv.tab, &cv.tiles, &cv.kpos, &cv.cls, &df_scratch, &df_meta};
+                &cv.tab, &cv.tiles, &cv.kpos, &cv.cls, &df_scratch, &df_meta, &pl_list, &pl_counts, &pl_tab, &pl_img, &pl_part, &pl_status};
     }
 };
 

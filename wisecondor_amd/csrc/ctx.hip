@@ -49,6 +49,8 @@ void wc_destroy(wc_ctx *ctx) {
     (void)hipDeviceSynchronize();
     for (wc::DevBuf *b : ctx->all_buffers()) b->release();
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
+    if (ctx->pl_host) (void)hipHostFree(ctx->pl_host);
+    if (ctx->pl_sent) (void)hipEventDestroy(ctx->pl_sent);
     if (ctx->side) (void)hipStreamDestroy(ctx->side);
     if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
     if (ctx->ev_join) (void)hipEventDestroy(ctx->ev_join);

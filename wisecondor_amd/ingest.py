@@ -396,3 +396,87 @@ def run_testbatch(reference, paths, outdir, threshold, args, writer=None, max_ca
     wall = time.time() - began
     return dict(files=n, wall_s=wall, files_per_s=n / wall if wall > 0 else 0.0, gpu_s=gpu_s,
                 wait_writers_s=wait_s, h2d_and_kernels_s=run_s, d2h_s=d2h_s)
+
+
+# ------------------------------------------------------------------------------------------ plotbatch ----
+def plot_output_names(paths, outdir, filetype='png'):
+    """<outdir>/<stem>_z.<filetype> per input (upstream's outfile + '_z.' + filetype); two inputs with the same stem are
+    an error up front."""
+    names, seen = [], {}
+    for path in paths:
+        stem = os.path.basename(path)
+        stem = stem[:-4] if stem.endswith('.npz') else stem
+        if stem in seen:
+            raise ValueError('plotbatch: %s and %s would both be written to %s_z.%s; rename one of them'
+                             % (seen[stem], path, stem, filetype))
+        seen[stem] = path
+        names.append(os.path.join(outdir, '%s_z.%s' % (stem, filetype)))
+    return names
+
+
+def _load_result(path):
+    """What `plotbatch` needs of a result file, or the exception that reading it raised."""
+    try:
+        with np.load(path, allow_pickle=True, encoding='latin1') as f:
+            return dict(results_z=[np.asarray(c, dtype=np.float64) for c in f['results_z']],
+                        results_calls=np.asarray(f['results_calls'], dtype=np.float64),
+                        threshold_z=np.asarray(f['threshold_z']).item(), binsize=np.asarray(f['binsize']).item())
+    except Exception as exc:           # reported by name, the run goes on
+        return exc
+
+
+def _write_bytes(path, data):
+    with open(path, 'wb') as f:
+        f.write(data)
+
+
+def run_plotbatch(paths, outdir, args, device=0):
+    """`plotbatch`: one PNG per result file, in GPU batches of args.batch samples (wt.plot_batch).  The files of batch
+    i + 1 are read (np.load in the I/O thread pool) and the files of batch i - 1 written while batch i is on the GPU.
+    Every file must share the chromosome lengths and the bin size of the first readable one; one that does not, or
+    cannot be read, is named and skipped.  A -chromosomes entry the files do not hold is a ValueError.  Returns (files written, [(path, reason)] skipped, wall seconds)."""
+    began = time.time()
+    outs = plot_output_names(paths, outdir, getattr(args, 'filetype', 'png'))
+    batch = max(1, int(getattr(args, 'batch', 64)))
+    io_threads = max(1, int(getattr(args, 'io', 8)))
+    table = wt.loadCytoBands(args.cytofile) if getattr(args, 'cytofile', None) else None      # once, not once per panel
+    pool = concurrent.futures.ThreadPoolExecutor(max_workers=io_threads)
+    skipped, writes, shape = [], [], None
+    try:
+        def start_read(at):
+            return [pool.submit(_load_result, p) for p in paths[at:at + batch]]
+        ahead = start_read(0)
+        for at in range(0, len(paths), batch):
+            loaded = [f.result() for f in ahead]
+            if at + batch < len(paths):
+                ahead = start_read(at + batch)
+            keep = []
+            for k, res in enumerate(loaded):
+                path = paths[at + k]
+                if isinstance(res, Exception):
+                    skipped.append((path, 'cannot be read: %s' % res))
+                    continue
+                mine = ([len(c) for c in res['results_z']], res['binsize'])
+                if shape is None:
+                    shape = mine
+                    beyond = [c for c in args.chromosomes if not 1 <= c <= len(mine[0])]
+                    if beyond:
+                        raise ValueError('plotbatch: -chromosomes names %s, %s holds chromosomes 1..%d'
+                                         % (','.join(str(c) for c in beyond), path, len(mine[0])))
+                if mine[0] != shape[0]:
+                    skipped.append((path, 'other chromosome lengths than the first file'))
+                elif mine[1] != shape[1]:
+                    skipped.append((path, 'bin size %s, the first file has %s' % (mine[1], shape[1])))
+                else:
+                    keep.append((at + k, res))
+            if not keep:
+                continue
+            pngs = wt.plot_batch([res for _, res in keep], [wt.sampleNameOf(paths[i]) for i, _ in keep], cytofile=table,
+                                 chromosomes=args.chromosomes, columns=args.columns, size=args.size, mineffect=args.mineffect,
+                                 dpi=getattr(args, 'dpi', 100), device=device)
+            writes.extend(pool.submit(_write_bytes, outs[i], data) for (i, _), data in zip(keep, pngs))
+        for job in writes:
+            job.result()
+    finally:
+        pool.shutdown(wait=True)
+    return len(writes), skipped, time.time() - began

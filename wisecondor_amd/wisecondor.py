@@ -9,8 +9,9 @@ Everything numeric runs on the GPU through libwisecondor_hip.so (no CPU path).
 
 Build-only additions, all off by default: `-gpus N` on `newref` / `testbatch`
 (one process per GPU), the `testbatch` sub-command (many samples per GPU batch), the `convertbatch`
-sub-command (many BAM files, reading file i + 1 while file i is on the GPU and file i - 1 is written).
-`plot` is not part of this build.
+sub-command (many BAM files, reading file i + 1 while file i is on the GPU and file i - 1 is written), the
+`plotbatch` sub-command (result files to z-score panel PNGs, drawn and deflated on the GPU).
+`plot` itself stays refused: its default output is a matplotlib PDF, which this build does not make.
 """
 import argparse
 import copy
@@ -553,9 +554,36 @@ def toolTestBatch(args):
     reference.close()
 
 
+# ------------------------------------------------------------------- plotbatch ----
+def toolPlotBatch(args):
+    """`plotbatch infiles... outdir` (build-only): <outdir>/<stem>_z.png per result file, what upstream `plot` draws
+    (wisecondor.py:284-295) by this build's own rasteriser on the GPU.  A file that cannot be read, or whose chromosome
+    lengths or bin size differ from the first file's, is named and skipped; the exit status is then 1."""
+    if args.filetype != 'png':
+        print('ERROR: plotbatch writes png only (-filetype %s asked for); upstream plot makes the other formats' % args.filetype)
+        sys.exit(2)
+    if args.columns < 1 or args.dpi < 1 or not args.chromosomes:
+        print('ERROR: plotbatch needs -columns >= 1, -dpi >= 1 and at least one chromosome')
+        sys.exit(2)
+    from . import ingest
+    try:
+        ingest.plot_output_names(args.infiles, args.outdir, args.filetype)      # two inputs with one stem: before anything is made
+        os.makedirs(args.outdir, exist_ok=True)
+        written, skipped, wall = ingest.run_plotbatch(args.infiles, args.outdir, args)
+    except ValueError as exc:
+        print('ERROR:', exc)
+        sys.exit(2)
+    print('%d plots written in %.2f s (%.1f files/s end to end)' % (written, wall, written / wall if wall > 0 else 0.0))
+    for path, reason in skipped:
+        print('ERROR: %s skipped: %s' % (path, reason))
+    if skipped:
+        sys.exit(1)
+
+
 # ---------------------------------------------------------------------- parser ----
 def _not_in_this_build(args):
-    print('ERROR: this sub-command is not part of the MI355X build (convert, newref*, test, report only); '
+    print('ERROR: this sub-command is not part of the MI355X build (convert, newref*, test, report, plotbatch only): '
+          'plot writes a matplotlib PDF by default, which this build does not make; use plotbatch for PNG files or '
           'run it with the upstream wisecondor.py')
     sys.exit(2)
 
@@ -634,6 +662,22 @@ def buildParser():
     p.add_argument('-mineffect', type=float, default=1.5,
                    help='Minimal percentual change in read depth of a call to report')
     p.set_defaults(func=toolReport)
+
+    p = sub.add_parser('plotbatch', description='z-score panel PNGs of many result files, drawn on the GPU (build-only)')
+    p.add_argument('infiles', type=str, nargs='+', help='result files written by test / testbatch (.npz)')
+    p.add_argument('outdir', type=str, help='directory receiving <name>_z.png per result file')
+    # the first five as upstream plot (wisecondor.py:460-479)
+    p.add_argument('-cytofile', type=str, default=None, help='File containing cytoband information')
+    p.add_argument('-chromosomes', type=_chromosome_list, default=list(range(1, 23)),
+                   help='Integer representation of chromosomes to plot, comma separated (default 1..22)')
+    p.add_argument('-columns', type=int, default=2, help='Amount of columns to distribute plots over')
+    p.add_argument('-size', type=float, nargs=2, default=[11.7, 8.3], help='Size of plot in inches, default is A4 landscape')
+    p.add_argument('-mineffect', type=float, default=1.5, help='Minimal percentual change in read depth of a call to plot')
+    p.add_argument('-filetype', type=str, default='png', help='png only')
+    p.add_argument('-dpi', type=int, default=100, help='pixels per inch')
+    p.add_argument('-batch', type=int, default=64, help='images per GPU batch')
+    p.add_argument('-io', type=int, default=8, help='file read / write threads')
+    p.set_defaults(func=toolPlotBatch)
 
     p = sub.add_parser('newref', description='Build a reference from healthy samples in one go')
     p.add_argument('infiles', type=str, nargs='*', help='converted reference samples (.npz)')

@@ -1045,3 +1045,196 @@ class ResultMembers(object):
                     int(rows.stride(0)) if n > 1 else self.n_total, part, out[done:].data_ptr(), self.stride))
             done += part
         return out[:, :self.member_bytes]
+
+
+# ------------------------------------------------------------------- plotbatch: z-score panel PNGs ----
+def loadCytoBands(cytoFile):
+    """chromosome name -> [(start, end, stain)] of a UCSC cytoBand table, read once.  Upstream's loadCytoBands
+    (wisetools.py:73-86) never stores the table's last chromosome and plotLines then dies on it; here every
+    chromosome of the table is kept and one that is absent simply has no bands."""
+    table = {}
+    with open(cytoFile, 'r') as cytoData:
+        for line in cytoData:
+            parts = line.split()
+            if parts:
+                table.setdefault(parts[0][3:], []).append((parts[1], parts[2], parts[4]))
+    return table
+
+
+def plotBands(table, chromosomes, binsize):
+    """The bands of the plotted chromosomes in bins (wisetools.py:566-598): float64 [n, 4] rows (x0, x1, alpha, hatch:
+    0 none, 1 '//', 2 '\\', -1 no rectangle) and the offsets int32 [panels + 1] of every panel's rows.  gneg and other
+    stains get no rectangle but keep their row: the reference draws the -1.5 thr line once per band of the table,
+    whatever its stain, so a panel has that line exactly when it has rows here."""
+    rows, offs = [], [0]
+    for chrom in chromosomes:
+        for start, end, stain in table.get(str(chrom), []):
+            x0, x1 = float(start) / binsize, float(end) / binsize
+            if stain[1:4] == 'pos':
+                rows.append((x0, x1, float(stain[4:]) / 100 * 0.5, 0.0))
+            elif stain == 'acen':
+                rows.append((x0, x1, 1 * 0.5, 1.0))
+            elif stain == 'gvar':
+                rows.append((x0, x1, 0.75 * 0.5, 2.0))
+            else:
+                rows.append((x0, x1, 0.0, -1.0))
+        offs.append(len(rows))
+    return np.array(rows, dtype=np.float64).reshape(-1, 4), np.array(offs, dtype=np.int32)
+
+
+def plotImageSize(size, dpi):
+    """(width, height) in pixels of a figure of size[0] x size[1] inches."""
+    return int(np.floor(size[0] * dpi + 0.5)), int(np.floor(size[1] * dpi + 0.5))
+
+
+def plotLayout(width, height, rows, columns, n_panels):
+    """The panels' pixel boxes [x0, y0, x1, y1), int32 [n_panels, 4] (wc_plot_layout; host only)."""
+    boxes = np.zeros((n_panels, 4), dtype=np.int32)
+    _lib.check(_lib.load().wc_plot_layout(int(width), int(height), int(rows), int(columns), int(n_panels), _lib.ptr(boxes)))
+    return boxes
+
+
+def _dense_results(zs_list, calls_list, max_calls=None):
+    """Per-sample lists of per-chromosome z arrays and call tables -> the dense layout wc_test_batch_dev leaves on the
+    device: rows [n, total], sizes int64 [n_chrom], calls [n, max_calls, 5], n_calls int32 [n]."""
+    sizes = np.array([len(c) for c in zs_list[0]], dtype=np.int64)
+    total = int(sizes.sum())
+    rows = np.zeros((len(zs_list), max(total, 1)), dtype=np.float64)
+    for i, zs in enumerate(zs_list):
+        if [len(c) for c in zs] != [int(v) for v in sizes]:
+            raise ValueError('sample %d has other chromosome lengths than the first' % i)
+        if total:
+            rows[i, :total] = np.concatenate([np.asarray(c, dtype=np.float64) for c in zs])
+    tables = [np.asarray(c, dtype=np.float64).reshape(-1, 5) for c in calls_list]      # (an empty list is stored with shape (0,))
+    cap = max([len(t) for t in tables] + [1]) if max_calls is None else int(max_calls)
+    calls = np.zeros((len(tables), cap, 5), dtype=np.float64)
+    n_calls = np.zeros(len(tables), dtype=np.int32)
+    for i, t in enumerate(tables):
+        calls[i, :len(t)] = t
+        n_calls[i] = len(t)
+    return rows, sizes, calls, n_calls
+
+
+def plotList(zs_list, calls_list, threshold, chromosomes=range(1, 23), mineffect=0, capacity=None, device=0):
+    """The display lists the GPU makes of the samples' z-scores and calls (wc_plot_list): entries float64 [n, panels,
+    capacity, 9] rows (kind, panel, x0, x1, y0, y1, colour id, alpha, value), counts int32 [n, panels] of the entries
+    every panel needs, and the status word (bit 0: some panel needs more than `capacity`; default: the worst case)."""
+    rows, sizes, calls, n_calls = _dense_results(zs_list, calls_list)
+    panels = np.array(list(chromosomes), dtype=np.int32)
+    if capacity is None:
+        capacity = 1 + (int(max([sizes[c - 1] for c in panels] + [0])) + 1) // 2 + calls.shape[1]
+    n = rows.shape[0]
+    entries = np.zeros((n, len(panels), int(capacity), 9), dtype=np.float64)
+    counts = np.zeros((n, len(panels)), dtype=np.int32)
+    status = np.zeros(1, dtype=np.int32)
+    _lib.check(_lib.load().wc_plot_list(_lib.context(device), _lib.ptr(rows), rows.shape[1], n, _lib.ptr(sizes), len(sizes),
+                                        _lib.ptr(calls), _lib.ptr(n_calls), calls.shape[1], float(threshold), float(mineffect),
+                                        _lib.ptr(panels), len(panels), int(capacity), _lib.ptr(entries), _lib.ptr(counts),
+                                        _lib.ptr(status)))
+    return entries, counts, int(status[0])
+
+
+def pngAssemble(width, height, stream, adler):
+    """The PNG file of one image from its raw deflate stream and the Adler-32 of its scanlines (wc_png_assemble; host
+    only): signature, IHDR, IDAT = 78 01 + stream + Adler-32, IEND."""
+    lib = _lib.load()
+    stream = np.ascontiguousarray(np.frombuffer(bytes(stream), dtype=np.uint8))
+    out = np.zeros(max(1, int(lib.wc_png_bytes(len(stream)))), dtype=np.uint8)
+    n = np.zeros(1, dtype=np.int64)
+    _lib.check(lib.wc_png_assemble(int(width), int(height), _lib.ptr(stream), len(stream), int(adler) & 0xffffffff, _lib.ptr(out),
+                                   len(out), _lib.ptr(n)))
+    return out[:int(n[0])].tobytes()
+
+
+def adler32Rows(rows, device=0):
+    """zlib.adler32 of every row of a 2-d uint8 array, computed on the GPU (wc_adler32_rows_dev)."""
+    import torch
+    rows = np.ascontiguousarray(rows, dtype=np.uint8)
+    assert rows.ndim == 2
+    n, row_bytes = rows.shape
+    dev = torch.device('cuda', device)
+    out = torch.zeros((max(n, 1),), dtype=torch.int32, device=dev)
+    src = torch.from_numpy(rows).to(dev) if rows.size else torch.zeros((1,), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().wc_adler32_rows_dev(_lib.context(device), torch.cuda.current_stream().cuda_stream, src.data_ptr(), n,
+                                                   row_bytes, row_bytes, out.data_ptr()))
+        torch.cuda.synchronize()
+    return out.cpu().numpy().view(np.uint32)[:n]
+
+
+def sampleNameOf(infile):
+    """The sample name of the title, as upstream toolPlot takes it from the file name (wisecondor.py:286)."""
+    return infile.split('/')[-1].split('.')[0]
+
+
+def plot_batch(results, names, cytofile=None, chromosomes=range(1, 23), columns=2, size=(11.7, 8.3), mineffect=0, dpi=100,
+               device=0, ctx=None, details=None):
+    """The z-score panel plots of upstream `plot` (plotLines, wisetools.py:527-662) for a batch of `test` results, drawn,
+    checksummed and deflated on the GPU (wc_plot_batch): a list of PNG files as bytes, one per result.
+    results   per sample a mapping with results_z (per-chromosome arrays), results_calls, threshold_z and binsize, as a
+              result file holds them; all must share their chromosome lengths and bin size
+    names     the sample names of the titles
+    cytofile  a cytoBand table (or an already loaded one: loadCytoBands), None: no bands
+    details   a dict that receives 'scanlines' (uint8 [n, height, 1 + 3 width]; not when it holds want_scanlines =
+              False), 'size' and 'times_ms' (per GPU call: copy in, list, raster, Adler-32, deflate, copy out), for tests
+              and measurements
+    Samples with different threshold_z values take one GPU call per value."""
+    if len(results) != len(names):
+        raise ValueError('plot_batch: %d results, %d names' % (len(results), len(names)))
+    if not results:
+        return []
+    lib = _lib.load()
+    chromosomes = [int(c) for c in chromosomes]
+    width, height = plotImageSize(size, dpi)
+    binsize = np.asarray(results[0]['binsize']).item()
+    for i, res in enumerate(results):
+        if np.asarray(res['binsize']).item() != binsize:
+            raise ValueError('sample %d has another bin size than the first' % i)
+    zs_list = [list(res['results_z']) for res in results]
+    rows, sizes, calls, n_calls = _dense_results(zs_list, [res['results_calls'] for res in results])
+    panels = np.array(chromosomes, dtype=np.int32)
+    bands = band_off = None
+    if cytofile is not None:
+        table = cytofile if isinstance(cytofile, dict) else loadCytoBands(cytofile)
+        bands, band_off = plotBands(table, chromosomes, binsize)
+    name_cap = max(len(n.encode('latin1', 'replace')) for n in names) + 1
+    image = int(lib.wc_plot_image_bytes(width, height))
+    if image < 0:
+        raise ValueError('plot_batch: %d x %d pixels' % (width, height))
+    stride = int(lib.wc_deflate_bound(image))
+    thresholds = [float(np.asarray(res['threshold_z']).item()) for res in results]
+    out = [None] * len(results)
+    scan = np.zeros((len(results), image), dtype=np.uint8) if details is not None and details.get('want_scanlines', True) else None
+    times = []
+    handle = ctx or _lib.context(device)
+    for thr in sorted(set(thresholds)):
+        pick = [i for i, t in enumerate(thresholds) if t == thr]
+        n = len(pick)
+        name_block = np.zeros((n, name_cap), dtype=np.uint8)
+        for k, i in enumerate(pick):
+            raw = names[i].encode('latin1', 'replace')
+            name_block[k, :len(raw)] = np.frombuffer(raw, dtype=np.uint8)
+        z_part = np.ascontiguousarray(rows[pick])
+        c_part, k_part = np.ascontiguousarray(calls[pick]), np.ascontiguousarray(n_calls[pick])
+        streams = np.zeros((n, stride), dtype=np.uint8)
+        lengths = np.zeros(n, dtype=np.int64)
+        adlers = np.zeros(n, dtype=np.uint32)
+        lines = np.zeros((n, image), dtype=np.uint8) if scan is not None else None
+        t_ms = np.zeros(8, dtype=np.float64) if details is not None else None
+        _lib.check(lib.wc_plot_batch(handle, _lib.ptr(z_part), z_part.shape[1], n, _lib.ptr(sizes), len(sizes), _lib.ptr(c_part),
+                                     _lib.ptr(k_part), c_part.shape[1], thr, float(mineffect), _lib.ptr(panels), len(panels),
+                                     int(columns), _lib.ptr(bands), _lib.ptr(band_off), _lib.ptr(name_block), name_cap, width, height,
+                                     int(dpi), _lib.ptr(lines), _lib.ptr(streams), stride, _lib.ptr(lengths), _lib.ptr(adlers),
+                                     _lib.ptr(t_ms)))
+        for k, i in enumerate(pick):
+            out[i] = pngAssemble(width, height, streams[k, :lengths[k]], adlers[k])
+            if scan is not None:
+                scan[i] = lines[k]
+        if t_ms is not None:
+            times.append(t_ms[:6].tolist())
+    if details is not None:
+        if scan is not None:
+            details['scanlines'] = scan.reshape(len(results), height, 1 + 3 * width)
+        details['times_ms'] = times
+        details['size'] = (width, height)
+    return out
