@@ -670,7 +670,9 @@ int wc_write_test_results_packed(int n_files, int n_threads, const char *const *
  * integer blending, half-open rectangles, a column-wise polyline, a bitmap font), so that the bytes are reproducible.
  *
  * wc_plot_layout (host): the pixel boxes [x0, y0, x1, y1) of n_panels panels in `rows` rows of `columns`, int32
- *   [n_panels, 4], inside the reference's figure margins.  A box may be empty in a very small image.
+ *   [n_panels, 4], inside the reference's figure margins.  A box may be empty in a very small image.  width and height
+ *   are whole units up to 2097152: an image's pixels (wc_plot_image_bytes holds those to 32768) or a PDF page's
+ *   centipoints (plotpdf, below).
  * wc_plot_list: the display list a kernel makes of dense z-score rows and calls in the layout wc_test_batch_dev leaves
  *   them in (results_z [n_samples, row_stride], chromosome c at the sum of chrom_sizes before it; calls [n_samples,
  *   max_calls, 5]; n_calls [n_samples]) for the panels panel_chrom[n_panels] (1-based chromosome numbers).  HOST pointers.
@@ -722,6 +724,63 @@ int wc_adler32_rows_dev(wc_ctx *ctx, void *stream, const unsigned char *src, int
                         uint32_t *adler);
 int64_t wc_png_bytes(int64_t deflate_len);
 int wc_png_assemble(int width, int height, const unsigned char *deflate, int64_t deflate_len, uint32_t adler, unsigned char *out,
+                    int64_t cap, int64_t *out_len);
+
+/* ---- plotpdf: result files -> vector PDF pages, the content stream written on the device ------
+ * The same display list as plotbatch, drawn as PDF operators.  All geometry is in centipoints (1 / 100 pt): the page is
+ * width_cp x height_cp, the panel boxes are wc_plot_layout(width_cp, height_cp, ...), the mappings are the rasteriser's
+ * with the box in centipoints, q = floor(v + 0.5) limited to +-9 999 999, the flip is height_cp - qy, and every number is
+ * one field of 9 bytes (right-aligned: an optional '-', the whole points, '.', two digits).  A page's content is a row of
+ * sections; a section is a run of records of one kind and one width, each ending in '\n'; a record with nothing to draw
+ * is spaces.  Per panel, in the painter's order: head (q, the box as clip path; 1 x 49 bytes), cytobands (the table's rows
+ * x 138), list rectangles (slots x 73: uncallable patches, then calls), the four grey lines (4 x 81), two edge lines per
+ * slot (slots x 162), the polyline's head (1 x 57), one vertex per bin (bins x 22), S (1 x 2), labels (slots x 96), frame
+ * and Q (1 x 82), the chromosome number (1 x 96); behind the last panel the title (1 x 73 + 2 * (45 + name_cap - 1)) and
+ * the legend (4 x 179).  slots of a panel = the longest list among the samples of the call, less its range entry: every
+ * sample of a call has the same row_bytes and the same section starts.
+ *
+ * wc_plot_pdf_sections (host): the section starts for given slots (int32 [n_panels]) into starts_out (may be NULL) int64
+ *   [11 * n_panels + 3], the last entry and the return value the row's bytes; -1: unusable arguments.
+ * wc_plot_pdf_row_bound (host): the most bytes a page can take: ceil(bins / 2) + max_calls slots in every panel.
+ * wc_plot_pdf_batch_dev: list, content, Adler-32 and deflate for n_samples pages.  Inputs as wc_plot_batch_dev's
+ *   (results_z / calls / n_calls DEVICE pointers in the layout wc_test_batch_dev leaves them, the tables HOST memory).
+ *   IT SYNCHRONISES `stream` ONCE, behind the list kernel, to read the lists' counts back (one small copy): the slot
+ *   counts size the sections.  Everything behind that is enqueued without synchronising.  Outputs, DEVICE memory:
+ *   content (may be NULL: the context keeps it) page i's uncompressed content at i * content_stride, a multiple of 16 and
+ *   at least wc_plot_pdf_row_bound rounded up to one (the bytes from the row's end to the next multiple of 16 are written
+ *   as spaces); streams (raw deflate, page i at i * out_stride, out_stride >= wc_deflate_bound(wc_plot_pdf_row_bound));
+ *   out_len; adler; *status (as wc_plot_list's).  HOST outputs, valid on return: *row_bytes_host the row_bytes used,
+ *   offsets_host (may be NULL) as wc_plot_pdf_sections' starts_out.  It uses wc_deflate_rows_dev and shares its rule: one
+ *   call in flight per context.  WC_E_LIMIT, before anything runs: more pages, or a larger bound, than that call accepts,
+ *   or more than 65535 pages.  threshold must be positive and finite, the page at most 1 440 000 centipoints each way.
+ * wc_plot_pdf_batch: the same from HOST pointers, synchronising.  content_out (may be NULL) [n_samples, content_stride],
+ *   row_bytes of every row written; streams_out rows out_stride >= wc_deflate_bound(wc_plot_pdf_row_bound) apart, only
+ *   out_len[i] bytes of each written; times_ms (may be NULL) double [8]: milliseconds of [0] copy in [1] list and the
+ *   counts' way back [2] content [3] Adler-32 [4] deflate [5] copy out.
+ * wc_pdf_bytes / wc_pdf_assemble (host): the file around one content stream: %PDF-1.4 and a binary comment; Catalog,
+ *   Pages, Page (MediaBox [0 0 width_cp / 100 height_cp / 100]); the font /Courier; the ExtGState dictionary /A000 ..
+ *   /A255 (/ca and /CA = a / 255); the two tiling patterns /P1 ('//') and /P2 ('\'); the content object (/Filter
+ *   /FlateDecode /Length n, data = 78 01 + the raw stream + the big-endian Adler-32); a classic xref table with 20-byte
+ *   entries; trailer, startxref, %%EOF.  No /Info, no date, no /ID: the bytes depend on the inputs alone, and
+ *   wc_pdf_bytes(deflate_len) is the file's size whatever the page (numbers that vary stand in fixed-width fields). */
+int64_t wc_plot_pdf_sections(const int64_t *chrom_sizes, int n_chrom, const int32_t *panel_chrom, int n_panels, const int32_t *band_off,
+                             const int32_t *slots, int name_cap, int64_t *starts_out);
+int64_t wc_plot_pdf_row_bound(const int64_t *chrom_sizes, int n_chrom, const int32_t *panel_chrom, int n_panels, const int32_t *band_off,
+                              int max_calls, int name_cap);
+int wc_plot_pdf_batch_dev(wc_ctx *ctx, void *stream, const double *results_z, int64_t row_stride, int64_t n_samples,
+                          const int64_t *chrom_sizes_host, int n_chrom, const double *calls, const int32_t *n_calls, int max_calls,
+                          double threshold, double mineffect, const int32_t *panel_chrom_host, int n_panels, int columns,
+                          const double *bands_host, const int32_t *band_off_host, const char *names_host, int name_cap, int width_cp,
+                          int height_cp, unsigned char *content, int64_t content_stride, unsigned char *streams, int64_t out_stride,
+                          int64_t *out_len, uint32_t *adler, int64_t *row_bytes_host, int64_t *offsets_host, int32_t *status);
+int wc_plot_pdf_batch(wc_ctx *ctx, const double *results_z, int64_t row_stride, int64_t n_samples, const int64_t *chrom_sizes, int n_chrom,
+                      const double *calls, const int32_t *n_calls, int max_calls, double threshold, double mineffect,
+                      const int32_t *panel_chrom, int n_panels, int columns, const double *bands, const int32_t *band_off, const char *names,
+                      int name_cap, int width_cp, int height_cp, unsigned char *content_out, int64_t content_stride,
+                      unsigned char *streams_out, int64_t out_stride, int64_t *out_len, uint32_t *adler_out, int64_t *row_bytes_out,
+                      int64_t *offsets_out, double *times_ms);
+int64_t wc_pdf_bytes(int64_t deflate_len);
+int wc_pdf_assemble(int width_cp, int height_cp, const unsigned char *deflate, int64_t deflate_len, uint32_t adler, unsigned char *out,
                     int64_t cap, int64_t *out_len);
 
 #ifdef __cplusplus

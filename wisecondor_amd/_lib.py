@@ -71,6 +71,14 @@ SIGNATURES = {
     "wc_adler32_rows_dev": (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _vp]),
     "wc_png_bytes": (_i64, [_i64]),
     "wc_png_assemble": (_i32, [_i32, _i32, _vp, _i64, _c.c_uint32, _vp, _i64, _vp]),
+    "wc_plot_pdf_sections": (_i64, [_vp, _i32, _vp, _i32, _vp, _vp, _i32, _vp]),
+    "wc_plot_pdf_row_bound": (_i64, [_vp, _i32, _vp, _i32, _vp, _i32, _i32]),
+    "wc_plot_pdf_batch_dev": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _i32, _vp, _vp, _i32, _dbl, _dbl, _vp, _i32, _i32, _vp, _vp, _vp,
+                                     _i32, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "wc_plot_pdf_batch": (_i32, [_vp, _vp, _i64, _i64, _vp, _i32, _vp, _vp, _i32, _dbl, _dbl, _vp, _i32, _i32, _vp, _vp, _vp,
+                                 _i32, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "wc_pdf_bytes": (_i64, [_i64]),
+    "wc_pdf_assemble": (_i32, [_i32, _i32, _vp, _i64, _c.c_uint32, _vp, _i64, _vp]),
     "wc_bam_open": (_i32, [_c.c_char_p, _i32, _vp]),
     "wc_bam_info": (_i32, [_vp, _vp]),
     "wc_bam_refs": (_i32, [_vp, _vp, _i64, _vp, _vp]),

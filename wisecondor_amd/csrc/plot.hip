@@ -17,6 +17,7 @@
 
 #include "ctx.h"
 #include "plot_font.h"
+#include "plot_label.h"
 
 namespace {
 
@@ -201,45 +202,6 @@ __device__ __forceinline__ bool pl_glyph(const unsigned char *font, int ch, int 
     if (ch < 32 || ch > 126) ch = '?';
     return (font[(ch - 32) * WC_FONT_H + dy / s] >> (7 - (dx / s) % WC_FONT_W)) & 1;
 }
-// decimal digits of v >= 0 (at least one)
-__device__ __forceinline__ int pl_digits(unsigned long long v) {
-    int n = 1;
-    while (v >= 10ull) {
-        v /= 10ull;
-        ++n;
-    }
-    return n;
-}
-// digit `k` (0 = the most significant) of the `n`-digit number v
-__device__ __forceinline__ int pl_digit(unsigned long long v, int n, int k) {
-    for (int i = n - 1; i > k; --i) v /= 10ull;
-    return '0' + (int)(v % 10ull);
-}
-// "{:.1f}".format(z) without a buffer: tenths = the correctly rounded abs(z) * 10 (ties to even on the exact value, which
-// v * 8 + v * 2 with the error of the one addition gives); false: the label is "?" (not finite, or abs(z) >= 1e9)
-__device__ __forceinline__ bool pl_label_tenths(double zc, unsigned long long &tenths, int &neg) {
-    const double v = fabs(zc);
-    neg = __builtin_signbit(zc) ? 1 : 0;
-    if (!(v < 1e9)) return false;
-    const double a = v * 8.0, b = v * 2.0, sum = a + b, bb = sum - a;
-    const double err = (a - (sum - bb)) + (b - bb);
-    const double whole = floor(sum), r = (sum - whole) - 0.5;
-    unsigned long long n = (unsigned long long)whole;
-    if (r > 0.0 || (r == 0.0 && (err > 0.0 || (err == 0.0 && (n & 1ull))))) ++n;
-    tenths = n;
-    return true;
-}
-__device__ __forceinline__ int pl_label_len(bool ok, unsigned long long tenths, int neg) {
-    return ok ? neg + pl_digits(tenths / 10ull) + 2 : 1;
-}
-__device__ __forceinline__ int pl_label_char(bool ok, unsigned long long tenths, int neg, int n, int k) {
-    if (!ok) return '?';
-    if (neg && k == 0) return '-';
-    if (k == n - 1) return '0' + (int)(tenths % 10ull);
-    if (k == n - 2) return '.';
-    return pl_digit(tenths / 10ull, n - neg - 2, k - neg);
-}
-
 // (the arguments are read from the call's table block where they are needed: held in registers for the whole kernel
 //  they did not fit the scalar file)
 __global__ __launch_bounds__(PL_T) void k_plot_raster(const RasterArgs *args) {
@@ -551,13 +513,9 @@ int launch_list(wc_ctx *ctx, hipStream_t stream, const Tables &T, const double *
                 const double *calls, const int32_t *n_calls, int max_calls, double thr, double mineffect, int n_panels, int cap,
                 double *entries, int *counts, int *status) {
     const unsigned char *tab = ctx->pl_tab.as<unsigned char>();
-    WC_HIP(hipMemsetAsync(status, 0, sizeof(int), stream));
-    hipLaunchKernelGGL(k_plot_list, dim3((unsigned)n_panels, (unsigned)n_samples), dim3(PL_T), 0, stream, z, (long long)row_stride,
-                       (const long long *)(tab + T.off_chrom_off), (const long long *)(tab + T.off_chrom_len),
-                       (const int *)(tab + T.off_panel), calls, (const int *)n_calls, max_calls, thr, mineffect, cap, entries, counts,
-                       status);
-    WC_HIP(hipGetLastError());
-    return WC_OK;
+    return wc::plot_list_launch(stream, z, row_stride, n_samples, (const long long *)(tab + T.off_chrom_off),
+                                (const long long *)(tab + T.off_chrom_len), (const int *)(tab + T.off_panel), calls, n_calls, max_calls,
+                                thr, mineffect, n_panels, cap, entries, counts, status);
 }
 
 void put32(unsigned char *p, uint32_t v) {
@@ -569,13 +527,30 @@ void put32(unsigned char *p, uint32_t v) {
 
 }  // namespace
 
+namespace wc {
+int plot_check_panels(const int64_t *chrom_sizes, int n_chrom, const int32_t *panel_chrom, int n_panels, int64_t row_stride) {
+    return check_panels(chrom_sizes, n_chrom, panel_chrom, n_panels, row_stride);
+}
+int plot_list_launch(hipStream_t stream, const double *z, int64_t row_stride, int64_t n_samples, const long long *chrom_off_dev,
+                     const long long *chrom_len_dev, const int *panel_chrom_dev, const double *calls, const int32_t *n_calls,
+                     int max_calls, double thr, double mineffect, int n_panels, int cap, double *entries, int *counts, int *status) {
+    WC_HIP(hipMemsetAsync(status, 0, sizeof(int), stream));
+    hipLaunchKernelGGL(k_plot_list, dim3((unsigned)n_panels, (unsigned)n_samples), dim3(PL_T), 0, stream, z, (long long)row_stride,
+                       chrom_off_dev, chrom_len_dev, panel_chrom_dev, calls, (const int *)n_calls, max_calls, thr, mineffect, cap, entries,
+                       counts, status);
+    WC_HIP(hipGetLastError());
+    return WC_OK;
+}
+}  // namespace wc
+
 extern "C" {
 
 int wc_plot_layout(int width, int height, int rows, int columns, int n_panels, int32_t *boxes_out) {
     WC_CHECK(width >= 1 && height >= 1 && rows >= 1 && columns >= 1 && n_panels >= 0 && n_panels <= rows * columns && boxes_out &&
-                 width <= 32768 && height <= 32768,
-             WC_E_ARG, "plot layout: %d x %d pixels (at most 32768 each), %d panels in %d rows of %d", width, height, n_panels, rows, columns);
-    // the figure margins of the reference's subplots (left 0.125, right 0.9, top 0.88, bottom 0.11), in whole pixels
+                 width <= (1 << 21) && height <= (1 << 21),
+             WC_E_ARG, "plot layout: %d x %d units (at most 2097152 each), %d panels in %d rows of %d", width, height, n_panels, rows, columns);
+    // the figure margins of the reference's subplots (left 0.125, right 0.9, top 0.88, bottom 0.11), in whole units: the
+    // pixels of an image (wc_plot_image_bytes holds those to 32768) or the centipoints of a PDF page
     const int gx0 = width * 125 / 1000, gx1 = width - width / 10, gy0 = height * 12 / 100, gy1 = height - height * 11 / 100;
     const int cw = (gx1 - gx0) / columns, ch = (gy1 - gy0) / rows;
     for (int p = 0; p < n_panels; ++p) {

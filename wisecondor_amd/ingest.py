@@ -399,7 +399,7 @@ def run_testbatch(reference, paths, outdir, threshold, args, writer=None, max_ca
 
 
 # ------------------------------------------------------------------------------------------ plotbatch ----
-def plot_output_names(paths, outdir, filetype='png'):
+def plot_output_names(paths, outdir, filetype='png', command='plotbatch'):
     """<outdir>/<stem>_z.<filetype> per input (upstream's outfile + '_z.' + filetype); two inputs with the same stem are
     an error up front."""
     names, seen = [], {}
@@ -407,8 +407,8 @@ def plot_output_names(paths, outdir, filetype='png'):
         stem = os.path.basename(path)
         stem = stem[:-4] if stem.endswith('.npz') else stem
         if stem in seen:
-            raise ValueError('plotbatch: %s and %s would both be written to %s_z.%s; rename one of them'
-                             % (seen[stem], path, stem, filetype))
+            raise ValueError('%s: %s and %s would both be written to %s_z.%s; rename one of them'
+                             % (command, seen[stem], path, stem, filetype))
         seen[stem] = path
         names.append(os.path.join(outdir, '%s_z.%s' % (stem, filetype)))
     return names
@@ -430,13 +430,34 @@ def _write_bytes(path, data):
         f.write(data)
 
 
+def _draw_png(results, names, table, args, device):
+    return wt.plot_batch(results, names, cytofile=table, chromosomes=args.chromosomes, columns=args.columns, size=args.size,
+                         mineffect=args.mineffect, dpi=getattr(args, 'dpi', 100), device=device)
+
+
+def _draw_pdf(results, names, table, args, device):
+    return wt.plot_pdf_batch(results, names, cytofile=table, chromosomes=args.chromosomes, columns=args.columns, size=args.size,
+                             mineffect=args.mineffect, device=device)
+
+
 def run_plotbatch(paths, outdir, args, device=0):
     """`plotbatch`: one PNG per result file, in GPU batches of args.batch samples (wt.plot_batch).  The files of batch
     i + 1 are read (np.load in the I/O thread pool) and the files of batch i - 1 written while batch i is on the GPU.
     Every file must share the chromosome lengths and the bin size of the first readable one; one that does not, or
     cannot be read, is named and skipped.  A -chromosomes entry the files do not hold is a ValueError.  Returns (files written, [(path, reason)] skipped, wall seconds)."""
+    return _run_plots(paths, outdir, args, device, 'plotbatch', getattr(args, 'filetype', 'png'), _draw_png)
+
+
+def run_plotpdf(paths, outdir, args, device=0):
+    """`plotpdf`: one vector PDF per result file (wt.plot_pdf_batch), by run_plotbatch's pipeline and rules."""
+    return _run_plots(paths, outdir, args, device, 'plotpdf', 'pdf', _draw_pdf)
+
+
+def _run_plots(paths, outdir, args, device, command, filetype, draw):
+    """The read / draw / write pipeline of `plotbatch` and `plotpdf`: draw(results, names, cytoband table, args, device)
+    returns the files' bytes."""
     began = time.time()
-    outs = plot_output_names(paths, outdir, getattr(args, 'filetype', 'png'))
+    outs = plot_output_names(paths, outdir, filetype, command)
     batch = max(1, int(getattr(args, 'batch', 64)))
     io_threads = max(1, int(getattr(args, 'io', 8)))
     table = wt.loadCytoBands(args.cytofile) if getattr(args, 'cytofile', None) else None      # once, not once per panel
@@ -461,8 +482,8 @@ def run_plotbatch(paths, outdir, args, device=0):
                     shape = mine
                     beyond = [c for c in args.chromosomes if not 1 <= c <= len(mine[0])]
                     if beyond:
-                        raise ValueError('plotbatch: -chromosomes names %s, %s holds chromosomes 1..%d'
-                                         % (','.join(str(c) for c in beyond), path, len(mine[0])))
+                        raise ValueError('%s: -chromosomes names %s, %s holds chromosomes 1..%d'
+                                         % (command, ','.join(str(c) for c in beyond), path, len(mine[0])))
                 if mine[0] != shape[0]:
                     skipped.append((path, 'other chromosome lengths than the first file'))
                 elif mine[1] != shape[1]:
@@ -471,10 +492,8 @@ def run_plotbatch(paths, outdir, args, device=0):
                     keep.append((at + k, res))
             if not keep:
                 continue
-            pngs = wt.plot_batch([res for _, res in keep], [wt.sampleNameOf(paths[i]) for i, _ in keep], cytofile=table,
-                                 chromosomes=args.chromosomes, columns=args.columns, size=args.size, mineffect=args.mineffect,
-                                 dpi=getattr(args, 'dpi', 100), device=device)
-            writes.extend(pool.submit(_write_bytes, outs[i], data) for (i, _), data in zip(keep, pngs))
+            files = draw([res for _, res in keep], [wt.sampleNameOf(paths[i]) for i, _ in keep], table, args, device)
+            writes.extend(pool.submit(_write_bytes, outs[i], data) for (i, _), data in zip(keep, files))
         for job in writes:
             job.result()
     finally:

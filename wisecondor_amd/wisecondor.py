@@ -10,7 +10,8 @@ Everything numeric runs on the GPU through libwisecondor_hip.so (no CPU path).
 Build-only additions, all off by default: `-gpus N` on `newref` / `testbatch`
 (one process per GPU), the `testbatch` sub-command (many samples per GPU batch), the `convertbatch`
 sub-command (many BAM files, reading file i + 1 while file i is on the GPU and file i - 1 is written), the
-`plotbatch` sub-command (result files to z-score panel PNGs, drawn and deflated on the GPU).
+`plotbatch` sub-command (result files to z-score panel PNGs, drawn and deflated on the GPU) and the `plotpdf`
+sub-command (the same panels as vector PDF pages, the content stream written on the GPU).
 `plot` itself stays refused: its default output is a matplotlib PDF, which this build does not make.
 """
 import argparse
@@ -580,6 +581,30 @@ def toolPlotBatch(args):
         sys.exit(1)
 
 
+# ------------------------------------------------------------------- plotpdf ----
+def toolPlotPdf(args):
+    """`plotpdf infiles... outdir` (build-only): <outdir>/<stem>_z.pdf per result file, the name and the vector format of
+    upstream `plot`'s default output (wisecondor.py:284-295), the page's content stream written on the GPU.  Files are
+    treated as `plotbatch` treats them: one that cannot be read, or whose chromosome lengths or bin size differ from the
+    first file's, is named and skipped; the exit status is then 1."""
+    if args.columns < 1 or not args.chromosomes or min(args.size) <= 0:
+        print('ERROR: plotpdf needs -columns >= 1, a -size above 0 and at least one chromosome')
+        sys.exit(2)
+    from . import ingest
+    try:
+        ingest.plot_output_names(args.infiles, args.outdir, 'pdf', 'plotpdf')      # two inputs with one stem: before anything is made
+        os.makedirs(args.outdir, exist_ok=True)
+        written, skipped, wall = ingest.run_plotpdf(args.infiles, args.outdir, args)
+    except ValueError as exc:
+        print('ERROR:', exc)
+        sys.exit(2)
+    print('%d plots written in %.2f s (%.1f files/s end to end)' % (written, wall, written / wall if wall > 0 else 0.0))
+    for path, reason in skipped:
+        print('ERROR: %s skipped: %s' % (path, reason))
+    if skipped:
+        sys.exit(1)
+
+
 # ---------------------------------------------------------------------- parser ----
 def _not_in_this_build(args):
     print('ERROR: this sub-command is not part of the MI355X build (convert, newref*, test, report, plotbatch only): '
@@ -678,6 +703,20 @@ def buildParser():
     p.add_argument('-batch', type=int, default=64, help='images per GPU batch')
     p.add_argument('-io', type=int, default=8, help='file read / write threads')
     p.set_defaults(func=toolPlotBatch)
+
+    p = sub.add_parser('plotpdf', description='z-score panel PDFs (vector) of many result files, written on the GPU (build-only)')
+    p.add_argument('infiles', type=str, nargs='+', help='result files written by test / testbatch (.npz)')
+    p.add_argument('outdir', type=str, help='directory receiving <name>_z.pdf per result file')
+    # the five options of upstream plot (wisecondor.py:460-479), with its defaults
+    p.add_argument('-cytofile', type=str, default=None, help='File containing cytoband information')
+    p.add_argument('-chromosomes', type=_chromosome_list, default=list(range(1, 23)),
+                   help='Integer representation of chromosomes to plot, comma separated (default 1..22)')
+    p.add_argument('-columns', type=int, default=2, help='Amount of columns to distribute plots over')
+    p.add_argument('-size', type=float, nargs=2, default=[11.7, 8.3], help='Size of plot in inches, default is A4 landscape')
+    p.add_argument('-mineffect', type=float, default=1.5, help='Minimal percentual change in read depth of a call to plot')
+    p.add_argument('-batch', type=int, default=64, help='pages per GPU batch')
+    p.add_argument('-io', type=int, default=8, help='file read / write threads')
+    p.set_defaults(func=toolPlotPdf)
 
     p = sub.add_parser('newref', description='Build a reference from healthy samples in one go')
     p.add_argument('infiles', type=str, nargs='*', help='converted reference samples (.npz)')

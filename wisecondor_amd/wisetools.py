@@ -1238,3 +1238,114 @@ def plot_batch(results, names, cytofile=None, chromosomes=range(1, 23), columns=
         details['times_ms'] = times
         details['size'] = (width, height)
     return out
+
+
+# ------------------------------------------------------------------- plotpdf: vector PDF pages ----
+def pdfPageSize(size):
+    """(width, height) of a page of size[0] x size[1] inches in centipoints (1 / 100 pt)."""
+    return int(np.floor(size[0] * 7200 + 0.5)), int(np.floor(size[1] * 7200 + 0.5))
+
+
+def pdfSections(sizes, chromosomes, band_off, slots, name_cap):
+    """The section starts of a page's content for the given slot counts per panel, int64 [11 panels + 3], the last entry
+    the row's bytes (wc_plot_pdf_sections; host only)."""
+    sizes = np.ascontiguousarray(sizes, dtype=np.int64)
+    panels = np.ascontiguousarray(list(chromosomes), dtype=np.int32)
+    slots = np.ascontiguousarray(slots, dtype=np.int32)
+    band_off = None if band_off is None else np.ascontiguousarray(band_off, dtype=np.int32)
+    starts = np.zeros(11 * len(panels) + 3, dtype=np.int64)
+    if len(slots) != len(panels) or _lib.load().wc_plot_pdf_sections(_lib.ptr(sizes), len(sizes), _lib.ptr(panels), len(panels),
+                                                                  _lib.ptr(band_off), _lib.ptr(slots), int(name_cap),
+                                                                  _lib.ptr(starts)) < 0:
+        raise ValueError('pdfSections: unusable arguments')
+    return starts
+
+
+def pdfAssemble(width_cp, height_cp, stream, adler):
+    """The PDF file of one page from the raw deflate stream of its content and the content's Adler-32 (wc_pdf_assemble;
+    host only): header, Catalog, Pages, Page, the font Courier, the graphics states /A000 .. /A255, the two hatch patterns,
+    the content object = 78 01 + stream + Adler-32, xref, trailer."""
+    lib = _lib.load()
+    stream = np.ascontiguousarray(np.frombuffer(bytes(stream), dtype=np.uint8))
+    out = np.zeros(max(1, int(lib.wc_pdf_bytes(len(stream)))), dtype=np.uint8)
+    n = np.zeros(1, dtype=np.int64)
+    _lib.check(lib.wc_pdf_assemble(int(width_cp), int(height_cp), _lib.ptr(stream), len(stream), int(adler) & 0xffffffff, _lib.ptr(out),
+                                   len(out), _lib.ptr(n)))
+    return out[:int(n[0])].tobytes()
+
+
+def plot_pdf_batch(results, names, cytofile=None, chromosomes=range(1, 23), columns=2, size=(11.7, 8.3), mineffect=0, device=0,
+                   ctx=None, details=None):
+    """The z-score panel plots of upstream `plot` as vector PDF pages, the content streams written, checksummed and
+    deflated on the GPU (wc_plot_pdf_batch): a list of PDF files as bytes, one per result.  Arguments as plot_batch's.
+    details   a dict that receives 'content' (per sample the uncompressed content stream, bytes; not when it holds
+              want_content = False), 'row_bytes' and 'offsets' (per GPU call: the bytes of every sample's stream and its
+              section starts), 'size' (the page in centipoints) and 'times_ms' (per GPU call: copy in, list, content,
+              Adler-32, deflate, copy out)
+    Samples with different threshold_z values take one GPU call per value."""
+    if len(results) != len(names):
+        raise ValueError('plot_pdf_batch: %d results, %d names' % (len(results), len(names)))
+    if not results:
+        return []
+    lib = _lib.load()
+    chromosomes = [int(c) for c in chromosomes]
+    width, height = pdfPageSize(size)
+    binsize = np.asarray(results[0]['binsize']).item()
+    for i, res in enumerate(results):
+        if np.asarray(res['binsize']).item() != binsize:
+            raise ValueError('sample %d has another bin size than the first' % i)
+    zs_list = [list(res['results_z']) for res in results]
+    rows, sizes, calls, n_calls = _dense_results(zs_list, [res['results_calls'] for res in results])
+    panels = np.array(chromosomes, dtype=np.int32)
+    bands = band_off = None
+    if cytofile is not None:
+        table = cytofile if isinstance(cytofile, dict) else loadCytoBands(cytofile)
+        bands, band_off = plotBands(table, chromosomes, binsize)
+    name_cap = max(len(n.encode('latin1', 'replace')) for n in names) + 1
+    bound = int(lib.wc_plot_pdf_row_bound(_lib.ptr(sizes), len(sizes), _lib.ptr(panels), len(panels), _lib.ptr(band_off), calls.shape[1],
+                                          name_cap))
+    if bound < 0:
+        raise ValueError('plot_pdf_batch: unusable chromosomes, cytoband table or names')
+    stride = int(lib.wc_deflate_bound(bound))
+    thresholds = [float(np.asarray(res['threshold_z']).item()) for res in results]
+    out = [None] * len(results)
+    content = [None] * len(results)
+    times, row_bytes, offsets = [], [], []
+    handle = ctx or _lib.context(device)
+    for thr in sorted(set(thresholds)):
+        pick = [i for i, t in enumerate(thresholds) if t == thr]
+        n = len(pick)
+        name_block = np.zeros((n, name_cap), dtype=np.uint8)
+        for k, i in enumerate(pick):
+            raw = names[i].encode('latin1', 'replace')
+            name_block[k, :len(raw)] = np.frombuffer(raw, dtype=np.uint8)
+        z_part = np.ascontiguousarray(rows[pick])
+        c_part, k_part = np.ascontiguousarray(calls[pick]), np.ascontiguousarray(n_calls[pick])
+        # (rows of the worst case's size: the pages they hold are written, the rest is never touched)
+        streams = np.zeros((n, stride), dtype=np.uint8)
+        lengths = np.zeros(n, dtype=np.int64)
+        adlers = np.zeros(n, dtype=np.uint32)
+        lines = np.zeros((n, bound), dtype=np.uint8) if details is not None and details.get('want_content', True) else None
+        t_ms = np.zeros(8, dtype=np.float64) if details is not None else None
+        used = np.zeros(1, dtype=np.int64)
+        starts = np.zeros(11 * len(panels) + 3, dtype=np.int64)
+        _lib.check(lib.wc_plot_pdf_batch(handle, _lib.ptr(z_part), z_part.shape[1], n, _lib.ptr(sizes), len(sizes), _lib.ptr(c_part),
+                                         _lib.ptr(k_part), c_part.shape[1], thr, float(mineffect), _lib.ptr(panels), len(panels),
+                                         int(columns), _lib.ptr(bands), _lib.ptr(band_off), _lib.ptr(name_block), name_cap, width,
+                                         height, _lib.ptr(lines), bound, _lib.ptr(streams), stride, _lib.ptr(lengths),
+                                         _lib.ptr(adlers), _lib.ptr(used), _lib.ptr(starts), _lib.ptr(t_ms)))
+        for k, i in enumerate(pick):
+            out[i] = pdfAssemble(width, height, streams[k, :lengths[k]], adlers[k])
+            if lines is not None:
+                content[i] = lines[k, :int(used[0])].tobytes()
+        if t_ms is not None:
+            times.append(t_ms[:6].tolist())
+        row_bytes.append(int(used[0]))
+        offsets.append(starts)
+    if details is not None:
+        details['content'] = content
+        details['row_bytes'] = row_bytes
+        details['offsets'] = offsets
+        details['times_ms'] = times
+        details['size'] = (width, height)
+    return out
