@@ -6864,7 +6864,12 @@ int wc_test_batch_dev(wc_ctx *ctx, void *stream_, const wc_reference *ref, const
     const HostStatus *hs = (const HostStatus *)ctx->pinned;
     // anything the latency kernels are not built for -> the general path computes the call again
     // (non-finite region, tie overflow, deep stack: lat_counters[6]; many queued pairs; stdDevAvg's serial kernel)
-    if (hs->lat_counters[6] || hs->lat_tail_overflow || hs->lat_sd_fail) return general();
+    if (hs->lat_counters[6] || hs->lat_tail_overflow || hs->lat_sd_fail) {
+        if (sw.verbose)
+            fprintf(stderr, "wisecondor_amd: call repeated on the general path (latency status: walk %d, tail %d, sd %d)\n",
+                    hs->lat_counters[6], hs->lat_tail_overflow, hs->lat_sd_fail);
+        return general();
+    }
     WC_CHECK(!hs->lat_call_overflow, WC_E_LIMIT, "test: a sample has more than max_calls=%d calls", max_calls);
     return WC_OK;
 }
