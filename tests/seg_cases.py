@@ -264,12 +264,9 @@ def case_sample(name):
     return smp
 
 
-@functools.lru_cache(maxsize=None)
-def oracle_of(name):
-    """wo.test_sample of a case, computed once; `tris`: the triangle of every chromosome as test_sample filled it,
+def oracle_of_sample(lay, smp, repeats=REPEATS, thr=THR):
+    """wo.test_sample of one sample of a layout; `tris`: the triangle of every chromosome as test_sample filled it,
     `regions`: the cleaned z of every chromosome (what the triangles were filled from)."""
-    case = case_of(name)
-    lay, smp = layout_of(name), case_sample(name)
     tris, regions = [], []
     fill = wo.fill_tri
 
@@ -281,13 +278,19 @@ def oracle_of(name):
     wo.fill_tri = keeping
     try:
         with np.errstate(all="ignore"):
-            out = wo.test_sample(smp["counts"], BINSIZE, cc.reference_of(lay, smp), minzscore=THR, minrefbins=MINREF,
-                                 repeats=case["repeats"])
+            out = wo.test_sample(smp["counts"], BINSIZE, cc.reference_of(lay, smp), minzscore=thr, minrefbins=MINREF,
+                                 repeats=repeats)
     finally:
         wo.fill_tri = fill
     assert len(tris) == 22
     out["tris"], out["regions"] = tris, regions
     return out
+
+
+@functools.lru_cache(maxsize=None)
+def oracle_of(name):
+    """oracle_of_sample of a case, computed once."""
+    return oracle_of_sample(layout_of(name), case_sample(name), case_of(name)["repeats"])
 
 
 def rows_of(out):
