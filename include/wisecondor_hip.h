@@ -783,6 +783,47 @@ int64_t wc_pdf_bytes(int64_t deflate_len);
 int wc_pdf_assemble(int width_cp, int height_cp, const unsigned char *deflate, int64_t deflate_len, uint32_t adler, unsigned char *out,
                     int64_t cap, int64_t *out_len);
 
+/* ---- exportjson: result rows -> lossless JSON text, the digits made on the device ------------
+ * A value's text is what CPython's float.__repr__ / json.dumps gives, byte for byte: the shortest digits that read
+ * back to the same double (the closest of them, a tie to even), positional or d.ddde+XX as repr chooses, ".0" behind
+ * whole numbers, "-0.0"; at most 24 bytes.  Not finite: Infinity, -Infinity, NaN (sign and payload of a NaN are
+ * dropped); with strict != 0 all three are null.  The digits are Ryu's, exact for every double (csrc/fmt_double.h).
+ *
+ * wc_format_doubles_host (host only, no GPU needed): text [n, 24] = the text of v[i] padded with zero bytes, len[i]
+ *   its length.  wc_format_doubles: the same from the device's kernel; HOST pointers, synchronising.  WC_E_LIMIT:
+ *   more than INT_MAX / 24 values.
+ * wc_json_row_bound (host): the most bytes a row's text takes: 25 per value + 2 per chromosome + 2, and 1 more for
+ *   every empty chromosome beyond the first ("[]," is three bytes); -1: a negative size, more than 64 chromosomes or
+ *   more than INT_MAX - 512 values.
+ * wc_json_rows_dev: row i of `rows` (DEVICE float64, row_stride elements apart, the dense layout wc_test_batch_dev
+ *   leaves: chromosome c at the sum of the sizes before it) becomes the compact text [[v,v,...],[...],...]: no white
+ *   space, a chromosome of length 0 is [], no chromosome at all is [].  text_len[i] (DEVICE int64) bytes at text +
+ *   i * text_stride (DEVICE), dense.  BYTES BEHIND text_len[i] ARE NOT WRITTEN.  text is 16-byte aligned and
+ *   text_stride a multiple of 16, at least wc_json_row_bound.  chrom_sizes_host is HOST memory and travels as a kernel
+ *   argument.  Enqueues on `stream` without synchronising, except that a call which has to grow the context's working
+ *   memory (16 bytes per value, 12 per 256 values) allocates, which waits for the device; one call in flight per
+ *   context.  Refused before anything runs, outputs untouched: WC_E_ARG for a negative size or row count, a
+ *   row_stride below the row's values, a text_stride below the bound or no multiple of 16, a NULL pointer; WC_E_LIMIT
+ *   for more than 65535 rows, more than 64 chromosomes, more than INT_MAX - 512 values in a row.
+ * wc_json_rows: the same from HOST pointers, synchronising; text rows need no alignment, only text_len[i] bytes of
+ *   each are written.  times_ms (may be NULL) double [4]: milliseconds of [0] copy in [1] lengths and scan [2] bytes
+ *   [3] copy out.
+ * wc_gzip_bytes / wc_gzip_assemble (host): one gzip member around a raw deflate stream: the fixed header 1f 8b 08 00,
+ *   no time, no name, XFL 0, OS 255; the stream; CRC-32 and ISIZE (input_len modulo 2^32), little-endian.
+ *   wc_gzip_bytes(deflate_len) = deflate_len + 18 is its size; a smaller cap is WC_E_ARG.  The bytes depend on the
+ *   arguments alone.  Members in a row read as one stream.                                                       */
+int wc_format_doubles_host(const double *v, int64_t n, int strict, char *text, uint8_t *len);
+int wc_format_doubles(wc_ctx *ctx, const double *v, int64_t n, int strict, char *text, uint8_t *len);
+int64_t wc_json_row_bound(const int64_t *chrom_sizes, int n_chrom);
+int wc_json_rows_dev(wc_ctx *ctx, void *stream, const double *rows, int64_t row_stride, int64_t n_rows,
+                     const int64_t *chrom_sizes_host, int n_chrom, int strict, unsigned char *text, int64_t text_stride,
+                     int64_t *text_len);
+int wc_json_rows(wc_ctx *ctx, const double *rows, int64_t row_stride, int64_t n_rows, const int64_t *chrom_sizes, int n_chrom,
+                 int strict, unsigned char *text, int64_t text_stride, int64_t *text_len, double *times_ms);
+int64_t wc_gzip_bytes(int64_t deflate_len);
+int wc_gzip_assemble(const unsigned char *deflate, int64_t deflate_len, uint32_t crc, int64_t input_len, unsigned char *out,
+                     int64_t cap, int64_t *out_len);
+
 #ifdef __cplusplus
 }
 #endif

@@ -453,11 +453,56 @@ def run_plotpdf(paths, outdir, args, device=0):
     return _run_plots(paths, outdir, args, device, 'plotpdf', 'pdf', _draw_pdf)
 
 
-def _run_plots(paths, outdir, args, device, command, filetype, draw):
-    """The read / draw / write pipeline of `plotbatch` and `plotpdf`: draw(results, names, cytoband table, args, device)
-    returns the files' bytes."""
+def export_output_names(paths, outdir, gz=False):
+    """<outdir>/<stem>.json (.json.gz) per input; two inputs with the same stem are an error up front."""
+    names, seen = [], {}
+    ending = 'json.gz' if gz else 'json'
+    for path in paths:
+        stem = os.path.basename(path)
+        stem = stem[:-4] if stem.endswith('.npz') else stem
+        if stem in seen:
+            raise ValueError('exportjson: %s and %s would both be written to %s.%s; rename one of them' % (seen[stem], path, stem, ending))
+        seen[stem] = path
+        names.append(os.path.join(outdir, '%s.%s' % (stem, ending)))
+    return names
+
+
+def _load_export(path):
+    """What `exportjson` writes of a result file, or the exception that reading it raised.  `arguments` whose pickle
+    does not load here (a function of another program, stored by reference) are exported as {}."""
+    try:
+        with np.load(path, allow_pickle=True, encoding='latin1') as f:
+            res = dict(results_z=[np.asarray(c, dtype=np.float64) for c in f['results_z']],
+                       results_r=[np.asarray(c, dtype=np.float64) for c in f['results_r']],
+                       results_calls=np.asarray(f['results_calls'], dtype=np.float64),
+                       results_cwz=np.asarray(f['results_cwz'], dtype=np.float64))
+            for key in ('binsize', 'threshold_z', 'asdef', 'aasdef'):
+                res[key] = np.asarray(f[key]).item()
+            try:
+                arguments = f['arguments'].item()
+            except Exception:
+                arguments = {}
+            res['arguments'] = arguments if isinstance(arguments, dict) else {}
+            if [len(c) for c in res['results_r']] != [len(c) for c in res['results_z']]:
+                raise ValueError('results_r and results_z differ in their chromosome lengths')
+            return res
+    except Exception as exc:           # reported by name, the run goes on
+        return exc
+
+
+def run_exportjson(paths, outdir, args, device=0):
+    """`exportjson`: one JSON file per result file (wt.export_json_batch), by run_plotbatch's pipeline and rules."""
+    def draw(results, names, table, args, device):
+        return wt.export_json_batch(results, strict=bool(getattr(args, 'strict', False)), gz=bool(getattr(args, 'gz', False)), device=device)
+    return _run_plots(paths, outdir, args, device, 'exportjson', 'json', draw, load=_load_export,
+                      outs=export_output_names(paths, outdir, bool(getattr(args, 'gz', False))))
+
+
+def _run_plots(paths, outdir, args, device, command, filetype, draw, load=_load_result, outs=None):
+    """The read / draw / write pipeline of `plotbatch`, `plotpdf` and `exportjson`: draw(results, names, cytoband table,
+    args, device) returns the files' bytes; load(path) a result or the exception; outs the files' names."""
     began = time.time()
-    outs = plot_output_names(paths, outdir, filetype, command)
+    outs = plot_output_names(paths, outdir, filetype, command) if outs is None else outs
     batch = max(1, int(getattr(args, 'batch', 64)))
     io_threads = max(1, int(getattr(args, 'io', 8)))
     table = wt.loadCytoBands(args.cytofile) if getattr(args, 'cytofile', None) else None      # once, not once per panel
@@ -465,7 +510,7 @@ def _run_plots(paths, outdir, args, device, command, filetype, draw):
     skipped, writes, shape = [], [], None
     try:
         def start_read(at):
-            return [pool.submit(_load_result, p) for p in paths[at:at + batch]]
+            return [pool.submit(load, p) for p in paths[at:at + batch]]
         ahead = start_read(0)
         for at in range(0, len(paths), batch):
             loaded = [f.result() for f in ahead]
@@ -480,7 +525,7 @@ def _run_plots(paths, outdir, args, device, command, filetype, draw):
                 mine = ([len(c) for c in res['results_z']], res['binsize'])
                 if shape is None:
                     shape = mine
-                    beyond = [c for c in args.chromosomes if not 1 <= c <= len(mine[0])]
+                    beyond = [c for c in getattr(args, 'chromosomes', ()) if not 1 <= c <= len(mine[0])]
                     if beyond:
                         raise ValueError('%s: -chromosomes names %s, %s holds chromosomes 1..%d'
                                          % (command, ','.join(str(c) for c in beyond), path, len(mine[0])))

@@ -10,8 +10,9 @@ Everything numeric runs on the GPU through libwisecondor_hip.so (no CPU path).
 Build-only additions, all off by default: `-gpus N` on `newref` / `testbatch`
 (one process per GPU), the `testbatch` sub-command (many samples per GPU batch), the `convertbatch`
 sub-command (many BAM files, reading file i + 1 while file i is on the GPU and file i - 1 is written), the
-`plotbatch` sub-command (result files to z-score panel PNGs, drawn and deflated on the GPU) and the `plotpdf`
-sub-command (the same panels as vector PDF pages, the content stream written on the GPU).
+`plotbatch` sub-command (result files to z-score panel PNGs, drawn and deflated on the GPU), the `plotpdf`
+sub-command (the same panels as vector PDF pages, the content stream written on the GPU) and the `exportjson`
+sub-command (result files to lossless JSON, the numbers' digits made on the GPU).
 `plot` itself stays refused: its default output is a matplotlib PDF, which this build does not make.
 """
 import argparse
@@ -605,6 +606,27 @@ def toolPlotPdf(args):
         sys.exit(1)
 
 
+# ------------------------------------------------------------------- exportjson ----
+def toolExportJson(args):
+    """`exportjson infiles... outdir` (build-only): <outdir>/<stem>.json (.json.gz with -gz) per result file, every
+    number as json.dumps writes it, so that json.loads gives the stored doubles back bit for bit; the digits of
+    results_z and results_r are made on the GPU.  Files are treated as `plotbatch` treats them: one that cannot be read,
+    or whose chromosome lengths or bin size differ from the first file's, is named and skipped; the exit status is then 1."""
+    from . import ingest
+    try:
+        ingest.export_output_names(args.infiles, args.outdir, args.gz)      # two inputs with one stem: before anything is made
+        os.makedirs(args.outdir, exist_ok=True)
+        written, skipped, wall = ingest.run_exportjson(args.infiles, args.outdir, args)
+    except ValueError as exc:
+        print('ERROR:', exc)
+        sys.exit(2)
+    print('%d files written in %.2f s (%.1f files/s end to end)' % (written, wall, written / wall if wall > 0 else 0.0))
+    for path, reason in skipped:
+        print('ERROR: %s skipped: %s' % (path, reason))
+    if skipped:
+        sys.exit(1)
+
+
 # ---------------------------------------------------------------------- parser ----
 def _not_in_this_build(args):
     print('ERROR: this sub-command is not part of the MI355X build (convert, newref*, test, report, plotbatch only): '
@@ -717,6 +739,15 @@ def buildParser():
     p.add_argument('-batch', type=int, default=64, help='pages per GPU batch')
     p.add_argument('-io', type=int, default=8, help='file read / write threads')
     p.set_defaults(func=toolPlotPdf)
+
+    p = sub.add_parser('exportjson', description='result files as lossless JSON, the digits made on the GPU (build-only)')
+    p.add_argument('infiles', type=str, nargs='+', help='result files written by test / testbatch (.npz)')
+    p.add_argument('outdir', type=str, help='directory receiving <name>.json per result file')
+    p.add_argument('-strict', action='store_true', help='write null for Infinity, -Infinity and NaN (strict JSON)')
+    p.add_argument('-gz', action='store_true', help='write <name>.json.gz, the arrays deflated on the GPU')
+    p.add_argument('-batch', type=int, default=64, help='files per GPU batch')
+    p.add_argument('-io', type=int, default=8, help='file read / write threads')
+    p.set_defaults(func=toolExportJson)
 
     p = sub.add_parser('newref', description='Build a reference from healthy samples in one go')
     p.add_argument('infiles', type=str, nargs='*', help='converted reference samples (.npz)')

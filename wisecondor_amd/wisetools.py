@@ -1349,3 +1349,209 @@ def plot_pdf_batch(results, names, cytofile=None, chromosomes=range(1, 23), colu
         details['times_ms'] = times
         details['size'] = (width, height)
     return out
+
+
+# ------------------------------------------------------------------- exportjson: lossless JSON ----
+JSON_KEYS = ('binsize', 'threshold_z', 'asdef', 'aasdef', 'arguments', 'results_cwz', 'results_calls', 'results_z', 'results_r')
+
+
+def formatDoubles(values, strict=False, device=None):
+    """The text json.dumps gives for every float64 of `values`, as a list of bytes (wc_format_doubles_host; with a
+    device number wc_format_doubles, the same routine in the GPU's kernel)."""
+    lib = _lib.load()
+    v = np.ascontiguousarray(values, dtype=np.float64).ravel()
+    text = np.zeros((len(v), 24), dtype=np.uint8)
+    lens = np.zeros(len(v), dtype=np.uint8)
+    if device is None:
+        _lib.check(lib.wc_format_doubles_host(_lib.ptr(v), len(v), int(bool(strict)), _lib.ptr(text), _lib.ptr(lens)))
+    else:
+        _lib.check(lib.wc_format_doubles(_lib.context(device), _lib.ptr(v), len(v), int(bool(strict)), _lib.ptr(text), _lib.ptr(lens)))
+    flat = text.tobytes()
+    return [flat[24 * i:24 * i + int(n)] for i, n in enumerate(lens)]
+
+
+def jsonRowBound(sizes):
+    """Most bytes the JSON text of one dense row takes (wc_json_row_bound; host only)."""
+    sizes = np.ascontiguousarray(sizes, dtype=np.int64)
+    bound = int(_lib.load().wc_json_row_bound(_lib.ptr(sizes), len(sizes)))
+    if bound < 0:
+        raise ValueError('jsonRowBound: unusable chromosome sizes')
+    return bound
+
+
+def jsonRows(rows, sizes, strict=False, device=0, ctx=None, row_stride=None, times=None):
+    """The compact JSON text [[v,...],[...],...] of every dense float64 row (host array [n, >= sum(sizes)]), written on
+    the GPU (wc_json_rows): a list of bytes.  times: a list that receives [copy in, lengths and scan, bytes, copy out] ms."""
+    lib = _lib.load()
+    rows = np.ascontiguousarray(rows, dtype=np.float64)
+    sizes = np.ascontiguousarray(sizes, dtype=np.int64)
+    n = rows.shape[0]
+    stride = jsonRowBound(sizes)
+    text = np.zeros((n, stride), dtype=np.uint8)
+    lens = np.zeros(n, dtype=np.int64)
+    t_ms = np.zeros(4, dtype=np.float64) if times is not None else None
+    _lib.check(lib.wc_json_rows(ctx or _lib.context(device), _lib.ptr(rows), int(rows.shape[1] if row_stride is None else row_stride), n,
+                                _lib.ptr(sizes), len(sizes), int(bool(strict)), _lib.ptr(text), stride, _lib.ptr(lens), _lib.ptr(t_ms)))
+    if times is not None:
+        times.extend(t_ms.tolist())
+    return [text[i, :lens[i]].tobytes() for i in range(n)]
+
+
+def gzipAssemble(stream, crc, input_len):
+    """One gzip member around a raw deflate stream (wc_gzip_assemble; host only): a fixed header without name or time, the
+    stream, the CRC-32 and the length of the uncompressed bytes."""
+    lib = _lib.load()
+    stream = np.ascontiguousarray(np.frombuffer(bytes(stream), dtype=np.uint8))
+    out = np.zeros(max(1, int(lib.wc_gzip_bytes(len(stream)))), dtype=np.uint8)
+    n = np.zeros(1, dtype=np.int64)
+    _lib.check(lib.wc_gzip_assemble(_lib.ptr(stream), len(stream), int(crc) & 0xffffffff, int(input_len), _lib.ptr(out), len(out), _lib.ptr(n)))
+    return out[:int(n[0])].tobytes()
+
+
+def _json_plain(value):
+    """(True, the value as json.dumps takes it) for bool, int, float, str, None and lists or tuples of those (numpy scalars
+    through .item()); (False, None) for everything else."""
+    if isinstance(value, np.generic):
+        value = value.item()
+    if value is None or isinstance(value, (bool, int, float, str)):
+        return True, value
+    if isinstance(value, (list, tuple)):
+        items = [_json_plain(v) for v in value]
+        if all(ok for ok, _ in items):
+            return True, [v for _, v in items]
+    return False, None
+
+
+def jsonArguments(arguments):
+    """The `arguments` of a result file as the export keeps them: the entries _json_plain takes, keys sorted; everything
+    else (the `func` entry, nested objects) is left out."""
+    kept = {}
+    for key in sorted(arguments, key=str):
+        ok, value = _json_plain(arguments[key])
+        if ok:
+            kept[str(key)] = value
+    return kept
+
+
+def _json_nulls(value):
+    """`value` with every float that is not finite replaced by None."""
+    if isinstance(value, float):
+        return value if value - value == 0 else None
+    if isinstance(value, list):
+        return [_json_nulls(v) for v in value]
+    if isinstance(value, dict):
+        return {k: _json_nulls(v) for k, v in value.items()}
+    return value
+
+
+def jsonHead(result, strict=False):
+    """The host's part of an exported file: '{' and the keys binsize .. results_calls (JSON_KEYS), without the closing
+    brace, as bytes.  result: a dict with binsize, threshold_z, asdef, aasdef (scalars, written as .item() gives them),
+    arguments (a dict), results_cwz and results_calls (rows [int, int, int, float, float]; empty: [])."""
+    import json
+    calls = np.asarray(result['results_calls'], dtype=np.float64).reshape(-1, 5)
+    head = {key: np.asarray(result[key]).item() for key in JSON_KEYS[:4]}
+    head['arguments'] = jsonArguments(result['arguments'])
+    head['results_cwz'] = np.asarray(result['results_cwz'], dtype=np.float64).ravel().tolist()
+    head['results_calls'] = [[int(c[0]), int(c[1]), int(c[2]), float(c[3]), float(c[4])] for c in calls]
+    if strict:
+        head = _json_nulls(head)
+    return json.dumps(head, separators=(',', ':'), allow_nan=not strict)[:-1].encode('ascii')
+
+
+def export_json_batch(results, strict=False, gz=False, device=0, ctx=None, max_rows=65535, details=None):
+    """Result files as lossless JSON: a list of the files' bytes, one per result.  A file is one object with
+    the keys JSON_KEYS in that order; the host writes everything up to results_calls (jsonHead), results_z and results_r
+    are text the GPU writes (wc_json_rows_dev: CPython's own digits, so json.loads returns the stored doubles bit for
+    bit).  strict: Infinity, -Infinity and NaN become null in both parts.  gz: the file is three gzip members in a row,
+    the host part through zlib, `,"results_z":` + the z text and `,"results_r":` + the r text + `}` deflated on the GPU
+    (wc_deflate_rows_dev, one call per row since the rows differ in length), from which only compressed bytes are copied.
+    results: dicts with JSON_KEYS' entries, results_z / results_r as per-chromosome arrays; all share the chromosome
+    lengths.  max_rows: rows per wc_json_rows_dev call (a larger batch is split).  details: a dict that receives
+    'times_ms' (per GPU call [copy in, text, deflate, copy out]) and 'text_bytes' (per file: z, r)."""
+    import torch
+    import zlib
+    if not results:
+        return []
+    lib = _lib.load()
+    sizes = np.array([len(c) for c in results[0]['results_z']], dtype=np.int64)
+    total = int(sizes.sum())
+    for i, res in enumerate(results):
+        for key in ('results_z', 'results_r'):
+            if [len(c) for c in res[key]] != [int(v) for v in sizes]:
+                raise ValueError('sample %d has other chromosome lengths in %s than the first has in results_z' % (i, key))
+    bound = jsonRowBound(sizes)
+    lead = 16                                   # room for the key in front of a row's text, which starts on a multiple of 16
+    stride = lead + (bound + 1 + 15) // 16 * 16
+    keys = (b',"results_z":', b',"results_r":')
+    dev = torch.device('cuda', device)
+    handle = ctx or _lib.context(device)
+    per_call = max(1, int(max_rows) // 2)
+    out = []
+    times, text_bytes = [], []
+    for at in range(0, len(results), per_call):
+        part = results[at:at + per_call]
+        n = len(part)
+        rows = np.zeros((2 * n, max(total, 1)), dtype=np.float64)
+        for i, res in enumerate(part):
+            if total:
+                rows[i, :total] = np.concatenate([np.asarray(c, dtype=np.float64) for c in res['results_z']])
+                rows[n + i, :total] = np.concatenate([np.asarray(c, dtype=np.float64) for c in res['results_r']])
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream().cuda_stream
+            marks = [torch.cuda.Event(enable_timing=True) for _ in range(5)] if details is not None else None
+            if marks:
+                marks[0].record()
+            d_rows = torch.from_numpy(rows).to(dev)
+            text = torch.empty((2 * n, stride), dtype=torch.uint8, device=dev)
+            lens = torch.empty((2 * n,), dtype=torch.int64, device=dev)
+            if marks:
+                marks[1].record()
+            _lib.check(lib.wc_json_rows_dev(handle, stream, d_rows.data_ptr(), rows.shape[1], 2 * n, _lib.ptr(sizes), len(sizes),
+                                            int(bool(strict)), text.data_ptr() + lead, stride, lens.data_ptr()))
+            if marks:
+                marks[2].record()
+            h_lens = lens.cpu().numpy()
+            if np.any(h_lens < 2) or np.any(h_lens > bound):
+                raise _lib.WisecondorHipError('export_json_batch: a row of %d bytes, the bound is %d' % (int(h_lens.max()), bound))
+            if gz:
+                # the key goes in front of the text and the brace behind the r text, so a row is one gzip member's input
+                for k in range(2):
+                    text[k * n:(k + 1) * n, lead - len(keys[k]):lead] = torch.from_numpy(np.frombuffer(keys[k], dtype=np.uint8).copy()).to(dev)
+                text[torch.arange(n, 2 * n, device=dev), lead + lens[n:]] = ord('}')
+                member = h_lens + len(keys[0])
+                member[n:] += 1
+                out_stride = deflateBound(int(member.max()))
+                streams = torch.empty((2 * n, out_stride), dtype=torch.uint8, device=dev)
+                z_lens = torch.empty((2 * n,), dtype=torch.int64, device=dev)
+                crcs = torch.empty((2 * n,), dtype=torch.int32, device=dev)
+                for i in range(2 * n):
+                    _lib.check(lib.wc_deflate_rows_dev(handle, stream, text[i].data_ptr() + lead - len(keys[0]), 1, int(member[i]),
+                                                       int(member[i]), streams[i].data_ptr(), out_stride, z_lens[i:].data_ptr(),
+                                                       crcs[i:].data_ptr()))
+                if marks:
+                    marks[3].record()
+                h_z = z_lens.cpu().numpy()
+                h_crc = crcs.cpu().numpy().view(np.uint32)
+                pieces = [gzipAssemble(streams[i, :int(h_z[i])].cpu().numpy(), h_crc[i], int(member[i])) for i in range(2 * n)]
+            else:
+                if marks:
+                    marks[3].record()
+                pieces = [text[i, lead:lead + int(h_lens[i])].cpu().numpy().tobytes() for i in range(2 * n)]
+            if marks:
+                marks[4].record()
+                marks[4].synchronize()
+                times.append([marks[k].elapsed_time(marks[k + 1]) for k in range(4)])
+        for i, res in enumerate(part):
+            head = jsonHead(res, strict)
+            if gz:
+                packer = zlib.compressobj(6, zlib.DEFLATED, -15)
+                raw = packer.compress(head) + packer.flush()
+                out.append(gzipAssemble(raw, zlib.crc32(head), len(head)) + pieces[i] + pieces[n + i])
+            else:
+                out.append(head + keys[0] + pieces[i] + keys[1] + pieces[n + i] + b'}')
+            text_bytes.append((int(h_lens[i]), int(h_lens[n + i])))
+    if details is not None:
+        details['times_ms'] = times
+        details['text_bytes'] = text_bytes
+    return out
