@@ -263,6 +263,30 @@ def test_png_assemble_with_zlibs_own_stream(lib_plot):
         wt.pngAssemble(0, 75, stream, adler)
 
 
+def test_the_three_assemblers_size_their_files_and_keep_the_stream(lib_plot):
+    """pngAssemble, pdfAssemble and gzipAssemble share one wrapper: each on a zlib stream of its own, the file as long as
+    the library's wc_*_bytes says and the stream read back out of it."""
+    import gzip
+    import pdf_reader as rd
+    from wisecondor_amd import wisetools as wt
+    raws, streams = [], []
+    for k in range(3):
+        raws.append(bytes(bytearray((7 * i * (k + 1) + i // 5) % 251 for i in range(303 + 100 * k))))      # (303: 3 scanlines of 100 pixels)
+        comp = zlib.compressobj(1 + 4 * k, zlib.DEFLATED, -15)
+        streams.append(comp.compress(raws[k]) + comp.flush())
+    assert len({len(s) for s in streams}) == 3
+    png = wt.pngAssemble(100, 3, streams[0], zlib.adler32(raws[0]))
+    assert len(png) == lib_plot.wc_png_bytes(len(streams[0]))
+    assert zlib.decompress(pr.png_chunks(png)[1][1]) == raws[0]
+    pdf = wt.pdfAssemble(28800, 21600, streams[1], zlib.adler32(raws[1]))
+    assert len(pdf) == lib_plot.wc_pdf_bytes(len(streams[1]))
+    assert rd.Document(pdf).page()[1] == raws[1]
+    assert rd.Document(pdf).obj(8)[1][2:-4] == streams[1]
+    gz = wt.gzipAssemble(streams[2], zlib.crc32(raws[2]), len(raws[2]))
+    assert len(gz) == lib_plot.wc_gzip_bytes(len(streams[2]))
+    assert gzip.decompress(gz) == raws[2] and gz[10:-8] == streams[2]
+
+
 def _parse(argv):
     from wisecondor_amd import wisecondor as cli
     return cli.buildParser().parse_args(argv)

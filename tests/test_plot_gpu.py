@@ -140,6 +140,28 @@ def test_the_same_bytes_twice_and_after_a_larger_job(wt, cyto_path):
     assert np.array_equal(scan1[1], want)
 
 
+def test_interleaved_thresholds_keep_their_places(wt):
+    """Five samples whose thresholds alternate take two GPU calls, samples 0, 2, 4 and samples 1, 3: file and scanlines i
+    are those of sample i drawn alone."""
+    case = BY_NAME["one_c1"]
+    results = _results(case, SHIFT3, (1, 0, 2, 3, 1))
+    for res, thr in zip(results, (5.0, 4.0, 5.0, 4.0, 5.0)):
+        res['threshold_z'] = thr
+    names = ["a", "bb_longer", "ccc", "d_the_longest_name", "ee"]
+    W, H = SIZES[0]
+    kw = dict(chromosomes=case['chromosomes'], columns=case['columns'], size=(W / 100.0, H / 100.0), mineffect=case['mineffect'], dpi=100)
+    details = {}
+    pngs = wt.plot_batch(results, names, details=details, **kw)
+    assert len(details['times_ms']) == 2 and details['scanlines'].shape == (5, H, 1 + 3 * W)
+    for i in range(5):
+        one = {}
+        alone = wt.plot_batch(results[i:i + 1], names[i:i + 1], details=one, **kw)
+        assert pngs[i] == alone[0], i
+        assert np.array_equal(details['scanlines'][i], one['scanlines'][0]), i
+        assert len(one['times_ms']) == 1
+    assert len(set(pngs)) == 5                                     # (a sample in another's place would show)
+
+
 @pytest.mark.parametrize("n_bytes", (0, 1, 5551, 5552, 5553, 65536, 65537, 200003))
 def test_adler32_rows_against_zlib(n_bytes, wt):
     rng = np.random.RandomState(n_bytes % 1000)

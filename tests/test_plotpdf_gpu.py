@@ -187,6 +187,73 @@ def test_the_same_bytes_twice_and_after_a_larger_job(wt, cyto_path):
     assert title['text'].rstrip() == pr.TITLE + "b?"
 
 
+def test_interleaved_thresholds_keep_their_places(wt):
+    """Five samples whose thresholds alternate take two GPU calls, samples 0, 2, 4 and samples 1, 3.  A page's bytes
+    depend on its call: the title's record is as wide as the whole batch's longest name needs and a section has the slots of
+    the call's longest list, so a sample drawn alone has other bytes by design (its title record alone is 2 bytes shorter
+    per character its name lacks to the longest).  Byte for byte the batch is therefore held to one call per threshold --
+    the longest name's length occurs in both, so those calls' title width is the batch's -- and to the five single-sample
+    calls in what the reader draws of them."""
+    case = BY_NAME["one_c1"]
+    thresholds = (5.0, 4.0, 5.0, 4.0, 5.0)
+    results = [_case_result(case, s, step) for s, step in zip(SHIFT3, (1, 0, 2, 3, 1))]
+    for res, thr in zip(results, thresholds):
+        res['threshold_z'] = thr
+    names = ["a", "bb_longer", "c_the_longest_name", "d_the_longest_name", "ee"]
+    chroms, size = case['chromosomes'], SIZES[0]
+    files, details = _draw(wt, results, names, chroms, case['columns'], case['mineffect'], size)
+    assert len(details['times_ms']) == len(details['row_bytes']) == len(details['offsets']) == 2
+    assert len(set(files)) == 5 and len(set(details['content'])) == 5     # (a sample in another's place would show)
+    for call, thr in enumerate((4.0, 5.0)):                                 # the calls go by ascending threshold
+        pick = [i for i, t in enumerate(thresholds) if t == thr]
+        part, d = _draw(wt, [results[i] for i in pick], [names[i] for i in pick], chroms, case['columns'], case['mineffect'], size)
+        assert d['row_bytes'] == [details['row_bytes'][call]] and np.array_equal(d['offsets'][0], details['offsets'][call])
+        for k, i in enumerate(pick):
+            assert files[i] == part[k], i
+            assert details['content'][i] == d['content'][k], (i, _first_difference(details['content'][i], d['content'][k]))
+    rstrip = lambda prims: [dict(q, text=q['text'].rstrip()) if q['kind'] == 'text' else q for q in prims]
+    for i in range(5):
+        alone, d = _draw(wt, results[i:i + 1], names[i:i + 1], chroms, case['columns'], case['mineffect'], size)
+        assert rstrip(rd.interpret(d['content'][0])) == rstrip(rd.interpret(details['content'][i])), i
+        assert rd.Document(files[i]).page()[1] == details['content'][i]
+
+
+def test_the_two_tools_alternate_on_one_context(wt, cyto_path):
+    """plotbatch and plotpdf share the context's pinned table block and its device copy, each with a tail of its own
+    behind the tables: PNG of two samples at the largest size, PDF of one with cytobands, PNG of one at the smallest size
+    without, the PDF again -- each as the same call gives it as the first call on a fresh context."""
+    from wisecondor_amd import _lib
+    big, cyto, small = BY_NAME["all22_c2"], BY_NAME["cyto"], BY_NAME["one_c1"]
+
+    def png(ctx, case, n, W, H):
+        details = {}
+        results = [_case_result(case, s) for s in SHIFT3[:n]]
+        files = wt.plot_batch(results, ["png%d" % i for i in range(n)], chromosomes=case['chromosomes'], columns=case['columns'],
+                              size=(W / 100.0, H / 100.0), mineffect=case['mineffect'], dpi=100, ctx=ctx, details=details)
+        return files, details['scanlines'].tobytes()
+
+    def pdf(ctx):
+        details = {}
+        files = wt.plot_pdf_batch([_case_result(cyto)], ["a_pdf_name"], cytofile=cyto_path, chromosomes=cyto['chromosomes'], columns=2,
+                                  size=SIZES[0], mineffect=1.5, ctx=ctx, details=details)
+        return files, details['content'], details['row_bytes'], [list(o) for o in details['offsets']]
+
+    steps = (lambda ctx: png(ctx, big, 2, 400, 300), pdf, lambda ctx: png(ctx, small, 1, 20, 10), pdf)
+    shared = _lib.new_context(0)
+    try:
+        got = [step(shared) for step in steps]
+    finally:
+        _lib.destroy_context(shared)
+    for k, step in enumerate(steps):
+        fresh = _lib.new_context(0)
+        try:
+            want = step(fresh)
+        finally:
+            _lib.destroy_context(fresh)
+        assert got[k] == want, k
+    assert got[1] == got[3] and got[0] != got[2]
+
+
 @pytest.mark.parametrize("size", SIZES, ids=("4x3", "a4"))
 def test_whole_file_through_the_reader(size, wt, cyto_path):
     case = BY_NAME["cyto"]

@@ -170,6 +170,27 @@ struct wc_ctx {
 };
 
 namespace wc {
+// N events for the stage times of a host-array call, destroyed on every way out of it
+template <int N> struct Events {
+    hipEvent_t e[N] = {};
+    ~Events() {
+        for (int i = 0; i < N; ++i)
+            if (e[i]) (void)hipEventDestroy(e[i]);
+    }
+    int create() {
+        for (int i = 0; i < N; ++i) WC_HIP(hipEventCreate(&e[i]));
+        return WC_OK;
+    }
+    // ms[i] = the time from event from[i] to event to[i], for n stages
+    void elapsed(int n, const int *from, const int *to, double *ms) const {
+        for (int i = 0; i < n; ++i) {
+            float t = 0.f;
+            (void)hipEventElapsedTime(&t, e[from[i]], e[to[i]]);
+            ms[i] = t;
+        }
+    }
+};
+
 // eigh.hip: leading eigenpairs of a device-resident symmetric matrix (host outputs)
 int sym_eigh_leading(wc_ctx *ctx, const double *matrix_dev, int64_t n, int n_pairs, double *eigvals_out,
                      double *eigvecs_out);

@@ -253,14 +253,6 @@ int enqueue_rows(wc_ctx *ctx, hipStream_t stream, const double *rows, int64_t ro
     return WC_OK;
 }
 
-struct Events {                                           // destroyed on every way out of a call
-    hipEvent_t e[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    ~Events() {
-        for (int i = 0; i < 5; ++i)
-            if (e[i]) (void)hipEventDestroy(e[i]);
-    }
-};
-
 }  // namespace
 
 extern "C" {
@@ -325,10 +317,9 @@ int wc_json_rows(wc_ctx *ctx, const double *rows, int64_t row_stride, int64_t n_
     if ((rc = ctx->tmp_a.reserve(in_bytes + 16)) || (rc = ctx->tmp_b.reserve((size_t)n_rows * dev_stride)) ||
         (rc = ctx->tmp_c.reserve((size_t)n_rows * 8)))
         return rc;
-    Events events;
+    wc::Events<5> events;
     hipEvent_t *ev = events.e;
-    if (times_ms)
-        for (int i = 0; i < 5; ++i) WC_HIP(hipEventCreate(&ev[i]));
+    if (times_ms && (rc = events.create())) return rc;
     if (times_ms) (void)hipEventRecord(ev[3], nullptr);
     if (in_bytes) WC_HIP(hipMemcpy(ctx->tmp_a.p, rows, in_bytes, hipMemcpyHostToDevice));
     if ((rc = enqueue_rows(ctx, nullptr, ctx->tmp_a.as<double>(), row_stride, n_rows, tab, strict != 0, ctx->tmp_b.as<unsigned char>(), dev_stride,
@@ -345,11 +336,7 @@ int wc_json_rows(wc_ctx *ctx, const double *rows, int64_t row_stride, int64_t n_
         (void)hipEventSynchronize(ev[4]);
         // [0] copy in [1] lengths and scan [2] bytes [3] copy out
         const int from[4] = {3, 0, 1, 2}, to[4] = {0, 1, 2, 4};
-        for (int i = 0; i < 4; ++i) {
-            float ms = 0.f;
-            (void)hipEventElapsedTime(&ms, ev[from[i]], ev[to[i]]);
-            times_ms[i] = ms;
-        }
+        events.elapsed(4, from, to, times_ms);
     }
     return WC_OK;
 }

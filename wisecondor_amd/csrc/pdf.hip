@@ -60,13 +60,16 @@ __device__ const unsigned char PD_CENTS[9][3] = {{0, 0, 0},   {90, 60, 0}, {35, 
                                                  {0, 45, 70}, {80, 40, 0}, {80, 60, 70}, {70, 70, 70}};
 const int PD_GREY = 8;
 
-// floor(v + 0.5) limited to +-PD_LIM; NaN lies at the lower limit
+// pl_rnd limited to +-PD_LIM; NaN lies at the lower limit (where pl_rnd's own value for it would end up: the test is
+// spelled out because without it k_pdf_content takes 90 vector registers instead of 83)
 __device__ __forceinline__ int pd_rnd(double v) {
     if (!(v == v)) return -PD_LIM;
-    v = v < -1e9 ? -1e9 : (v > 1e9 ? 1e9 : v);
-    const int q = (int)floor(v + 0.5);
+    const int q = pl_rnd(v);
     return q < -PD_LIM ? -PD_LIM : (q > PD_LIM ? PD_LIM : q);
 }
+
+// pl_alpha's value through pd_rnd: with pl_alpha itself the kernel's instructions change and the content stage measured
+// 0.6 - 1.1 % slower; this form compiles to the instructions it had before
 __device__ __forceinline__ int pd_alpha(double alpha) {
     const int a = pd_rnd(255.0 * alpha);
     return a < 0 ? 0 : (a > 255 ? 255 : a);
@@ -160,11 +163,7 @@ __device__ __forceinline__ Panel pd_panel(const PdfArgs &A, long long smp, int p
     const int n = A.counts[smp * A.P + p];
     Q.n_ent = n > A.cap ? A.cap : n;
     Q.nb = A.band_off ? A.band_off[p + 1] - A.band_off[p] : 0;
-    const double thr = A.thr, cyto_y = -thr - thr / 2.0, base = A.has_cyto ? cyto_y : -thr;
-    const double lo = Q.ent[4] < base ? Q.ent[4] : base, hi = Q.ent[5] > thr ? Q.ent[5] : thr;
-    const double pad = (hi - lo) * 0.05, ylo = lo - pad;
-    Q.yhi = hi + pad;
-    Q.yspan = Q.yhi - ylo;
+    pl_yrange(Q.ent[4], Q.ent[5], A.thr, A.has_cyto, Q.yhi, Q.yspan);
     return Q;
 }
 
@@ -392,24 +391,20 @@ int64_t build_sections(const int64_t *chrom_sizes, const int32_t *panel_chrom, i
     return at;
 }
 
-int check_page(const int64_t *chrom_sizes, int n_chrom, const int32_t *panel_chrom, int n_panels, const int32_t *band_off, int name_cap) {
+int check_page(const int64_t *chrom_sizes, int n_chrom, const int32_t *panel_chrom, int n_panels, int64_t row_stride,
+               const int32_t *band_off, int name_cap) {
     int rc;
-    if ((rc = wc::plot_check_panels(chrom_sizes, n_chrom, panel_chrom, n_panels, LLONG_MAX))) return rc;
+    if ((rc = wc::plot_check_page("pdf", chrom_sizes, n_chrom, panel_chrom, n_panels, row_stride, band_off))) return rc;
     WC_CHECK(name_cap >= 1 && name_cap <= 4096, WC_E_ARG, "pdf: names of %d bytes (1 .. 4096)", name_cap);
-    if (band_off) {
-        WC_CHECK(band_off[0] == 0, WC_E_ARG, "pdf: unusable cytoband table");
-        for (int p = 0; p < n_panels; ++p) WC_CHECK(band_off[p + 1] >= band_off[p], WC_E_ARG, "pdf: unusable cytoband table");
-    }
     return WC_OK;
 }
 
-// the call's small tables in one pinned block: what the list kernel needs goes first and is sent before it, the
-// section table and the content kernel's arguments follow once the counts are known
+// a call's page plan (plot_label.h) -- its tail is the section table, then the content kernel's arguments, sent once the
+// lists' counts are known -- and what pdf_lists leaves for pdf_pages
 struct Plan {
-    size_t off_chrom_off = 0, off_chrom_len = 0, off_bands = 0, off_panel = 0, off_boxes = 0, off_band_off = 0, off_names = 0,
-           off_secs = 0, off_args = 0, bytes = 0;
-    int n_panels = 0, n_sec = 0, cap = 0, name_cap = 0, Wc = 0, Hc = 0, has_cyto = 0;
-    int64_t n_samples = 0, row_stride = 0, row_bytes = 0, bound = 0;
+    wc::PagePlan page;
+    int n_sec = 0, Wc = 0, Hc = 0;
+    int64_t n_samples = 0, row_stride = 0, row_bytes = 0;
     double thr = 0.0;
     const double *z = nullptr;
     std::vector<int32_t> slots;
@@ -419,8 +414,7 @@ struct Plan {
 // the arguments and, for the worst case, what the deflate stage takes in one call: held before anything is touched
 int pdf_check(const wc_ctx *ctx, const double *results_z, int64_t row_stride, int64_t n_samples, const int64_t *chrom_sizes, int n_chrom,
               const double *calls, const int32_t *n_calls, int max_calls, double threshold, const int32_t *panel_chrom, int n_panels,
-              int columns, const double *bands, const int32_t *band_off, const char *names, int name_cap, int width_cp, int height_cp,
-              int64_t *bound_out) {
+              int columns, const int32_t *band_off, const char *names, int name_cap, int width_cp, int height_cp, int64_t *bound_out) {
     WC_CHECK(ctx && n_samples >= 1 && max_calls >= 0 && (max_calls == 0 || (calls && n_calls)) && names && columns >= 1 &&
                  row_stride >= 0 && (results_z || row_stride == 0),
              WC_E_ARG, "pdf: unusable argument");
@@ -428,10 +422,7 @@ int pdf_check(const wc_ctx *ctx, const double *results_z, int64_t row_stride, in
     WC_CHECK(width_cp >= 1 && height_cp >= 1 && width_cp <= 1440000 && height_cp <= 1440000, WC_E_ARG,
              "pdf: a page of %d x %d centipoints (1 .. 1440000 each)", width_cp, height_cp);
     int rc;
-    if ((rc = wc::plot_check_panels(chrom_sizes, n_chrom, panel_chrom, n_panels, row_stride)) ||
-        (rc = check_page(chrom_sizes, n_chrom, panel_chrom, n_panels, band_off, name_cap)))
-        return rc;
-    WC_CHECK(!band_off || bands || band_off[n_panels] == 0, WC_E_ARG, "pdf: unusable cytoband table");
+    if ((rc = check_page(chrom_sizes, n_chrom, panel_chrom, n_panels, row_stride, band_off, name_cap))) return rc;
     const int64_t bound = wc_plot_pdf_row_bound(chrom_sizes, n_chrom, panel_chrom, n_panels, band_off, max_calls, name_cap);
     WC_CHECK(bound > 0, WC_E_LIMIT, "pdf: the page's content does not fit a row");
     const int64_t n_blk = (bound + wc_deflate_block_bytes() - 1) / wc_deflate_block_bytes();
@@ -441,65 +432,23 @@ int pdf_check(const wc_ctx *ctx, const double *results_z, int64_t row_stride, in
     return WC_OK;
 }
 
-// tables, the display lists, and the read-back of their counts (the call's one synchronise)
+// tables, the display lists, and the read-back of their counts (the call's one synchronise); `bound` is pdf_check's
 int pdf_lists(wc_ctx *ctx, hipStream_t stream, const double *results_z, int64_t row_stride, int64_t n_samples,
               const int64_t *chrom_sizes, int n_chrom, const double *calls, const int32_t *n_calls, int max_calls, double threshold,
               double mineffect, const int32_t *panel_chrom, int n_panels, int columns, const double *bands, const int32_t *band_off,
-              const char *names, int name_cap, int width_cp, int height_cp, Plan &L, hipEvent_t *ev) {
+              const char *names, int name_cap, int width_cp, int height_cp, int64_t bound, Plan &L, hipEvent_t *ev) {
     int rc;
-    int64_t bound = 0;
-    if ((rc = pdf_check(ctx, results_z, row_stride, n_samples, chrom_sizes, n_chrom, calls, n_calls, max_calls, threshold, panel_chrom,
-                        n_panels, columns, bands, band_off, names, name_cap, width_cp, height_cp, &bound)))
-        return rc;
-    const int rows = (n_panels + columns - 1) / columns;
-    std::vector<int32_t> boxes(4 * (size_t)n_panels);
-    if ((rc = wc_plot_layout(width_cp, height_cp, rows, columns, n_panels, boxes.data()))) return rc;
-    int64_t longest = 0;
-    for (int p = 0; p < n_panels; ++p) longest = chrom_sizes[panel_chrom[p] - 1] > longest ? chrom_sizes[panel_chrom[p] - 1] : longest;
-    const int64_t cap64 = 1 + (longest + 1) / 2 + max_calls;
-    WC_CHECK(cap64 <= INT_MAX / 2, WC_E_LIMIT, "pdf: lists of %lld entries", (long long)cap64);
-    L.n_panels = n_panels; L.n_sec = PD_PER_PANEL * n_panels + 2; L.cap = (int)cap64; L.name_cap = name_cap;
-    L.Wc = width_cp; L.Hc = height_cp; L.has_cyto = band_off ? 1 : 0; L.n_samples = n_samples; L.row_stride = row_stride;
-    L.bound = bound; L.thr = threshold; L.z = results_z;
-    const int n_bands = band_off ? band_off[n_panels] : 0;
-    size_t at = 0;
-    L.off_chrom_off = at; at += 8 * (size_t)n_chrom;
-    L.off_chrom_len = at; at += 8 * (size_t)n_chrom;
-    L.off_bands = at; at += 32 * (size_t)n_bands;
-    L.off_panel = at; at += 4 * (size_t)n_panels;
-    L.off_boxes = at; at += 16 * (size_t)n_panels;
-    L.off_band_off = at; at += 4 * (size_t)(n_panels + 1);
-    L.off_names = at; at += (size_t)n_samples * name_cap;
-    at = (at + 7) & ~(size_t)7;
-    L.off_secs = at; at += sizeof(PdfSec) * (size_t)L.n_sec;
-    L.off_args = at; at += sizeof(PdfArgs);
-    L.bytes = (at + 7) & ~(size_t)7;
-    WC_HIP(hipSetDevice(ctx->device));
-    if ((rc = ctx->pl_host_reserve(L.bytes)) || (rc = ctx->pl_tab.reserve(L.bytes)) ||
-        (rc = ctx->pl_list.reserve((size_t)n_samples * n_panels * L.cap * PD_F * 8)) ||
+    wc::PagePlan &P = L.page;
+    L.n_sec = PD_PER_PANEL * n_panels + 2; L.Wc = width_cp; L.Hc = height_cp; L.n_samples = n_samples; L.row_stride = row_stride;
+    L.thr = threshold; L.z = results_z;
+    if ((rc = wc::page_plan(ctx, "pdf", chrom_sizes, n_chrom, panel_chrom, n_panels, row_stride, max_calls, columns, width_cp, height_cp,
+                            bands, band_off, names, n_samples, name_cap, sizeof(PdfSec) * (size_t)L.n_sec + sizeof(PdfArgs), P)) ||
+        (rc = ctx->pl_list.reserve((size_t)n_samples * n_panels * P.cap * PD_F * 8)) ||
         (rc = ctx->pl_counts.reserve((size_t)n_samples * (n_panels + 1) * 4)) || (rc = ctx->pl_status.reserve(8)) ||
-        (rc = ctx->ensure_pinned((size_t)n_samples * n_panels * 4)))
+        (rc = ctx->ensure_pinned((size_t)n_samples * n_panels * 4)) || (rc = wc::page_send(ctx, stream, 0, P.tail)))
         return rc;
-    unsigned char *h = ctx->pl_host;
-    memset(h, 0, L.bytes);
-    int64_t run = 0;
-    for (int c = 0; c < n_chrom; ++c) {
-        memcpy(h + L.off_chrom_off + 8 * c, &run, 8);
-        memcpy(h + L.off_chrom_len + 8 * c, &chrom_sizes[c], 8);
-        run += chrom_sizes[c];
-    }
-    if (n_bands) memcpy(h + L.off_bands, bands, 32 * (size_t)n_bands);
-    memcpy(h + L.off_panel, panel_chrom, 4 * (size_t)n_panels);
-    memcpy(h + L.off_boxes, boxes.data(), 16 * (size_t)n_panels);
-    if (band_off) memcpy(h + L.off_band_off, band_off, 4 * (size_t)(n_panels + 1));
-    memcpy(h + L.off_names, names, (size_t)n_samples * name_cap);
-    WC_HIP(hipMemcpyAsync(ctx->pl_tab.p, h, L.off_secs, hipMemcpyHostToDevice, stream));
     if (ev) WC_HIP(hipEventRecord(ev[0], stream));
-    const unsigned char *tab = ctx->pl_tab.as<unsigned char>();
-    if ((rc = wc::plot_list_launch(stream, results_z, row_stride, n_samples, (const long long *)(tab + L.off_chrom_off),
-                                   (const long long *)(tab + L.off_chrom_len), (const int *)(tab + L.off_panel), calls, n_calls, max_calls,
-                                   threshold, mineffect, n_panels, L.cap, ctx->pl_list.as<double>(), ctx->pl_counts.as<int>(),
-                                   ctx->pl_status.as<int>())))
+    if ((rc = wc::plot_list_launch(ctx, stream, P, results_z, row_stride, n_samples, calls, n_calls, max_calls, threshold, mineffect, P.cap)))
         return rc;
     // the slot counts of the sections: per panel the largest list among the samples
     WC_HIP(hipMemcpyAsync(ctx->pinned, ctx->pl_counts.p, (size_t)n_samples * n_panels * 4, hipMemcpyDeviceToHost, stream));
@@ -509,7 +458,7 @@ int pdf_lists(wc_ctx *ctx, hipStream_t stream, const double *results_z, int64_t 
     for (int64_t s = 0; s < n_samples; ++s)
         for (int p = 0; p < n_panels; ++p) {
             int n = counts[s * n_panels + p] - 1;
-            n = n > L.cap - 1 ? L.cap - 1 : n;
+            n = n > P.cap - 1 ? P.cap - 1 : n;
             L.slots[p] = n > L.slots[p] ? n : L.slots[p];
         }
     L.row_bytes = build_sections(chrom_sizes, panel_chrom, n_panels, band_off, L.slots.data(), name_cap, &L.secs);
@@ -522,37 +471,34 @@ int pdf_lists(wc_ctx *ctx, hipStream_t stream, const double *results_z, int64_t 
 // the content kernel, Adler-32 and deflate, enqueued
 int pdf_pages(wc_ctx *ctx, hipStream_t stream, const Plan &L, unsigned char *content, int64_t content_stride, unsigned char *streams,
               int64_t out_stride, int64_t *out_len, uint32_t *adler, hipEvent_t *ev) {
+    const wc::PagePlan &P = L.page;
     const int64_t padded = (L.row_bytes + 15) / 16 * 16;
     WC_CHECK(content_stride >= padded && content_stride % 16 == 0 && ((uintptr_t)content & 15) == 0, WC_E_ARG,
              "pdf: content rows %lld bytes apart (a multiple of 16, at least %lld, from an address that is one)", (long long)content_stride,
              (long long)padded);
     WC_CHECK(out_stride >= wc_deflate_bound(L.row_bytes), WC_E_ARG, "pdf: %lld bytes per stream, wc_deflate_bound(%lld) is %lld",
              (long long)out_stride, (long long)L.row_bytes, (long long)wc_deflate_bound(L.row_bytes));
-    unsigned char *h = ctx->pl_host;
-    const unsigned char *tab = ctx->pl_tab.as<unsigned char>();
+    const size_t sec_bytes = sizeof(PdfSec) * L.secs.size();
     PdfArgs A;
-    A.Wc = L.Wc; A.Hc = L.Hc; A.P = L.n_panels; A.cap = L.cap; A.has_cyto = L.has_cyto; A.name_cap = L.name_cap; A.n_sec = L.n_sec;
-    A.title_cap = title_cap_of(L.name_cap); A.row_stride = L.row_stride; A.row_bytes = L.row_bytes; A.out_stride = content_stride;
+    A.Wc = L.Wc; A.Hc = L.Hc; A.P = P.n_panels; A.cap = P.cap; A.has_cyto = P.has_cyto; A.name_cap = P.name_cap; A.n_sec = L.n_sec;
+    A.title_cap = title_cap_of(P.name_cap); A.row_stride = L.row_stride; A.row_bytes = L.row_bytes; A.out_stride = content_stride;
     A.thr = L.thr; A.z = L.z;
-    A.chrom_off = (const long long *)(tab + L.off_chrom_off); A.chrom_len = (const long long *)(tab + L.off_chrom_len);
-    A.panel_chrom = (const int *)(tab + L.off_panel); A.boxes = (const int *)(tab + L.off_boxes);
-    A.band_off = L.has_cyto ? (const int *)(tab + L.off_band_off) : nullptr; A.bands = (const double *)(tab + L.off_bands);
-    A.entries = ctx->pl_list.as<double>(); A.counts = ctx->pl_counts.as<int>(); A.names = (const char *)(tab + L.off_names);
-    A.secs = (const PdfSec *)(tab + L.off_secs);
-    memcpy(h + L.off_secs, L.secs.data(), sizeof(PdfSec) * L.secs.size());
-    memcpy(h + L.off_args, &A, sizeof(PdfArgs));
-    WC_HIP(hipMemcpyAsync(ctx->pl_tab.as<unsigned char>() + L.off_secs, h + L.off_secs, L.bytes - L.off_secs, hipMemcpyHostToDevice, stream));
-    WC_HIP(hipEventRecord(ctx->pl_sent, stream));
+    A.chrom_off = P.chrom_off; A.chrom_len = P.chrom_len; A.panel_chrom = P.panel_chrom; A.boxes = P.boxes; A.band_off = P.band_off;
+    A.bands = P.bands; A.entries = ctx->pl_list.as<double>(); A.counts = ctx->pl_counts.as<int>(); A.names = P.names;
+    A.secs = (const PdfSec *)P.tail_dev;
+    memcpy(P.tail_host, L.secs.data(), sec_bytes);
+    memcpy(P.tail_host + sec_bytes, &A, sizeof(PdfArgs));
+    int rc;
+    if ((rc = wc::page_send(ctx, stream, P.tail, P.bytes))) return rc;
     hipLaunchKernelGGL(k_pdf_content, dim3((unsigned)((padded + PD_CHUNK - 1) / PD_CHUNK), (unsigned)L.n_samples), dim3(PD_T), 0, stream,
-                       (const PdfArgs *)(tab + L.off_args), content);
+                       (const PdfArgs *)(P.tail_dev + sec_bytes), content);
     WC_HIP(hipGetLastError());
     if (ev) WC_HIP(hipEventRecord(ev[2], stream));
-    int rc;
     if ((rc = wc_adler32_rows_dev(ctx, stream, content, L.n_samples, L.row_bytes, content_stride, adler))) return rc;
     if (ev) WC_HIP(hipEventRecord(ev[3], stream));
     // the CRC-32 words of the deflate call are not needed; they go behind the lists' counts
     if ((rc = wc_deflate_rows_dev(ctx, stream, content, L.n_samples, L.row_bytes, content_stride, streams, out_stride, out_len,
-                                  ctx->pl_counts.as<uint32_t>() + L.n_samples * L.n_panels)))
+                                  ctx->pl_counts.as<uint32_t>() + L.n_samples * P.n_panels)))
         return rc;
     if (ev) WC_HIP(hipEventRecord(ev[4], stream));
     return WC_OK;
@@ -616,7 +562,7 @@ extern "C" {
 
 int64_t wc_plot_pdf_sections(const int64_t *chrom_sizes, int n_chrom, const int32_t *panel_chrom, int n_panels, const int32_t *band_off,
                              const int32_t *slots, int name_cap, int64_t *starts_out) {
-    if (!slots || check_page(chrom_sizes, n_chrom, panel_chrom, n_panels, band_off, name_cap)) return -1;
+    if (!slots || check_page(chrom_sizes, n_chrom, panel_chrom, n_panels, LLONG_MAX, band_off, name_cap)) return -1;
     double most = 0.0;                                       // held in floating point first: the sum below must not wrap
     for (int p = 0; p < n_panels; ++p) {
         if (slots[p] < 0) return -1;
@@ -634,7 +580,7 @@ int64_t wc_plot_pdf_sections(const int64_t *chrom_sizes, int n_chrom, const int3
 
 int64_t wc_plot_pdf_row_bound(const int64_t *chrom_sizes, int n_chrom, const int32_t *panel_chrom, int n_panels, const int32_t *band_off,
                               int max_calls, int name_cap) {
-    if (max_calls < 0 || check_page(chrom_sizes, n_chrom, panel_chrom, n_panels, band_off, name_cap)) return -1;
+    if (max_calls < 0 || check_page(chrom_sizes, n_chrom, panel_chrom, n_panels, LLONG_MAX, band_off, name_cap)) return -1;
     std::vector<int32_t> slots((size_t)n_panels);
     for (int p = 0; p < n_panels; ++p) {
         const int64_t n = (chrom_sizes[panel_chrom[p] - 1] + 1) / 2 + max_calls;      // alternating zeros: ceil(bins / 2) patches
@@ -653,10 +599,14 @@ int wc_plot_pdf_batch_dev(wc_ctx *ctx, void *stream_, const double *results_z, i
     WC_CHECK(streams && out_len && adler && status && row_bytes_host, WC_E_ARG, "pdf: NULL output");
     hipStream_t stream = (hipStream_t)stream_;
     Plan L;
-    int rc = pdf_lists(ctx, stream, results_z, row_stride, n_samples, chrom_sizes_host, n_chrom, calls, n_calls, max_calls, threshold,
-                       mineffect, panel_chrom_host, n_panels, columns, bands_host, band_off_host, names_host, name_cap, width_cp, height_cp,
-                       L, nullptr);
-    if (rc) return rc;
+    int rc;
+    int64_t bound = 0;
+    if ((rc = pdf_check(ctx, results_z, row_stride, n_samples, chrom_sizes_host, n_chrom, calls, n_calls, max_calls, threshold,
+                        panel_chrom_host, n_panels, columns, band_off_host, names_host, name_cap, width_cp, height_cp, &bound)) ||
+        (rc = pdf_lists(ctx, stream, results_z, row_stride, n_samples, chrom_sizes_host, n_chrom, calls, n_calls, max_calls, threshold,
+                        mineffect, panel_chrom_host, n_panels, columns, bands_host, band_off_host, names_host, name_cap, width_cp,
+                        height_cp, bound, L, nullptr)))
+        return rc;
     const int64_t padded = (L.row_bytes + 15) / 16 * 16;
     if (!content) {
         if ((rc = ctx->pl_img.reserve((size_t)n_samples * padded))) return rc;
@@ -680,76 +630,30 @@ int wc_plot_pdf_batch(wc_ctx *ctx, const double *results_z, int64_t row_stride, 
     int64_t bound = 0;
     // (with the host's pointers standing in for the device's: only whether they are there is looked at)
     if ((rc = pdf_check(ctx, results_z, row_stride, n_samples, chrom_sizes, n_chrom, calls, n_calls, max_calls, threshold, panel_chrom,
-                        n_panels, columns, bands, band_off, names, name_cap, width_cp, height_cp, &bound)))
+                        n_panels, columns, band_off, names, name_cap, width_cp, height_cp, &bound)))
         return rc;
     WC_HIP(hipSetDevice(ctx->device));
-    const size_t zb = (size_t)n_samples * row_stride * 8, cb = (size_t)n_samples * max_calls * 40, nb = (size_t)n_samples * 4;
-    // tmp_a: z rows | calls | call counts; tmp_b: the streams; tmp_c: their lengths; tmp_d: the Adler-32 words
-    const size_t off_calls = (zb + 15) & ~(size_t)15, off_n = off_calls + ((cb + 15) & ~(size_t)15);
-    if ((rc = ctx->tmp_a.reserve(off_n + nb + 16)) || (rc = ctx->tmp_c.reserve((size_t)n_samples * 8)) ||
-        (rc = ctx->tmp_d.reserve((size_t)n_samples * 4)))
-        return rc;
-    struct Events {                                       // destroyed on every way out of the call
-        hipEvent_t e[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-        ~Events() {
-            for (int i = 0; i < 7; ++i)
-                if (e[i]) (void)hipEventDestroy(e[i]);
-        }
-    } events;
-    hipEvent_t *ev = events.e;
-    if (times_ms)
-        for (int i = 0; i < 7; ++i) WC_HIP(hipEventCreate(&ev[i]));
-    unsigned char *base = ctx->tmp_a.as<unsigned char>();
-    if (times_ms) (void)hipEventRecord(ev[5], nullptr);
-    if (zb && results_z) WC_HIP(hipMemcpy(base, results_z, zb, hipMemcpyHostToDevice));
-    if (cb && calls) WC_HIP(hipMemcpy(base + off_calls, calls, cb, hipMemcpyHostToDevice));
-    if (max_calls && n_calls) WC_HIP(hipMemcpy(base + off_n, n_calls, nb, hipMemcpyHostToDevice));
+    wc::HostBatch B;
     Plan L;
-    rc = pdf_lists(ctx, nullptr, results_z ? (const double *)base : nullptr, row_stride, n_samples, chrom_sizes, n_chrom,
-                   calls ? (const double *)(base + off_calls) : nullptr, n_calls ? (const int32_t *)(base + off_n) : nullptr, max_calls,
-                   threshold, mineffect, panel_chrom, n_panels, columns, bands, band_off, names, name_cap, width_cp, height_cp, L,
-                   times_ms ? ev : nullptr);
-    if (rc) return rc;
+    if ((rc = B.stage(ctx, results_z, row_stride, n_samples, calls, n_calls, max_calls, times_ms != nullptr)) ||
+        (rc = pdf_lists(ctx, nullptr, B.z, row_stride, n_samples, chrom_sizes, n_chrom, B.calls, B.n_calls, max_calls, threshold, mineffect,
+                        panel_chrom, n_panels, columns, bands, band_off, names, name_cap, width_cp, height_cp, bound, L, B.ev)))
+        return rc;
     // the device's rows and streams are sized by what this batch needs, the caller's by the bound it could know
     const int64_t padded = (L.row_bytes + 15) / 16 * 16, dev_stride = wc_deflate_bound(L.row_bytes);
     WC_CHECK(out_stride >= dev_stride && (!content_out || content_stride >= L.row_bytes), WC_E_ARG,
              "pdf: %lld bytes per stream and %lld per content row, %lld and %lld are needed", (long long)out_stride,
              (long long)content_stride, (long long)dev_stride, (long long)L.row_bytes);
-    if ((rc = ctx->pl_img.reserve((size_t)n_samples * padded)) || (rc = ctx->tmp_b.reserve((size_t)n_samples * dev_stride))) return rc;
-    if ((rc = pdf_pages(ctx, nullptr, L, ctx->pl_img.as<unsigned char>(), padded, ctx->tmp_b.as<unsigned char>(), dev_stride,
-                        ctx->tmp_c.as<int64_t>(), ctx->tmp_d.as<uint32_t>(), times_ms ? ev : nullptr)))
+    if ((rc = ctx->pl_img.reserve((size_t)n_samples * padded)) || (rc = ctx->tmp_b.reserve((size_t)n_samples * dev_stride)) ||
+        (rc = pdf_pages(ctx, nullptr, L, ctx->pl_img.as<unsigned char>(), padded, ctx->tmp_b.as<unsigned char>(), dev_stride,
+                        ctx->tmp_c.as<int64_t>(), ctx->tmp_d.as<uint32_t>(), B.ev)) ||
+        (rc = B.collect(ctx, "pdf", n_samples, dev_stride, streams_out, out_stride, out_len, adler_out)))
         return rc;
-    int status = 0;
-    WC_HIP(hipMemcpy(&status, ctx->pl_status.p, 4, hipMemcpyDeviceToHost));
-    if (status) {
-        wc::set_error("pdf: a display list outgrew its capacity (status %d)", status);
-        return WC_E_INTERNAL;
-    }
-    WC_HIP(hipMemcpy(out_len, ctx->tmp_c.p, (size_t)n_samples * 8, hipMemcpyDeviceToHost));
-    WC_HIP(hipMemcpy(adler_out, ctx->tmp_d.p, (size_t)n_samples * 4, hipMemcpyDeviceToHost));
-    for (int64_t i = 0; i < n_samples; ++i) {
-        WC_CHECK(out_len[i] >= 0 && out_len[i] <= dev_stride, WC_E_INTERNAL, "pdf: a stream of %lld bytes in a slot of %lld",
-                 (long long)out_len[i], (long long)dev_stride);
-        if (out_len[i] > 0)
-            WC_HIP(hipMemcpy(streams_out + i * out_stride, ctx->tmp_b.as<unsigned char>() + i * dev_stride, (size_t)out_len[i],
-                             hipMemcpyDeviceToHost));
-    }
     if (content_out && L.row_bytes > 0)
         WC_HIP(hipMemcpy2D(content_out, (size_t)content_stride, ctx->pl_img.p, (size_t)padded, (size_t)L.row_bytes, (size_t)n_samples,
                            hipMemcpyDeviceToHost));
     report(L, row_bytes_out, offsets_out);
-    if (times_ms) {
-        (void)hipEventRecord(ev[6], nullptr);
-        (void)hipEventSynchronize(ev[6]);
-        // [0] copy in (inputs and tables) [1] list and the counts' way back [2] content [3] Adler-32 [4] deflate [5] copy out
-        const int from[6] = {5, 0, 1, 2, 3, 4}, to[6] = {0, 1, 2, 3, 4, 6};
-        for (int i = 0; i < 6; ++i) {
-            float ms = 0.f;
-            (void)hipEventElapsedTime(&ms, ev[from[i]], ev[to[i]]);
-            times_ms[i] = ms;
-        }
-        times_ms[6] = times_ms[7] = 0.0;
-    }
+    B.times(times_ms);      // [1] list and the counts' way back [2] content [3] Adler-32 [4] deflate
     return WC_OK;
 }
 
@@ -782,7 +686,7 @@ int wc_pdf_assemble(int width_cp, int height_cp, const unsigned char *deflate, i
     p[1] = 0x01;
     memcpy(p + 2, deflate, (size_t)deflate_len);
     p += 2 + deflate_len;
-    p[0] = (unsigned char)(adler >> 24); p[1] = (unsigned char)(adler >> 16); p[2] = (unsigned char)(adler >> 8); p[3] = (unsigned char)adler;
+    wc::put32(p, adler);
     p += 4;
     memcpy(p, PD_CONTENT_TAIL, strlen(PD_CONTENT_TAIL));
     p += strlen(PD_CONTENT_TAIL);

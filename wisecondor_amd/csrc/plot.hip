@@ -175,21 +175,6 @@ struct RasterArgs {
     unsigned char *out;
 };
 
-// floor(v + 0.5) and floor(v) as int; values beyond +-1e9 stop there, NaN lies nowhere
-__device__ __forceinline__ int pl_rnd(double v) {
-    if (!(v == v)) return -2000000000;
-    v = v < -1e9 ? -1e9 : (v > 1e9 ? 1e9 : v);
-    return (int)floor(v + 0.5);
-}
-__device__ __forceinline__ int pl_flr(double v) {
-    if (!(v == v)) return -2000000000;
-    v = v < -1e9 ? -1e9 : (v > 1e9 ? 1e9 : v);
-    return (int)floor(v);
-}
-__device__ __forceinline__ int pl_alpha(double alpha) {
-    const int a = pl_rnd(255.0 * alpha);
-    return a < 0 ? 0 : (a > 255 ? 255 : a);
-}
 struct Rgb {
     int r, g, b;
 };
@@ -251,11 +236,7 @@ __global__ __launch_bounds__(PL_T) void k_plot_raster(const RasterArgs *args) {
                 n_ent = n_ent > A.cap ? A.cap : n_ent;
                 nz = (int)ent[8];
                 has_bands = A.band_off && A.band_off[cur + 1] > A.band_off[cur];
-                const double base = A.has_cyto ? cyto_y : -thr;
-                const double lo = ent[4] < base ? ent[4] : base, hi = ent[5] > thr ? ent[5] : thr;
-                const double pad = (hi - lo) * 0.05, ylo = lo - pad;
-                yhi = hi + pad;
-                yspan = yhi - ylo;
+                pl_yrange(ent[4], ent[5], thr, A.has_cyto, yhi, yspan);
                 // the polyline in this column: min and max of the segments that cross it, taken at the column's edges
                 span_lo = INT_MAX;
                 span_hi = INT_MIN;
@@ -442,12 +423,6 @@ __global__ void k_adler_rows(const unsigned *__restrict__ part, long long row_by
 
 int64_t adler_blocks_of(int64_t row_bytes) { return row_bytes <= 0 ? 1 : (row_bytes + PL_ADLER_B - 1) / PL_ADLER_B; }
 
-// the host tables of a call, laid out in one block (8-byte fields first) and copied with one transfer
-struct Tables {
-    size_t off_chrom_off = 0, off_chrom_len = 0, off_bands = 0, off_panel = 0, off_boxes = 0, off_band_off = 0, off_names = 0,
-           off_font = 0, off_args = 0, bytes = 0;
-};
-
 int check_panels(const int64_t *chrom_sizes, int n_chrom, const int32_t *panel_chrom, int n_panels, int64_t row_stride) {
     WC_CHECK(chrom_sizes && n_chrom >= 1 && n_chrom <= WC_CV_MAX_CHROM && panel_chrom && n_panels >= 1 && n_panels <= 1024, WC_E_ARG,
              "plot: %d chromosomes (1 .. %d), %d panels (1 .. 1024)", n_chrom, WC_CV_MAX_CHROM, n_panels);
@@ -464,82 +439,125 @@ int check_panels(const int64_t *chrom_sizes, int n_chrom, const int32_t *panel_c
     return WC_OK;
 }
 
-// fills ctx->pl_host with the tables (bands, boxes, names may be absent) and sizes ctx->pl_tab for them
-int plan_tables(wc_ctx *ctx, hipStream_t stream, const int64_t *chrom_sizes, int n_chrom, const int32_t *panel_chrom, int n_panels,
-                  const double *bands, const int32_t *band_off, const int32_t *boxes, const char *names, int64_t n_samples,
-                  int name_cap, Tables &T) {
-    const int n_bands = band_off ? band_off[n_panels] : 0;
-    size_t at = 0;
-    T.off_chrom_off = at; at += 8 * (size_t)n_chrom;
-    T.off_chrom_len = at; at += 8 * (size_t)n_chrom;
-    T.off_bands = at; at += 32 * (size_t)n_bands;
-    T.off_panel = at; at += 4 * (size_t)n_panels;
-    T.off_boxes = at; at += 16 * (size_t)n_panels;
-    T.off_band_off = at; at += 4 * (size_t)(n_panels + 1);
-    T.off_font = at; at += sizeof(WC_FONT_ROWS);
-    T.off_names = at; at += names ? (size_t)n_samples * name_cap : 0;
-    at = (at + 7) & ~(size_t)7;
-    T.off_args = at; at += sizeof(RasterArgs);
-    T.bytes = (at + 7) & ~(size_t)7;
+}  // namespace
+
+namespace wc {
+int plot_check_page(const char *who, const int64_t *chrom_sizes, int n_chrom, const int32_t *panel_chrom, int n_panels,
+                    int64_t row_stride, const int32_t *band_off) {
     int rc;
-    if ((rc = ctx->pl_host_reserve(T.bytes))) return rc;
-    unsigned char *h = ctx->pl_host;
-    memset(h, 0, T.bytes);
-    int64_t run = 0;
-    for (int c = 0; c < n_chrom; ++c) {
-        memcpy(h + T.off_chrom_off + 8 * c, &run, 8);
-        memcpy(h + T.off_chrom_len + 8 * c, &chrom_sizes[c], 8);
-        run += chrom_sizes[c];
+    if ((rc = check_panels(chrom_sizes, n_chrom, panel_chrom, n_panels, row_stride))) return rc;
+    if (band_off) {
+        WC_CHECK(band_off[0] == 0, WC_E_ARG, "%s: unusable cytoband table", who);
+        for (int p = 0; p < n_panels; ++p) WC_CHECK(band_off[p + 1] >= band_off[p], WC_E_ARG, "%s: unusable cytoband table", who);
     }
-    if (n_bands) memcpy(h + T.off_bands, bands, 32 * (size_t)n_bands);
-    memcpy(h + T.off_panel, panel_chrom, 4 * (size_t)n_panels);
-    if (boxes) memcpy(h + T.off_boxes, boxes, 16 * (size_t)n_panels);
-    if (band_off) memcpy(h + T.off_band_off, band_off, 4 * (size_t)(n_panels + 1));
-    memcpy(h + T.off_font, WC_FONT_ROWS, sizeof(WC_FONT_ROWS));
-    if (names) memcpy(h + T.off_names, names, (size_t)n_samples * name_cap);
-    return ctx->pl_tab.reserve(T.bytes);
+    return WC_OK;
 }
 
-// enqueues the copy of the block (with the raster kernel's arguments, if any) from the context's pinned memory; the
-// next plan_tables waits for this copy before it writes the block again
-int send_tables(wc_ctx *ctx, hipStream_t stream, const Tables &T, const RasterArgs *args) {
-    if (args) memcpy(ctx->pl_host + T.off_args, args, sizeof(RasterArgs));
-    WC_HIP(hipMemcpyAsync(ctx->pl_tab.p, ctx->pl_host, T.bytes, hipMemcpyHostToDevice, stream));
+int page_plan(wc_ctx *ctx, const char *who, const int64_t *chrom_sizes, int n_chrom, const int32_t *panel_chrom, int n_panels,
+              int64_t row_stride, int max_calls, int columns, int width, int height, const double *bands, const int32_t *band_off,
+              const char *names, int64_t n_samples, int name_cap, size_t tail_bytes, PagePlan &P) {
+    int rc;
+    if ((rc = plot_check_page(who, chrom_sizes, n_chrom, panel_chrom, n_panels, row_stride, band_off))) return rc;
+    WC_CHECK(!band_off || bands || band_off[n_panels] == 0, WC_E_ARG, "%s: unusable cytoband table", who);
+    std::vector<int32_t> boxes(4 * (size_t)n_panels);
+    if (columns >= 1 && (rc = wc_plot_layout(width, height, (n_panels + columns - 1) / columns, columns, n_panels, boxes.data()))) return rc;
+    int64_t longest = 0;
+    for (int p = 0; p < n_panels; ++p) longest = chrom_sizes[panel_chrom[p] - 1] > longest ? chrom_sizes[panel_chrom[p] - 1] : longest;
+    const int64_t cap64 = 1 + (longest + 1) / 2 + max_calls;             // alternating zeros: ceil(bins / 2) stretches
+    WC_CHECK(cap64 <= INT_MAX / 2, WC_E_LIMIT, "%s: lists of %lld entries", who, (long long)cap64);
+    P.n_panels = n_panels; P.cap = (int)cap64; P.has_cyto = band_off ? 1 : 0; P.name_cap = name_cap;
+    // the block, 8-byte fields first
+    const size_t n_bands = band_off ? band_off[n_panels] : 0, name_bytes = names ? (size_t)n_samples * name_cap : 0;
+    const size_t off_chrom_off = 0, off_chrom_len = off_chrom_off + 8 * (size_t)n_chrom, off_bands = off_chrom_len + 8 * (size_t)n_chrom,
+                 off_panel = off_bands + 32 * n_bands, off_boxes = off_panel + 4 * (size_t)n_panels,
+                 off_band_off = off_boxes + 16 * (size_t)n_panels, off_names = off_band_off + 4 * (size_t)(n_panels + 1);
+    P.tail = (off_names + name_bytes + 7) & ~(size_t)7;
+    P.bytes = (P.tail + tail_bytes + 7) & ~(size_t)7;
+    WC_HIP(hipSetDevice(ctx->device));
+    if ((rc = ctx->pl_host_reserve(P.bytes)) || (rc = ctx->pl_tab.reserve(P.bytes))) return rc;
+    unsigned char *h = ctx->pl_host;
+    memset(h, 0, P.bytes);
+    int64_t run = 0;
+    for (int c = 0; c < n_chrom; ++c) {
+        memcpy(h + off_chrom_off + 8 * c, &run, 8);
+        memcpy(h + off_chrom_len + 8 * c, &chrom_sizes[c], 8);
+        run += chrom_sizes[c];
+    }
+    if (n_bands) memcpy(h + off_bands, bands, 32 * n_bands);
+    memcpy(h + off_panel, panel_chrom, 4 * (size_t)n_panels);
+    if (columns >= 1) memcpy(h + off_boxes, boxes.data(), 16 * (size_t)n_panels);
+    if (band_off) memcpy(h + off_band_off, band_off, 4 * (size_t)(n_panels + 1));
+    if (name_bytes) memcpy(h + off_names, names, name_bytes);
+    const unsigned char *tab = ctx->pl_tab.as<unsigned char>();
+    P.chrom_off = (const long long *)(tab + off_chrom_off); P.chrom_len = (const long long *)(tab + off_chrom_len);
+    P.bands = (const double *)(tab + off_bands); P.panel_chrom = (const int *)(tab + off_panel);
+    P.boxes = (const int *)(tab + off_boxes); P.band_off = band_off ? (const int *)(tab + off_band_off) : nullptr;
+    P.names = (const char *)(tab + off_names);
+    P.tail_host = h + P.tail; P.tail_dev = tab + P.tail;
+    return WC_OK;
+}
+
+int page_send(wc_ctx *ctx, hipStream_t stream, size_t from, size_t to) {
+    WC_HIP(hipMemcpyAsync(ctx->pl_tab.as<unsigned char>() + from, ctx->pl_host + from, to - from, hipMemcpyHostToDevice, stream));
     WC_HIP(hipEventRecord(ctx->pl_sent, stream));
     return WC_OK;
 }
 
-int launch_list(wc_ctx *ctx, hipStream_t stream, const Tables &T, const double *z, int64_t row_stride, int64_t n_samples,
-                const double *calls, const int32_t *n_calls, int max_calls, double thr, double mineffect, int n_panels, int cap,
-                double *entries, int *counts, int *status) {
-    const unsigned char *tab = ctx->pl_tab.as<unsigned char>();
-    return wc::plot_list_launch(stream, z, row_stride, n_samples, (const long long *)(tab + T.off_chrom_off),
-                                (const long long *)(tab + T.off_chrom_len), (const int *)(tab + T.off_panel), calls, n_calls, max_calls,
-                                thr, mineffect, n_panels, cap, entries, counts, status);
-}
-
-void put32(unsigned char *p, uint32_t v) {
-    p[0] = (unsigned char)(v >> 24);
-    p[1] = (unsigned char)(v >> 16);
-    p[2] = (unsigned char)(v >> 8);
-    p[3] = (unsigned char)v;
-}
-
-}  // namespace
-
-namespace wc {
-int plot_check_panels(const int64_t *chrom_sizes, int n_chrom, const int32_t *panel_chrom, int n_panels, int64_t row_stride) {
-    return check_panels(chrom_sizes, n_chrom, panel_chrom, n_panels, row_stride);
-}
-int plot_list_launch(hipStream_t stream, const double *z, int64_t row_stride, int64_t n_samples, const long long *chrom_off_dev,
-                     const long long *chrom_len_dev, const int *panel_chrom_dev, const double *calls, const int32_t *n_calls,
-                     int max_calls, double thr, double mineffect, int n_panels, int cap, double *entries, int *counts, int *status) {
-    WC_HIP(hipMemsetAsync(status, 0, sizeof(int), stream));
-    hipLaunchKernelGGL(k_plot_list, dim3((unsigned)n_panels, (unsigned)n_samples), dim3(PL_T), 0, stream, z, (long long)row_stride,
-                       chrom_off_dev, chrom_len_dev, panel_chrom_dev, calls, (const int *)n_calls, max_calls, thr, mineffect, cap, entries,
-                       counts, status);
+int plot_list_launch(wc_ctx *ctx, hipStream_t stream, const PagePlan &P, const double *z, int64_t row_stride, int64_t n_samples,
+                     const double *calls, const int32_t *n_calls, int max_calls, double thr, double mineffect, int cap) {
+    WC_HIP(hipMemsetAsync(ctx->pl_status.p, 0, sizeof(int), stream));
+    hipLaunchKernelGGL(k_plot_list, dim3((unsigned)P.n_panels, (unsigned)n_samples), dim3(PL_T), 0, stream, z, (long long)row_stride,
+                       P.chrom_off, P.chrom_len, P.panel_chrom, calls, (const int *)n_calls, max_calls, thr, mineffect, cap,
+                       ctx->pl_list.as<double>(), ctx->pl_counts.as<int>(), ctx->pl_status.as<int>());
     WC_HIP(hipGetLastError());
     return WC_OK;
+}
+
+int HostBatch::stage(wc_ctx *ctx, const double *z_host, int64_t row_stride, int64_t n_samples, const double *calls_host,
+                     const int32_t *n_calls_host, int max_calls, bool timed) {
+    const size_t zb = (size_t)n_samples * row_stride * 8, cb = (size_t)n_samples * max_calls * 40, nb = (size_t)n_samples * 4;
+    const size_t off_calls = (zb + 15) & ~(size_t)15, off_n = off_calls + ((cb + 15) & ~(size_t)15);
+    int rc;
+    if ((rc = ctx->tmp_a.reserve(off_n + nb + 16)) || (rc = ctx->tmp_c.reserve((size_t)n_samples * 8)) ||
+        (rc = ctx->tmp_d.reserve((size_t)n_samples * 4)) || (timed && (rc = events.create())))
+        return rc;
+    unsigned char *base = ctx->tmp_a.as<unsigned char>();
+    if (timed) (void)hipEventRecord((ev = events.e)[5], nullptr);
+    if (zb && z_host) WC_HIP(hipMemcpy(base, z_host, zb, hipMemcpyHostToDevice));
+    if (cb && calls_host) WC_HIP(hipMemcpy(base + off_calls, calls_host, cb, hipMemcpyHostToDevice));
+    if (max_calls && n_calls_host) WC_HIP(hipMemcpy(base + off_n, n_calls_host, nb, hipMemcpyHostToDevice));
+    z = z_host ? (const double *)base : nullptr;
+    calls = calls_host ? (const double *)(base + off_calls) : nullptr;
+    n_calls = n_calls_host ? (const int32_t *)(base + off_n) : nullptr;
+    return WC_OK;
+}
+
+int HostBatch::collect(wc_ctx *ctx, const char *who, int64_t n_samples, int64_t dev_stride, unsigned char *streams_out,
+                       int64_t out_stride, int64_t *out_len, uint32_t *adler_out) {
+    int status = 0;
+    WC_HIP(hipMemcpy(&status, ctx->pl_status.p, 4, hipMemcpyDeviceToHost));
+    WC_CHECK(!status, WC_E_INTERNAL, "%s: a display list outgrew its capacity (status %d)", who, status);
+    WC_HIP(hipMemcpy(out_len, ctx->tmp_c.p, (size_t)n_samples * 8, hipMemcpyDeviceToHost));
+    WC_HIP(hipMemcpy(adler_out, ctx->tmp_d.p, (size_t)n_samples * 4, hipMemcpyDeviceToHost));
+    // only the streams cross, each in a transfer of its own: one strided transfer as wide as the longest stream
+    // (hipMemcpy2D) measured a quarter slower into the same pageable destination (DESIGN.md 6d)
+    for (int64_t i = 0; i < n_samples; ++i) {
+        WC_CHECK(out_len[i] >= 0 && out_len[i] <= dev_stride, WC_E_INTERNAL, "%s: a stream of %lld bytes in a slot of %lld", who,
+                 (long long)out_len[i], (long long)dev_stride);
+        if (out_len[i] > 0)
+            WC_HIP(hipMemcpy(streams_out + i * out_stride, ctx->tmp_b.as<unsigned char>() + i * dev_stride, (size_t)out_len[i],
+                             hipMemcpyDeviceToHost));
+    }
+    return WC_OK;
+}
+
+void HostBatch::times(double *times_ms) {
+    if (!ev) return;
+    (void)hipEventRecord(ev[6], nullptr);
+    (void)hipEventSynchronize(ev[6]);
+    const int from[6] = {5, 0, 1, 2, 3, 4}, to[6] = {0, 1, 2, 3, 4, 6};
+    events.elapsed(6, from, to, times_ms);
+    times_ms[6] = times_ms[7] = 0.0;
 }
 }  // namespace wc
 
@@ -570,11 +588,10 @@ int wc_plot_list(wc_ctx *ctx, const double *results_z, int64_t row_stride, int64
                  entries_out && counts_out && status_out && (results_z || row_stride == 0),
              WC_E_ARG, "plot list: unusable argument (1 .. 65535 samples)");
     int rc;
-    if ((rc = check_panels(chrom_sizes, n_chrom, panel_chrom, n_panels, row_stride))) return rc;
-    WC_HIP(hipSetDevice(ctx->device));
-    Tables T;
-    if ((rc = plan_tables(ctx, nullptr, chrom_sizes, n_chrom, panel_chrom, n_panels, nullptr, nullptr, nullptr, nullptr, 0, 0, T)) ||
-        (rc = send_tables(ctx, nullptr, T, nullptr)))
+    wc::PagePlan P;                                       // no bands, boxes or names; the capacity is the caller's
+    if ((rc = wc::page_plan(ctx, "plot", chrom_sizes, n_chrom, panel_chrom, n_panels, row_stride, 0, 0, 0, 0, nullptr, nullptr, nullptr, 0,
+                            0, 0, P)) ||
+        (rc = wc::page_send(ctx, nullptr, 0, P.bytes)))
         return rc;
     const size_t zb = (size_t)n_samples * row_stride * 8, cb = (size_t)n_samples * max_calls * 40, nb = (size_t)n_samples * 4;
     const size_t eb = (size_t)n_samples * n_panels * capacity * PL_F * 8, kb = (size_t)n_samples * n_panels * 4;
@@ -585,9 +602,8 @@ int wc_plot_list(wc_ctx *ctx, const double *results_z, int64_t row_stride, int64
     if (cb) WC_HIP(hipMemcpy(ctx->tmp_b.p, calls, cb, hipMemcpyHostToDevice));
     if (max_calls) WC_HIP(hipMemcpy(ctx->tmp_c.p, n_calls, nb, hipMemcpyHostToDevice));
     if (eb) WC_HIP(hipMemset(ctx->pl_list.p, 0, eb));
-    if ((rc = launch_list(ctx, nullptr, T, ctx->tmp_a.as<double>(), row_stride, n_samples, ctx->tmp_b.as<double>(),
-                          max_calls ? ctx->tmp_c.as<int32_t>() : nullptr, max_calls, threshold, mineffect, n_panels, capacity,
-                          ctx->pl_list.as<double>(), ctx->pl_counts.as<int>(), ctx->pl_status.as<int>())))
+    if ((rc = wc::plot_list_launch(ctx, nullptr, P, ctx->tmp_a.as<double>(), row_stride, n_samples, ctx->tmp_b.as<double>(),
+                                   max_calls ? ctx->tmp_c.as<int32_t>() : nullptr, max_calls, threshold, mineffect, capacity)))
         return rc;
     if (eb) WC_HIP(hipMemcpy(entries_out, ctx->pl_list.p, eb, hipMemcpyDeviceToHost));
     WC_HIP(hipMemcpy(counts_out, ctx->pl_counts.p, kb, hipMemcpyDeviceToHost));
@@ -633,8 +649,6 @@ static int plot_batch_enqueue(wc_ctx *ctx, hipStream_t stream, const double *res
                  dpi >= 1 && dpi <= 100000 && streams && out_len && adler && (results_z || row_stride == 0),
              WC_E_ARG, "plot: unusable argument");
     WC_CHECK(threshold > 0.0 && threshold <= DBL_MAX, WC_E_ARG, "plot: threshold_z %g is not a positive finite number", threshold);
-    int rc;
-    if ((rc = check_panels(chrom_sizes, n_chrom, panel_chrom, n_panels, row_stride))) return rc;
     const int64_t img = wc_plot_image_bytes(width, height);
     WC_CHECK(img > 0, WC_E_ARG, "plot: %d x %d pixels (1 .. 32768 each)", width, height);
     // what the deflate stage takes in one call (wc_deflate_rows_dev), held up front
@@ -645,46 +659,33 @@ static int plot_batch_enqueue(wc_ctx *ctx, hipStream_t stream, const double *res
              (long long)out_stride, (long long)img, (long long)wc_deflate_bound(img));
     WC_CHECK(!scanlines || (scan_stride >= img && scan_stride % 16 == 0), WC_E_ARG, "plot: scanline stride %lld (a multiple of 16, at least %lld)",
              (long long)scan_stride, (long long)img);
-    if (band_off) {
-        WC_CHECK(band_off[0] == 0 && (bands || band_off[n_panels] == 0), WC_E_ARG, "plot: unusable cytoband table");
-        for (int p = 0; p < n_panels; ++p) WC_CHECK(band_off[p + 1] >= band_off[p], WC_E_ARG, "plot: unusable cytoband table");
-    }
-    const int rows = (n_panels + columns - 1) / columns;
-    std::vector<int32_t> boxes(4 * (size_t)n_panels);
-    if ((rc = wc_plot_layout(width, height, rows, columns, n_panels, boxes.data()))) return rc;
-    int64_t longest = 0;
-    for (int p = 0; p < n_panels; ++p) longest = chrom_sizes[panel_chrom[p] - 1] > longest ? chrom_sizes[panel_chrom[p] - 1] : longest;
-    const int64_t cap64 = 1 + (longest + 1) / 2 + max_calls;             // alternating zeros: ceil(bins / 2) stretches
-    WC_CHECK(cap64 <= INT_MAX / 2, WC_E_LIMIT, "plot: lists of %lld entries", (long long)cap64);
-    const int cap = (int)cap64;
-    WC_HIP(hipSetDevice(ctx->device));
-    Tables T;
-    if ((rc = plan_tables(ctx, stream, chrom_sizes, n_chrom, panel_chrom, n_panels, bands, band_off, boxes.data(), names, n_samples,
-                          name_cap, T)))
+    int rc;
+    wc::PagePlan P;                                       // the tail: the raster kernel's arguments, then the font
+    if ((rc = wc::page_plan(ctx, "plot", chrom_sizes, n_chrom, panel_chrom, n_panels, row_stride, max_calls, columns, width, height, bands,
+                            band_off, names, n_samples, name_cap, sizeof(RasterArgs) + sizeof(WC_FONT_ROWS), P)))
         return rc;
+    const int cap = P.cap;
     const int64_t stride = scanlines ? scan_stride : (img + 15) / 16 * 16;     // the stride is padded, never the row
     if ((rc = ctx->pl_list.reserve((size_t)n_samples * n_panels * cap * PL_F * 8)) || (rc = ctx->pl_counts.reserve((size_t)n_samples * (n_panels + 1) * 4)) ||
         (rc = ctx->pl_status.reserve(8)) || (!scanlines && (rc = ctx->pl_img.reserve((size_t)n_samples * stride))))
         return rc;
     unsigned char *image = scanlines ? scanlines : ctx->pl_img.as<unsigned char>();
-    const unsigned char *tab = ctx->pl_tab.as<unsigned char>();
     RasterArgs A;
     A.W = width; A.H = height; A.s = (2 * dpi + 100) / 200 > 1 ? (2 * dpi + 100) / 200 : 1;       // max(1, round(dpi / 100))
-    A.P = n_panels; A.cap = cap; A.has_cyto = band_off ? 1 : 0; A.name_cap = name_cap;
+    A.P = n_panels; A.cap = cap; A.has_cyto = P.has_cyto; A.name_cap = name_cap;
     A.row_stride = row_stride; A.img_stride = stride; A.thr = threshold; A.z = results_z;
-    A.chrom_off = (const long long *)(tab + T.off_chrom_off); A.chrom_len = (const long long *)(tab + T.off_chrom_len);
-    A.panel_chrom = (const int *)(tab + T.off_panel); A.boxes = (const int *)(tab + T.off_boxes);
-    A.band_off = band_off ? (const int *)(tab + T.off_band_off) : nullptr; A.bands = (const double *)(tab + T.off_bands);
-    A.entries = ctx->pl_list.as<double>(); A.counts = ctx->pl_counts.as<int>(); A.names = (const char *)(tab + T.off_names);
-    A.font = tab + T.off_font; A.out = image;
-    if ((rc = send_tables(ctx, stream, T, &A))) return rc;
+    A.chrom_off = P.chrom_off; A.chrom_len = P.chrom_len; A.panel_chrom = P.panel_chrom; A.boxes = P.boxes; A.band_off = P.band_off;
+    A.bands = P.bands; A.entries = ctx->pl_list.as<double>(); A.counts = ctx->pl_counts.as<int>(); A.names = P.names;
+    A.font = P.tail_dev + sizeof(RasterArgs); A.out = image;
+    memcpy(P.tail_host, &A, sizeof(RasterArgs));
+    memcpy(P.tail_host + sizeof(RasterArgs), WC_FONT_ROWS, sizeof(WC_FONT_ROWS));
+    if ((rc = wc::page_send(ctx, stream, 0, P.bytes))) return rc;      // the whole block in one transfer
     if (ev) WC_HIP(hipEventRecord(ev[0], stream));
-    if ((rc = launch_list(ctx, stream, T, results_z, row_stride, n_samples, calls, n_calls, max_calls, threshold, mineffect, n_panels, cap,
-                          ctx->pl_list.as<double>(), ctx->pl_counts.as<int>(), ctx->pl_status.as<int>())))
+    if ((rc = wc::plot_list_launch(ctx, stream, P, results_z, row_stride, n_samples, calls, n_calls, max_calls, threshold, mineffect, cap)))
         return rc;
     if (ev) WC_HIP(hipEventRecord(ev[1], stream));
     hipLaunchKernelGGL(k_plot_raster, dim3((unsigned)((width + PL_T - 1) / PL_T), (unsigned)((height + PL_BAND_ROWS - 1) / PL_BAND_ROWS), (unsigned)n_samples),
-                       dim3(PL_T), 0, stream, (const RasterArgs *)(tab + T.off_args));
+                       dim3(PL_T), 0, stream, (const RasterArgs *)P.tail_dev);
     WC_HIP(hipGetLastError());
     if (ev) WC_HIP(hipEventRecord(ev[2], stream));
     if ((rc = wc_adler32_rows_dev(ctx, stream, image, n_samples, img, stride, adler))) return rc;
@@ -726,67 +727,20 @@ int wc_plot_batch(wc_ctx *ctx, const double *results_z, int64_t row_stride, int6
     WC_CHECK(n_samples <= 65535 && (double)n_samples * (double)out_stride < 1e12, WC_E_LIMIT, "plot: %lld images of %lld bytes in one call; split the batch",
              (long long)n_samples, (long long)img);
     WC_HIP(hipSetDevice(ctx->device));
-    const size_t zb = (size_t)n_samples * row_stride * 8, cb = (size_t)n_samples * max_calls * 40, nb = (size_t)n_samples * 4;
     const int64_t stride = (img + 15) / 16 * 16;
-    // tmp_a: z rows | calls | call counts; tmp_b: the streams; tmp_c: their lengths; tmp_d: the Adler-32 words
-    const size_t off_calls = (zb + 15) & ~(size_t)15, off_n = off_calls + ((cb + 15) & ~(size_t)15);
     int rc;
-    if ((rc = ctx->tmp_a.reserve(off_n + nb + 16)) || (rc = ctx->tmp_b.reserve((size_t)n_samples * out_stride)) ||
-        (rc = ctx->tmp_c.reserve((size_t)n_samples * 8)) || (rc = ctx->tmp_d.reserve((size_t)n_samples * 4)) ||
-        (rc = ctx->pl_img.reserve((size_t)n_samples * stride)))
+    wc::HostBatch B;
+    if ((rc = ctx->tmp_b.reserve((size_t)n_samples * out_stride)) || (rc = ctx->pl_img.reserve((size_t)n_samples * stride)) ||
+        (rc = B.stage(ctx, results_z, row_stride, n_samples, calls, n_calls, max_calls, times_ms != nullptr)) ||
+        (rc = plot_batch_enqueue(ctx, nullptr, B.z, row_stride, n_samples, chrom_sizes, n_chrom, B.calls, B.n_calls, max_calls, threshold,
+                                 mineffect, panel_chrom, n_panels, columns, bands, band_off, names, name_cap, width, height, dpi,
+                                 ctx->pl_img.as<unsigned char>(), stride, ctx->tmp_b.as<unsigned char>(), out_stride,
+                                 ctx->tmp_c.as<int64_t>(), ctx->tmp_d.as<uint32_t>(), B.ev)) ||
+        (rc = B.collect(ctx, "plot", n_samples, out_stride, streams_out, out_stride, out_len, adler_out)))
         return rc;
-    struct Events {                                       // destroyed on every way out of the call
-        hipEvent_t e[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-        ~Events() {
-            for (int i = 0; i < 7; ++i)
-                if (e[i]) (void)hipEventDestroy(e[i]);
-        }
-    } events;
-    hipEvent_t *ev = events.e;
-    if (times_ms)
-        for (int i = 0; i < 7; ++i) WC_HIP(hipEventCreate(&ev[i]));
-    unsigned char *base = ctx->tmp_a.as<unsigned char>();
-    if (times_ms) (void)hipEventRecord(ev[5], nullptr);
-    if (zb && results_z) WC_HIP(hipMemcpy(base, results_z, zb, hipMemcpyHostToDevice));
-    if (cb && calls) WC_HIP(hipMemcpy(base + off_calls, calls, cb, hipMemcpyHostToDevice));
-    if (max_calls && n_calls) WC_HIP(hipMemcpy(base + off_n, n_calls, nb, hipMemcpyHostToDevice));
-    rc = plot_batch_enqueue(ctx, nullptr, results_z ? (const double *)base : nullptr, row_stride, n_samples, chrom_sizes, n_chrom,
-                            calls ? (const double *)(base + off_calls) : nullptr, n_calls ? (const int32_t *)(base + off_n) : nullptr,
-                            max_calls, threshold, mineffect, panel_chrom, n_panels, columns, bands, band_off, names, name_cap, width, height,
-                            dpi, ctx->pl_img.as<unsigned char>(), stride, ctx->tmp_b.as<unsigned char>(), out_stride,
-                            ctx->tmp_c.as<int64_t>(), ctx->tmp_d.as<uint32_t>(), times_ms ? ev : nullptr);
-    if (rc) return rc;
-    int status = 0;
-    WC_HIP(hipMemcpy(&status, ctx->pl_status.p, 4, hipMemcpyDeviceToHost));
-    if (status) {
-        wc::set_error("plot: a display list outgrew its capacity (status %d)", status);
-        return WC_E_INTERNAL;
-    }
-    WC_HIP(hipMemcpy(out_len, ctx->tmp_c.p, (size_t)n_samples * 8, hipMemcpyDeviceToHost));
-    WC_HIP(hipMemcpy(adler_out, ctx->tmp_d.p, (size_t)n_samples * 4, hipMemcpyDeviceToHost));
-    // only the streams cross, each in a transfer of its own: one strided transfer as wide as the longest stream
-    // (hipMemcpy2D) measured a quarter slower into the same pageable destination (DESIGN.md 6d)
-    for (int64_t i = 0; i < n_samples; ++i) {
-        WC_CHECK(out_len[i] >= 0 && out_len[i] <= out_stride, WC_E_INTERNAL, "plot: a stream of %lld bytes in a slot of %lld",
-                 (long long)out_len[i], (long long)out_stride);
-        if (out_len[i] > 0)
-            WC_HIP(hipMemcpy(streams_out + i * out_stride, ctx->tmp_b.as<unsigned char>() + i * out_stride, (size_t)out_len[i],
-                             hipMemcpyDeviceToHost));
-    }
     if (scanlines_out)
         WC_HIP(hipMemcpy2D(scanlines_out, (size_t)img, ctx->pl_img.p, (size_t)stride, (size_t)img, (size_t)n_samples, hipMemcpyDeviceToHost));
-    if (times_ms) {
-        (void)hipEventRecord(ev[6], nullptr);
-        (void)hipEventSynchronize(ev[6]);
-        // [0] copy in (inputs and tables) [1] list [2] raster [3] Adler-32 [4] deflate [5] copy out
-        const int from[6] = {5, 0, 1, 2, 3, 4}, to[6] = {0, 1, 2, 3, 4, 6};
-        for (int i = 0; i < 6; ++i) {
-            float ms = 0.f;
-            (void)hipEventElapsedTime(&ms, ev[from[i]], ev[to[i]]);
-            times_ms[i] = ms;
-        }
-        times_ms[6] = times_ms[7] = 0.0;
-    }
+    B.times(times_ms);      // [1] list [2] raster [3] Adler-32 [4] deflate
     return WC_OK;
 }
 
@@ -798,6 +752,7 @@ int wc_png_assemble(int width, int height, const unsigned char *deflate, int64_t
     WC_CHECK(deflate_len <= (int64_t)INT_MAX - 6, WC_E_LIMIT, "png: a stream of %lld bytes does not fit one IDAT chunk", (long long)deflate_len);
     WC_CHECK(cap >= wc_png_bytes(deflate_len), WC_E_ARG, "png: room for %lld bytes, wc_png_bytes(%lld) is %lld", (long long)cap,
              (long long)deflate_len, (long long)wc_png_bytes(deflate_len));
+    using wc::put32;
     static const unsigned char sig[8] = {0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a};
     unsigned char *p = out;
     memcpy(p, sig, 8);

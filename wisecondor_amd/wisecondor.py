@@ -556,7 +556,25 @@ def toolTestBatch(args):
     reference.close()
 
 
-# ------------------------------------------------------------------- plotbatch ----
+# ------------------------------------------------------------------- plotbatch, plotpdf, exportjson ----
+def _run_result_tool(args, name_outputs, run, noun):
+    """What the three result-file tools do once their options are checked: name_outputs() refuses two inputs with one stem
+    before anything is made, run(infiles, outdir, args) gives (written, skipped, seconds); the summary line counts `noun`,
+    every skipped file is named, and one of them makes the exit status 1."""
+    try:
+        name_outputs()
+        os.makedirs(args.outdir, exist_ok=True)
+        written, skipped, wall = run(args.infiles, args.outdir, args)
+    except ValueError as exc:
+        print('ERROR:', exc)
+        sys.exit(2)
+    print('%d %s written in %.2f s (%.1f files/s end to end)' % (written, noun, wall, written / wall if wall > 0 else 0.0))
+    for path, reason in skipped:
+        print('ERROR: %s skipped: %s' % (path, reason))
+    if skipped:
+        sys.exit(1)
+
+
 def toolPlotBatch(args):
     """`plotbatch infiles... outdir` (build-only): <outdir>/<stem>_z.png per result file, what upstream `plot` draws
     (wisecondor.py:284-295) by this build's own rasteriser on the GPU.  A file that cannot be read, or whose chromosome
@@ -568,21 +586,9 @@ def toolPlotBatch(args):
         print('ERROR: plotbatch needs -columns >= 1, -dpi >= 1 and at least one chromosome')
         sys.exit(2)
     from . import ingest
-    try:
-        ingest.plot_output_names(args.infiles, args.outdir, args.filetype)      # two inputs with one stem: before anything is made
-        os.makedirs(args.outdir, exist_ok=True)
-        written, skipped, wall = ingest.run_plotbatch(args.infiles, args.outdir, args)
-    except ValueError as exc:
-        print('ERROR:', exc)
-        sys.exit(2)
-    print('%d plots written in %.2f s (%.1f files/s end to end)' % (written, wall, written / wall if wall > 0 else 0.0))
-    for path, reason in skipped:
-        print('ERROR: %s skipped: %s' % (path, reason))
-    if skipped:
-        sys.exit(1)
+    _run_result_tool(args, lambda: ingest.plot_output_names(args.infiles, args.outdir, args.filetype), ingest.run_plotbatch, 'plots')
 
 
-# ------------------------------------------------------------------- plotpdf ----
 def toolPlotPdf(args):
     """`plotpdf infiles... outdir` (build-only): <outdir>/<stem>_z.pdf per result file, the name and the vector format of
     upstream `plot`'s default output (wisecondor.py:284-295), the page's content stream written on the GPU.  Files are
@@ -592,39 +598,16 @@ def toolPlotPdf(args):
         print('ERROR: plotpdf needs -columns >= 1, a -size above 0 and at least one chromosome')
         sys.exit(2)
     from . import ingest
-    try:
-        ingest.plot_output_names(args.infiles, args.outdir, 'pdf', 'plotpdf')      # two inputs with one stem: before anything is made
-        os.makedirs(args.outdir, exist_ok=True)
-        written, skipped, wall = ingest.run_plotpdf(args.infiles, args.outdir, args)
-    except ValueError as exc:
-        print('ERROR:', exc)
-        sys.exit(2)
-    print('%d plots written in %.2f s (%.1f files/s end to end)' % (written, wall, written / wall if wall > 0 else 0.0))
-    for path, reason in skipped:
-        print('ERROR: %s skipped: %s' % (path, reason))
-    if skipped:
-        sys.exit(1)
+    _run_result_tool(args, lambda: ingest.plot_output_names(args.infiles, args.outdir, 'pdf', 'plotpdf'), ingest.run_plotpdf, 'plots')
 
 
-# ------------------------------------------------------------------- exportjson ----
 def toolExportJson(args):
     """`exportjson infiles... outdir` (build-only): <outdir>/<stem>.json (.json.gz with -gz) per result file, every
     number as json.dumps writes it, so that json.loads gives the stored doubles back bit for bit; the digits of
     results_z and results_r are made on the GPU.  Files are treated as `plotbatch` treats them: one that cannot be read,
     or whose chromosome lengths or bin size differ from the first file's, is named and skipped; the exit status is then 1."""
     from . import ingest
-    try:
-        ingest.export_output_names(args.infiles, args.outdir, args.gz)      # two inputs with one stem: before anything is made
-        os.makedirs(args.outdir, exist_ok=True)
-        written, skipped, wall = ingest.run_exportjson(args.infiles, args.outdir, args)
-    except ValueError as exc:
-        print('ERROR:', exc)
-        sys.exit(2)
-    print('%d files written in %.2f s (%.1f files/s end to end)' % (written, wall, written / wall if wall > 0 else 0.0))
-    for path, reason in skipped:
-        print('ERROR: %s skipped: %s' % (path, reason))
-    if skipped:
-        sys.exit(1)
+    _run_result_tool(args, lambda: ingest.export_output_names(args.infiles, args.outdir, args.gz), ingest.run_exportjson, 'files')
 
 
 # ---------------------------------------------------------------------- parser ----

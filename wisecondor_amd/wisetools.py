@@ -1094,17 +1094,24 @@ def plotLayout(width, height, rows, columns, n_panels):
     return boxes
 
 
+def _dense_rows(arrays_list, sizes, out=None):
+    """Per-sample lists of per-chromosome arrays of the lengths `sizes` -> float64 rows [n, max(sum(sizes), 1)], every
+    sample's arrays end to end (written into `out` where one is given)."""
+    total = int(np.sum(sizes))
+    rows = np.zeros((len(arrays_list), max(total, 1)), dtype=np.float64) if out is None else out
+    for i, arrays in enumerate(arrays_list):
+        if [len(c) for c in arrays] != [int(v) for v in sizes]:
+            raise ValueError('sample %d has other chromosome lengths than the first' % i)
+        if total:
+            rows[i, :total] = np.concatenate([np.asarray(c, dtype=np.float64) for c in arrays])
+    return rows
+
+
 def _dense_results(zs_list, calls_list, max_calls=None):
     """Per-sample lists of per-chromosome z arrays and call tables -> the dense layout wc_test_batch_dev leaves on the
     device: rows [n, total], sizes int64 [n_chrom], calls [n, max_calls, 5], n_calls int32 [n]."""
     sizes = np.array([len(c) for c in zs_list[0]], dtype=np.int64)
-    total = int(sizes.sum())
-    rows = np.zeros((len(zs_list), max(total, 1)), dtype=np.float64)
-    for i, zs in enumerate(zs_list):
-        if [len(c) for c in zs] != [int(v) for v in sizes]:
-            raise ValueError('sample %d has other chromosome lengths than the first' % i)
-        if total:
-            rows[i, :total] = np.concatenate([np.asarray(c, dtype=np.float64) for c in zs])
+    rows = _dense_rows(zs_list, sizes)
     tables = [np.asarray(c, dtype=np.float64).reshape(-1, 5) for c in calls_list]      # (an empty list is stored with shape (0,))
     cap = max([len(t) for t in tables] + [1]) if max_calls is None else int(max_calls)
     calls = np.zeros((len(tables), cap, 5), dtype=np.float64)
@@ -1134,16 +1141,22 @@ def plotList(zs_list, calls_list, threshold, chromosomes=range(1, 23), mineffect
     return entries, counts, int(status[0])
 
 
+def _assemble(stream, bytes_of, assemble):
+    """The file one of the library's assemblers puts around a raw deflate stream: bytes_of(stream length) sizes the room,
+    assemble(stream, its length, room, its size, where the file's length goes) fills it."""
+    stream = np.ascontiguousarray(np.frombuffer(bytes(stream), dtype=np.uint8))
+    out = np.zeros(max(1, int(bytes_of(len(stream)))), dtype=np.uint8)
+    n = np.zeros(1, dtype=np.int64)
+    _lib.check(assemble(_lib.ptr(stream), len(stream), _lib.ptr(out), len(out), _lib.ptr(n)))
+    return out[:int(n[0])].tobytes()
+
+
 def pngAssemble(width, height, stream, adler):
     """The PNG file of one image from its raw deflate stream and the Adler-32 of its scanlines (wc_png_assemble; host
     only): signature, IHDR, IDAT = 78 01 + stream + Adler-32, IEND."""
     lib = _lib.load()
-    stream = np.ascontiguousarray(np.frombuffer(bytes(stream), dtype=np.uint8))
-    out = np.zeros(max(1, int(lib.wc_png_bytes(len(stream)))), dtype=np.uint8)
-    n = np.zeros(1, dtype=np.int64)
-    _lib.check(lib.wc_png_assemble(int(width), int(height), _lib.ptr(stream), len(stream), int(adler) & 0xffffffff, _lib.ptr(out),
-                                   len(out), _lib.ptr(n)))
-    return out[:int(n[0])].tobytes()
+    return _assemble(stream, lib.wc_png_bytes, lambda s, n, *room: lib.wc_png_assemble(int(width), int(height), s, n,
+                                                                                      int(adler) & 0xffffffff, *room))
 
 
 def adler32Rows(rows, device=0):
@@ -1167,6 +1180,44 @@ def sampleNameOf(infile):
     return infile.split('/')[-1].split('.')[0]
 
 
+def _plot_job(what, results, names, cytofile, chromosomes):
+    """What plot_batch and plot_pdf_batch (`what`) make of their arguments before they differ: the dense rows, sizes, calls
+    and n_calls of _dense_results, panels (int32), bands and band_off (plotBands; None without a cytofile), name_cap and
+    the samples' thresholds, as attributes of one object.  None: there are no results."""
+    import types
+    if len(results) != len(names):
+        raise ValueError('%s: %d results, %d names' % (what, len(results), len(names)))
+    if not results:
+        return None
+    chromosomes = [int(c) for c in chromosomes]
+    binsize = np.asarray(results[0]['binsize']).item()
+    for i, res in enumerate(results):
+        if np.asarray(res['binsize']).item() != binsize:
+            raise ValueError('sample %d has another bin size than the first' % i)
+    rows, sizes, calls, n_calls = _dense_results([list(res['results_z']) for res in results], [res['results_calls'] for res in results])
+    bands = band_off = None
+    if cytofile is not None:
+        table = cytofile if isinstance(cytofile, dict) else loadCytoBands(cytofile)
+        bands, band_off = plotBands(table, chromosomes, binsize)
+    return types.SimpleNamespace(rows=rows, sizes=sizes, calls=calls, n_calls=n_calls, panels=np.array(chromosomes, dtype=np.int32),
+                                 bands=bands, band_off=band_off,
+                                 name_cap=max(len(n.encode('latin1', 'replace')) for n in names) + 1,
+                                 thresholds=[float(np.asarray(res['threshold_z']).item()) for res in results])
+
+
+def _threshold_groups(job, names):
+    """Per threshold_z value of a _plot_job, ascending -- one GPU call each: (threshold, the samples' indices, their names
+    as a zero-padded uint8 block [n, name_cap], their contiguous z rows, calls and call counts)."""
+    for thr in sorted(set(job.thresholds)):
+        pick = [i for i, t in enumerate(job.thresholds) if t == thr]
+        name_block = np.zeros((len(pick), job.name_cap), dtype=np.uint8)
+        for k, i in enumerate(pick):
+            raw = names[i].encode('latin1', 'replace')
+            name_block[k, :len(raw)] = np.frombuffer(raw, dtype=np.uint8)
+        yield (thr, pick, name_block, np.ascontiguousarray(job.rows[pick]), np.ascontiguousarray(job.calls[pick]),
+               np.ascontiguousarray(job.n_calls[pick]))
+
+
 def plot_batch(results, names, cytofile=None, chromosomes=range(1, 23), columns=2, size=(11.7, 8.3), mineffect=0, dpi=100,
                device=0, ctx=None, details=None):
     """The z-score panel plots of upstream `plot` (plotLines, wisetools.py:527-662) for a batch of `test` results, drawn,
@@ -1179,43 +1230,22 @@ def plot_batch(results, names, cytofile=None, chromosomes=range(1, 23), columns=
               False), 'size' and 'times_ms' (per GPU call: copy in, list, raster, Adler-32, deflate, copy out), for tests
               and measurements
     Samples with different threshold_z values take one GPU call per value."""
-    if len(results) != len(names):
-        raise ValueError('plot_batch: %d results, %d names' % (len(results), len(names)))
-    if not results:
+    job = _plot_job('plot_batch', results, names, cytofile, chromosomes)
+    if job is None:
         return []
     lib = _lib.load()
-    chromosomes = [int(c) for c in chromosomes]
+    sizes, panels, bands, band_off, name_cap = job.sizes, job.panels, job.bands, job.band_off, job.name_cap
     width, height = plotImageSize(size, dpi)
-    binsize = np.asarray(results[0]['binsize']).item()
-    for i, res in enumerate(results):
-        if np.asarray(res['binsize']).item() != binsize:
-            raise ValueError('sample %d has another bin size than the first' % i)
-    zs_list = [list(res['results_z']) for res in results]
-    rows, sizes, calls, n_calls = _dense_results(zs_list, [res['results_calls'] for res in results])
-    panels = np.array(chromosomes, dtype=np.int32)
-    bands = band_off = None
-    if cytofile is not None:
-        table = cytofile if isinstance(cytofile, dict) else loadCytoBands(cytofile)
-        bands, band_off = plotBands(table, chromosomes, binsize)
-    name_cap = max(len(n.encode('latin1', 'replace')) for n in names) + 1
     image = int(lib.wc_plot_image_bytes(width, height))
     if image < 0:
         raise ValueError('plot_batch: %d x %d pixels' % (width, height))
     stride = int(lib.wc_deflate_bound(image))
-    thresholds = [float(np.asarray(res['threshold_z']).item()) for res in results]
     out = [None] * len(results)
     scan = np.zeros((len(results), image), dtype=np.uint8) if details is not None and details.get('want_scanlines', True) else None
     times = []
     handle = ctx or _lib.context(device)
-    for thr in sorted(set(thresholds)):
-        pick = [i for i, t in enumerate(thresholds) if t == thr]
+    for thr, pick, name_block, z_part, c_part, k_part in _threshold_groups(job, names):
         n = len(pick)
-        name_block = np.zeros((n, name_cap), dtype=np.uint8)
-        for k, i in enumerate(pick):
-            raw = names[i].encode('latin1', 'replace')
-            name_block[k, :len(raw)] = np.frombuffer(raw, dtype=np.uint8)
-        z_part = np.ascontiguousarray(rows[pick])
-        c_part, k_part = np.ascontiguousarray(calls[pick]), np.ascontiguousarray(n_calls[pick])
         streams = np.zeros((n, stride), dtype=np.uint8)
         lengths = np.zeros(n, dtype=np.int64)
         adlers = np.zeros(n, dtype=np.uint32)
@@ -1266,12 +1296,8 @@ def pdfAssemble(width_cp, height_cp, stream, adler):
     host only): header, Catalog, Pages, Page, the font Courier, the graphics states /A000 .. /A255, the two hatch patterns,
     the content object = 78 01 + stream + Adler-32, xref, trailer."""
     lib = _lib.load()
-    stream = np.ascontiguousarray(np.frombuffer(bytes(stream), dtype=np.uint8))
-    out = np.zeros(max(1, int(lib.wc_pdf_bytes(len(stream)))), dtype=np.uint8)
-    n = np.zeros(1, dtype=np.int64)
-    _lib.check(lib.wc_pdf_assemble(int(width_cp), int(height_cp), _lib.ptr(stream), len(stream), int(adler) & 0xffffffff, _lib.ptr(out),
-                                   len(out), _lib.ptr(n)))
-    return out[:int(n[0])].tobytes()
+    return _assemble(stream, lib.wc_pdf_bytes, lambda s, n, *room: lib.wc_pdf_assemble(int(width_cp), int(height_cp), s, n,
+                                                                                      int(adler) & 0xffffffff, *room))
 
 
 def plot_pdf_batch(results, names, cytofile=None, chromosomes=range(1, 23), columns=2, size=(11.7, 8.3), mineffect=0, device=0,
@@ -1283,44 +1309,23 @@ def plot_pdf_batch(results, names, cytofile=None, chromosomes=range(1, 23), colu
               section starts), 'size' (the page in centipoints) and 'times_ms' (per GPU call: copy in, list, content,
               Adler-32, deflate, copy out)
     Samples with different threshold_z values take one GPU call per value."""
-    if len(results) != len(names):
-        raise ValueError('plot_pdf_batch: %d results, %d names' % (len(results), len(names)))
-    if not results:
+    job = _plot_job('plot_pdf_batch', results, names, cytofile, chromosomes)
+    if job is None:
         return []
     lib = _lib.load()
-    chromosomes = [int(c) for c in chromosomes]
+    sizes, panels, bands, band_off, name_cap = job.sizes, job.panels, job.bands, job.band_off, job.name_cap
     width, height = pdfPageSize(size)
-    binsize = np.asarray(results[0]['binsize']).item()
-    for i, res in enumerate(results):
-        if np.asarray(res['binsize']).item() != binsize:
-            raise ValueError('sample %d has another bin size than the first' % i)
-    zs_list = [list(res['results_z']) for res in results]
-    rows, sizes, calls, n_calls = _dense_results(zs_list, [res['results_calls'] for res in results])
-    panels = np.array(chromosomes, dtype=np.int32)
-    bands = band_off = None
-    if cytofile is not None:
-        table = cytofile if isinstance(cytofile, dict) else loadCytoBands(cytofile)
-        bands, band_off = plotBands(table, chromosomes, binsize)
-    name_cap = max(len(n.encode('latin1', 'replace')) for n in names) + 1
-    bound = int(lib.wc_plot_pdf_row_bound(_lib.ptr(sizes), len(sizes), _lib.ptr(panels), len(panels), _lib.ptr(band_off), calls.shape[1],
-                                          name_cap))
+    bound = int(lib.wc_plot_pdf_row_bound(_lib.ptr(sizes), len(sizes), _lib.ptr(panels), len(panels), _lib.ptr(band_off),
+                                          job.calls.shape[1], name_cap))
     if bound < 0:
         raise ValueError('plot_pdf_batch: unusable chromosomes, cytoband table or names')
     stride = int(lib.wc_deflate_bound(bound))
-    thresholds = [float(np.asarray(res['threshold_z']).item()) for res in results]
     out = [None] * len(results)
     content = [None] * len(results)
     times, row_bytes, offsets = [], [], []
     handle = ctx or _lib.context(device)
-    for thr in sorted(set(thresholds)):
-        pick = [i for i, t in enumerate(thresholds) if t == thr]
+    for thr, pick, name_block, z_part, c_part, k_part in _threshold_groups(job, names):
         n = len(pick)
-        name_block = np.zeros((n, name_cap), dtype=np.uint8)
-        for k, i in enumerate(pick):
-            raw = names[i].encode('latin1', 'replace')
-            name_block[k, :len(raw)] = np.frombuffer(raw, dtype=np.uint8)
-        z_part = np.ascontiguousarray(rows[pick])
-        c_part, k_part = np.ascontiguousarray(calls[pick]), np.ascontiguousarray(n_calls[pick])
         # (rows of the worst case's size: the pages they hold are written, the rest is never touched)
         streams = np.zeros((n, stride), dtype=np.uint8)
         lengths = np.zeros(n, dtype=np.int64)
@@ -1401,11 +1406,7 @@ def gzipAssemble(stream, crc, input_len):
     """One gzip member around a raw deflate stream (wc_gzip_assemble; host only): a fixed header without name or time, the
     stream, the CRC-32 and the length of the uncompressed bytes."""
     lib = _lib.load()
-    stream = np.ascontiguousarray(np.frombuffer(bytes(stream), dtype=np.uint8))
-    out = np.zeros(max(1, int(lib.wc_gzip_bytes(len(stream)))), dtype=np.uint8)
-    n = np.zeros(1, dtype=np.int64)
-    _lib.check(lib.wc_gzip_assemble(_lib.ptr(stream), len(stream), int(crc) & 0xffffffff, int(input_len), _lib.ptr(out), len(out), _lib.ptr(n)))
-    return out[:int(n[0])].tobytes()
+    return _assemble(stream, lib.wc_gzip_bytes, lambda s, n, *room: lib.wc_gzip_assemble(s, n, int(crc) & 0xffffffff, int(input_len), *room))
 
 
 def _json_plain(value):
@@ -1493,10 +1494,8 @@ def export_json_batch(results, strict=False, gz=False, device=0, ctx=None, max_r
         part = results[at:at + per_call]
         n = len(part)
         rows = np.zeros((2 * n, max(total, 1)), dtype=np.float64)
-        for i, res in enumerate(part):
-            if total:
-                rows[i, :total] = np.concatenate([np.asarray(c, dtype=np.float64) for c in res['results_z']])
-                rows[n + i, :total] = np.concatenate([np.asarray(c, dtype=np.float64) for c in res['results_r']])
+        _dense_rows([res['results_z'] for res in part], sizes, out=rows[:n])
+        _dense_rows([res['results_r'] for res in part], sizes, out=rows[n:])
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream().cuda_stream
             marks = [torch.cuda.Event(enable_timing=True) for _ in range(5)] if details is not None else None
