@@ -824,6 +824,60 @@ int64_t wc_gzip_bytes(int64_t deflate_len);
 int wc_gzip_assemble(const unsigned char *deflate, int64_t deflate_len, uint32_t crc, int64_t input_len, unsigned char *out,
                      int64_t cap, int64_t *out_len);
 
+/* ---- exporttracks: result rows -> bedGraph text, BGZF on the device ---------------------------------
+ * A row is the dense layout of wc_json_rows_dev.  Chromosome c (0-based) is named prefix + decimal(c + 1); inside a
+ * chromosome a RUN is a maximal stretch of bins a..b whose doubles have the same 64 bits (-0.0 beside 0.0: two runs).
+ * A run is one line
+ *     name \t a * binsize \t min((b + 1) * binsize, clip_len[c]) \t value \n
+ * with the value's text as wc_format_doubles_host writes it (not strict).  A run that is not finite is left out; with
+ * bit 0 of flags set (nozero) a run of 0.0 of either sign too.  No header, no track line; a row with nothing kept is
+ * 0 bytes.
+ *
+ * wc_bedgraph_row_bound (host): the most bytes a row's text takes, every bin a line of its own:
+ *     sum over the chromosomes with n > 0 bins of
+ *         n * (prefix_len + digits(c + 1) + digits((n - 1) * binsize) + digits(n * binsize) + 28)
+ *   (28 = three tabs, the newline and 24 bytes of value).  -1 for arguments wc_bedgraph_rows_dev refuses.
+ * wc_bedgraph_rows_dev: text_len[i] (DEVICE int64) bytes at text + i * text_stride (DEVICE), dense; dropped[i]
+ *   (DEVICE int64) the row's bins that are not finite.  BYTES BEHIND text_len[i] ARE NOT WRITTEN.  text is 16-byte
+ *   aligned and text_stride a multiple of 16, at least the bound.  chrom_sizes_host, clip_len_host (may be NULL:
+ *   nothing is clipped) and prefix are HOST memory and travel as a kernel argument.  Three kernel launches on
+ *   `stream`, no synchronisation, except that a call which has to grow the context's working memory (shared with
+ *   wc_json_rows_dev: 16 bytes per value, 16 per 256 values) allocates, which waits for the device; one call in flight
+ *   per context.  Refused before anything runs, outputs untouched: WC_E_ARG for a negative size or row count, a
+ *   binsize below 1, a row_stride below the row's values, a text_stride below the bound or no multiple of 16, a NULL
+ *   pointer, a prefix of more than 16 bytes or with a byte that is 0, a tab, a newline or not ASCII, a flag bit other
+ *   than bit 0, a clip_len[c] at or below the start of chromosome c's last bin; WC_E_LIMIT for more than 65535 rows,
+ *   more than 64 chromosomes, more than INT_MAX - 512 bins in a row, a chromosome whose bins * binsize reaches 10^15
+ *   (every coordinate has at most 15 digits).
+ * wc_bedgraph_rows: the same from HOST pointers, synchronising; text rows need no alignment, only text_len[i] bytes
+ *   of each are written.  times_ms (may be NULL) double [4]: milliseconds of [0] copy in [1] lengths and scan
+ *   [2] bytes [3] copy out.
+ *
+ * wc_bgzf_rows_dev: the first row_len[i] (DEVICE int64, read on the device) bytes of row i of src (DEVICE, src_stride
+ *   apart) become a BGZF file (the SAM specification, section 4.1) of out_len[i] (DEVICE int64) bytes at out +
+ *   i * out_stride: the bytes are cut into blocks of wc_deflate_block_bytes input bytes, each coded as
+ *   wc_deflate_rows_dev codes a row's last block (the same tokens and Huffman code, a stored block where that is
+ *   shorter, the final bit set) and framed by the 18-byte header with the BC extra field and BSIZE - 1, the block's
+ *   own CRC-32 and its ISIZE; the 28-byte end-of-file block closes the row, and is all of a row of 0 bytes.  The grid
+ *   is sized by max_row_bytes and the blocks behind a row's end do nothing: one call serves rows of unequal lengths
+ *   without a read-back.  A row_len[i] outside 0 .. max_row_bytes gives out_len[i] = -1 and nothing else for that
+ *   row.  out_stride is at least wc_bgzf_bound of max_row_bytes: row_bytes + 31 per block + 28.  Bytes behind
+ *   out_len[i] are not written.  Two kernel launches, no synchronisation unless the working memory grows (shared
+ *   with wc_deflate_rows_dev, 16 400 bytes per block of the grid).
+ * wc_bgzf_rows: the same from HOST pointers, synchronising; a row_len[i] outside 0 .. max_row_bytes is WC_E_ARG.    */
+int64_t wc_bedgraph_row_bound(const int64_t *chrom_sizes, int n_chrom, int64_t binsize, int prefix_len);
+int wc_bedgraph_rows_dev(wc_ctx *ctx, void *stream, const double *rows, int64_t row_stride, int64_t n_rows,
+                         const int64_t *chrom_sizes_host, int n_chrom, int64_t binsize, const int64_t *clip_len_host, const char *prefix,
+                         int prefix_len, int flags, unsigned char *text, int64_t text_stride, int64_t *text_len, int64_t *dropped);
+int wc_bedgraph_rows(wc_ctx *ctx, const double *rows, int64_t row_stride, int64_t n_rows, const int64_t *chrom_sizes, int n_chrom,
+                     int64_t binsize, const int64_t *clip_len, const char *prefix, int prefix_len, int flags, unsigned char *text,
+                     int64_t text_stride, int64_t *text_len, int64_t *dropped, double *times_ms);
+int64_t wc_bgzf_bound(int64_t row_bytes);
+int wc_bgzf_rows_dev(wc_ctx *ctx, void *stream, const unsigned char *src, int64_t n_rows, const int64_t *row_len, int64_t max_row_bytes,
+                     int64_t src_stride, unsigned char *out, int64_t out_stride, int64_t *out_len);
+int wc_bgzf_rows(wc_ctx *ctx, const unsigned char *src, int64_t n_rows, const int64_t *row_len, int64_t max_row_bytes, int64_t src_stride,
+                 unsigned char *out, int64_t out_stride, int64_t *out_len);
+
 #ifdef __cplusplus
 }
 #endif

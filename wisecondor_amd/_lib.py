@@ -86,6 +86,12 @@ SIGNATURES = {
     "wc_json_rows": (_i32, [_vp, _vp, _i64, _i64, _vp, _i32, _i32, _vp, _i64, _vp, _vp]),
     "wc_gzip_bytes": (_i64, [_i64]),
     "wc_gzip_assemble": (_i32, [_vp, _i64, _c.c_uint32, _i64, _vp, _i64, _vp]),
+    "wc_bedgraph_row_bound": (_i64, [_vp, _i32, _i64, _i32]),
+    "wc_bedgraph_rows_dev": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _i32, _i64, _vp, _c.c_char_p, _i32, _i32, _vp, _i64, _vp, _vp]),
+    "wc_bedgraph_rows": (_i32, [_vp, _vp, _i64, _i64, _vp, _i32, _i64, _vp, _c.c_char_p, _i32, _i32, _vp, _i64, _vp, _vp, _vp]),
+    "wc_bgzf_bound": (_i64, [_i64]),
+    "wc_bgzf_rows_dev": (_i32, [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _vp]),
+    "wc_bgzf_rows": (_i32, [_vp, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _vp]),
     "wc_bam_open": (_i32, [_c.c_char_p, _i32, _vp]),
     "wc_bam_info": (_i32, [_vp, _vp]),
     "wc_bam_refs": (_i32, [_vp, _vp, _i64, _vp, _vp]),

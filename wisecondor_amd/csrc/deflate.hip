@@ -5,6 +5,9 @@
 //                  block's share of the row's CRC-32
 //   k_df_gather    the blocks' bytes to their place in the row's stream (prefix sum of the block lengths), the row's
 //                  length and CRC-32
+//   k_bgzf_encode  k_df_encode's block coder on rows of unequal lengths, which it reads on the device: every block a
+//   k_bgzf_gather  deflate stream of its own, framed as a BGZF block (header with its size, CRC-32, ISIZE), and the
+//                  end-of-file block behind the row's last (`exporttracks -gz`)
 //   k_df_assemble  the .npy members results_r / results_z of a batch from their framing (a template with gaps) and the
 //                  float64 rows on the device
 //
@@ -157,20 +160,13 @@ template <class F> __device__ __forceinline__ void df_tokens(const uint8_t *slic
     }
 }
 
-__global__ void __launch_bounds__(DF_T) k_df_encode(const uint8_t *__restrict__ src, long long row_bytes, long long src_stride,
-                                                    int n_blk, uint8_t *__restrict__ scratch, int *__restrict__ blk_len,
-                                                    uint32_t *__restrict__ blk_crc) {
-    __shared__ DfLds S;
+// One block: the n bytes at `in` coded into `slot`, its length into *len_out, and into *crc_out the block's CRC-32 share
+// (register started at zero) moved `behind` bytes on: to the end of the stream the block is part of, 0 for the block's own.
+// final_blk: the deflate stream ends with this block.
+__device__ __forceinline__ void df_encode_block(DfLds &S, const uint8_t *__restrict__ in, const int n, const bool final_blk,
+                                                const long long behind, uint8_t *__restrict__ slot, int *__restrict__ len_out,
+                                                uint32_t *__restrict__ crc_out) {
     const int t = threadIdx.x;
-    const long long id = blockIdx.x;
-    const long long row = id / n_blk;
-    const int b = (int)(id - row * n_blk);
-    const long long start = (long long)b * DF_B;
-    const int n = (int)(row_bytes - start < DF_B ? row_bytes - start : DF_B);      // 0 only in an empty row
-    const bool final_blk = b == n_blk - 1;
-    const uint8_t *in = src + row * src_stride + start;
-    uint8_t *slot = scratch + id * DF_CAP;
-
     {
         uint32_t c = (uint32_t)t;
         for (int k = 0; k < 8; ++k) c = (c >> 1) ^ ((c & 1u) ? 0xEDB88320u : 0u);
@@ -222,7 +218,7 @@ __global__ void __launch_bounds__(DF_T) k_df_encode(const uint8_t *__restrict__ 
         wc_sync();
         if (t == 0) {
             const uint32_t x = (uint32_t)(S.wtot[0] ^ S.wtot[1] ^ S.wtot[2] ^ S.wtot[3]);
-            S.crc = x ? df_mulmod(df_xpow8((uint64_t)(row_bytes - start - n)), x) : 0u;       // ... and to the row's end
+            S.crc = x ? df_mulmod(df_xpow8((uint64_t)behind), x) : 0u;       // ... and to the stream's end
         }
         wc_sync();
     }
@@ -359,14 +355,72 @@ __global__ void __launch_bounds__(DF_T) k_df_encode(const uint8_t *__restrict__ 
         }
     }
     if (t == 0) {
-        blk_len[id] = coded ? coded_bytes : stored_bytes;
-        blk_crc[id] = S.crc;
+        *len_out = coded ? coded_bytes : stored_bytes;
+        *crc_out = S.crc;
     }
 }
 
+__global__ void __launch_bounds__(DF_T) k_df_encode(const uint8_t *__restrict__ src, long long row_bytes, long long src_stride,
+                                                    int n_blk, uint8_t *__restrict__ scratch, int *__restrict__ blk_len,
+                                                    uint32_t *__restrict__ blk_crc) {
+    __shared__ DfLds S;
+    const long long id = blockIdx.x;
+    const long long row = id / n_blk;
+    const int b = (int)(id - row * n_blk);
+    const long long start = (long long)b * DF_B;
+    const int n = (int)(row_bytes - start < DF_B ? row_bytes - start : DF_B);      // 0 only in an empty row
+    df_encode_block(S, src + row * src_stride + start, n, b == n_blk - 1, row_bytes - start - n, scratch + id * DF_CAP, &blk_len[id],
+                    &blk_crc[id]);
+}
+
+// BGZF (the SAM specification, section 4.1): every block of a row is a gzip member of its own with the extra field BC
+// that holds the member's size, and the 28-byte empty member ends the file.
+const int BZ_HEAD = 18, BZ_TAIL = 8, BZ_EOF = 28;
+__constant__ uint8_t bz_eof[BZ_EOF] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+
+// blocks of a row of `len` bytes, read on the device: none for an empty row; -1 for a length outside 0 .. max_row_bytes
+__device__ __forceinline__ long long bz_blocks(long long len, long long max_row_bytes) {
+    return len < 0 || len > max_row_bytes ? -1 : (len + DF_B - 1) / DF_B;
+}
+
+// Workgroup (row, b) of a grid sized by the longest row: block b of the row's first row_len[row] bytes as a deflate stream
+// of its own (the final bit set) with the block's own CRC-32 share; blocks behind the row's end do nothing.
+__global__ void __launch_bounds__(DF_T) k_bgzf_encode(const uint8_t *__restrict__ src, const long long *__restrict__ row_len,
+                                                      long long max_row_bytes, long long src_stride, int n_blk,
+                                                      uint8_t *__restrict__ scratch, int *__restrict__ blk_len,
+                                                      uint32_t *__restrict__ blk_crc) {
+    __shared__ DfLds S;
+    const long long id = blockIdx.x;
+    const long long row = id / n_blk;
+    const int b = (int)(id - row * n_blk);
+    const long long len = row_len[row];
+    if (b >= bz_blocks(len, max_row_bytes)) return;             // (the same in every lane)
+    const long long start = (long long)b * DF_B;
+    const int n = (int)(len - start < DF_B ? len - start : DF_B);
+    df_encode_block(S, src + row * src_stride + start, n, true, 0, scratch + id * DF_CAP, &blk_len[id], &blk_crc[id]);
+}
+
+// len bytes of a scratch slot to `to`.  The destination is arbitrary to the byte, the slot is 16-byte aligned: whole
+// destination words are put together from two source words.
+__device__ __forceinline__ void df_copy_block(const uint8_t *__restrict__ from, uint8_t *__restrict__ to, const int len, const int t) {
+    int head = (int)((4u - (unsigned)(reinterpret_cast<uintptr_t>(to) & 3u)) & 3u);
+    if (head > len) head = len;
+    const int words = (len - head) >> 2;
+    if (t < head) to[t] = from[t];
+    const uint32_t *from32 = reinterpret_cast<const uint32_t *>(from);
+    uint32_t *to32 = reinterpret_cast<uint32_t *>(to + head);
+    const int sh = 8 * (head & 3);
+    for (int w = t; w < words; w += DF_T) {
+        const int at = (head >> 2) + w;         // (head < 4: at == w; the second word stays inside the slot, DF_CAP - DF_B - 5 > 7)
+        const uint32_t lo = from32[at], hi = from32[at + 1];
+        to32[w] = sh ? (lo >> sh) | (hi << (32 - sh)) : lo;
+    }
+    const int done = head + 4 * words;
+    if (t < len - done) to[done + t] = from[done + t];
+}
+
 // Block (row, b): its bytes from the scratch slot to out + row * out_stride + (the lengths of the row's blocks before it);
-// the row's last block also leaves the row's length and CRC-32.  The destination is arbitrary to the byte, the slot is
-// 16-byte aligned: whole destination words are put together from two source words.
+// the row's last block also leaves the row's length and CRC-32.
 __global__ void __launch_bounds__(DF_T) k_df_gather(const uint8_t *__restrict__ scratch, const int *__restrict__ blk_len,
                                                     const uint32_t *__restrict__ blk_crc, int n_blk, long long row_bytes,
                                                     uint8_t *__restrict__ out, long long out_stride, long long *__restrict__ out_len,
@@ -398,22 +452,54 @@ __global__ void __launch_bounds__(DF_T) k_df_gather(const uint8_t *__restrict__ 
         // the registers above started at zero; zlib's starts at all ones and is inverted at the end
         crc_out[row] = x ^ df_mulmod(df_xpow8((uint64_t)row_bytes), 0xFFFFFFFFu) ^ 0xFFFFFFFFu;
     }
-    const uint8_t *from = scratch + id * DF_CAP;
-    uint8_t *to = out + row * out_stride + off;
-    int head = (int)((4u - (unsigned)(reinterpret_cast<uintptr_t>(to) & 3u)) & 3u);
-    if (head > len) head = len;
-    const int words = (len - head) >> 2;
-    if (t < head) to[t] = from[t];
-    const uint32_t *from32 = reinterpret_cast<const uint32_t *>(from);
-    uint32_t *to32 = reinterpret_cast<uint32_t *>(to + head);
-    const int sh = 8 * (head & 3);
-    for (int w = t; w < words; w += DF_T) {
-        const int at = (head >> 2) + w;         // (head < 4: at == w; the second word stays inside the slot, DF_CAP - DF_B - 5 > 7)
-        const uint32_t lo = from32[at], hi = from32[at + 1];
-        to32[w] = sh ? (lo >> sh) | (hi << (32 - sh)) : lo;
+    df_copy_block(scratch + id * DF_CAP, out + row * out_stride + off, len, t);
+}
+
+// A BGZF block's place is the sum of the sizes of the row's blocks before it, each BZ_HEAD + its stream + BZ_TAIL; the
+// row's last block (block 0 of an empty row, which has none) also leaves the end-of-file block and the row's length.
+// out_len[row] = -1 and nothing else for a row_len[row] outside 0 .. max_row_bytes.
+__global__ void __launch_bounds__(DF_T) k_bgzf_gather(const uint8_t *__restrict__ scratch, const int *__restrict__ blk_len,
+                                                      const uint32_t *__restrict__ blk_crc, const long long *__restrict__ row_len,
+                                                      long long max_row_bytes, int n_blk, uint8_t *__restrict__ out,
+                                                      long long out_stride, long long *__restrict__ out_len) {
+    __shared__ long long s_off[4];
+    const int t = threadIdx.x;
+    const long long id = blockIdx.x;
+    const long long row = id / n_blk;
+    const int b = (int)(id - row * n_blk);
+    const long long rlen = row_len[row];
+    const long long nb = bz_blocks(rlen, max_row_bytes);
+    uint8_t *base = out + row * out_stride;
+    if (nb <= 0) {
+        if (b == 0 && nb == 0 && t < BZ_EOF) base[t] = bz_eof[t];
+        if (b == 0 && t == 0) out_len[row] = nb == 0 ? BZ_EOF : -1;
+        return;
     }
-    const int done = head + 4 * words;
-    if (t < len - done) to[done + t] = from[done + t];
+    if (b >= nb) return;
+    long long off = 0;
+    for (int k = t; k < b; k += DF_T) off += blk_len[row * n_blk + k] + BZ_HEAD + BZ_TAIL;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) off += __shfl_xor(off, d);
+    if ((t & 63) == 0) s_off[t >> 6] = off;
+    wc_sync();
+    off = s_off[0] + s_off[1] + s_off[2] + s_off[3];
+    const int len = blk_len[id];
+    const long long start = (long long)b * DF_B;
+    const uint32_t n = (uint32_t)(rlen - start < DF_B ? rlen - start : DF_B);
+    uint8_t *to = base + off;
+    if (t < BZ_HEAD) {
+        const uint32_t bsize = (uint32_t)(BZ_HEAD + len + BZ_TAIL - 1);
+        to[t] = t < 16 ? bz_eof[t] : (uint8_t)(bsize >> (8 * (t - 16)));
+    } else if (t < BZ_HEAD + BZ_TAIL) {
+        // the register of the block's share started at zero; zlib's starts at all ones and is inverted at the end
+        const uint32_t crc = blk_crc[id] ^ df_mulmod(df_xpow8((uint64_t)n), 0xFFFFFFFFu) ^ 0xFFFFFFFFu;
+        const int k = t - BZ_HEAD;
+        to[BZ_HEAD + len + k] = (uint8_t)((k < 4 ? crc : n) >> (8 * (k & 3)));
+    } else if (b == nb - 1 && t >= 64 && t < 64 + BZ_EOF) {
+        to[BZ_HEAD + len + BZ_TAIL + (t - 64)] = bz_eof[t - 64];
+    }
+    if (b == nb - 1 && t == 0) out_len[row] = off + BZ_HEAD + len + BZ_TAIL + BZ_EOF;
+    df_copy_block(scratch + id * DF_CAP, to + BZ_HEAD, len, t);
 }
 
 // image[row, p] = the member's byte p: the template's, or inside gap c byte p - dst[c] of the doubles
@@ -526,6 +612,70 @@ int wc_deflate_rows(wc_ctx *ctx, const unsigned char *src, int64_t n_rows, int64
         if (out_len[i] > 0)
             WC_HIP(hipMemcpy(out + i * out_stride, ctx->tmp_b.as<unsigned char>() + i * out_stride, (size_t)out_len[i],
                              hipMemcpyDeviceToHost));
+    return WC_OK;
+}
+
+int64_t wc_bgzf_bound(int64_t row_bytes) {
+    if (row_bytes < 0) return -1;
+    return row_bytes + (BZ_HEAD + 5 + BZ_TAIL) * ((row_bytes + DF_B - 1) / DF_B) + BZ_EOF;
+}
+
+int wc_bgzf_rows_dev(wc_ctx *ctx, void *stream_, const unsigned char *src, int64_t n_rows, const int64_t *row_len, int64_t max_row_bytes,
+                     int64_t src_stride, unsigned char *out, int64_t out_stride, int64_t *out_len) {
+    WC_CHECK(ctx && n_rows >= 0 && max_row_bytes >= 0 && src_stride >= max_row_bytes && (src || n_rows == 0 || max_row_bytes == 0) &&
+                 (n_rows == 0 || (row_len && out && out_len)),
+             WC_E_ARG, "bgzf: unusable argument");
+    WC_CHECK(out_stride >= wc_bgzf_bound(max_row_bytes), WC_E_ARG, "bgzf: %lld bytes per output row, wc_bgzf_bound(%lld) is %lld",
+             (long long)out_stride, (long long)max_row_bytes, (long long)wc_bgzf_bound(max_row_bytes));
+    if (n_rows == 0) return WC_OK;
+    const int64_t n_blk = blocks_of(max_row_bytes);
+    WC_CHECK(n_blk <= INT_MAX / 2 && n_rows <= (int64_t)INT_MAX / n_blk, WC_E_LIMIT, "bgzf: %lld rows of up to %lld blocks in one call",
+             (long long)n_rows, (long long)n_blk);
+    const int64_t total = n_rows * n_blk;
+    WC_HIP(hipSetDevice(ctx->device));
+    hipStream_t stream = (hipStream_t)stream_;
+    int rc;
+    if ((rc = ctx->df_scratch.reserve((size_t)total * DF_CAP)) || (rc = ctx->df_meta.reserve((size_t)total * 8))) return rc;
+    int *blk_len = ctx->df_meta.as<int>();
+    uint32_t *blk_crc = ctx->df_meta.as<uint32_t>() + total;
+    hipLaunchKernelGGL(k_bgzf_encode, dim3((unsigned)total), dim3(DF_T), 0, stream, (const uint8_t *)src, (const long long *)row_len,
+                       (long long)max_row_bytes, (long long)src_stride, (int)n_blk, ctx->df_scratch.as<uint8_t>(), blk_len, blk_crc);
+    WC_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_bgzf_gather, dim3((unsigned)total), dim3(DF_T), 0, stream, (const uint8_t *)ctx->df_scratch.as<uint8_t>(),
+                       (const int *)blk_len, (const uint32_t *)blk_crc, (const long long *)row_len, (long long)max_row_bytes, (int)n_blk,
+                       (uint8_t *)out, (long long)out_stride, (long long *)out_len);
+    WC_HIP(hipGetLastError());
+    return WC_OK;
+}
+
+int wc_bgzf_rows(wc_ctx *ctx, const unsigned char *src, int64_t n_rows, const int64_t *row_len, int64_t max_row_bytes, int64_t src_stride,
+                 unsigned char *out, int64_t out_stride, int64_t *out_len) {
+    WC_CHECK(ctx && n_rows >= 0 && max_row_bytes >= 0 && src_stride >= max_row_bytes && (src || n_rows == 0 || max_row_bytes == 0) &&
+                 (n_rows == 0 || (row_len && out && out_len)),
+             WC_E_ARG, "bgzf: unusable argument");
+    WC_CHECK(out_stride >= wc_bgzf_bound(max_row_bytes), WC_E_ARG, "bgzf: %lld bytes per output row, wc_bgzf_bound(%lld) is %lld",
+             (long long)out_stride, (long long)max_row_bytes, (long long)wc_bgzf_bound(max_row_bytes));
+    for (int64_t i = 0; i < n_rows; ++i)
+        WC_CHECK(row_len[i] >= 0 && row_len[i] <= max_row_bytes, WC_E_ARG, "bgzf: row %lld has %lld bytes, max_row_bytes is %lld", (long long)i,
+                 (long long)row_len[i], (long long)max_row_bytes);
+    if (n_rows == 0) return WC_OK;
+    WC_HIP(hipSetDevice(ctx->device));
+    const size_t in_bytes = (size_t)((n_rows - 1) * src_stride + row_len[n_rows - 1]), out_bytes = (size_t)(n_rows * out_stride);
+    int rc;
+    if ((rc = ctx->tmp_a.reserve(in_bytes + 4)) || (rc = ctx->tmp_b.reserve(out_bytes)) || (rc = ctx->tmp_c.reserve((size_t)n_rows * 8)) ||
+        (rc = ctx->tmp_d.reserve((size_t)n_rows * 8)))
+        return rc;
+    if (in_bytes) WC_HIP(hipMemcpy(ctx->tmp_a.p, src, in_bytes, hipMemcpyHostToDevice));
+    WC_HIP(hipMemcpy(ctx->tmp_d.p, row_len, (size_t)n_rows * 8, hipMemcpyHostToDevice));
+    rc = wc_bgzf_rows_dev(ctx, nullptr, ctx->tmp_a.as<unsigned char>(), n_rows, ctx->tmp_d.as<int64_t>(), max_row_bytes, src_stride,
+                          ctx->tmp_b.as<unsigned char>(), out_stride, ctx->tmp_c.as<int64_t>());
+    if (rc) return rc;
+    WC_HIP(hipMemcpy(out_len, ctx->tmp_c.p, (size_t)n_rows * 8, hipMemcpyDeviceToHost));
+    // only the files: the bytes behind them are whatever the staging buffer held
+    for (int64_t i = 0; i < n_rows; ++i) {
+        WC_CHECK(out_len[i] >= BZ_EOF && out_len[i] <= out_stride, WC_E_INTERNAL, "bgzf: a row of %lld bytes", (long long)out_len[i]);
+        WC_HIP(hipMemcpy(out + i * out_stride, ctx->tmp_b.as<unsigned char>() + i * out_stride, (size_t)out_len[i], hipMemcpyDeviceToHost));
+    }
     return WC_OK;
 }
 

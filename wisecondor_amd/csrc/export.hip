@@ -16,10 +16,11 @@
 
 #include "ctx.h"
 #include "fmt_double.h"
+#include "tile_text.h"
 
 namespace {
 
-const int JS_T = 256;                   // values per tile = lanes per workgroup (the kernels' one tile and trip size)
+const int JS_T = TT_T;                  // values per tile = lanes per workgroup (the kernels' one tile and trip size; tile_text.h)
 const int JS_IMG = 32 * JS_T;           // bytes of a tile's image: two 16-byte lines per lane
 // the most a tile's image holds: up to 15 bytes in front (the image starts on a multiple of 16), the head (tile 0), JS_T
 // fields of 24 bytes and a comma or bracket each, and at most once per call the rest of the brackets and commas
@@ -53,48 +54,9 @@ __host__ __device__ inline int js_gap(const long long *off, int n_chrom, int a, 
     return k + 1;
 }
 
-// the chromosome of value j (0 <= j < off[n_chrom]): the last one that starts at or before j and is not empty
-__device__ __forceinline__ int js_chrom_of(const long long *off, int n_chrom, long long j) {
-    int lo = 0, hi = n_chrom;           // off[lo] <= j < off[hi]
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (off[mid] <= j) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
-
 __device__ __forceinline__ void js_load_tab(const JsTab &tab, long long *s_off) {
     for (int i = threadIdx.x; i <= tab.n_chrom; i += JS_T) s_off[i] = tab.off[i];
     wc_sync();
-}
-
-// inclusive sum over the workgroup's lanes (buf: JS_T ints); every lane calls it
-__device__ __forceinline__ int js_scan(int v, int *buf) {
-    const int t = threadIdx.x;
-    buf[t] = v;
-    wc_sync();
-    for (int step = 1; step < JS_T; step <<= 1) {
-        const int add = t >= step ? buf[t - step] : 0;
-        wc_sync();
-        buf[t] += add;
-        wc_sync();
-    }
-    return buf[t];
-}
-
-// image[g - a0] for the global bytes g of [r0, r1), a0 = r0 rounded down to 16: whole lines as 16-byte stores, the
-// parts of the first and the last line byte by byte (`out` + a0 is 16-byte aligned)
-__device__ __forceinline__ void js_store(const unsigned char *image, long long a0, long long r0, long long r1, unsigned char *out) {
-    for (int line = threadIdx.x; a0 + 16ll * line < r1; line += JS_T) {
-        const long long g = a0 + 16ll * line;
-        if (g >= r0 && g + 16 <= r1) {
-            *reinterpret_cast<uint4 *>(out + g) = reinterpret_cast<const uint4 *>(image)[line];
-        } else {
-            const long long from = g > r0 ? g : r0, to = g + 16 < r1 ? g + 16 : r1;
-            for (long long q = from; q < to; ++q) out[q] = image[q - a0];
-        }
-    }
 }
 
 __global__ __launch_bounds__(JS_T) void k_js_len(const double *__restrict__ rows, long long row_stride, const JsTab tab, int strict,
@@ -108,7 +70,7 @@ __global__ __launch_bounds__(JS_T) void k_js_len(const double *__restrict__ rows
     if (j < tab.total) {
         const FdDec d = fd_decimal((uint64_t)__double_as_longlong(rows[row * row_stride + j]));
         slots[row * tab.total + j] = make_uint4((unsigned)d.digits, (unsigned)(d.digits >> 32), (unsigned)d.exp, d.kind);
-        const int c = js_chrom_of(s_off, tab.n_chrom, j);
+        const int c = tt_chrom_of(s_off, tab.n_chrom, j);
         w = fd_length(d, strict) + (j + 1 < s_off[c + 1] ? 1 : js_gap(s_off, tab.n_chrom, c, nullptr));
     }
     for (int d = 32; d >= 1; d >>= 1) w += __shfl_down(w, d, 64);
@@ -130,7 +92,7 @@ __global__ __launch_bounds__(JS_T) void k_js_scan(const int *__restrict__ sums, 
     for (long long base = 0; base < n_tiles; base += JS_T) {
         const long long b = base + t;
         const int v = b < n_tiles ? sums[row * n_tiles + b] : 0;
-        const int incl = js_scan(v, s_buf);
+        const int incl = tt_scan(v, s_buf);
         if (b < n_tiles) tile_off[row * n_tiles + b] = carry + incl - v;
         carry += s_buf[JS_T - 1];
         wc_sync();                              // (the next trip writes s_buf again)
@@ -154,11 +116,11 @@ __global__ __launch_bounds__(JS_T) void k_js_bytes(const uint4 *__restrict__ slo
         d.digits = (uint64_t)s.x | ((uint64_t)s.y << 32);
         d.exp = (int32_t)s.z;
         d.kind = s.w;
-        c = js_chrom_of(s_off, tab.n_chrom, j);
+        c = tt_chrom_of(s_off, tab.n_chrom, j);
         gap = j + 1 < s_off[c + 1] ? 0 : js_gap(s_off, tab.n_chrom, c, nullptr);
         w = fd_length(d, strict) + (gap ? gap : 1);
     }
-    const int incl = js_scan(w, s_buf);
+    const int incl = tt_scan(w, s_buf);
     const long long start = tab.head + tile_off[row * gridDim.x + blockIdx.x];      // where the tile's first field begins
     const long long r0 = blockIdx.x == 0 ? 0 : start, r1 = start + s_buf[JS_T - 1], a0 = r0 & ~15ll;
     if (j < tab.total) {
@@ -169,7 +131,7 @@ __global__ __launch_bounds__(JS_T) void k_js_bytes(const uint4 *__restrict__ slo
     }
     if (blockIdx.x == 0 && t == 0) js_gap(s_off, tab.n_chrom, -1, image);
     wc_sync();
-    js_store(image, a0, r0, r1, text + row * text_stride);
+    tt_store(image, a0, r0, r1, text + row * text_stride);
 }
 
 __global__ __launch_bounds__(JS_T) void k_js_format(const double *__restrict__ v, long long n, int strict, unsigned char *__restrict__ text,
@@ -185,7 +147,7 @@ __global__ __launch_bounds__(JS_T) void k_js_format(const double *__restrict__ v
     }
     wc_sync();
     const long long r0 = (long long)blockIdx.x * JS_T * FD_MAX_TEXT, end = n * FD_MAX_TEXT;
-    js_store(image, r0, r0, r0 + JS_T * FD_MAX_TEXT < end ? r0 + JS_T * FD_MAX_TEXT : end, text);
+    tt_store(image, r0, r0, r0 + JS_T * FD_MAX_TEXT < end ? r0 + JS_T * FD_MAX_TEXT : end, text);
 }
 
 // ---- the host's half ----------------------------------------------------------------------------------------------------

@@ -426,6 +426,11 @@ def _load_result(path):
 
 
 def _write_bytes(path, data):
+    """`data` to the file `path`; a tuple of names takes a tuple of files."""
+    if isinstance(path, tuple):
+        for one, part in zip(path, data):
+            _write_bytes(one, part)
+        return
     with open(path, 'wb') as f:
         f.write(data)
 
@@ -498,9 +503,101 @@ def run_exportjson(paths, outdir, args, device=0):
                       outs=export_output_names(paths, outdir, bool(getattr(args, 'gz', False))))
 
 
+def tracks_output_names(paths, outdir, gz=False, only=None):
+    """Per input the tuple (<outdir>/<stem>_z.bedgraph, <stem>_r.bedgraph, <stem>_calls.bed), the tracks .bedgraph.gz with
+    gz and one of them alone with only = 'z' or 'r'; two inputs with the same stem are an error up front."""
+    names, seen = [], {}
+    ending = 'bedgraph.gz' if gz else 'bedgraph'
+    for path in paths:
+        stem = os.path.basename(path)
+        stem = stem[:-4] if stem.endswith('.npz') else stem
+        if stem in seen:
+            raise ValueError('exporttracks: %s and %s would both be written to %s_calls.bed; rename one of them' % (seen[stem], path, stem))
+        seen[stem] = path
+        tracks = [os.path.join(outdir, '%s_%s.%s' % (stem, key, ending)) for key in wt.TRACKS if only in (None, key)]
+        names.append(tuple(tracks) + (os.path.join(outdir, '%s_calls.bed' % stem),))
+    return names
+
+
+def read_chrom_sizes(path):
+    """A chromosome sizes file (name<TAB>length per line, further columns ignored) as {name: length}; ValueError for a
+    file that cannot be read or a line that is not that."""
+    lengths = {}
+    try:
+        with open(path) as f:
+            for number, line in enumerate(f, 1):
+                if not line.strip() or line.startswith('#'):
+                    continue
+                fields = line.rstrip('\r\n').split('\t')
+                if len(fields) < 2 or not fields[1].strip().isdigit():
+                    raise ValueError('line %d is not name<TAB>length' % number)
+                lengths[fields[0]] = int(fields[1])
+    except (OSError, ValueError) as exc:
+        raise ValueError('exporttracks: -chromsizes %s: %s' % (path, exc))
+    return lengths
+
+
+def chrom_lengths_for(lengths, prefix, sizes, binsize, path='the -chromsizes file'):
+    """The lengths of the chromosomes <prefix>1 .. <prefix>n in the order of `sizes` (their bin counts); ValueError if one
+    is missing or a chromosome's last bin starts at or beyond its length."""
+    out = []
+    for i, bins in enumerate(sizes):
+        name = '%s%d' % (prefix, i + 1)
+        if name not in lengths:
+            raise ValueError('exporttracks: %s has no chromosome %s' % (path, name))
+        if bins > 0 and (bins - 1) * binsize >= lengths[name]:
+            raise ValueError('exporttracks: %s gives %s %d bases, the result files have %d bins of %d in it'
+                             % (path, name, lengths[name], bins, binsize))
+        out.append(lengths[name])
+    return out
+
+
+def _load_tracks(path):
+    """What `exporttracks` writes of a result file, or the exception that reading it raised."""
+    try:
+        with np.load(path, allow_pickle=True, encoding='latin1') as f:
+            res = dict(results_z=[np.asarray(c, dtype=np.float64) for c in f['results_z']],
+                       results_r=[np.asarray(c, dtype=np.float64) for c in f['results_r']],
+                       results_calls=np.asarray(f['results_calls'], dtype=np.float64))
+            binsize = np.asarray(f['binsize']).item()
+            if isinstance(binsize, bool) or not isinstance(binsize, (int, float)) or not binsize >= 1 or binsize != int(binsize):
+                raise ValueError('its bin size %r is not a positive whole number' % (binsize,))
+            res['binsize'] = int(binsize)
+            if [len(c) for c in res['results_r']] != [len(c) for c in res['results_z']]:
+                raise ValueError('results_r and results_z differ in their chromosome lengths')
+            return res
+    except Exception as exc:           # reported by name, the run goes on
+        return exc
+
+
+def run_exporttracks(paths, outdir, args, device=0, stats=None):
+    """`exporttracks`: two bedGraph tracks and a BED file of the calls per result file (wt.export_tracks_batch), by
+    run_plotbatch's pipeline and rules.  args.chromsizes: a chromosome sizes file whose lengths clip the ends; it is
+    checked against the first readable file (ValueError).  stats: a dict whose 'dropped' grows by the bins left out as
+    not finite."""
+    gz, only = bool(getattr(args, 'gz', False)), getattr(args, 'only', None)
+    prefix = getattr(args, 'chrprefix', 'chr')
+    table = read_chrom_sizes(args.chromsizes) if getattr(args, 'chromsizes', None) else None
+    clip = []
+
+    def draw(results, names, cytobands, args, device):
+        if table is not None and not clip:
+            clip.append(chrom_lengths_for(table, prefix, [len(c) for c in results[0]['results_z']], results[0]['binsize'], args.chromsizes))
+        details = {}
+        files = wt.export_tracks_batch(results, only=only, gz=gz, nozero=bool(getattr(args, 'nozero', False)), prefix=prefix,
+                                       chrom_lengths=clip[0] if clip else None, mineffect=getattr(args, 'mineffect', 0), device=device,
+                                       details=details)
+        if stats is not None:
+            stats['dropped'] = stats.get('dropped', 0) + sum(sum(counts) for counts in details['dropped'])
+        return files
+    return _run_plots(paths, outdir, args, device, 'exporttracks', 'bedgraph', draw, load=_load_tracks,
+                      outs=tracks_output_names(paths, outdir, gz, only))
+
+
 def _run_plots(paths, outdir, args, device, command, filetype, draw, load=_load_result, outs=None):
-    """The read / draw / write pipeline of `plotbatch`, `plotpdf` and `exportjson`: draw(results, names, cytoband table,
-    args, device) returns the files' bytes; load(path) a result or the exception; outs the files' names."""
+    """The read / draw / write pipeline of `plotbatch`, `plotpdf`, `exportjson` and `exporttracks`: draw(results, names,
+    cytoband table, args, device) returns the files' bytes; load(path) a result or the exception; outs the files' names
+    (a tuple of names per input where draw returns a tuple of files per result)."""
     began = time.time()
     outs = plot_output_names(paths, outdir, filetype, command) if outs is None else outs
     batch = max(1, int(getattr(args, 'batch', 64)))

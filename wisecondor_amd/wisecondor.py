@@ -11,8 +11,9 @@ Build-only additions, all off by default: `-gpus N` on `newref` / `testbatch`
 (one process per GPU), the `testbatch` sub-command (many samples per GPU batch), the `convertbatch`
 sub-command (many BAM files, reading file i + 1 while file i is on the GPU and file i - 1 is written), the
 `plotbatch` sub-command (result files to z-score panel PNGs, drawn and deflated on the GPU), the `plotpdf`
-sub-command (the same panels as vector PDF pages, the content stream written on the GPU) and the `exportjson`
-sub-command (result files to lossless JSON, the numbers' digits made on the GPU).
+sub-command (the same panels as vector PDF pages, the content stream written on the GPU), the `exportjson`
+sub-command (result files to lossless JSON, the numbers' digits made on the GPU) and the `exporttracks` sub-command
+(result files to bedGraph tracks and BED calls for genome browsers, the text and its BGZF blocks made on the GPU).
 `plot` itself stays refused: its default output is a matplotlib PDF, which this build does not make.
 """
 import argparse
@@ -558,9 +559,10 @@ def toolTestBatch(args):
 
 # ------------------------------------------------------------------- plotbatch, plotpdf, exportjson ----
 def _run_result_tool(args, name_outputs, run, noun):
-    """What the three result-file tools do once their options are checked: name_outputs() refuses two inputs with one stem
-    before anything is made, run(infiles, outdir, args) gives (written, skipped, seconds); the summary line counts `noun`,
-    every skipped file is named, and one of them makes the exit status 1."""
+    """What the result-file tools do once their options are checked: name_outputs() refuses two inputs with one stem
+    before anything is made, run(infiles, outdir, args) gives (written, skipped, seconds); the summary line counts `noun`
+    (a text, or a function that gives it once the run is over), every skipped file is named, and one of them makes the
+    exit status 1."""
     try:
         name_outputs()
         os.makedirs(args.outdir, exist_ok=True)
@@ -568,7 +570,8 @@ def _run_result_tool(args, name_outputs, run, noun):
     except ValueError as exc:
         print('ERROR:', exc)
         sys.exit(2)
-    print('%d %s written in %.2f s (%.1f files/s end to end)' % (written, noun, wall, written / wall if wall > 0 else 0.0))
+    print('%d %s written in %.2f s (%.1f files/s end to end)' % (written, noun() if callable(noun) else noun, wall,
+                                                                 written / wall if wall > 0 else 0.0))
     for path, reason in skipped:
         print('ERROR: %s skipped: %s' % (path, reason))
     if skipped:
@@ -608,6 +611,23 @@ def toolExportJson(args):
     or whose chromosome lengths or bin size differ from the first file's, is named and skipped; the exit status is then 1."""
     from . import ingest
     _run_result_tool(args, lambda: ingest.export_output_names(args.infiles, args.outdir, args.gz), ingest.run_exportjson, 'files')
+
+
+def toolExportTracks(args):
+    """`exporttracks infiles... outdir` (build-only): <outdir>/<stem>_z.bedgraph, <stem>_r.bedgraph (.bedgraph.gz, BGZF,
+    with -gz) and <stem>_calls.bed per result file, for genome browsers: a line per run of equal bins, every value as
+    repr writes it; the tracks' text and the BGZF blocks are made on the GPU.  Files are treated as `exportjson` treats
+    them; one whose bin size is no positive whole number is skipped too."""
+    from . import ingest
+    stats = {'dropped': 0}
+
+    def name_outputs():
+        wt._track_prefix(args.chrprefix)
+        if args.chromsizes:
+            ingest.read_chrom_sizes(args.chromsizes)
+        return ingest.tracks_output_names(args.infiles, args.outdir, args.gz, args.only)
+    _run_result_tool(args, name_outputs, lambda infiles, outdir, args: ingest.run_exporttracks(infiles, outdir, args, stats=stats),
+                     lambda: 'result files as tracks (%d bins left out as not finite)' % stats['dropped'])
 
 
 # ---------------------------------------------------------------------- parser ----
@@ -731,6 +751,20 @@ def buildParser():
     p.add_argument('-batch', type=int, default=64, help='files per GPU batch')
     p.add_argument('-io', type=int, default=8, help='file read / write threads')
     p.set_defaults(func=toolExportJson)
+
+    p = sub.add_parser('exporttracks', description='result files as bedGraph tracks and BED calls for genome browsers, '
+                                                   'text and BGZF made on the GPU (build-only)')
+    p.add_argument('infiles', type=str, nargs='+', help='result files written by test / testbatch (.npz)')
+    p.add_argument('outdir', type=str, help='directory receiving <name>_z.bedgraph, <name>_r.bedgraph and <name>_calls.bed per result file')
+    p.add_argument('-gz', action='store_true', help='write the tracks as <name>_z.bedgraph.gz / _r.bedgraph.gz (BGZF, made on the GPU)')
+    p.add_argument('-nozero', action='store_true', help='leave out runs of 0.0 (the fill of masked bins) as well as those not finite')
+    p.add_argument('-only', choices=('z', 'r'), default=None, help='write one of the two tracks')
+    p.add_argument('-chrprefix', type=str, default='chr', help='chromosome i is named <prefix>i (may be empty, at most 16 bytes)')
+    p.add_argument('-chromsizes', type=str, default=None, help='name<TAB>length file; ends are clipped to the lengths')
+    p.add_argument('-mineffect', type=float, default=0, help='Minimal percentual change in read depth of a call to export')
+    p.add_argument('-batch', type=int, default=64, help='files per GPU batch')
+    p.add_argument('-io', type=int, default=8, help='file read / write threads')
+    p.set_defaults(func=toolExportTracks)
 
     p = sub.add_parser('newref', description='Build a reference from healthy samples in one go')
     p.add_argument('infiles', type=str, nargs='*', help='converted reference samples (.npz)')

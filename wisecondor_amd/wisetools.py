@@ -1554,3 +1554,163 @@ def export_json_batch(results, strict=False, gz=False, device=0, ctx=None, max_r
         details['times_ms'] = times
         details['text_bytes'] = text_bytes
     return out
+
+
+# ------------------------------------------------------------------- exporttracks: bedGraph / BED ----
+def _track_prefix(prefix):
+    """The chromosome names' prefix as bytes: at most 16 ASCII bytes, no tab, no newline."""
+    try:
+        raw = prefix.encode('ascii') if isinstance(prefix, str) else bytes(prefix)
+    except UnicodeEncodeError:
+        raise ValueError('a chromosome prefix must be ASCII: %r' % (prefix,))
+    if len(raw) > 16 or any(b in (0, 9, 10) or b > 127 for b in raw):
+        raise ValueError('a chromosome prefix is at most 16 ASCII bytes without tab or newline: %r' % (prefix,))
+    return raw
+
+
+def bedgraphRowBound(sizes, binsize, prefix_len=3):
+    """Most bytes the bedGraph text of one dense row takes (wc_bedgraph_row_bound; host only)."""
+    sizes = np.ascontiguousarray(sizes, dtype=np.int64)
+    bound = int(_lib.load().wc_bedgraph_row_bound(_lib.ptr(sizes), len(sizes), int(binsize), int(prefix_len)))
+    if bound < 0:
+        raise ValueError('bedgraphRowBound: unusable chromosome sizes, bin size or prefix')
+    return bound
+
+
+def bedgraphRows(rows, sizes, binsize, prefix='chr', clip=None, nozero=False, device=0, ctx=None, row_stride=None, times=None):
+    """The bedGraph text of every dense float64 row (host array [n, >= sum(sizes)]), written on the GPU (wc_bedgraph_rows):
+    (a list of bytes, the rows' counts of bins that are not finite).  clip: the chromosomes' lengths, or None.  times: a
+    list that receives [copy in, lengths and scan, bytes, copy out] ms."""
+    lib = _lib.load()
+    rows = np.ascontiguousarray(rows, dtype=np.float64)
+    sizes = np.ascontiguousarray(sizes, dtype=np.int64)
+    raw = _track_prefix(prefix)
+    clip = None if clip is None else np.ascontiguousarray(clip, dtype=np.int64)
+    n = rows.shape[0]
+    stride = max(bedgraphRowBound(sizes, binsize, len(raw)), 1)
+    text = np.zeros((n, stride), dtype=np.uint8)
+    lens = np.zeros(n, dtype=np.int64)
+    dropped = np.zeros(n, dtype=np.int64)
+    t_ms = np.zeros(4, dtype=np.float64) if times is not None else None
+    _lib.check(lib.wc_bedgraph_rows(ctx or _lib.context(device), _lib.ptr(rows), int(rows.shape[1] if row_stride is None else row_stride), n,
+                                    _lib.ptr(sizes), len(sizes), int(binsize), _lib.ptr(clip), raw, len(raw), int(bool(nozero)),
+                                    _lib.ptr(text), stride, _lib.ptr(lens), _lib.ptr(dropped), _lib.ptr(t_ms)))
+    if times is not None:
+        times.extend(t_ms.tolist())
+    return [text[i, :lens[i]].tobytes() for i in range(n)], dropped.tolist()
+
+
+def callsBed(calls, binsize, prefix='chr', chrom_lengths=None, mineffect=0):
+    """The calls of a result file as BED9 lines, as bytes (host only): one line per call [chromosome (from 1), first bin,
+    last bin, z, effect] with abs(effect * 100) > mineffect (`report`'s rule), sorted by (chromosome, start, end), ties
+    in the file's order.  The name column is z=%.2f;effect=%.2f%%, the score min(1000, round(|z| * 10)) (1000 for an
+    infinite z, 0 for NaN), the colour 213,94,0 for a gain and 0,114,178 for a loss; ends are clipped to chrom_lengths."""
+    name = _track_prefix(prefix).decode('ascii')
+    binsize = int(binsize)
+    lines = []
+    for call in np.asarray(calls, dtype=np.float64).reshape(-1, 5):
+        z, effect = float(call[3]), float(call[4])
+        if not abs(effect * 100) > mineffect:
+            continue
+        chrom, start, end = int(call[0]), int(call[1]) * binsize, (int(call[2]) + 1) * binsize
+        if chrom_lengths is not None and 1 <= chrom <= len(chrom_lengths):
+            end = min(end, int(chrom_lengths[chrom - 1]))
+        score = 0 if z != z else 1000 if z - z != 0 else min(1000, int(round(abs(z) * 10)))
+        lines.append((chrom, start, end, '%s%d\t%d\t%d\tz=%.2f;effect=%.2f%%\t%d\t.\t%d\t%d\t%s\n'
+                      % (name, chrom, start, end, z, effect * 100, score, start, end, '213,94,0' if effect > 0 else '0,114,178')))
+    lines.sort(key=lambda line: line[:3])         # (stable: ties keep the file's order)
+    return ''.join(line[3] for line in lines).encode('ascii')
+
+
+TRACKS = ('z', 'r')
+
+
+def export_tracks_batch(results, only=None, gz=False, nozero=False, prefix='chr', chrom_lengths=None, device=0, ctx=None, details=None,
+                        mineffect=0, max_rows=65535, max_bytes=4 << 30):
+    """Result files as genome browser tracks: per result a tuple of the files' bytes, the bedGraph text of
+    results_z and of results_r (`only`: 'z' or 'r' alone) and the calls as BED9 (callsBed, on the host).  A track has one
+    line per run of bins with the same bits inside a chromosome, written by the GPU (wc_bedgraph_rows_dev); with gz it
+    is BGZF, made from the text where it lies (wc_bgzf_rows_dev, one call for the rows of a GPU call, their lengths read
+    on the device), and only the compressed bytes are copied.  results: dicts with binsize, results_z, results_r,
+    results_calls; all share the chromosome lengths and the bin size.  chrom_lengths: the chromosomes' lengths in bases
+    (ends are clipped to them), or None.  mineffect: callsBed's.  A batch is split at max_rows rows and at max_bytes of device memory per GPU
+    call.  details: a dict that receives 'times_ms' (per GPU call [copy in, text, BGZF, copy out]), 'text_bytes' (per file
+    and track), 'dropped' (per file and track: bins that are not finite)."""
+    import torch
+    if only not in (None,) + TRACKS:
+        raise ValueError("only: 'z', 'r' or None, not %r" % (only,))
+    if not results:
+        return []
+    lib = _lib.load()
+    which = [k for k in TRACKS if only in (None, k)]
+    raw = _track_prefix(prefix)
+    binsize = int(results[0]['binsize'])
+    sizes = np.array([len(c) for c in results[0]['results_z']], dtype=np.int64)
+    total = int(sizes.sum())
+    for i, res in enumerate(results):
+        if int(res['binsize']) != binsize or res['binsize'] != binsize:
+            raise ValueError('sample %d has bin size %s, the first has %s' % (i, res['binsize'], binsize))
+    clip = None
+    if chrom_lengths is not None:
+        clip = np.ascontiguousarray(chrom_lengths, dtype=np.int64)
+        if len(clip) != len(sizes):
+            raise ValueError('%d chromosome lengths for %d chromosomes' % (len(clip), len(sizes)))
+    bound = bedgraphRowBound(sizes, binsize, len(raw))
+    stride = max(16, (bound + 15) // 16 * 16)
+    out_stride = int(lib.wc_bgzf_bound(bound)) if gz else 0
+    # device bytes of a row: the values, their digits between the passes, the text; with gz the blocks' slots and the file
+    per_row = 24 * max(total, 1) + stride + (2 * out_stride + 64 * (bound // int(lib.wc_deflate_block_bytes()) + 1) if gz else 0)
+    per_call = max(1, min(int(max_rows), int(max_bytes) // per_row) // len(which))
+    dev = torch.device('cuda', device)
+    handle = ctx or _lib.context(device)
+    out, times, text_bytes, dropped_bins = [], [], [], []
+    for at in range(0, len(results), per_call):
+        part = results[at:at + per_call]
+        n, rows_n = len(part), len(part) * len(which)
+        rows = _pinned((rows_n, max(total, 1)))
+        for k, key in enumerate(which):
+            _dense_rows([res['results_' + key] for res in part], sizes, out=rows[k * n:(k + 1) * n])
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream().cuda_stream
+            marks = [torch.cuda.Event(enable_timing=True) for _ in range(5)] if details is not None else None
+            if marks:
+                marks[0].record()
+            d_rows = torch.from_numpy(rows).to(dev, non_blocking=True)
+            text = torch.empty((rows_n, stride), dtype=torch.uint8, device=dev)
+            counts = torch.empty((3, rows_n), dtype=torch.int64, device=dev)        # text_len, dropped, out_len
+            if marks:
+                marks[1].record()
+            _lib.check(lib.wc_bedgraph_rows_dev(handle, stream, d_rows.data_ptr(), rows.shape[1], rows_n, _lib.ptr(sizes), len(sizes),
+                                                binsize, _lib.ptr(clip), raw, len(raw), int(bool(nozero)), text.data_ptr(), stride,
+                                                counts[0].data_ptr(), counts[1].data_ptr()))
+            if marks:
+                marks[2].record()
+            if gz:
+                files = torch.empty((rows_n, out_stride), dtype=torch.uint8, device=dev)
+                _lib.check(lib.wc_bgzf_rows_dev(handle, stream, text.data_ptr(), rows_n, counts[0].data_ptr(), bound, stride,
+                                                files.data_ptr(), out_stride, counts[2].data_ptr()))
+            if marks:
+                marks[3].record()
+            h_counts = counts.cpu().numpy()
+            if np.any(h_counts[0] < 0) or np.any(h_counts[0] > bound):
+                raise _lib.WisecondorHipError('export_tracks_batch: a row of %d bytes, the bound is %d' % (int(h_counts[0].max()), bound))
+            if gz:
+                if np.any(h_counts[2] < 28) or np.any(h_counts[2] > out_stride):
+                    raise _lib.WisecondorHipError('export_tracks_batch: a BGZF row of %d bytes' % int(h_counts[2].max()))
+                pieces = [files[i, :int(h_counts[2][i])].cpu().numpy().tobytes() for i in range(rows_n)]
+            else:
+                pieces = [text[i, :int(h_counts[0][i])].cpu().numpy().tobytes() for i in range(rows_n)]
+            if marks:
+                marks[4].record()
+                marks[4].synchronize()
+                times.append([marks[k].elapsed_time(marks[k + 1]) for k in range(4)])
+        for i, res in enumerate(part):
+            bed = callsBed(res['results_calls'], binsize, prefix=prefix, chrom_lengths=chrom_lengths, mineffect=mineffect)
+            out.append(tuple(pieces[k * n + i] for k in range(len(which))) + (bed,))
+            text_bytes.append(tuple(int(h_counts[0][k * n + i]) for k in range(len(which))))
+            dropped_bins.append(tuple(int(h_counts[1][k * n + i]) for k in range(len(which))))
+    if details is not None:
+        details['times_ms'] = times
+        details['text_bytes'] = text_bytes
+        details['dropped'] = dropped_bins
+    return out
