@@ -48,6 +48,8 @@ typedef double f64x2_u __attribute__((ext_vector_type(2), aligned(8)));   // row
 typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) void lds_void_t;          // operands of __builtin_amdgcn_global_load_lds
 typedef __attribute__((address_space(1))) const void glb_void_t;
+typedef __attribute__((address_space(3))) char lds_char_t;          // LDS addresses kept as such (32 bits, one register)
+typedef __attribute__((address_space(3))) f64x2 lds_f64x2_t;
 
 // ------------------------------------------------------------------ prepare ----
 // Robust per-sample centre from a strided subset of rows: mean -> 8 x mean absolute
@@ -1629,10 +1631,111 @@ struct RowSum {
 // Dynamic LDS: [target row: Sp doubles][wave slabs: 8 KB each]; after the sums (one barrier) the
 // slab memory holds dk / jv (distances and candidates as computed) and sd / sj (in order).
 constexpr int SLAB_DOUBLES = 64 * ST_CH;
+// A wave's passes follow its pairs: the nb pairs of a trip fill (nb + 7) / 8 passes of eight candidate rows ((nb + 15) / 16
+// DMA groups of sixteen), and the chunk loop is instantiated on that count -- the staging registers of a pass keep
+// compile-time indexes, a pass left out issues no gather, forms no squares and writes no slab piece.  The slab rows of
+// such a pass keep whatever an earlier trip, row or kernel left there: only lanes >= nb read them, and their sums are
+// dropped where the trip's result is formed.
 // GLDS: the candidates' chunks arrive by LDS-DMA (global_load_lds_dwordx4) instead of through staging
 // registers + a ds_write pass: the XOR swizzle moves to the source address, the owning lane forms
 // (candidate - target)^2 itself from the raw values (the same two roundings per element), and the next
 // chunk's DMA runs under the sums of this one.
+// The slab as two halves of 64 rows x 64 B: samples 0-7 and 8-15 of the chunk.  A DMA instruction
+// covers 16 rows (lane l: row 16 j + (l >> 2), slot l & 3, piece slot ^ ((row >> 2) & 3)); as soon as
+// a half has been read into registers the same half of the NEXT chunk is requested, so the DMA runs
+// under this chunk's arithmetic without a second slab (LDS per wave as in the register-staged form)
+template <bool SEQ, int NGRP>
+__device__ __forceinline__ void rescore_chunks_dma(const FinishArgs &a, RowSum<SEQ> &sum, const char *base, const double *xs,
+                                                   char *slab, int cj, int Sp, int nchunk, int lane) {
+    const int l4 = lane & 3, rq = lane >> 2;
+    unsigned int src[NGRP];                              // byte offset of this lane's 16 bytes in chunk 0 of row 16 j + rq
+#pragma unroll
+    for (int j = 0; j < NGRP; ++j) {
+        const int rw = 16 * j + rq;
+        src[j] = ((unsigned int)__shfl(cj, rw) * (unsigned int)Sp + 2u * (unsigned int)(l4 ^ ((rw >> 2) & 3))) * 8u;
+    }
+    int rd[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) rd[q] = lane * 64 + ((q ^ ((lane >> 2) & 3)) << 4);
+    auto dma = [&](int c, int half) {
+        const char *cb = base + (size_t)c * (ST_CH * 8) + half * 64;
+        char *dst = slab + half * 4096;
+#pragma unroll
+        for (int j = 0; j < NGRP; ++j)
+            __builtin_amdgcn_global_load_lds((glb_void_t *)(cb + src[j]), (lds_void_t *)(dst + j * 1024), 16, 0, 0);
+    };
+    dma(0, 0);
+    dma(0, 1);
+    for (int c = 0; c < nchunk; ++c) {
+        __builtin_amdgcn_s_waitcnt(0x0070);          // vmcnt(0) lgkmcnt(0): both halves of chunk c have landed
+        __builtin_amdgcn_wave_barrier();
+        f64x2 t[8];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) t[q] = *(const f64x2 *)(slab + rd[q]);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) t[4 + q] = *(const f64x2 *)(slab + 4096 + rd[q]);
+        __builtin_amdgcn_s_waitcnt(0xC07F);          // lgkmcnt(0) only: the reads are in registers
+        __builtin_amdgcn_wave_barrier();
+        if (c + 1 < nchunk) { dma(c + 1, 0); dma(c + 1, 1); }
+        double v[ST_CH];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            const f64x2 x2 = *(const f64x2 *)&xs[c * ST_CH + 2 * q];     // wave-uniform: a broadcast read
+            const double d0 = t[q].x - x2.x, d1 = t[q].y - x2.y;
+            v[2 * q] = d0 * d0;
+            v[2 * q + 1] = d1 * d1;
+        }
+        sum.chunk_regs(a, v, (int64_t)c * ST_CH, (c + 1) * ST_CH <= a.S);
+    }
+}
+
+// the register-staged form; a lane reads all eight pieces of its own slab row whatever NPASS is
+template <bool SEQ, int NPASS>
+__device__ __forceinline__ void rescore_chunks_staged(const FinishArgs &a, RowSum<SEQ> &sum, const char *base, const double *xs,
+                                                      int cj, int Sp, int nchunk, int lane,
+                                                      lds_char_t *const (&wptr)[8], lds_char_t *const (&rptr)[8]) {
+    const int l8 = lane & 7, r0 = lane >> 3;
+    unsigned int src[NPASS];                             // byte offset of this lane's 16 bytes in chunk 0 of row r0 + 8 q
+#pragma unroll
+    for (int q = 0; q < NPASS; ++q)
+        src[q] = ((unsigned int)__shfl(cj, r0 + 8 * q) * (unsigned int)Sp + 2u * (unsigned int)l8) * 8u;
+    f64x2 pre[NPASS];
+#pragma unroll
+    for (int q = 0; q < NPASS; ++q) {
+        asm volatile("" : "+v"(src[q]));                 // (see the header: the base stays in scalar registers)
+        pre[q] = *(const f64x2 *)(base + src[q]);
+    }
+    for (int c = 0; c < nchunk; ++c) {
+        const f64x2 x2 = *(const f64x2 *)&xs[c * ST_CH + 2 * l8];
+        wave_lds_fence();                                // the previous chunk's reads are done
+#pragma unroll
+        for (int q = 0; q < NPASS; ++q) {
+            const double d0 = pre[q].x - x2.x, d1 = pre[q].y - x2.y;
+            f64x2 sq2;
+            sq2.x = d0 * d0;
+            sq2.y = d1 * d1;
+            *(lds_f64x2_t *)wptr[q] = sq2;
+        }
+        wave_lds_fence();
+        if (c + 1 < nchunk) {
+            const char *cb = base + (size_t)(c + 1) * (ST_CH * 8);      // wave-uniform chunk base
+#pragma unroll
+            for (int q = 0; q < NPASS; ++q) {
+                asm volatile("" : "+v"(src[q]));
+                pre[q] = *(const f64x2 *)(cb + src[q]);
+            }
+        }
+        double v[ST_CH];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            const f64x2 t2 = *(const lds_f64x2_t *)rptr[q];
+            v[2 * q] = t2.x;
+            v[2 * q + 1] = t2.y;
+        }
+        sum.chunk_regs(a, v, (int64_t)c * ST_CH, (c + 1) * ST_CH <= a.S);
+    }
+}
+
 template <bool SEQ, bool GLDS>
 __global__ __launch_bounds__(PS_MAX, (SEQ && !GLDS) ? 4 : (SEQ ? 5 : 3)) void k_rescore(PickArgs p, const double *__restrict__ Xp, int Sp) {
     const FinishArgs &a = p.f;
@@ -1658,12 +1761,22 @@ __global__ __launch_bounds__(PS_MAX, (SEQ && !GLDS) ? 4 : (SEQ ? 5 : 3)) void k_
     constexpr int NP = 8;                                // 8 rows per pass x 8 passes = the wave's 64 candidates
     constexpr int TRIPS = RMAX / 128;                    // a wave's trips with the smallest workgroup (two waves)
     auto swz = [](int r) { return ((r >> 1) & 3) | (((r >> 4) & 1) << 2); };
-    int waddr[NP], raddr[NP];                            // byte offsets in the slab: written pieces, read pieces
+    // LDS addresses of the written and of the read pieces in the wave's slab, pinned in registers: left to itself the
+    // compiler keeps a common part and the piece parts apart and adds them per piece and chunk in every instance of the
+    // chunk loop (ten address adds beside the 48 float64 operations of a chunk).  The written pieces of passes q and
+    // q + 2 differ by a constant (bit 4 of the row is bit 1 of q), which goes into the instruction's offset.
+    lds_char_t *wptr[NP], *rptr[NP], *wbase[2];
+    lds_char_t *slab3 = (lds_char_t *)slab;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        wbase[h] = slab3 + r0 * 128 + ((l8 ^ swz(r0 + 16 * h)) << 4);
+        asm volatile("" : "+v"(wbase[h]));
+    }
 #pragma unroll
     for (int q = 0; q < NP; ++q) {
-        const int rw = r0 + 8 * q;
-        waddr[q] = rw * 128 + ((l8 ^ swz(rw)) << 4);
-        raddr[q] = lane * 128 + ((q ^ swz(lane)) << 4);
+        wptr[q] = wbase[(q >> 1) & 1] + q * 1024;        // row r0 + 8 q
+        rptr[q] = slab3 + lane * 128 + ((q ^ swz(lane)) << 4);
+        asm volatile("" : "+v"(rptr[q]));
     }
     unsigned long long my_d[TRIPS];
     int my_j[TRIPS];
@@ -1675,92 +1788,27 @@ __global__ __launch_bounds__(PS_MAX, (SEQ && !GLDS) ? 4 : (SEQ ? 5 : 3)) void k_
         const int *cjp = p.pairs + row * RMAX + b0;
         int cj = trip == 0 ? cj_first : cjp[lane < nb ? lane : 0];
         if (trip == 0) cj = __shfl(cj, lane < nb ? lane : 0);   // lanes beyond nb take the trip's first candidate; their sums are dropped
-        unsigned int src[NP];                            // byte offset of this lane's 16 bytes in chunk 0 of row r0 + 8 q
         RowSum<SEQ> sum;
         sum.init(a);
+        // the chunk loop on the number of passes (DMA groups) the wave's nb pairs fill
         if constexpr (GLDS) {
-            // the slab as two halves of 64 rows x 64 B: samples 0-7 and 8-15 of the chunk.  A DMA instruction
-            // covers 16 rows (lane l: row 16 j + (l >> 2), slot l & 3, piece slot ^ ((row >> 2) & 3)); as soon as
-            // a half has been read into registers the same half of the NEXT chunk is requested, so the DMA runs
-            // under this chunk's arithmetic without a second slab (LDS per wave as in the register-staged form)
-            const int l4 = lane & 3, rq = lane >> 2;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int rw = 16 * j + rq;
-                src[j] = ((unsigned int)__shfl(cj, rw) * (unsigned int)Sp + 2u * (unsigned int)(l4 ^ ((rw >> 2) & 3))) * 8u;
-            }
-            int rd[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) rd[q] = lane * 64 + ((q ^ ((lane >> 2) & 3)) << 4);
-            auto dma = [&](int c, int half) {
-                const char *cb = base + (size_t)c * (ST_CH * 8) + half * 64;
-                char *dst = slab + half * 4096;
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    __builtin_amdgcn_global_load_lds((glb_void_t *)(cb + src[j]), (lds_void_t *)(dst + j * 1024), 16, 0, 0);
-            };
-            dma(0, 0);
-            dma(0, 1);
-            for (int c = 0; c < nchunk; ++c) {
-                __builtin_amdgcn_s_waitcnt(0x0070);          // vmcnt(0) lgkmcnt(0): both halves of chunk c have landed
-                __builtin_amdgcn_wave_barrier();
-                f64x2 t[8];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) t[q] = *(const f64x2 *)(slab + rd[q]);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) t[4 + q] = *(const f64x2 *)(slab + 4096 + rd[q]);
-                __builtin_amdgcn_s_waitcnt(0xC07F);          // lgkmcnt(0) only: the reads are in registers
-                __builtin_amdgcn_wave_barrier();
-                if (c + 1 < nchunk) { dma(c + 1, 0); dma(c + 1, 1); }
-                double v[ST_CH];
-#pragma unroll
-                for (int q = 0; q < NP; ++q) {
-                    const f64x2 x2 = *(const f64x2 *)&xs[c * ST_CH + 2 * q];     // wave-uniform: a broadcast read
-                    const double d0 = t[q].x - x2.x, d1 = t[q].y - x2.y;
-                    v[2 * q] = d0 * d0;
-                    v[2 * q + 1] = d1 * d1;
-                }
-                sum.chunk_regs(a, v, (int64_t)c * ST_CH, (c + 1) * ST_CH <= a.S);
+            switch (__builtin_amdgcn_readfirstlane((nb + 15) >> 4)) {
+                case 1: rescore_chunks_dma<SEQ, 1>(a, sum, base, xs, slab, cj, Sp, nchunk, lane); break;
+                case 2: rescore_chunks_dma<SEQ, 2>(a, sum, base, xs, slab, cj, Sp, nchunk, lane); break;
+                case 3: rescore_chunks_dma<SEQ, 3>(a, sum, base, xs, slab, cj, Sp, nchunk, lane); break;
+                default: rescore_chunks_dma<SEQ, 4>(a, sum, base, xs, slab, cj, Sp, nchunk, lane); break;
             }
         } else {
-#pragma unroll
-        for (int q = 0; q < NP; ++q)
-            src[q] = ((unsigned int)__shfl(cj, r0 + 8 * q) * (unsigned int)Sp + 2u * (unsigned int)l8) * 8u;
-        f64x2 pre[NP];
-#pragma unroll
-        for (int q = 0; q < NP; ++q) {
-            asm volatile("" : "+v"(src[q]));                 // (see the header: the base stays in scalar registers)
-            pre[q] = *(const f64x2 *)(base + src[q]);
-        }
-        for (int c = 0; c < nchunk; ++c) {
-            const f64x2 x2 = *(const f64x2 *)&xs[c * ST_CH + 2 * l8];
-            wave_lds_fence();                            // the previous chunk's reads are done
-#pragma unroll
-            for (int q = 0; q < NP; ++q) {
-                const double d0 = pre[q].x - x2.x, d1 = pre[q].y - x2.y;
-                f64x2 sq2;
-                sq2.x = d0 * d0;
-                sq2.y = d1 * d1;
-                *(f64x2 *)(slab + waddr[q]) = sq2;
+            switch (__builtin_amdgcn_readfirstlane((nb + 7) >> 3)) {
+                case 1:                                  // (with case 2: one gather in front of a wait is a lone round trip per chunk)
+                case 2: rescore_chunks_staged<SEQ, 2>(a, sum, base, xs, cj, Sp, nchunk, lane, wptr, rptr); break;
+                case 3: rescore_chunks_staged<SEQ, 3>(a, sum, base, xs, cj, Sp, nchunk, lane, wptr, rptr); break;
+                case 4: rescore_chunks_staged<SEQ, 4>(a, sum, base, xs, cj, Sp, nchunk, lane, wptr, rptr); break;
+                case 5: rescore_chunks_staged<SEQ, 5>(a, sum, base, xs, cj, Sp, nchunk, lane, wptr, rptr); break;
+                case 6: rescore_chunks_staged<SEQ, 6>(a, sum, base, xs, cj, Sp, nchunk, lane, wptr, rptr); break;
+                case 7: rescore_chunks_staged<SEQ, 7>(a, sum, base, xs, cj, Sp, nchunk, lane, wptr, rptr); break;
+                default: rescore_chunks_staged<SEQ, 8>(a, sum, base, xs, cj, Sp, nchunk, lane, wptr, rptr); break;
             }
-            wave_lds_fence();
-            if (c + 1 < nchunk) {
-                const char *cb = base + (size_t)(c + 1) * (ST_CH * 8);      // wave-uniform chunk base
-#pragma unroll
-                for (int q = 0; q < NP; ++q) {
-                    asm volatile("" : "+v"(src[q]));
-                    pre[q] = *(const f64x2 *)(cb + src[q]);
-                }
-            }
-            double v[ST_CH];
-#pragma unroll
-            for (int q = 0; q < NP; ++q) {
-                const f64x2 t2 = *(const f64x2 *)(slab + raddr[q]);
-                v[2 * q] = t2.x;
-                v[2 * q + 1] = t2.y;
-            }
-            sum.chunk_regs(a, v, (int64_t)c * ST_CH, (c + 1) * ST_CH <= a.S);
-        }
         }
         const double d = sum.result();
         const bool ok = lane < nb && d < SENTINEL_DISTANCE;  // NaN and >= 1e10 are never admitted (wisetools.py:314)
