@@ -84,12 +84,14 @@ def test_oracle_synthetic(wt, n_samples, binsize, k, order):
 
 
 @pytest.mark.parametrize("order", ["C", "F"])
-def test_more_samples_than_the_row_cache_holds(wt, order):
-    """Above 2048 samples the target row of the float64 re-score is read from global memory
-    instead of LDS, and numpy's pairwise tree is several levels deep."""
+@pytest.mark.parametrize("k", [40, 1, 101, 256])
+def test_more_samples_than_the_row_cache_holds(wt, k, order):
+    """Above 2048 samples (k_finish: one workgroup per row does selection, re-score and order) the target row of
+    the float64 re-score is read from global memory instead of LDS, and numpy's pairwise tree is several levels
+    deep.  k = 256 is more than any row has candidates."""
     rng = np.random.RandomState(11)
     bins = np.array([70, 1, 55, 64], dtype=np.int64)
-    B, S, k = int(bins.sum()), 2500, 40
+    B, S = int(bins.sum()), 2049
     data = 1.0 + 0.03 * rng.standard_normal((B, S))
     data[5] = data[150]
     if order == "F":
