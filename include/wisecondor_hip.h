@@ -629,11 +629,19 @@ int wc_test_profile_read(wc_ctx *ctx, double out[8]);
  * code-length alphabet to 7), or a stored block where that is not smaller.  Behind every coded block but the last an
  * empty stored block pads to a byte boundary.  wc_deflate_bound(n) = n + 10 * (ceil(n / B) + 1).
  * The streams depend on the input bytes alone.  wc_deflate_rows_dev enqueues on `stream` without synchronising
- * (scratch memory of `ctx`: one call in flight per context).                                              */
+ * (scratch memory of `ctx`: one call in flight per context).
+ * wc_deflate_rows_len_dev: the same for rows of unequal lengths, in the shape of wc_bgzf_rows_dev: the stream of the
+ * first row_len[i] (DEVICE int64, read on the device) bytes of row i, an empty row one empty final block; the grid is
+ * sized by max_row_bytes, out_stride >= wc_deflate_bound(max_row_bytes).  A row_len[i] outside 0 .. max_row_bytes
+ * gives out_len[i] = -1 and nothing else for that row.  A row's stream, length and CRC are those of
+ * wc_deflate_rows_dev called on that row alone.                                                           */
 int wc_deflate_block_bytes(void);
 int64_t wc_deflate_bound(int64_t row_bytes);
 int wc_deflate_rows_dev(wc_ctx *ctx, void *stream, const unsigned char *src, int64_t n_rows, int64_t row_bytes,
                         int64_t src_stride, unsigned char *out, int64_t out_stride, int64_t *out_len, uint32_t *crc);
+int wc_deflate_rows_len_dev(wc_ctx *ctx, void *stream, const unsigned char *src, int64_t n_rows, const int64_t *row_len,
+                            int64_t max_row_bytes, int64_t src_stride, unsigned char *out, int64_t out_stride, int64_t *out_len,
+                            uint32_t *crc);
 int wc_deflate_rows(wc_ctx *ctx, const unsigned char *src, int64_t n_rows, int64_t row_bytes, int64_t src_stride,
                     unsigned char *out, int64_t out_stride, int64_t *out_len, uint32_t *crc);
 /* The encoder's Huffman construction, host only (no GPU needed): len_out[s] = code length of symbol s, 0 where

@@ -325,3 +325,87 @@ def test_testbatch_with_the_gpu_encoder(tmp_path, golden):
         assert args_b["outfile"].endswith("s_%d_test.npz" % i)
         assert {k: v for k, v in args_b.items() if k not in ("encoder", "outdir", "outfile")} == \
             {k: v for k, v in args_a.items() if k not in ("outdir", "outfile")}
+
+
+def _text_like(n, seed):
+    """n bytes of result-like text: the repr of float64 noise between commas, a fifth of the values 0.0."""
+    rng = np.random.RandomState(seed)
+    values = rng.standard_normal(n // 4 + 2) * (rng.uniform(size=n // 4 + 2) > 0.2)
+    return np.frombuffer(",".join(repr(float(v)) for v in values).encode("ascii")[:n], dtype=np.uint8)
+
+
+def _runs_over_cuts(n, B):
+    """n distinct bytes with a run of 255 across every block cut (and up to the end, where the cut is the row's last byte)."""
+    row = _distinct(n, 11, 64)
+    for cut in range(B, n + 1, B):
+        row[cut - 300:cut + 300] = 255
+    return row
+
+
+def test_rows_of_unequal_lengths_in_one_call():
+    """wc_deflate_rows_len_dev: rows of every length regime, of text, of noise (stored blocks) and with runs over the block
+    cuts, in ONE call from a source 3 bytes past a 16-byte boundary (export_json_batch's offset: the block coder's
+    unaligned load), max_row_bytes the longest, so that short rows leave idle workgroups.  Every row's stream, length
+    and CRC are those of wc_deflate_rows_dev on that row alone; a length out of range gives -1 and touches nothing."""
+    import torch
+    lib = _lib.load()
+    ctx = _lib.context(0)
+    B = _B()
+    lengths = [0, 1, 63, 64, B - 1, B, B + 1, 2 * B, 2 * B + 5, 3 * B + 7]
+    rng = np.random.RandomState(5)
+    datas = []
+    for length in lengths:
+        datas += [_text_like(length, length), rng.randint(0, 256, size=length).astype(np.uint8), _runs_over_cuts(length, B)]
+    n, most, fill = len(datas), max(lengths), 0xA5
+    src_stride = (most + 3 + 15) // 16 * 16 + 16
+    out_stride = int(lib.wc_deflate_bound(most)) + 13
+    held = np.full(16 + n * src_stride, 0x5A, dtype=np.uint8)
+    for i, data in enumerate(datas):
+        held[3 + i * src_stride:3 + i * src_stride + len(data)] = data
+    src = torch.from_numpy(held).cuda()
+    assert src.data_ptr() % 16 == 0
+    base = src.data_ptr() + 3
+    stream = torch.cuda.current_stream().cuda_stream
+
+    def run(row_len):
+        out = torch.full((n, out_stride), fill, dtype=torch.uint8, device="cuda")
+        out_len = torch.full((n,), -7, dtype=torch.int64, device="cuda")
+        crc = torch.full((n,), 0x5A5A5A5A, dtype=torch.int32, device="cuda")
+        d_len = torch.tensor(row_len, dtype=torch.int64, device="cuda")
+        _lib.check(lib.wc_deflate_rows_len_dev(ctx, stream, base, n, d_len.data_ptr(), most, src_stride, out.data_ptr(), out_stride,
+                                               out_len.data_ptr(), crc.data_ptr()))
+        torch.cuda.synchronize()
+        return out.cpu().numpy(), out_len.cpu().numpy(), crc.cpu().numpy().view(np.uint32)
+
+    # the reference: every row alone through the fixed-length entry, from where it lies
+    alone = []
+    for i, data in enumerate(datas):
+        one = torch.full((out_stride,), fill, dtype=torch.uint8, device="cuda")
+        one_len = torch.zeros(1, dtype=torch.int64, device="cuda")
+        one_crc = torch.zeros(1, dtype=torch.int32, device="cuda")
+        _lib.check(lib.wc_deflate_rows_dev(ctx, stream, base + i * src_stride, 1, len(data), len(data), one.data_ptr(), out_stride,
+                                           one_len.data_ptr(), one_crc.data_ptr()))
+        alone.append((one.cpu().numpy(), int(one_len[0]), int(one_crc[0]) & 0xffffffff))
+
+    def check_row(i, out, out_len, crc):
+        data = datas[i].tobytes()
+        want, want_len, want_crc = alone[i]
+        assert int(out_len[i]) == want_len and 0 < want_len <= out_stride, (i, int(out_len[i]), want_len)
+        assert out[i, :want_len].tobytes() == want[:want_len].tobytes(), i
+        assert int(crc[i]) == want_crc == zlib.crc32(data), i
+        assert zlib.decompress(out[i, :want_len].tobytes(), -15) == data, i
+        assert np.all(out[i, want_len:] == fill), i
+
+    row_len = [len(d) for d in datas]
+    got = run(row_len)
+    for i in range(n):
+        check_row(i, *got)
+    stored = [i for i in range(n) if i % 3 == 1 and len(datas[i]) >= 64]
+    assert all(got[1][i] >= len(datas[i]) for i in stored)                 # noise takes the stored fallback
+    bad = {13: -1, 22: most + 1}
+    got = run([bad.get(i, v) for i, v in enumerate(row_len)])
+    for i in range(n):
+        if i in bad:
+            assert int(got[1][i]) == -1 and np.all(got[0][i] == fill), i
+        else:
+            check_row(i, *got)

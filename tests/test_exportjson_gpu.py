@@ -8,6 +8,7 @@ import gzip
 import json
 import os
 import sys
+import zlib
 
 import numpy as np
 import pytest
@@ -300,9 +301,34 @@ def test_exportjson_command_line_gz(tmp_path, capsys, strict):
             _read_back(data, path)
 
 
+def test_gz_members_are_the_fixed_length_encoders_bytes(wt):
+    """Each of the two GPU members of a -gz file is gzipAssemble(deflateRows(member input)), the member's input deflated
+    on its own as one row of its own length (wc_deflate_rows_dev): the call that takes all rows with their lengths on
+    the device writes the bytes the row-by-row calls wrote."""
+    import torch
+    results = [json_cases.synthetic_result(70 + i) for i in range(3)]
+    files = wt.export_json_batch(results, gz=True)
+    for res, blob in zip(results, files):
+        whole = jr.file_text(res)
+        z_at, r_at = whole.index(b',"results_z":'), whole.index(b',"results_r":')
+        assert gzip.decompress(blob) == whole
+        rest = blob
+        for k, want in enumerate((whole[:z_at], whole[z_at:r_at], whole[r_at:])):
+            d = zlib.decompressobj(31)
+            assert d.decompress(rest) == want and d.eof
+            member, rest = rest[:len(rest) - len(d.unused_data)], d.unused_data
+            if k == 0:
+                continue                    # (the host's part, through zlib)
+            row = torch.from_numpy(np.frombuffer(want, dtype=np.uint8).copy()).cuda()[None, :]
+            streams, lengths, crcs = wt.deflateRows(row)
+            stream = streams[0, :int(lengths[0])].cpu().numpy()
+            assert member == wt.gzipAssemble(stream, int(crcs[0].item()) & 0xffffffff, len(want)), k
+        assert not rest
+
+
 def test_a_batch_larger_than_one_call_comes_out_whole(wt):
     """export_json_batch splits at max_rows rows per GPU call (65 535, what wc_json_rows_dev accepts; here 4).  The
-    deflate stage is called row by row, the rows differing in length, so none of its limits can bind."""
+    deflate stage takes the rows of a GPU call in one call, their lengths read on the device, so it is split with them."""
     results = [json_cases.synthetic_result(60 + i) for i in range(5)]
     for gz in (False, True):
         files = wt.export_json_batch(results, gz=gz, max_rows=4)

@@ -11,8 +11,8 @@ Per shape, after one warm-up call each, `--repeats` (5) times:
   wisetools.export_tracks_batch plain and gz, each without and with nozero (host arrays in, the files' bytes out; its
   stages between device events: copy in, text, BGZF, copy out) followed by the write of the files by the I/O thread
   pool: files per second end to end
-  wisetools.export_json_batch with gz: its deflate stage, which calls the deflate entry once per row -- the calling
-  pattern wc_bgzf_rows_dev exists to replace -- beside the BGZF stage above, per batch
+  wisetools.export_json_batch with gz: its deflate stage, the same encoder in its raw framing (one call per GPU call,
+  the lengths read on the device), beside the BGZF stage above, per batch
 then the .bedgraph.gz size beside zlib level 6 of the same text cut into BGZF blocks of 65 280 bytes on the host (first
 sample), and the baseline: tracks_restated.track_text of the z and r rows of `--baseline-files` (8) of the same files on
 one core, as files per second.  No figure is asserted anywhere; the baseline is the restatement, never the code under test."""
@@ -107,7 +107,7 @@ def main():
                             packed = files[0][0]
                         if not gz and not nozero:
                             plain = files[0][0]
-            # exportjson -gz's deflate stage on the same files: one call of the deflate entry per row
+            # exportjson -gz's deflate stage on the same files: the raw framing of the same encoder
             json_stages = []
             for _ in range(args.repeats):
                 details = {}
@@ -132,7 +132,7 @@ def main():
               "note": "end to end = wisetools.export_tracks_batch from host arrays to the files' bytes (two tracks and the calls per "
                       "file) plus the write of the files; reading the result files is not in it.  rows_stage_milliseconds is "
                       "wc_bedgraph_rows on the batch's z rows alone.  bgzf (exporttracks, one call per GPU call for all rows) and "
-                      "deflate (exportjson -gz, one call per row) are the two stages the same session puts side by side; their "
+                      "deflate (exportjson -gz, the raw framing, one call too) are the two stages the same session puts side by side; their "
                       "inputs differ: bedGraph text of merged runs against JSON text of every value.  The baseline ran in this "
                       "session on the first files of the same cohort.  Figures of different sessions do not compare"}
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)

@@ -59,6 +59,7 @@ SIGNATURES = {
     "wc_deflate_block_bytes": (_i32, []),
     "wc_deflate_bound": (_i64, [_i64]),
     "wc_deflate_rows_dev": (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp]),
+    "wc_deflate_rows_len_dev": (_i32, [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _vp, _vp]),
     "wc_deflate_rows": (_i32, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp]),
     "wc_huffman_lengths": (_i32, [_vp, _i32, _i32, _vp]),
     "wc_plot_layout": (_i32, [_i32, _i32, _i32, _i32, _i32, _vp]),

@@ -1,15 +1,16 @@
-// Raw deflate streams and CRC-32 of many equally long rows on the GPU: the output side of `testbatch` (-encoder gpu).
+// Deflate and CRC-32 of many rows on the GPU, equally long or of lengths read on the device, in one of two framings
+// (DESIGN.md 6c).  RAW: a row is one raw deflate stream (`testbatch -encoder gpu`, the page exports, `exportjson -gz`).
+// BGZF: every block of a row is a deflate stream of its own inside a BGZF block (header with its size, CRC-32, ISIZE), and
+// the end-of-file block stands behind the row's last (`exporttracks -gz`).
 //
-//   k_df_encode    one workgroup per (row, block of DF_B input bytes): run-length tokens, the block's own Huffman code
-//                  (dynamic header) or a stored block, byte-aligned, into the block's slot of a scratch image; the
-//                  block's share of the row's CRC-32
-//   k_df_gather    the blocks' bytes to their place in the row's stream (prefix sum of the block lengths), the row's
-//                  length and CRC-32
-//   k_bgzf_encode  k_df_encode's block coder on rows of unequal lengths, which it reads on the device: every block a
-//   k_bgzf_gather  deflate stream of its own, framed as a BGZF block (header with its size, CRC-32, ISIZE), and the
-//                  end-of-file block behind the row's last (`exporttracks -gz`)
-//   k_df_assemble  the .npy members results_r / results_z of a batch from their framing (a template with gaps) and the
-//                  float64 rows on the device
+//   k_df_encode<BGZF, LEN>  one workgroup per (row, block of DF_B input bytes), the grid sized by the longest row (LEN: the
+//                           rows' lengths are read on the device): run-length tokens, the block's own Huffman code
+//                           (dynamic header) or a stored block, byte-aligned, into the block's slot of a scratch
+//                           image; the block's CRC-32 share (RAW: moved to the row's end)
+//   k_df_gather<BGZF>       the blocks' bytes to their place in the row (prefix sum of the block lengths) with what
+//                           the framing puts around them; the row's length, and with RAW its CRC-32
+//   k_df_assemble           the .npy members results_r / results_z of a batch from their framing (a template with
+//                           gaps) and the float64 rows on the device
 //
 // The strategy is zlib's Z_RLE at level 1: a run of equal bytes is one literal and distance-1 matches, nothing else is
 // searched.  Every position decides its own token from the run it lies in, so a block is coded by 256 lanes at once;
@@ -360,44 +361,39 @@ __device__ __forceinline__ void df_encode_block(DfLds &S, const uint8_t *__restr
     }
 }
 
-__global__ void __launch_bounds__(DF_T) k_df_encode(const uint8_t *__restrict__ src, long long row_bytes, long long src_stride,
-                                                    int n_blk, uint8_t *__restrict__ scratch, int *__restrict__ blk_len,
-                                                    uint32_t *__restrict__ blk_crc) {
-    __shared__ DfLds S;
-    const long long id = blockIdx.x;
-    const long long row = id / n_blk;
-    const int b = (int)(id - row * n_blk);
-    const long long start = (long long)b * DF_B;
-    const int n = (int)(row_bytes - start < DF_B ? row_bytes - start : DF_B);      // 0 only in an empty row
-    df_encode_block(S, src + row * src_stride + start, n, b == n_blk - 1, row_bytes - start - n, scratch + id * DF_CAP, &blk_len[id],
-                    &blk_crc[id]);
-}
-
 // BGZF (the SAM specification, section 4.1): every block of a row is a gzip member of its own with the extra field BC
 // that holds the member's size, and the 28-byte empty member ends the file.
 const int BZ_HEAD = 18, BZ_TAIL = 8, BZ_EOF = 28;
 __constant__ uint8_t bz_eof[BZ_EOF] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 
-// blocks of a row of `len` bytes, read on the device: none for an empty row; -1 for a length outside 0 .. max_row_bytes
-__device__ __forceinline__ long long bz_blocks(long long len, long long max_row_bytes) {
-    return len < 0 || len > max_row_bytes ? -1 : (len + DF_B - 1) / DF_B;
+// blocks of a row of `len` bytes: an empty row is one empty final block of a raw stream and no BGZF block at all; -1 for
+// a length outside 0 .. max_row_bytes
+template <bool BGZF> __device__ __forceinline__ long long df_blocks(long long len, long long max_row_bytes) {
+    if (len < 0 || len > max_row_bytes) return -1;
+    return !BGZF && len == 0 ? 1 : (len + DF_B - 1) / DF_B;
 }
 
-// Workgroup (row, b) of a grid sized by the longest row: block b of the row's first row_len[row] bytes as a deflate stream
-// of its own (the final bit set) with the block's own CRC-32 share; blocks behind the row's end do nothing.
-__global__ void __launch_bounds__(DF_T) k_bgzf_encode(const uint8_t *__restrict__ src, const long long *__restrict__ row_len,
-                                                      long long max_row_bytes, long long src_stride, int n_blk,
-                                                      uint8_t *__restrict__ scratch, int *__restrict__ blk_len,
-                                                      uint32_t *__restrict__ blk_crc) {
+// Workgroup (row, b) of a grid of n_blk blocks per row, enough for max_row_bytes: block b of the row's bytes.  LEN: the
+// row has row_len[row] bytes and blocks behind its end do nothing; otherwise every row has max_row_bytes and fills the
+// grid.  RAW: the deflate stream ends with the row's last block, and the CRC-32 shares are moved to the row's end.
+// BGZF: every block is a stream of its own.  (LEN is a template parameter because the fixed-length kernel, 50 KB of
+// code, ran 1 % slower with the length's source chosen at run time: EXPERIMENTS.md.)
+template <bool BGZF, bool LEN>
+__global__ void __launch_bounds__(DF_T) k_df_encode(const uint8_t *__restrict__ src, const long long *__restrict__ row_len,
+                                                    long long max_row_bytes, long long src_stride, int n_blk,
+                                                    uint8_t *__restrict__ scratch, int *__restrict__ blk_len,
+                                                    uint32_t *__restrict__ blk_crc) {
     __shared__ DfLds S;
     const long long id = blockIdx.x;
     const long long row = id / n_blk;
     const int b = (int)(id - row * n_blk);
-    const long long len = row_len[row];
-    if (b >= bz_blocks(len, max_row_bytes)) return;             // (the same in every lane)
+    const long long len = LEN ? row_len[row] : max_row_bytes;
+    const int nb = LEN ? (int)df_blocks<BGZF>(len, max_row_bytes) : n_blk;  // (at most n_blk)
+    if (LEN && b >= nb) return;                                // (the same in every lane)
     const long long start = (long long)b * DF_B;
-    const int n = (int)(len - start < DF_B ? len - start : DF_B);
-    df_encode_block(S, src + row * src_stride + start, n, true, 0, scratch + id * DF_CAP, &blk_len[id], &blk_crc[id]);
+    const int n = (int)(len - start < DF_B ? len - start : DF_B);                   // 0 only in an empty row
+    df_encode_block(S, src + row * src_stride + start, n, BGZF || b == nb - 1, BGZF ? 0 : len - start - n, scratch + id * DF_CAP,
+                    &blk_len[id], &blk_crc[id]);
 }
 
 // len bytes of a scratch slot to `to`.  The destination is arbitrary to the byte, the slot is 16-byte aligned: whole
@@ -419,56 +415,23 @@ __device__ __forceinline__ void df_copy_block(const uint8_t *__restrict__ from, 
     if (t < len - done) to[done + t] = from[done + t];
 }
 
-// Block (row, b): its bytes from the scratch slot to out + row * out_stride + (the lengths of the row's blocks before it);
-// the row's last block also leaves the row's length and CRC-32.
+// Block (row, b): its bytes from the scratch slot to their place in the row at out + row * out_stride, the sum of what the
+// row's blocks before it take.  RAW: the streams alone, and the row's last block leaves the row's length and CRC-32.
+// BGZF: BZ_HEAD + the stream + BZ_TAIL per block, and the row's last block (block 0 of an empty row, which has none) also
+// leaves the end-of-file block and the row's length.  out_len[row] = -1 and nothing else for a length out of range.
+template <bool BGZF>
 __global__ void __launch_bounds__(DF_T) k_df_gather(const uint8_t *__restrict__ scratch, const int *__restrict__ blk_len,
-                                                    const uint32_t *__restrict__ blk_crc, int n_blk, long long row_bytes,
-                                                    uint8_t *__restrict__ out, long long out_stride, long long *__restrict__ out_len,
-                                                    uint32_t *__restrict__ crc_out) {
+                                                    const uint32_t *__restrict__ blk_crc, const long long *__restrict__ row_len,
+                                                    long long max_row_bytes, int n_blk, uint8_t *__restrict__ out, long long out_stride,
+                                                    long long *__restrict__ out_len, uint32_t *__restrict__ crc_out) {
     __shared__ long long s_off[4];
     __shared__ uint32_t s_crc[4];
     const int t = threadIdx.x;
     const long long id = blockIdx.x;
     const long long row = id / n_blk;
     const int b = (int)(id - row * n_blk);
-    long long off = 0;
-    uint32_t x = 0;
-    for (int k = t; k <= b; k += DF_T) {
-        if (k < b) off += blk_len[row * n_blk + k];
-        x ^= blk_crc[row * n_blk + k];
-    }
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        off += __shfl_xor(off, d);
-        x ^= (uint32_t)__shfl_xor((int)x, d);
-    }
-    if ((t & 63) == 0) { s_off[t >> 6] = off; s_crc[t >> 6] = x; }
-    wc_sync();
-    off = s_off[0] + s_off[1] + s_off[2] + s_off[3];
-    x = s_crc[0] ^ s_crc[1] ^ s_crc[2] ^ s_crc[3];
-    const int len = blk_len[id];
-    if (b == n_blk - 1 && t == 0) {
-        out_len[row] = off + len;
-        // the registers above started at zero; zlib's starts at all ones and is inverted at the end
-        crc_out[row] = x ^ df_mulmod(df_xpow8((uint64_t)row_bytes), 0xFFFFFFFFu) ^ 0xFFFFFFFFu;
-    }
-    df_copy_block(scratch + id * DF_CAP, out + row * out_stride + off, len, t);
-}
-
-// A BGZF block's place is the sum of the sizes of the row's blocks before it, each BZ_HEAD + its stream + BZ_TAIL; the
-// row's last block (block 0 of an empty row, which has none) also leaves the end-of-file block and the row's length.
-// out_len[row] = -1 and nothing else for a row_len[row] outside 0 .. max_row_bytes.
-__global__ void __launch_bounds__(DF_T) k_bgzf_gather(const uint8_t *__restrict__ scratch, const int *__restrict__ blk_len,
-                                                      const uint32_t *__restrict__ blk_crc, const long long *__restrict__ row_len,
-                                                      long long max_row_bytes, int n_blk, uint8_t *__restrict__ out,
-                                                      long long out_stride, long long *__restrict__ out_len) {
-    __shared__ long long s_off[4];
-    const int t = threadIdx.x;
-    const long long id = blockIdx.x;
-    const long long row = id / n_blk;
-    const int b = (int)(id - row * n_blk);
-    const long long rlen = row_len[row];
-    const long long nb = bz_blocks(rlen, max_row_bytes);
+    const long long rlen = row_len ? row_len[row] : max_row_bytes;
+    const long long nb = df_blocks<BGZF>(rlen, max_row_bytes);
     uint8_t *base = out + row * out_stride;
     if (nb <= 0) {
         if (b == 0 && nb == 0 && t < BZ_EOF) base[t] = bz_eof[t];
@@ -476,30 +439,48 @@ __global__ void __launch_bounds__(DF_T) k_bgzf_gather(const uint8_t *__restrict_
         return;
     }
     if (b >= nb) return;
+    const int around = BGZF ? BZ_HEAD + BZ_TAIL : 0;
     long long off = 0;
-    for (int k = t; k < b; k += DF_T) off += blk_len[row * n_blk + k] + BZ_HEAD + BZ_TAIL;
+    uint32_t x = 0;
+    for (int k = t; k <= b; k += DF_T) {
+        if (k < b) off += blk_len[row * n_blk + k] + around;
+        if (!BGZF) x ^= blk_crc[row * n_blk + k];
+    }
 #pragma unroll
-    for (int d = 1; d < 64; d <<= 1) off += __shfl_xor(off, d);
-    if ((t & 63) == 0) s_off[t >> 6] = off;
+    for (int d = 1; d < 64; d <<= 1) {
+        off += __shfl_xor(off, d);
+        if (!BGZF) x ^= (uint32_t)__shfl_xor((int)x, d);
+    }
+    if ((t & 63) == 0) {
+        s_off[t >> 6] = off;
+        if (!BGZF) s_crc[t >> 6] = x;
+    }
     wc_sync();
     off = s_off[0] + s_off[1] + s_off[2] + s_off[3];
     const int len = blk_len[id];
-    const long long start = (long long)b * DF_B;
-    const uint32_t n = (uint32_t)(rlen - start < DF_B ? rlen - start : DF_B);
+    const bool last = b == nb - 1;
     uint8_t *to = base + off;
-    if (t < BZ_HEAD) {
-        const uint32_t bsize = (uint32_t)(BZ_HEAD + len + BZ_TAIL - 1);
-        to[t] = t < 16 ? bz_eof[t] : (uint8_t)(bsize >> (8 * (t - 16)));
-    } else if (t < BZ_HEAD + BZ_TAIL) {
-        // the register of the block's share started at zero; zlib's starts at all ones and is inverted at the end
-        const uint32_t crc = blk_crc[id] ^ df_mulmod(df_xpow8((uint64_t)n), 0xFFFFFFFFu) ^ 0xFFFFFFFFu;
-        const int k = t - BZ_HEAD;
-        to[BZ_HEAD + len + k] = (uint8_t)((k < 4 ? crc : n) >> (8 * (k & 3)));
-    } else if (b == nb - 1 && t >= 64 && t < 64 + BZ_EOF) {
-        to[BZ_HEAD + len + BZ_TAIL + (t - 64)] = bz_eof[t - 64];
+    // the CRC registers started at zero; zlib's starts at all ones and is inverted at the end
+    if (BGZF) {
+        const long long start = (long long)b * DF_B;
+        const uint32_t n = (uint32_t)(rlen - start < DF_B ? rlen - start : DF_B);
+        if (t < BZ_HEAD) {
+            const uint32_t bsize = (uint32_t)(BZ_HEAD + len + BZ_TAIL - 1);
+            to[t] = t < 16 ? bz_eof[t] : (uint8_t)(bsize >> (8 * (t - 16)));
+        } else if (t < BZ_HEAD + BZ_TAIL) {
+            const uint32_t crc = blk_crc[id] ^ df_mulmod(df_xpow8((uint64_t)n), 0xFFFFFFFFu) ^ 0xFFFFFFFFu;
+            const int k = t - BZ_HEAD;
+            to[BZ_HEAD + len + k] = (uint8_t)((k < 4 ? crc : n) >> (8 * (k & 3)));
+        } else if (last && t >= 64 && t < 64 + BZ_EOF) {
+            to[BZ_HEAD + len + BZ_TAIL + (t - 64)] = bz_eof[t - 64];
+        }
+        to += BZ_HEAD;
+    } else if (last && t == 0) {
+        x = s_crc[0] ^ s_crc[1] ^ s_crc[2] ^ s_crc[3];
+        crc_out[row] = x ^ df_mulmod(df_xpow8((uint64_t)rlen), 0xFFFFFFFFu) ^ 0xFFFFFFFFu;
     }
-    if (b == nb - 1 && t == 0) out_len[row] = off + BZ_HEAD + len + BZ_TAIL + BZ_EOF;
-    df_copy_block(scratch + id * DF_CAP, to + BZ_HEAD, len, t);
+    if (last && t == 0) out_len[row] = off + len + (BGZF ? around + BZ_EOF : 0);
+    df_copy_block(scratch + id * DF_CAP, to, len, t);
 }
 
 // image[row, p] = the member's byte p: the template's, or inside gap c byte p - dst[c] of the doubles
@@ -535,7 +516,83 @@ __global__ void __launch_bounds__(256) k_df_assemble(const uint8_t *__restrict__
     reinterpret_cast<uint32_t *>(image + row * image_stride)[w] = word;
 }
 
-int64_t blocks_of(int64_t row_bytes) { return row_bytes <= 0 ? 1 : (row_bytes + DF_B - 1) / DF_B; }
+// ---- the host's half: one check, one enqueue and one staging wrapper for both framings --------------------------------
+struct DfFrame {
+    bool bgzf;
+    const char *name, *bound_name;      // the words of the messages
+    int64_t (*bound)(int64_t);
+    int64_t least;                      // bytes of the shortest row there is: a final block, the end-of-file block
+};
+const DfFrame DF_RAW = {false, "deflate", "wc_deflate_bound", wc_deflate_bound, 1};
+const DfFrame DF_BGZF = {true, "bgzf", "wc_bgzf_bound", wc_bgzf_bound, BZ_EOF};
+
+// row_len (may be NULL: every row has row_bytes bytes) is not looked into: it may be a device array
+int df_check(const wc_ctx *ctx, const DfFrame &f, const unsigned char *src, int64_t n_rows, const int64_t *row_len, int64_t row_bytes,
+             int64_t src_stride, const unsigned char *out, int64_t out_stride, const int64_t *out_len, const uint32_t *crc) {
+    WC_CHECK(ctx && n_rows >= 0 && row_bytes >= 0 && src_stride >= row_bytes && (src || n_rows == 0 || row_bytes == 0) &&
+                 (n_rows == 0 || (out && out_len && (f.bgzf ? row_len != nullptr : crc != nullptr))),
+             WC_E_ARG, "%s: unusable argument", f.name);
+    WC_CHECK(out_stride >= f.bound(row_bytes), WC_E_ARG, "%s: %lld bytes per output row, %s(%lld) is %lld", f.name, (long long)out_stride,
+             f.bound_name, (long long)row_bytes, (long long)f.bound(row_bytes));
+    return WC_OK;
+}
+
+// the two kernels, enqueued (DEVICE pointers): rows of row_len[i] <= row_bytes bytes, or without row_len of row_bytes
+int df_enqueue(wc_ctx *ctx, hipStream_t stream, const DfFrame &f, const unsigned char *src, int64_t n_rows, const int64_t *row_len,
+               int64_t row_bytes, int64_t src_stride, unsigned char *out, int64_t out_stride, int64_t *out_len, uint32_t *crc) {
+    int rc;
+    if ((rc = df_check(ctx, f, src, n_rows, row_len, row_bytes, src_stride, out, out_stride, out_len, crc))) return rc;
+    if (n_rows == 0) return WC_OK;
+    const int64_t n_blk = row_bytes <= 0 ? 1 : (row_bytes + DF_B - 1) / DF_B;
+    WC_CHECK(n_blk <= INT_MAX / 2 && n_rows <= (int64_t)INT_MAX / n_blk, WC_E_LIMIT, "%s: %lld rows of %s%lld blocks in one call", f.name,
+             (long long)n_rows, row_len ? "up to " : "", (long long)n_blk);
+    const int64_t total = n_rows * n_blk;
+    WC_HIP(hipSetDevice(ctx->device));
+    if ((rc = ctx->df_scratch.reserve((size_t)total * DF_CAP)) || (rc = ctx->df_meta.reserve((size_t)total * 8))) return rc;
+    int *blk_len = ctx->df_meta.as<int>();
+    uint32_t *blk_crc = ctx->df_meta.as<uint32_t>() + total;
+    const auto encode = !row_len ? k_df_encode<false, false> : f.bgzf ? k_df_encode<true, true> : k_df_encode<false, true>;
+    hipLaunchKernelGGL(encode, dim3((unsigned)total), dim3(DF_T), 0, stream, (const uint8_t *)src, (const long long *)row_len,
+                       (long long)row_bytes, (long long)src_stride, (int)n_blk, ctx->df_scratch.as<uint8_t>(), blk_len, blk_crc);
+    WC_HIP(hipGetLastError());
+    hipLaunchKernelGGL(f.bgzf ? k_df_gather<true> : k_df_gather<false>, dim3((unsigned)total), dim3(DF_T), 0, stream,
+                       (const uint8_t *)ctx->df_scratch.as<uint8_t>(), (const int *)blk_len, (const uint32_t *)blk_crc,
+                       (const long long *)row_len, (long long)row_bytes, (int)n_blk, (uint8_t *)out, (long long)out_stride,
+                       (long long *)out_len, crc);
+    WC_HIP(hipGetLastError());
+    return WC_OK;
+}
+
+// the same from HOST pointers, synchronising; crc may be NULL where the framing has none
+int df_stage(wc_ctx *ctx, const DfFrame &f, const unsigned char *src, int64_t n_rows, const int64_t *row_len, int64_t row_bytes,
+             int64_t src_stride, unsigned char *out, int64_t out_stride, int64_t *out_len, uint32_t *crc) {
+    int rc;
+    if ((rc = df_check(ctx, f, src, n_rows, row_len, row_bytes, src_stride, out, out_stride, out_len, crc))) return rc;
+    for (int64_t i = 0; row_len && i < n_rows; ++i)
+        WC_CHECK(row_len[i] >= 0 && row_len[i] <= row_bytes, WC_E_ARG, "%s: row %lld has %lld bytes, max_row_bytes is %lld", f.name,
+                 (long long)i, (long long)row_len[i], (long long)row_bytes);
+    if (n_rows == 0) return WC_OK;
+    WC_HIP(hipSetDevice(ctx->device));
+    const size_t in_bytes = (size_t)((n_rows - 1) * src_stride + (row_len ? row_len[n_rows - 1] : row_bytes));
+    if ((rc = ctx->tmp_a.reserve(in_bytes + 4)) || (rc = ctx->tmp_b.reserve((size_t)(n_rows * out_stride))) ||
+        (rc = ctx->tmp_c.reserve((size_t)n_rows * 8)) || (rc = ctx->tmp_d.reserve((size_t)n_rows * 12)))
+        return rc;
+    int64_t *d_len = ctx->tmp_d.as<int64_t>();
+    uint32_t *d_crc = reinterpret_cast<uint32_t *>(d_len + n_rows);
+    if (in_bytes) WC_HIP(hipMemcpy(ctx->tmp_a.p, src, in_bytes, hipMemcpyHostToDevice));
+    if (row_len) WC_HIP(hipMemcpy(d_len, row_len, (size_t)n_rows * 8, hipMemcpyHostToDevice));
+    if ((rc = df_enqueue(ctx, nullptr, f, ctx->tmp_a.as<unsigned char>(), n_rows, row_len ? d_len : nullptr, row_bytes, src_stride,
+                         ctx->tmp_b.as<unsigned char>(), out_stride, ctx->tmp_c.as<int64_t>(), d_crc)))
+        return rc;
+    WC_HIP(hipMemcpy(out_len, ctx->tmp_c.p, (size_t)n_rows * 8, hipMemcpyDeviceToHost));
+    if (crc) WC_HIP(hipMemcpy(crc, d_crc, (size_t)n_rows * 4, hipMemcpyDeviceToHost));
+    // only the rows' own bytes: what lies behind them is whatever the staging buffer held
+    for (int64_t i = 0; i < n_rows; ++i) {
+        WC_CHECK(out_len[i] >= f.least && out_len[i] <= out_stride, WC_E_INTERNAL, "%s: a row of %lld bytes", f.name, (long long)out_len[i]);
+        WC_HIP(hipMemcpy(out + i * out_stride, ctx->tmp_b.as<unsigned char>() + i * out_stride, (size_t)out_len[i], hipMemcpyDeviceToHost));
+    }
+    return WC_OK;
+}
 
 }  // namespace
 
@@ -559,60 +616,21 @@ int wc_huffman_lengths(const uint32_t *freq, int n, int limit, uint8_t *len_out)
     return WC_OK;
 }
 
-int wc_deflate_rows_dev(wc_ctx *ctx, void *stream_, const unsigned char *src, int64_t n_rows, int64_t row_bytes,
-                        int64_t src_stride, unsigned char *out, int64_t out_stride, int64_t *out_len, uint32_t *crc) {
-    WC_CHECK(ctx && n_rows >= 0 && row_bytes >= 0 && src_stride >= row_bytes && (src || n_rows == 0 || row_bytes == 0) &&
-                 (n_rows == 0 || (out && out_len && crc)),
-             WC_E_ARG, "deflate: unusable argument");
-    WC_CHECK(out_stride >= wc_deflate_bound(row_bytes), WC_E_ARG, "deflate: %lld bytes per output row, wc_deflate_bound(%lld) is %lld",
-             (long long)out_stride, (long long)row_bytes, (long long)wc_deflate_bound(row_bytes));
-    if (n_rows == 0) return WC_OK;
-    const int64_t n_blk = blocks_of(row_bytes);
-    WC_CHECK(n_blk <= INT_MAX / 2 && n_rows <= (int64_t)INT_MAX / n_blk, WC_E_LIMIT, "deflate: %lld rows of %lld blocks in one call",
-             (long long)n_rows, (long long)n_blk);
-    const int64_t total = n_rows * n_blk;
-    WC_HIP(hipSetDevice(ctx->device));
-    hipStream_t stream = (hipStream_t)stream_;
-    int rc;
-    if ((rc = ctx->df_scratch.reserve((size_t)total * DF_CAP)) || (rc = ctx->df_meta.reserve((size_t)total * 8))) return rc;
-    int *blk_len = ctx->df_meta.as<int>();
-    uint32_t *blk_crc = ctx->df_meta.as<uint32_t>() + total;
-    hipLaunchKernelGGL(k_df_encode, dim3((unsigned)total), dim3(DF_T), 0, stream, (const uint8_t *)src, (long long)row_bytes,
-                       (long long)src_stride, (int)n_blk, ctx->df_scratch.as<uint8_t>(), blk_len, blk_crc);
-    WC_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_df_gather, dim3((unsigned)total), dim3(DF_T), 0, stream, (const uint8_t *)ctx->df_scratch.as<uint8_t>(),
-                       (const int *)blk_len, (const uint32_t *)blk_crc, (int)n_blk, (long long)row_bytes, (uint8_t *)out,
-                       (long long)out_stride, (long long *)out_len, crc);
-    WC_HIP(hipGetLastError());
-    return WC_OK;
+int wc_deflate_rows_dev(wc_ctx *ctx, void *stream, const unsigned char *src, int64_t n_rows, int64_t row_bytes, int64_t src_stride,
+                        unsigned char *out, int64_t out_stride, int64_t *out_len, uint32_t *crc) {
+    return df_enqueue(ctx, (hipStream_t)stream, DF_RAW, src, n_rows, nullptr, row_bytes, src_stride, out, out_stride, out_len, crc);
 }
 
-int wc_deflate_rows(wc_ctx *ctx, const unsigned char *src, int64_t n_rows, int64_t row_bytes, int64_t src_stride,
-                    unsigned char *out, int64_t out_stride, int64_t *out_len, uint32_t *crc) {
-    WC_CHECK(ctx && n_rows >= 0 && row_bytes >= 0 && src_stride >= row_bytes && (src || n_rows == 0 || row_bytes == 0) &&
-                 (n_rows == 0 || (out && out_len && crc)),
-             WC_E_ARG, "deflate: unusable argument");
-    WC_CHECK(out_stride >= wc_deflate_bound(row_bytes), WC_E_ARG, "deflate: %lld bytes per output row, wc_deflate_bound(%lld) is %lld",
-             (long long)out_stride, (long long)row_bytes, (long long)wc_deflate_bound(row_bytes));
-    if (n_rows == 0) return WC_OK;
-    WC_HIP(hipSetDevice(ctx->device));
-    const size_t in_bytes = (size_t)((n_rows - 1) * src_stride + row_bytes), out_bytes = (size_t)(n_rows * out_stride);
-    int rc;
-    if ((rc = ctx->tmp_a.reserve(in_bytes + 4)) || (rc = ctx->tmp_b.reserve(out_bytes)) || (rc = ctx->tmp_c.reserve((size_t)n_rows * 8)) ||
-        (rc = ctx->tmp_d.reserve((size_t)n_rows * 4)))
-        return rc;
-    if (in_bytes) WC_HIP(hipMemcpy(ctx->tmp_a.p, src, in_bytes, hipMemcpyHostToDevice));
-    rc = wc_deflate_rows_dev(ctx, nullptr, ctx->tmp_a.as<unsigned char>(), n_rows, row_bytes, src_stride, ctx->tmp_b.as<unsigned char>(),
-                             out_stride, ctx->tmp_c.as<int64_t>(), ctx->tmp_d.as<uint32_t>());
-    if (rc) return rc;
-    WC_HIP(hipMemcpy(out_len, ctx->tmp_c.p, (size_t)n_rows * 8, hipMemcpyDeviceToHost));
-    WC_HIP(hipMemcpy(crc, ctx->tmp_d.p, (size_t)n_rows * 4, hipMemcpyDeviceToHost));
-    // only the streams: the bytes behind them are whatever the staging buffer held
-    for (int64_t i = 0; i < n_rows; ++i)
-        if (out_len[i] > 0)
-            WC_HIP(hipMemcpy(out + i * out_stride, ctx->tmp_b.as<unsigned char>() + i * out_stride, (size_t)out_len[i],
-                             hipMemcpyDeviceToHost));
-    return WC_OK;
+int wc_deflate_rows_len_dev(wc_ctx *ctx, void *stream, const unsigned char *src, int64_t n_rows, const int64_t *row_len,
+                            int64_t max_row_bytes, int64_t src_stride, unsigned char *out, int64_t out_stride, int64_t *out_len,
+                            uint32_t *crc) {
+    WC_CHECK(row_len || n_rows <= 0, WC_E_ARG, "deflate: unusable argument");
+    return df_enqueue(ctx, (hipStream_t)stream, DF_RAW, src, n_rows, row_len, max_row_bytes, src_stride, out, out_stride, out_len, crc);
+}
+
+int wc_deflate_rows(wc_ctx *ctx, const unsigned char *src, int64_t n_rows, int64_t row_bytes, int64_t src_stride, unsigned char *out,
+                    int64_t out_stride, int64_t *out_len, uint32_t *crc) {
+    return df_stage(ctx, DF_RAW, src, n_rows, nullptr, row_bytes, src_stride, out, out_stride, out_len, crc);
 }
 
 int64_t wc_bgzf_bound(int64_t row_bytes) {
@@ -620,63 +638,14 @@ int64_t wc_bgzf_bound(int64_t row_bytes) {
     return row_bytes + (BZ_HEAD + 5 + BZ_TAIL) * ((row_bytes + DF_B - 1) / DF_B) + BZ_EOF;
 }
 
-int wc_bgzf_rows_dev(wc_ctx *ctx, void *stream_, const unsigned char *src, int64_t n_rows, const int64_t *row_len, int64_t max_row_bytes,
+int wc_bgzf_rows_dev(wc_ctx *ctx, void *stream, const unsigned char *src, int64_t n_rows, const int64_t *row_len, int64_t max_row_bytes,
                      int64_t src_stride, unsigned char *out, int64_t out_stride, int64_t *out_len) {
-    WC_CHECK(ctx && n_rows >= 0 && max_row_bytes >= 0 && src_stride >= max_row_bytes && (src || n_rows == 0 || max_row_bytes == 0) &&
-                 (n_rows == 0 || (row_len && out && out_len)),
-             WC_E_ARG, "bgzf: unusable argument");
-    WC_CHECK(out_stride >= wc_bgzf_bound(max_row_bytes), WC_E_ARG, "bgzf: %lld bytes per output row, wc_bgzf_bound(%lld) is %lld",
-             (long long)out_stride, (long long)max_row_bytes, (long long)wc_bgzf_bound(max_row_bytes));
-    if (n_rows == 0) return WC_OK;
-    const int64_t n_blk = blocks_of(max_row_bytes);
-    WC_CHECK(n_blk <= INT_MAX / 2 && n_rows <= (int64_t)INT_MAX / n_blk, WC_E_LIMIT, "bgzf: %lld rows of up to %lld blocks in one call",
-             (long long)n_rows, (long long)n_blk);
-    const int64_t total = n_rows * n_blk;
-    WC_HIP(hipSetDevice(ctx->device));
-    hipStream_t stream = (hipStream_t)stream_;
-    int rc;
-    if ((rc = ctx->df_scratch.reserve((size_t)total * DF_CAP)) || (rc = ctx->df_meta.reserve((size_t)total * 8))) return rc;
-    int *blk_len = ctx->df_meta.as<int>();
-    uint32_t *blk_crc = ctx->df_meta.as<uint32_t>() + total;
-    hipLaunchKernelGGL(k_bgzf_encode, dim3((unsigned)total), dim3(DF_T), 0, stream, (const uint8_t *)src, (const long long *)row_len,
-                       (long long)max_row_bytes, (long long)src_stride, (int)n_blk, ctx->df_scratch.as<uint8_t>(), blk_len, blk_crc);
-    WC_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_bgzf_gather, dim3((unsigned)total), dim3(DF_T), 0, stream, (const uint8_t *)ctx->df_scratch.as<uint8_t>(),
-                       (const int *)blk_len, (const uint32_t *)blk_crc, (const long long *)row_len, (long long)max_row_bytes, (int)n_blk,
-                       (uint8_t *)out, (long long)out_stride, (long long *)out_len);
-    WC_HIP(hipGetLastError());
-    return WC_OK;
+    return df_enqueue(ctx, (hipStream_t)stream, DF_BGZF, src, n_rows, row_len, max_row_bytes, src_stride, out, out_stride, out_len, nullptr);
 }
 
 int wc_bgzf_rows(wc_ctx *ctx, const unsigned char *src, int64_t n_rows, const int64_t *row_len, int64_t max_row_bytes, int64_t src_stride,
                  unsigned char *out, int64_t out_stride, int64_t *out_len) {
-    WC_CHECK(ctx && n_rows >= 0 && max_row_bytes >= 0 && src_stride >= max_row_bytes && (src || n_rows == 0 || max_row_bytes == 0) &&
-                 (n_rows == 0 || (row_len && out && out_len)),
-             WC_E_ARG, "bgzf: unusable argument");
-    WC_CHECK(out_stride >= wc_bgzf_bound(max_row_bytes), WC_E_ARG, "bgzf: %lld bytes per output row, wc_bgzf_bound(%lld) is %lld",
-             (long long)out_stride, (long long)max_row_bytes, (long long)wc_bgzf_bound(max_row_bytes));
-    for (int64_t i = 0; i < n_rows; ++i)
-        WC_CHECK(row_len[i] >= 0 && row_len[i] <= max_row_bytes, WC_E_ARG, "bgzf: row %lld has %lld bytes, max_row_bytes is %lld", (long long)i,
-                 (long long)row_len[i], (long long)max_row_bytes);
-    if (n_rows == 0) return WC_OK;
-    WC_HIP(hipSetDevice(ctx->device));
-    const size_t in_bytes = (size_t)((n_rows - 1) * src_stride + row_len[n_rows - 1]), out_bytes = (size_t)(n_rows * out_stride);
-    int rc;
-    if ((rc = ctx->tmp_a.reserve(in_bytes + 4)) || (rc = ctx->tmp_b.reserve(out_bytes)) || (rc = ctx->tmp_c.reserve((size_t)n_rows * 8)) ||
-        (rc = ctx->tmp_d.reserve((size_t)n_rows * 8)))
-        return rc;
-    if (in_bytes) WC_HIP(hipMemcpy(ctx->tmp_a.p, src, in_bytes, hipMemcpyHostToDevice));
-    WC_HIP(hipMemcpy(ctx->tmp_d.p, row_len, (size_t)n_rows * 8, hipMemcpyHostToDevice));
-    rc = wc_bgzf_rows_dev(ctx, nullptr, ctx->tmp_a.as<unsigned char>(), n_rows, ctx->tmp_d.as<int64_t>(), max_row_bytes, src_stride,
-                          ctx->tmp_b.as<unsigned char>(), out_stride, ctx->tmp_c.as<int64_t>());
-    if (rc) return rc;
-    WC_HIP(hipMemcpy(out_len, ctx->tmp_c.p, (size_t)n_rows * 8, hipMemcpyDeviceToHost));
-    // only the files: the bytes behind them are whatever the staging buffer held
-    for (int64_t i = 0; i < n_rows; ++i) {
-        WC_CHECK(out_len[i] >= BZ_EOF && out_len[i] <= out_stride, WC_E_INTERNAL, "bgzf: a row of %lld bytes", (long long)out_len[i]);
-        WC_HIP(hipMemcpy(out + i * out_stride, ctx->tmp_b.as<unsigned char>() + i * out_stride, (size_t)out_len[i], hipMemcpyDeviceToHost));
-    }
-    return WC_OK;
+    return df_stage(ctx, DF_BGZF, src, n_rows, row_len, max_row_bytes, src_stride, out, out_stride, out_len, nullptr);
 }
 
 int wc_results_members_dev(wc_ctx *ctx, void *stream_, const unsigned char *tmpl, int64_t member_bytes, const int64_t *table,

@@ -16,6 +16,7 @@
 
 #include "ctx.h"
 #include "fmt_double.h"
+#include "text_rows.h"
 #include "tile_text.h"
 
 namespace {
@@ -174,45 +175,21 @@ int64_t bound_of(const JsTab &tab) {
     return 25 * (int64_t)tab.total + 2 * tab.n_chrom + 2 + (empty > 1 ? empty - 1 : 0);
 }
 
-int64_t tiles_of(const JsTab &tab) { return tab.total > 0 ? (tab.total + JS_T - 1) / JS_T : 1; }
-
-int check_rows(const wc_ctx *ctx, const double *rows, int64_t row_stride, int64_t n_rows, const int64_t *chrom_sizes, int n_chrom,
-               const unsigned char *text, int64_t text_stride, const int64_t *text_len, JsTab *tab) {
-    WC_CHECK(ctx && n_rows >= 0, WC_E_ARG, "json: unusable argument (%lld rows)", (long long)n_rows);
-    int rc;
-    if ((rc = make_tab(chrom_sizes, n_chrom, tab))) return rc;
-    WC_CHECK(n_rows <= 65535, WC_E_LIMIT, "json: %lld rows in one call (at most 65535); split the batch", (long long)n_rows);
-    WC_CHECK(row_stride >= tab->total && (rows || tab->total == 0 || n_rows == 0), WC_E_ARG, "json: rows %lld values apart hold %lld values",
-             (long long)row_stride, tab->total);
-    WC_CHECK(n_rows == 0 || (text && text_len), WC_E_ARG, "json: NULL output");
-    WC_CHECK(text_stride >= bound_of(*tab), WC_E_ARG, "json: %lld bytes per text row, wc_json_row_bound is %lld", (long long)text_stride,
-             (long long)bound_of(*tab));
-    return WC_OK;
-}
-
-// the three kernels, enqueued; ev (may be NULL): [0] in front, [1] behind the scan, [2] behind the bytes
-int enqueue_rows(wc_ctx *ctx, hipStream_t stream, const double *rows, int64_t row_stride, int64_t n_rows, const JsTab &tab, int strict,
-                 unsigned char *text, int64_t text_stride, int64_t *text_len, hipEvent_t *ev) {
-    const int64_t n_tiles = tiles_of(tab);
-    int rc;
-    // the slots | the tiles' sums | their offsets
-    const size_t slot_bytes = (size_t)n_rows * (size_t)tab.total * 16, sum_bytes = ((size_t)n_rows * n_tiles * 4 + 15) & ~(size_t)15;
-    if ((rc = ctx->js_slots.reserve(slot_bytes + 16)) || (rc = ctx->js_tiles.reserve(sum_bytes + (size_t)n_rows * n_tiles * 8))) return rc;
-    int *sums = ctx->js_tiles.as<int>();
-    long long *tile_off = reinterpret_cast<long long *>(ctx->js_tiles.as<unsigned char>() + sum_bytes);
-    const dim3 grid((unsigned)n_tiles, (unsigned)n_rows);
-    if (ev) WC_HIP(hipEventRecord(ev[0], stream));
-    hipLaunchKernelGGL(k_js_len, grid, dim3(JS_T), 0, stream, rows, (long long)row_stride, tab, strict, ctx->js_slots.as<uint4>(), sums);
-    WC_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_js_scan, dim3((unsigned)n_rows), dim3(JS_T), 0, stream, (const int *)sums, (long long)n_tiles, tab.head, tile_off,
-                       (long long *)text_len);
-    WC_HIP(hipGetLastError());
-    if (ev) WC_HIP(hipEventRecord(ev[1], stream));
-    hipLaunchKernelGGL(k_js_bytes, grid, dim3(JS_T), 0, stream, (const uint4 *)ctx->js_slots.as<uint4>(), (const long long *)tile_off, tab,
-                       strict, text, (long long)text_stride);
-    WC_HIP(hipGetLastError());
-    if (ev) WC_HIP(hipEventRecord(ev[2], stream));
-    return WC_OK;
+// a call's three launches, as wc::TextRows takes them (text_rows.h)
+auto launches(const JsTab &tab, int strict) {
+    return [&tab, strict](hipStream_t stream, const wc::TextWork &w, const wc::TextRows &call, hipEvent_t mid) -> int {
+        int *sums = static_cast<int *>(w.sums);
+        hipLaunchKernelGGL(k_js_len, w.grid, dim3(JS_T), 0, stream, call.rows, (long long)call.row_stride, tab, strict, w.slots, sums);
+        WC_HIP(hipGetLastError());
+        hipLaunchKernelGGL(k_js_scan, dim3(w.grid.y), dim3(JS_T), 0, stream, (const int *)sums, w.n_tiles, tab.head, w.tile_off,
+                           (long long *)call.counts[0]);
+        WC_HIP(hipGetLastError());
+        if (mid) WC_HIP(hipEventRecord(mid, stream));
+        hipLaunchKernelGGL(k_js_bytes, w.grid, dim3(JS_T), 0, stream, (const uint4 *)w.slots, (const long long *)w.tile_off, tab, strict,
+                           call.text, (long long)call.text_stride);
+        WC_HIP(hipGetLastError());
+        return WC_OK;
+    };
 }
 
 }  // namespace
@@ -255,52 +232,20 @@ int64_t wc_json_row_bound(const int64_t *chrom_sizes, int n_chrom) {
 
 int wc_json_rows_dev(wc_ctx *ctx, void *stream, const double *rows, int64_t row_stride, int64_t n_rows, const int64_t *chrom_sizes_host,
                      int n_chrom, int strict, unsigned char *text, int64_t text_stride, int64_t *text_len) {
+    const wc::TextRows call = {"json", "values", ctx, rows, row_stride, n_rows, text, text_stride, 1, {text_len, nullptr}};
     JsTab tab;
     int rc;
-    if ((rc = check_rows(ctx, rows, row_stride, n_rows, chrom_sizes_host, n_chrom, text, text_stride, text_len, &tab))) return rc;
-    WC_CHECK(text_stride % 16 == 0 && ((uintptr_t)text & 15) == 0, WC_E_ARG,
-             "json: text rows %lld bytes apart (a multiple of 16, from an address that is one)", (long long)text_stride);
-    if (n_rows == 0) return WC_OK;
-    WC_HIP(hipSetDevice(ctx->device));
-    return enqueue_rows(ctx, (hipStream_t)stream, rows, row_stride, n_rows, tab, strict != 0, text, text_stride, text_len, nullptr);
+    if ((rc = call.begin()) || (rc = make_tab(chrom_sizes_host, n_chrom, &tab)) || (rc = call.check(tab.total, bound_of(tab), true))) return rc;
+    return call.enqueue((hipStream_t)stream, tab.total, sizeof(int), nullptr, launches(tab, strict != 0));
 }
 
 int wc_json_rows(wc_ctx *ctx, const double *rows, int64_t row_stride, int64_t n_rows, const int64_t *chrom_sizes, int n_chrom, int strict,
                  unsigned char *text, int64_t text_stride, int64_t *text_len, double *times_ms) {
+    const wc::TextRows call = {"json", "values", ctx, rows, row_stride, n_rows, text, text_stride, 1, {text_len, nullptr}};
     JsTab tab;
     int rc;
-    if ((rc = check_rows(ctx, rows, row_stride, n_rows, chrom_sizes, n_chrom, text, text_stride, text_len, &tab))) return rc;
-    if (times_ms)
-        for (int i = 0; i < 4; ++i) times_ms[i] = 0.0;
-    if (n_rows == 0) return WC_OK;
-    WC_HIP(hipSetDevice(ctx->device));
-    const int64_t dev_stride = (bound_of(tab) + 15) / 16 * 16;
-    const size_t in_bytes = ((size_t)(n_rows - 1) * row_stride + (size_t)tab.total) * 8;
-    if ((rc = ctx->tmp_a.reserve(in_bytes + 16)) || (rc = ctx->tmp_b.reserve((size_t)n_rows * dev_stride)) ||
-        (rc = ctx->tmp_c.reserve((size_t)n_rows * 8)))
-        return rc;
-    wc::Events<5> events;
-    hipEvent_t *ev = events.e;
-    if (times_ms && (rc = events.create())) return rc;
-    if (times_ms) (void)hipEventRecord(ev[3], nullptr);
-    if (in_bytes) WC_HIP(hipMemcpy(ctx->tmp_a.p, rows, in_bytes, hipMemcpyHostToDevice));
-    if ((rc = enqueue_rows(ctx, nullptr, ctx->tmp_a.as<double>(), row_stride, n_rows, tab, strict != 0, ctx->tmp_b.as<unsigned char>(), dev_stride,
-                           ctx->tmp_c.as<int64_t>(), times_ms ? ev : nullptr)))
-        return rc;
-    WC_HIP(hipMemcpy(text_len, ctx->tmp_c.p, (size_t)n_rows * 8, hipMemcpyDeviceToHost));
-    for (int64_t i = 0; i < n_rows; ++i) {
-        WC_CHECK(text_len[i] >= 2 && text_len[i] <= bound_of(tab), WC_E_INTERNAL, "json: a row of %lld bytes, the bound is %lld",
-                 (long long)text_len[i], (long long)bound_of(tab));
-        WC_HIP(hipMemcpy(text + i * text_stride, ctx->tmp_b.as<unsigned char>() + i * dev_stride, (size_t)text_len[i], hipMemcpyDeviceToHost));
-    }
-    if (times_ms) {
-        (void)hipEventRecord(ev[4], nullptr);
-        (void)hipEventSynchronize(ev[4]);
-        // [0] copy in [1] lengths and scan [2] bytes [3] copy out
-        const int from[4] = {3, 0, 1, 2}, to[4] = {0, 1, 2, 4};
-        events.elapsed(4, from, to, times_ms);
-    }
-    return WC_OK;
+    if ((rc = call.begin()) || (rc = make_tab(chrom_sizes, n_chrom, &tab)) || (rc = call.check(tab.total, bound_of(tab), false))) return rc;
+    return call.stage(tab.total, bound_of(tab), 2, sizeof(int), times_ms, launches(tab, strict != 0));
 }
 
 int64_t wc_gzip_bytes(int64_t deflate_len) { return deflate_len < 0 ? -1 : deflate_len + 18; }

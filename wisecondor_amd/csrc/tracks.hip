@@ -20,6 +20,7 @@
 
 #include "ctx.h"
 #include "fmt_double.h"
+#include "text_rows.h"
 #include "tile_text.h"
 
 namespace {
@@ -253,46 +254,21 @@ int64_t bound_of(const BtTab &tab) {
     return bound;
 }
 
-int64_t tiles_of(const BtTab &tab) { return tab.total > 0 ? (tab.total + BT_T - 1) / BT_T : 1; }
-
-int check_rows(const wc_ctx *ctx, const double *rows, int64_t row_stride, int64_t n_rows, const int64_t *chrom_sizes, int n_chrom,
-               int64_t binsize, const int64_t *clip_len, const char *prefix, int prefix_len, int flags, const unsigned char *text,
-               int64_t text_stride, const int64_t *text_len, const int64_t *dropped, BtTab *tab) {
-    WC_CHECK(ctx && n_rows >= 0, WC_E_ARG, "bedgraph: unusable argument (%lld rows)", (long long)n_rows);
-    int rc;
-    if ((rc = make_tab(chrom_sizes, n_chrom, binsize, clip_len, prefix, prefix_len, flags, tab))) return rc;
-    WC_CHECK(n_rows <= 65535, WC_E_LIMIT, "bedgraph: %lld rows in one call (at most 65535); split the batch", (long long)n_rows);
-    WC_CHECK(row_stride >= tab->total && (rows || tab->total == 0 || n_rows == 0), WC_E_ARG, "bedgraph: rows %lld values apart hold %lld bins",
-             (long long)row_stride, tab->total);
-    WC_CHECK(n_rows == 0 || (text_len && dropped && (text || bound_of(*tab) == 0)), WC_E_ARG, "bedgraph: NULL output");
-    WC_CHECK(text_stride >= bound_of(*tab), WC_E_ARG, "bedgraph: %lld bytes per text row, wc_bedgraph_row_bound is %lld",
-             (long long)text_stride, (long long)bound_of(*tab));
-    return WC_OK;
-}
-
-// the three kernels, enqueued; ev (may be NULL): [0] in front, [1] behind the scan, [2] behind the bytes
-int enqueue_rows(wc_ctx *ctx, hipStream_t stream, const double *rows, int64_t row_stride, int64_t n_rows, const BtTab &tab,
-                 unsigned char *text, int64_t text_stride, int64_t *text_len, int64_t *dropped, hipEvent_t *ev) {
-    const int64_t n_tiles = tiles_of(tab);
-    int rc;
-    // the slots | the tiles' sums | their offsets (export.hip's working memory: one call in flight per context)
-    const size_t slot_bytes = (size_t)n_rows * (size_t)tab.total * 16, sum_bytes = ((size_t)n_rows * n_tiles * 8 + 15) & ~(size_t)15;
-    if ((rc = ctx->js_slots.reserve(slot_bytes + 16)) || (rc = ctx->js_tiles.reserve(sum_bytes + (size_t)n_rows * n_tiles * 8))) return rc;
-    int2 *sums = ctx->js_tiles.as<int2>();
-    long long *tile_off = reinterpret_cast<long long *>(ctx->js_tiles.as<unsigned char>() + sum_bytes);
-    const dim3 grid((unsigned)n_tiles, (unsigned)n_rows);
-    if (ev) WC_HIP(hipEventRecord(ev[0], stream));
-    hipLaunchKernelGGL(k_bt_len, grid, dim3(BT_T), 0, stream, rows, (long long)row_stride, tab, ctx->js_slots.as<uint4>(), sums);
-    WC_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_bt_scan, dim3((unsigned)n_rows), dim3(BT_T), 0, stream, (const int2 *)sums, (long long)n_tiles, tile_off,
-                       (long long *)text_len, (long long *)dropped);
-    WC_HIP(hipGetLastError());
-    if (ev) WC_HIP(hipEventRecord(ev[1], stream));
-    hipLaunchKernelGGL(k_bt_bytes, grid, dim3(BT_T), 0, stream, rows, (long long)row_stride, (const uint4 *)ctx->js_slots.as<uint4>(),
-                       (const long long *)tile_off, tab, text, (long long)text_stride);
-    WC_HIP(hipGetLastError());
-    if (ev) WC_HIP(hipEventRecord(ev[2], stream));
-    return WC_OK;
+// a call's three launches, as wc::TextRows takes them (text_rows.h); counts: text_len, dropped
+auto launches(const BtTab &tab) {
+    return [&tab](hipStream_t stream, const wc::TextWork &w, const wc::TextRows &call, hipEvent_t mid) -> int {
+        int2 *sums = static_cast<int2 *>(w.sums);
+        hipLaunchKernelGGL(k_bt_len, w.grid, dim3(BT_T), 0, stream, call.rows, (long long)call.row_stride, tab, w.slots, sums);
+        WC_HIP(hipGetLastError());
+        hipLaunchKernelGGL(k_bt_scan, dim3(w.grid.y), dim3(BT_T), 0, stream, (const int2 *)sums, w.n_tiles, w.tile_off,
+                           (long long *)call.counts[0], (long long *)call.counts[1]);
+        WC_HIP(hipGetLastError());
+        if (mid) WC_HIP(hipEventRecord(mid, stream));
+        hipLaunchKernelGGL(k_bt_bytes, w.grid, dim3(BT_T), 0, stream, call.rows, (long long)call.row_stride, (const uint4 *)w.slots,
+                           (const long long *)w.tile_off, tab, call.text, (long long)call.text_stride);
+        WC_HIP(hipGetLastError());
+        return WC_OK;
+    };
 }
 
 }  // namespace
@@ -308,60 +284,27 @@ int64_t wc_bedgraph_row_bound(const int64_t *chrom_sizes, int n_chrom, int64_t b
 int wc_bedgraph_rows_dev(wc_ctx *ctx, void *stream, const double *rows, int64_t row_stride, int64_t n_rows, const int64_t *chrom_sizes_host,
                          int n_chrom, int64_t binsize, const int64_t *clip_len_host, const char *prefix, int prefix_len, int flags,
                          unsigned char *text, int64_t text_stride, int64_t *text_len, int64_t *dropped) {
+    const wc::TextRows call = {"bedgraph", "bins", ctx, rows, row_stride, n_rows, text, text_stride, 2, {text_len, dropped}};
     BtTab tab;
     int rc;
-    if ((rc = check_rows(ctx, rows, row_stride, n_rows, chrom_sizes_host, n_chrom, binsize, clip_len_host, prefix, prefix_len, flags, text,
-                         text_stride, text_len, dropped, &tab)))
+    if ((rc = call.begin()) || (rc = make_tab(chrom_sizes_host, n_chrom, binsize, clip_len_host, prefix, prefix_len, flags, &tab)) ||
+        (rc = call.check(tab.total, bound_of(tab), true)))
         return rc;
-    WC_CHECK(text_stride % 16 == 0 && ((uintptr_t)text & 15) == 0, WC_E_ARG,
-             "bedgraph: text rows %lld bytes apart (a multiple of 16, from an address that is one)", (long long)text_stride);
-    if (n_rows == 0) return WC_OK;
-    WC_HIP(hipSetDevice(ctx->device));
-    return enqueue_rows(ctx, (hipStream_t)stream, rows, row_stride, n_rows, tab, text, text_stride, text_len, dropped, nullptr);
+    return call.enqueue((hipStream_t)stream, tab.total, sizeof(int2), nullptr, launches(tab));
 }
 
 int wc_bedgraph_rows(wc_ctx *ctx, const double *rows, int64_t row_stride, int64_t n_rows, const int64_t *chrom_sizes, int n_chrom,
                      int64_t binsize, const int64_t *clip_len, const char *prefix, int prefix_len, int flags, unsigned char *text,
                      int64_t text_stride, int64_t *text_len, int64_t *dropped, double *times_ms) {
+    const wc::TextRows call = {"bedgraph", "bins", ctx, rows, row_stride, n_rows, text, text_stride, 2, {text_len, dropped}};
     BtTab tab;
     int rc;
-    if ((rc = check_rows(ctx, rows, row_stride, n_rows, chrom_sizes, n_chrom, binsize, clip_len, prefix, prefix_len, flags, text, text_stride,
-                         text_len, dropped, &tab)))
+    if ((rc = call.begin()) || (rc = make_tab(chrom_sizes, n_chrom, binsize, clip_len, prefix, prefix_len, flags, &tab)) ||
+        (rc = call.check(tab.total, bound_of(tab), false)))
         return rc;
-    if (times_ms)
-        for (int i = 0; i < 4; ++i) times_ms[i] = 0.0;
-    if (n_rows == 0) return WC_OK;
-    WC_HIP(hipSetDevice(ctx->device));
-    const int64_t bound = bound_of(tab), dev_stride = (bound + 15) / 16 * 16;
-    const size_t in_bytes = ((size_t)(n_rows - 1) * row_stride + (size_t)tab.total) * 8;
-    if ((rc = ctx->tmp_a.reserve(in_bytes + 16)) || (rc = ctx->tmp_b.reserve((size_t)n_rows * dev_stride + 16)) ||
-        (rc = ctx->tmp_c.reserve((size_t)n_rows * 16)))
-        return rc;
-    wc::Events<5> events;
-    hipEvent_t *ev = events.e;
-    if (times_ms && (rc = events.create())) return rc;
-    if (times_ms) (void)hipEventRecord(ev[3], nullptr);
-    if (in_bytes) WC_HIP(hipMemcpy(ctx->tmp_a.p, rows, in_bytes, hipMemcpyHostToDevice));
-    int64_t *d_len = ctx->tmp_c.as<int64_t>(), *d_dropped = d_len + n_rows;
-    if ((rc = enqueue_rows(ctx, nullptr, ctx->tmp_a.as<double>(), row_stride, n_rows, tab, ctx->tmp_b.as<unsigned char>(), dev_stride, d_len,
-                           d_dropped, times_ms ? ev : nullptr)))
-        return rc;
-    WC_HIP(hipMemcpy(text_len, d_len, (size_t)n_rows * 8, hipMemcpyDeviceToHost));
-    WC_HIP(hipMemcpy(dropped, d_dropped, (size_t)n_rows * 8, hipMemcpyDeviceToHost));
-    for (int64_t i = 0; i < n_rows; ++i) {
-        WC_CHECK(text_len[i] >= 0 && text_len[i] <= bound, WC_E_INTERNAL, "bedgraph: a row of %lld bytes, the bound is %lld",
-                 (long long)text_len[i], (long long)bound);
-        if (text_len[i])
-            WC_HIP(hipMemcpy(text + i * text_stride, ctx->tmp_b.as<unsigned char>() + i * dev_stride, (size_t)text_len[i], hipMemcpyDeviceToHost));
-    }
-    if (times_ms) {
-        (void)hipEventRecord(ev[4], nullptr);
-        (void)hipEventSynchronize(ev[4]);
-        // [0] copy in [1] lengths and scan [2] bytes [3] copy out
-        const int from[4] = {3, 0, 1, 2}, to[4] = {0, 1, 2, 4};
-        events.elapsed(4, from, to, times_ms);
-    }
-    return WC_OK;
+    return call.stage(tab.total, bound_of(tab), 0, sizeof(int2), times_ms, launches(tab));
 }
+
+
 
 }  // extern "C"

@@ -1402,6 +1402,78 @@ def jsonRows(rows, sizes, strict=False, device=0, ctx=None, row_stride=None, tim
     return [text[i, :lens[i]].tobytes() for i in range(n)]
 
 
+def _text_export_batch(results, keys, sizes, bound, lead, room, min_len, text_call, pack, piece, device, ctx, max_rows, max_bytes,
+                       details):
+    """The GPU calls of export_json_batch and export_tracks_batch.  Per GPU call: the dense rows of results_<key> for every
+    key of `keys` (all of the first key, then all of the second) through a pinned staging array, the text of every row
+    `lead` bytes into its slot of lead + `room` bytes (text_call(handle, stream, rows, row_stride, n_rows, text,
+    text_stride, text_len, second): pointers of device memory), the optional pack stage, ONE read-back of the rows'
+    int64 counters [text_len, the text call's second counter, packed length] and the 32-bit CRCs, the range checks
+    (text_len in min_len .. bound), and per-row copies of the used bytes alone.
+    pack: None or (max_row_bytes, out_stride, least, call): call(handle, stream, text, counts, n, files) packs the rows
+    of `text` [rows, stride] into `files` [rows, out_stride] and leaves counts[2] (at least `least`) and, where it has
+    them, the rows' CRC-32 as the 32-bit words of counts[3]; n: results in this call.
+    piece(data, k, text_len, crc): the output bytes of a row of keys[k] from the uint8 array copied for it.
+    A batch is split at max_rows rows and at max_bytes of device memory per GPU call.  details (may be None) receives
+    'times_ms': per GPU call [copy in, text, pack, copy out].
+    Returns (pieces, text_bytes, second): per result a tuple over the keys."""
+    import torch
+    total = int(sizes.sum())
+    stride = lead + max(16, (room + 15) // 16 * 16)
+    max_row_bytes, out_stride, least, pack_call = pack or (0, 0, 0, None)
+    # device bytes of a row: the values, their digits between the passes, the text; packed: the blocks' slots and the file
+    per_row = 24 * max(total, 1) + stride + (2 * out_stride + 64 * (max_row_bytes // int(_lib.load().wc_deflate_block_bytes()) + 1) if pack else 0)
+    per_call = max(1, min(int(max_rows), int(max_bytes) // per_row) // len(keys))
+    dev = torch.device('cuda', device)
+    handle = ctx or _lib.context(device)
+    pieces, text_bytes, second, times = [], [], [], []
+    for at in range(0, len(results), per_call):
+        part = results[at:at + per_call]
+        n, rows_n = len(part), len(part) * len(keys)
+        rows = _pinned((rows_n, max(total, 1)))
+        for k, key in enumerate(keys):
+            _dense_rows([res['results_' + key] for res in part], sizes, out=rows[k * n:(k + 1) * n])
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream().cuda_stream
+            marks = [torch.cuda.Event(enable_timing=True) for _ in range(5)] if details is not None else None
+            if marks:
+                marks[0].record()
+            d_rows = torch.from_numpy(rows).to(dev, non_blocking=True)
+            text = torch.empty((rows_n, stride), dtype=torch.uint8, device=dev)
+            counts = torch.empty((4, rows_n), dtype=torch.int64, device=dev)
+            if marks:
+                marks[1].record()
+            text_call(handle, stream, d_rows.data_ptr(), rows.shape[1], rows_n, text.data_ptr() + lead, stride, counts[0].data_ptr(),
+                      counts[1].data_ptr())
+            if marks:
+                marks[2].record()
+            if pack:
+                files = torch.empty((rows_n, out_stride), dtype=torch.uint8, device=dev)
+                pack_call(handle, stream, text, counts, n, files)
+            if marks:
+                marks[3].record()
+            h_counts = counts.cpu().numpy()
+            h_crc = h_counts[3].view(np.uint32)
+            if np.any(h_counts[0] < min_len) or np.any(h_counts[0] > bound):
+                raise _lib.WisecondorHipError('a text row of %d bytes, the bound is %d' % (int(h_counts[0].max()), bound))
+            if pack and (np.any(h_counts[2] < least) or np.any(h_counts[2] > out_stride)):
+                raise _lib.WisecondorHipError('a packed row of %d bytes' % int(h_counts[2].max()))
+            used, src = (h_counts[2], files) if pack else (h_counts[0], text[:, lead:])
+            flat = [piece(src[i, :int(used[i])].cpu().numpy(), i // n, int(h_counts[0][i]), int(h_crc[i])) for i in range(rows_n)]
+            if marks:
+                marks[4].record()
+                marks[4].synchronize()
+                times.append([marks[k].elapsed_time(marks[k + 1]) for k in range(4)])
+        for i in range(n):
+            at_row = [k * n + i for k in range(len(keys))]
+            pieces.append(tuple(flat[j] for j in at_row))
+            text_bytes.append(tuple(int(h_counts[0][j]) for j in at_row))
+            second.append(tuple(int(h_counts[1][j]) for j in at_row))
+    if details is not None:
+        details['times_ms'] = times
+    return pieces, text_bytes, second
+
+
 def gzipAssemble(stream, crc, input_len):
     """One gzip member around a raw deflate stream (wc_gzip_assemble; host only): a fixed header without name or time, the
     stream, the CRC-32 and the length of the uncompressed bytes."""
@@ -1460,98 +1532,64 @@ def jsonHead(result, strict=False):
     return json.dumps(head, separators=(',', ':'), allow_nan=not strict)[:-1].encode('ascii')
 
 
-def export_json_batch(results, strict=False, gz=False, device=0, ctx=None, max_rows=65535, details=None):
+def export_json_batch(results, strict=False, gz=False, device=0, ctx=None, max_rows=65535, details=None, max_bytes=4 << 30):
     """Result files as lossless JSON: a list of the files' bytes, one per result.  A file is one object with
     the keys JSON_KEYS in that order; the host writes everything up to results_calls (jsonHead), results_z and results_r
     are text the GPU writes (wc_json_rows_dev: CPython's own digits, so json.loads returns the stored doubles bit for
     bit).  strict: Infinity, -Infinity and NaN become null in both parts.  gz: the file is three gzip members in a row,
-    the host part through zlib, `,"results_z":` + the z text and `,"results_r":` + the r text + `}` deflated on the GPU
-    (wc_deflate_rows_dev, one call per row since the rows differ in length), from which only compressed bytes are copied.
-    results: dicts with JSON_KEYS' entries, results_z / results_r as per-chromosome arrays; all share the chromosome
-    lengths.  max_rows: rows per wc_json_rows_dev call (a larger batch is split).  details: a dict that receives
-    'times_ms' (per GPU call [copy in, text, deflate, copy out]) and 'text_bytes' (per file: z, r)."""
+    the host part through zlib, `,"results_z":` + the z text and `,"results_r":` + the r text + `}` deflated on the GPU from
+    the text where it lies (wc_deflate_rows_len_dev, one call for the rows of a GPU call, their lengths made on the
+    device), from which only compressed bytes are copied.  results: dicts with JSON_KEYS' entries, results_z / results_r
+    as per-chromosome arrays; all share the chromosome lengths.  A batch is split at max_rows rows and at max_bytes of
+    device memory per GPU call.  details: a dict that receives 'times_ms' (per GPU call [copy in, text, deflate, copy
+    out]) and 'text_bytes' (per file: z, r)."""
     import torch
     import zlib
     if not results:
         return []
     lib = _lib.load()
     sizes = np.array([len(c) for c in results[0]['results_z']], dtype=np.int64)
-    total = int(sizes.sum())
     for i, res in enumerate(results):
         for key in ('results_z', 'results_r'):
             if [len(c) for c in res[key]] != [int(v) for v in sizes]:
                 raise ValueError('sample %d has other chromosome lengths in %s than the first has in results_z' % (i, key))
     bound = jsonRowBound(sizes)
     lead = 16                                   # room for the key in front of a row's text, which starts on a multiple of 16
-    stride = lead + (bound + 1 + 15) // 16 * 16
     keys = (b',"results_z":', b',"results_r":')
-    dev = torch.device('cuda', device)
-    handle = ctx or _lib.context(device)
-    per_call = max(1, int(max_rows) // 2)
+    assert len(keys[0]) == len(keys[1]) <= lead
+
+    def text_call(handle, stream, rows, row_stride, n_rows, text, text_stride, text_len, _):
+        _lib.check(lib.wc_json_rows_dev(handle, stream, rows, row_stride, n_rows, _lib.ptr(sizes), len(sizes), int(bool(strict)), text,
+                                        text_stride, text_len))
+
+    def pack_call(handle, stream, text, counts, n, files):
+        # the key goes in front of the text and the brace behind the r text, so a row is one gzip member's input; its
+        # length is made on the device, and one call deflates the rows of both keys
+        for k in range(2):
+            text[k * n:(k + 1) * n, lead - len(keys[k]):lead] = torch.from_numpy(np.frombuffer(keys[k], dtype=np.uint8).copy()).to(text.device)
+        text[torch.arange(n, 2 * n, device=text.device), lead + counts[0, n:].clamp(0, bound)] = ord('}')
+        member = counts[0] + len(keys[0])
+        member[n:] += 1
+        _lib.check(lib.wc_deflate_rows_len_dev(handle, stream, text.data_ptr() + lead - len(keys[0]), 2 * n, member.data_ptr(),
+                                               len(keys[0]) + bound + 1, text.shape[1], files.data_ptr(), files.shape[1],
+                                               counts[2].data_ptr(), counts[3].data_ptr()))
+
+    def piece(data, k, text_len, crc):
+        return gzipAssemble(data, crc, len(keys[k]) + text_len + k) if gz else data.tobytes()
+
+    pack = (len(keys[0]) + bound + 1, deflateBound(len(keys[0]) + bound + 1), 1, pack_call) if gz else None
+    pieces, text_bytes, _ = _text_export_batch(results, ('z', 'r'), sizes, bound, lead, bound + 1, 2, text_call, pack, piece, device, ctx,
+                                               max_rows, max_bytes, details)
     out = []
-    times, text_bytes = [], []
-    for at in range(0, len(results), per_call):
-        part = results[at:at + per_call]
-        n = len(part)
-        rows = np.zeros((2 * n, max(total, 1)), dtype=np.float64)
-        _dense_rows([res['results_z'] for res in part], sizes, out=rows[:n])
-        _dense_rows([res['results_r'] for res in part], sizes, out=rows[n:])
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream().cuda_stream
-            marks = [torch.cuda.Event(enable_timing=True) for _ in range(5)] if details is not None else None
-            if marks:
-                marks[0].record()
-            d_rows = torch.from_numpy(rows).to(dev)
-            text = torch.empty((2 * n, stride), dtype=torch.uint8, device=dev)
-            lens = torch.empty((2 * n,), dtype=torch.int64, device=dev)
-            if marks:
-                marks[1].record()
-            _lib.check(lib.wc_json_rows_dev(handle, stream, d_rows.data_ptr(), rows.shape[1], 2 * n, _lib.ptr(sizes), len(sizes),
-                                            int(bool(strict)), text.data_ptr() + lead, stride, lens.data_ptr()))
-            if marks:
-                marks[2].record()
-            h_lens = lens.cpu().numpy()
-            if np.any(h_lens < 2) or np.any(h_lens > bound):
-                raise _lib.WisecondorHipError('export_json_batch: a row of %d bytes, the bound is %d' % (int(h_lens.max()), bound))
-            if gz:
-                # the key goes in front of the text and the brace behind the r text, so a row is one gzip member's input
-                for k in range(2):
-                    text[k * n:(k + 1) * n, lead - len(keys[k]):lead] = torch.from_numpy(np.frombuffer(keys[k], dtype=np.uint8).copy()).to(dev)
-                text[torch.arange(n, 2 * n, device=dev), lead + lens[n:]] = ord('}')
-                member = h_lens + len(keys[0])
-                member[n:] += 1
-                out_stride = deflateBound(int(member.max()))
-                streams = torch.empty((2 * n, out_stride), dtype=torch.uint8, device=dev)
-                z_lens = torch.empty((2 * n,), dtype=torch.int64, device=dev)
-                crcs = torch.empty((2 * n,), dtype=torch.int32, device=dev)
-                for i in range(2 * n):
-                    _lib.check(lib.wc_deflate_rows_dev(handle, stream, text[i].data_ptr() + lead - len(keys[0]), 1, int(member[i]),
-                                                       int(member[i]), streams[i].data_ptr(), out_stride, z_lens[i:].data_ptr(),
-                                                       crcs[i:].data_ptr()))
-                if marks:
-                    marks[3].record()
-                h_z = z_lens.cpu().numpy()
-                h_crc = crcs.cpu().numpy().view(np.uint32)
-                pieces = [gzipAssemble(streams[i, :int(h_z[i])].cpu().numpy(), h_crc[i], int(member[i])) for i in range(2 * n)]
-            else:
-                if marks:
-                    marks[3].record()
-                pieces = [text[i, lead:lead + int(h_lens[i])].cpu().numpy().tobytes() for i in range(2 * n)]
-            if marks:
-                marks[4].record()
-                marks[4].synchronize()
-                times.append([marks[k].elapsed_time(marks[k + 1]) for k in range(4)])
-        for i, res in enumerate(part):
-            head = jsonHead(res, strict)
-            if gz:
-                packer = zlib.compressobj(6, zlib.DEFLATED, -15)
-                raw = packer.compress(head) + packer.flush()
-                out.append(gzipAssemble(raw, zlib.crc32(head), len(head)) + pieces[i] + pieces[n + i])
-            else:
-                out.append(head + keys[0] + pieces[i] + keys[1] + pieces[n + i] + b'}')
-            text_bytes.append((int(h_lens[i]), int(h_lens[n + i])))
+    for res, (z, r) in zip(results, pieces):
+        head = jsonHead(res, strict)
+        if gz:
+            packer = zlib.compressobj(6, zlib.DEFLATED, -15)
+            raw = packer.compress(head) + packer.flush()
+            out.append(gzipAssemble(raw, zlib.crc32(head), len(head)) + z + r)
+        else:
+            out.append(head + keys[0] + z + keys[1] + r + b'}')
     if details is not None:
-        details['times_ms'] = times
         details['text_bytes'] = text_bytes
     return out
 
@@ -1636,7 +1674,6 @@ def export_tracks_batch(results, only=None, gz=False, nozero=False, prefix='chr'
     (ends are clipped to them), or None.  mineffect: callsBed's.  A batch is split at max_rows rows and at max_bytes of device memory per GPU
     call.  details: a dict that receives 'times_ms' (per GPU call [copy in, text, BGZF, copy out]), 'text_bytes' (per file
     and track), 'dropped' (per file and track: bins that are not finite)."""
-    import torch
     if only not in (None,) + TRACKS:
         raise ValueError("only: 'z', 'r' or None, not %r" % (only,))
     if not results:
@@ -1646,7 +1683,6 @@ def export_tracks_batch(results, only=None, gz=False, nozero=False, prefix='chr'
     raw = _track_prefix(prefix)
     binsize = int(results[0]['binsize'])
     sizes = np.array([len(c) for c in results[0]['results_z']], dtype=np.int64)
-    total = int(sizes.sum())
     for i, res in enumerate(results):
         if int(res['binsize']) != binsize or res['binsize'] != binsize:
             raise ValueError('sample %d has bin size %s, the first has %s' % (i, res['binsize'], binsize))
@@ -1656,61 +1692,21 @@ def export_tracks_batch(results, only=None, gz=False, nozero=False, prefix='chr'
         if len(clip) != len(sizes):
             raise ValueError('%d chromosome lengths for %d chromosomes' % (len(clip), len(sizes)))
     bound = bedgraphRowBound(sizes, binsize, len(raw))
-    stride = max(16, (bound + 15) // 16 * 16)
-    out_stride = int(lib.wc_bgzf_bound(bound)) if gz else 0
-    # device bytes of a row: the values, their digits between the passes, the text; with gz the blocks' slots and the file
-    per_row = 24 * max(total, 1) + stride + (2 * out_stride + 64 * (bound // int(lib.wc_deflate_block_bytes()) + 1) if gz else 0)
-    per_call = max(1, min(int(max_rows), int(max_bytes) // per_row) // len(which))
-    dev = torch.device('cuda', device)
-    handle = ctx or _lib.context(device)
-    out, times, text_bytes, dropped_bins = [], [], [], []
-    for at in range(0, len(results), per_call):
-        part = results[at:at + per_call]
-        n, rows_n = len(part), len(part) * len(which)
-        rows = _pinned((rows_n, max(total, 1)))
-        for k, key in enumerate(which):
-            _dense_rows([res['results_' + key] for res in part], sizes, out=rows[k * n:(k + 1) * n])
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream().cuda_stream
-            marks = [torch.cuda.Event(enable_timing=True) for _ in range(5)] if details is not None else None
-            if marks:
-                marks[0].record()
-            d_rows = torch.from_numpy(rows).to(dev, non_blocking=True)
-            text = torch.empty((rows_n, stride), dtype=torch.uint8, device=dev)
-            counts = torch.empty((3, rows_n), dtype=torch.int64, device=dev)        # text_len, dropped, out_len
-            if marks:
-                marks[1].record()
-            _lib.check(lib.wc_bedgraph_rows_dev(handle, stream, d_rows.data_ptr(), rows.shape[1], rows_n, _lib.ptr(sizes), len(sizes),
-                                                binsize, _lib.ptr(clip), raw, len(raw), int(bool(nozero)), text.data_ptr(), stride,
-                                                counts[0].data_ptr(), counts[1].data_ptr()))
-            if marks:
-                marks[2].record()
-            if gz:
-                files = torch.empty((rows_n, out_stride), dtype=torch.uint8, device=dev)
-                _lib.check(lib.wc_bgzf_rows_dev(handle, stream, text.data_ptr(), rows_n, counts[0].data_ptr(), bound, stride,
-                                                files.data_ptr(), out_stride, counts[2].data_ptr()))
-            if marks:
-                marks[3].record()
-            h_counts = counts.cpu().numpy()
-            if np.any(h_counts[0] < 0) or np.any(h_counts[0] > bound):
-                raise _lib.WisecondorHipError('export_tracks_batch: a row of %d bytes, the bound is %d' % (int(h_counts[0].max()), bound))
-            if gz:
-                if np.any(h_counts[2] < 28) or np.any(h_counts[2] > out_stride):
-                    raise _lib.WisecondorHipError('export_tracks_batch: a BGZF row of %d bytes' % int(h_counts[2].max()))
-                pieces = [files[i, :int(h_counts[2][i])].cpu().numpy().tobytes() for i in range(rows_n)]
-            else:
-                pieces = [text[i, :int(h_counts[0][i])].cpu().numpy().tobytes() for i in range(rows_n)]
-            if marks:
-                marks[4].record()
-                marks[4].synchronize()
-                times.append([marks[k].elapsed_time(marks[k + 1]) for k in range(4)])
-        for i, res in enumerate(part):
-            bed = callsBed(res['results_calls'], binsize, prefix=prefix, chrom_lengths=chrom_lengths, mineffect=mineffect)
-            out.append(tuple(pieces[k * n + i] for k in range(len(which))) + (bed,))
-            text_bytes.append(tuple(int(h_counts[0][k * n + i]) for k in range(len(which))))
-            dropped_bins.append(tuple(int(h_counts[1][k * n + i]) for k in range(len(which))))
+
+    def text_call(handle, stream, rows, row_stride, n_rows, text, text_stride, text_len, dropped):
+        _lib.check(lib.wc_bedgraph_rows_dev(handle, stream, rows, row_stride, n_rows, _lib.ptr(sizes), len(sizes), binsize, _lib.ptr(clip),
+                                            raw, len(raw), int(bool(nozero)), text, text_stride, text_len, dropped))
+
+    def pack_call(handle, stream, text, counts, n, files):
+        _lib.check(lib.wc_bgzf_rows_dev(handle, stream, text.data_ptr(), text.shape[0], counts[0].data_ptr(), bound, text.shape[1],
+                                        files.data_ptr(), files.shape[1], counts[2].data_ptr()))
+
+    pack = (bound, int(lib.wc_bgzf_bound(bound)), 28, pack_call) if gz else None
+    pieces, text_bytes, dropped_bins = _text_export_batch(results, which, sizes, bound, 0, bound, 0, text_call, pack,
+                                                          lambda data, k, text_len, crc: data.tobytes(), device, ctx, max_rows,
+                                                          max_bytes, details)
     if details is not None:
-        details['times_ms'] = times
         details['text_bytes'] = text_bytes
         details['dropped'] = dropped_bins
-    return out
+    return [files + (callsBed(res['results_calls'], binsize, prefix=prefix, chrom_lengths=chrom_lengths, mineffect=mineffect),)
+            for res, files in zip(results, pieces)]
