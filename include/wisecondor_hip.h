@@ -886,6 +886,53 @@ int wc_bgzf_rows_dev(wc_ctx *ctx, void *stream, const unsigned char *src, int64_
 int wc_bgzf_rows(wc_ctx *ctx, const unsigned char *src, int64_t n_rows, const int64_t *row_len, int64_t max_row_bytes, int64_t src_stride,
                  unsigned char *out, int64_t out_stride, int64_t *out_len);
 
+/* ---- sensitivity: planted aberrations, spiked and judged on the device --------------------------------
+ * A PLAN is HOST memory in every call, int32 [n_trials, 5]: rows {base row, chromosome (1-based), first bin, bins, effect
+ *   in ppm}.  Bins are the chromosome's own bins in the chromosome_sizes layout (masked bins count); the span is
+ *   first .. first + bins - 1.  The effect is parts per million of the read depth, -1 000 000 .. +100 000 000; 0 is a
+ *   control trial, in which nothing is planted and nothing can match.  Every call checks every row before anything is
+ *   uploaded or launched and returns WC_E_ARG with the first bad row named in the error text, outputs untouched:
+ *   a base row outside 0 .. n_base - 1, a chromosome outside 1 .. n_chrom, first < 0, bins < 1, first + bins beyond the
+ *   chromosome's size, an effect out of range.  (The score has no sizes: it checks first, bins and the effect, and a
+ *   chromosome >= 1.)  One call in flight per context: the checked plan lives in the context.
+ * wc_spike_counts_dev: out [n_trials, n_total] int32 (DEVICE, n_total = sum(chrom_sizes)) = row plan[i][0] of base
+ *   [n_base, n_total] int32 (DEVICE), and inside the span every count c >= 0 becomes
+ *   min(2^31 - 1, (c * (1 000 000 + ppm) + 500 000) div 1 000 000) in 64-bit integers (half up, exact, no float); counts
+ *   below 0 and every bin outside the span are copied bit for bit.  saturated (DEVICE int64, may be NULL): how many bins
+ *   the minimum clipped.  base and out must not overlap and are aligned to 4 bytes; out need not be aligned to 16.
+ *   Enqueued on `stream`, nothing is waited for.  At most 2^31 - 9 bins in a row.
+ * wc_spike_counts: the same from HOST pointers (saturated: HOST int64, may be NULL), synchronising.
+ * wc_spike_score_dev: calls [n_trials, max_calls, 5] float64 rows [chrom, start, end, z, effect] and n_calls [n_trials]
+ *   int32 (DEVICE, the layout wc_test_batch_dev leaves; rows at and behind n_calls[i] are not read, n_calls is taken
+ *   as clipped to 0 .. max_calls).  start and end are compared as int64.  A call MATCHES trial i with span [s, e] on
+ *   chromosome c when its chromosome is c, its z has the effect's sign (z > 0 for a gain, z < 0 for a loss; NaN, +0.0 and
+ *   -0.0 match nothing) and min(e, end) - max(s, start) + 1 >= 1.
+ *   rec_i [n_trials, 8] int32 (DEVICE): {n_calls, n_match, overlap_bins (the sum of the matching calls' overlaps),
+ *   match_bins (the sum of their lengths end - start + 1), best_row (the matching call with the largest overlap, the
+ *   earliest row on a tie; -1: none), best_start, best_end (that call's; -1: none), 0}; the sums are formed in 64 bits
+ *   and stored clipped to 2^31 - 1.  rec_f [n_trials, 2] float64 (DEVICE): {best z, best effect}, copies of the stored
+ *   doubles, NaN when there is none.  Nothing in a record depends on a summation order.
+ * wc_spike_score: the same from HOST pointers, synchronising.
+ * wc_sensitivity_batch_dev: spike, then wc_test_batch_dev on the spiked rows, then the score, all on `stream` and on the
+ *   context's workspaces, with no wait between the stages besides those of wc_test_batch_dev.  chrom_sizes MUST be the
+ *   chromosome_sizes the reference was created with (the handle is opaque here, so, like the row length of the counts
+ *   wc_test_batch_dev takes, this is not checked).  threshold .. max_calls are passed on as they are, and so is every
+ *   error of that call (WC_E_LIMIT "max_calls": run the trials again with more room).  At most 60000 trials x selected
+ *   chromosomes per call.  rec_i, rec_f: as above; calls, n_calls (DEVICE, either may be NULL: the context's own) receive
+ *   what the test found.  The dense per-bin outputs of the test go to the context's workspaces and are not returned.      */
+int wc_spike_counts_dev(wc_ctx *ctx, void *stream, const int32_t *base, int64_t n_base, const int64_t *chrom_sizes_host, int n_chrom,
+                        const int32_t *plan_host, int64_t n_trials, int32_t *out, int64_t *saturated);
+int wc_spike_counts(wc_ctx *ctx, const int32_t *base, int64_t n_base, const int64_t *chrom_sizes, int n_chrom, const int32_t *plan,
+                    int64_t n_trials, int32_t *out, int64_t *saturated);
+int wc_spike_score_dev(wc_ctx *ctx, void *stream, const int32_t *plan_host, int64_t n_trials, const double *calls, const int32_t *n_calls,
+                       int max_calls, int32_t *rec_i, double *rec_f);
+int wc_spike_score(wc_ctx *ctx, const int32_t *plan, int64_t n_trials, const double *calls, const int32_t *n_calls, int max_calls,
+                   int32_t *rec_i, double *rec_f);
+int wc_sensitivity_batch_dev(wc_ctx *ctx, void *stream, const wc_reference *ref, const int32_t *base, int64_t n_base,
+                             const int64_t *chrom_sizes_host, int n_chrom, const int32_t *plan_host, int64_t n_trials, double threshold,
+                             int min_ref_bins, int repeats, double min_effect, const int32_t *chromosomes_host, int n_sel, int max_calls,
+                             int32_t *rec_i, double *rec_f, double *calls, int32_t *n_calls);
+
 #ifdef __cplusplus
 }
 #endif

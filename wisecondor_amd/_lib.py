@@ -163,6 +163,12 @@ SIGNATURES = {
     "wc_test_profile_read": (_i32, [_vp, _vp]),
     "wc_test_batch_dev": (_i32, [_vp, _vp, _vp, _vp, _i64, _dbl, _i32, _i32, _dbl, _vp, _i32, _i32,
                                  _vp, _vp, _vp, _vp, _vp, _vp]),
+    "wc_spike_counts_dev": (_i32, [_vp, _vp, _vp, _i64, _vp, _i32, _vp, _i64, _vp, _vp]),
+    "wc_spike_counts": (_i32, [_vp, _vp, _i64, _vp, _i32, _vp, _i64, _vp, _vp]),
+    "wc_spike_score_dev": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp, _vp]),
+    "wc_spike_score": (_i32, [_vp, _vp, _i64, _vp, _vp, _i32, _vp, _vp]),
+    "wc_sensitivity_batch_dev": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _i32, _vp, _i64, _dbl, _i32, _i32, _dbl, _vp, _i32, _i32,
+                                        _vp, _vp, _vp, _vp]),
 }
 
 SUM_PAIRWISE = 0

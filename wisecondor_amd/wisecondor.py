@@ -13,7 +13,9 @@ sub-command (many BAM files, reading file i + 1 while file i is on the GPU and f
 `plotbatch` sub-command (result files to z-score panel PNGs, drawn and deflated on the GPU), the `plotpdf`
 sub-command (the same panels as vector PDF pages, the content stream written on the GPU), the `exportjson`
 sub-command (result files to lossless JSON, the numbers' digits made on the GPU) and the `exporttracks` sub-command
-(result files to bedGraph tracks and BED calls for genome browsers, the text and its BGZF blocks made on the GPU).
+(result files to bedGraph tracks and BED calls for genome browsers, the text and its BGZF blocks made on the GPU) and
+the `sensitivity` sub-command (aberrations planted into healthy samples on the GPU, tested and judged there: how often
+a reference finds a span of a given length and effect).
 `plot` itself stays refused: its default output is a matplotlib PDF, which this build does not make.
 """
 import argparse
@@ -630,6 +632,56 @@ def toolExportTracks(args):
                      lambda: 'result files as tracks (%d bins left out as not finite)' % stats['dropped'])
 
 
+# ----------------------------------------------------------------- sensitivity ----
+def sensitivityOutputs(outfile):
+    """(out.npz, out.tsv) of the `out` argument (a trailing .npz is taken as part of neither)."""
+    stem = outfile[:-4] if outfile.endswith('.npz') else outfile
+    return stem + '.npz', stem + '.tsv'
+
+
+def toolSensitivity(args):
+    """`sensitivity healthy... out reference -lengths bp,... -effects percent,...` (build-only): spans of every length
+    are planted at -trials random places into every healthy sample with every effect, each spiked copy is tested as
+    `test` tests a sample, and every trial's calls are judged against what was planted, all on the GPU
+    (wt.sensitivity_batch).  Writes out.npz (the plan, a record per trial, the table) and out.tsv (the table), and prints
+    the table.  Everything that can be refused is refused before the GPU is touched: exit status 2."""
+    from . import ingest, sensitivity
+    try:
+        stored = _open_npz(args.reference)
+        binsize = stored['binsize'].item() if hasattr(stored['binsize'], 'item') else stored['binsize']
+        lengths_bins, effects_ppm = sensitivity.parseGrid(args.lengths, args.effects, binsize)
+        if args.trials < 1 or args.batch < 1 or not args.chromosomes or not 0 <= args.minoverlap <= 1:
+            raise ValueError('sensitivity needs -trials >= 1, -batch >= 1, -minoverlap in 0 .. 1 and at least one chromosome')
+        for path in args.infiles:
+            own = _open_npz(path)['arguments'].item()['binsize']
+            if own == 0 or binsize < own or binsize % own > 0:
+                raise ValueError('%s was binned at %s, which does not scale to the reference\'s %s' % (path, own, binsize))
+        plan = sensitivity.makePlan(stored, len(args.infiles), lengths_bins, effects_ppm, args.trials,
+                                    chromosomes=list(args.chromosomes), seed=args.seed)
+    except ValueError as exc:
+        print('ERROR:', exc)
+        sys.exit(2)
+    reference = wt.Reference.from_npz(stored)
+    cut = zThreshold([int(v) for v in stored['masked_sizes']], args.multitest, args.minzscore)
+    print('z-score threshold per bin:', cut)
+    samples = [ingest.read_sample(path, reference.binsize)[0] for path in args.infiles]
+    began = time.time()
+    rec_i, rec_f = sensitivity.sensitivity_batch(reference, samples, plan, cut, minrefbins=args.minrefbins, repeats=args.repeats,
+                                                 chromosomes=list(args.chromosomes), mineffectsize=args.mineffectsize,
+                                                 batch=args.batch)
+    print('%d trials took %.3f s' % (len(plan), time.time() - began))
+    table = sensitivity.sensitivityTable(plan, rec_i, rec_f, lengths_bins, effects_ppm, minoverlap=args.minoverlap)
+    text = sensitivity.tableText(table)
+    npz_path, tsv_path = sensitivityOutputs(args.outfile)
+    write_npz(npz_path, arguments=vars(args), runtime=getRuntime(), binsize=binsize, threshold_z=cut,
+              samples=np.array([str(p) for p in args.infiles]), lengths_bins=np.array(lengths_bins, dtype=np.int64),
+              effects_ppm=np.array(effects_ppm, dtype=np.int64), plan=plan, rec_i=rec_i, rec_f=rec_f, table=table)
+    with open(tsv_path, 'w') as handle:
+        handle.write(text)
+    print(text, end='')
+    reference.close()
+
+
 # ---------------------------------------------------------------------- parser ----
 def _not_in_this_build(args):
     print('ERROR: this sub-command is not part of the MI355X build (convert, newref*, test, report, plotbatch only): '
@@ -825,6 +877,24 @@ def buildParser():
     for flag, settings in _TEST_OPTIONS:
         p.add_argument(flag, **settings)
     p.set_defaults(func=toolTestBatch)
+
+    p = sub.add_parser('sensitivity', description='plant aberrations into healthy samples on the GPU and count how often the '
+                                                  'reference finds them (build-only)')
+    p.add_argument('infiles', type=str, nargs='+', help='converted healthy samples (.npz)')
+    p.add_argument('outfile', type=str, help='out: out.npz (plan, records, table) and out.tsv (table) are written')
+    p.add_argument('reference', type=str, help='reference built by newref')
+    p.add_argument('-lengths', type=str, required=True, help='span lengths in bp, comma separated (1e6,5e6,20e6)')
+    p.add_argument('-effects', type=str, required=True,
+                   help='changes in read depth in percent, comma separated, -100 .. 10000 (2.5,5,10,-2.5,-5,-10); a list that '
+                        'begins with a negative value is written -effects=-5,5')
+    p.add_argument('-trials', type=int, default=20, help='placements per sample and length')
+    p.add_argument('-seed', type=int, default=1, help='seed of the placements')
+    p.add_argument('-minoverlap', type=float, default=0.5,
+                   help='a trial counts as detected when its matching calls cover this share of the span')
+    p.add_argument('-batch', type=int, default=1024, help='trials per GPU batch')
+    for flag, settings in _TEST_OPTIONS:
+        p.add_argument(flag, **settings)
+    p.set_defaults(func=toolSensitivity)
     return parser
 
 

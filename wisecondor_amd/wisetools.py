@@ -1710,3 +1710,31 @@ def export_tracks_batch(results, only=None, gz=False, nozero=False, prefix='chr'
         details['dropped'] = dropped_bins
     return [files + (callsBed(res['results_calls'], binsize, prefix=prefix, chrom_lengths=chrom_lengths, mineffect=mineffect),)
             for res, files in zip(results, pieces)]
+
+
+# ---------------------------------------------------------------------------
+# sensitivity: thin mirrors of sensitivity.py, which imports this module
+# ---------------------------------------------------------------------------
+def spikeCounts(base, chrom_sizes, plan, device=0):
+    from . import sensitivity
+    return sensitivity.spikeCounts(base, chrom_sizes, plan, device=device)
+
+
+def scoreTrials(plan, calls, n_calls, device=0):
+    from . import sensitivity
+    return sensitivity.scoreTrials(plan, calls, n_calls, device=device)
+
+
+def makePlan(reference, n_samples, lengths_bins, effects_ppm, trials, chromosomes=None, seed=1):
+    from . import sensitivity
+    return sensitivity.makePlan(reference, n_samples, lengths_bins, effects_ppm, trials, chromosomes=chromosomes, seed=seed)
+
+
+def sensitivityTable(plan, rec_i, rec_f, lengths_bins, effects_ppm, minoverlap=0.5):
+    from . import sensitivity
+    return sensitivity.sensitivityTable(plan, rec_i, rec_f, lengths_bins, effects_ppm, minoverlap=minoverlap)
+
+
+def sensitivity_batch(reference, samples, plan, threshold, **options):
+    from . import sensitivity
+    return sensitivity.sensitivity_batch(reference, samples, plan, threshold, **options)
