@@ -1292,7 +1292,6 @@ int wc_convert_bam_dev(wc_ctx *ctx, void *stream_, const wc_bam_dev *h, const in
     int rc;
     if ((rc = ctx->tmp_c.reserve(sizeof(int32_t) * (size_t)(bins + 1) + 64))) return rc;
     int64_t *stats_dev = ctx->tmp_c.as<int64_t>();               // 8 words, then the counts
-    int32_t *counts_dev = reinterpret_cast<int32_t *>(stats_dev + 8);
     const int64_t lo = h->offsets[(size_t)refs[0]];
     const int32_t *pos = (const int32_t *)h->pos + lo, *mate = (const int32_t *)h->mate + lo;
     const uint8_t *mapq = (const uint8_t *)h->mapq + lo;
@@ -1319,15 +1318,10 @@ int wc_convert_bam_dev(wc_ctx *ctx, void *stream_, const wc_bam_dev *h, const in
         flag = flag_g;
     }
     rc = wc_convert_reads_ex_dev(ctx, stream, pos, mapq, paired ? flag : nullptr, paired ? mate : nullptr, ro.data(), n_chrom,
-                                 binsize, min_shift, threshold, min_mapq, demand_pair, bin_offsets, counts_dev, stats_dev);
+                                 binsize, min_shift, threshold, min_mapq, demand_pair, bin_offsets,
+                                 reinterpret_cast<int32_t *>(stats_dev + 8), stats_dev);
     if (rc) return rc;
-    WC_HIP(hipMemcpyAsync(stats_out, stats_dev, sizeof(int64_t) * 8, hipMemcpyDeviceToHost, stream));
-    if (bins) WC_HIP(hipMemcpyAsync(counts_out, counts_dev, sizeof(int32_t) * (size_t)bins, hipMemcpyDeviceToHost, stream));
-    WC_HIP(hipStreamSynchronize(stream));
-    WC_CHECK(stats_out[4] == 0, WC_E_ARG,
-             "convert: %lld read(s) lie beyond their chromosome's last bin (a position past the header's length)",
-             (long long)stats_out[4]);
-    return WC_OK;
+    return wc::convert_result(stream, stats_dev, bins, counts_out, stats_out, true);
 }
 
 }  // extern "C"

@@ -604,7 +604,6 @@ struct wc_convert_run {
     bool paired = false, finished = false;
     double binsize = 0.0;
     int64_t bins = 0;
-    std::vector<int> bo;
     int host_cur = -1;              // the last chromosome that got reads (the order check of the host-table feeds)
     int64_t pend_bound = 0;         // no more than this many positions are pending: min(max(threshold, 0), reads fed)
     int64_t slices = 0;             // slices that went through the kernels
@@ -639,6 +638,72 @@ int cv_grow_keep(wc::DevBuf &buf, size_t want, size_t keep, hipStream_t stream) 
     return WC_OK;
 }
 
+struct CvTiles {                     // the eight words per tile of a pass: n ints each, side by side in one buffer
+    int *keep, *off, *last, *first, *carry_last, *carry_next, *elast, *carry_e;
+};
+CvTiles cv_tiles(int *b, int n) { return {b, b + n, b + 2 * n, b + 3 * n, b + 4 * n, b + 5 * n, b + 6 * n, b + 7 * n}; }
+
+// One pass of the kernels over a whole call's or a slice's reads; buffers, tables and zeroed outputs are the caller's
+struct CvPass {
+    hipStream_t stream;
+    const int32_t *pos;
+    const uint8_t *mapq;
+    const uint16_t *flag;           // flag, mate_pos: the paired mode only
+    const int32_t *mate_pos;
+    CvTab *tab;
+    int n_chrom, n, n_tiles, n_ktiles;  // tiles of the reads (read n is the end marker); of the kept reads and the pending ones
+    CvTiles tiles;                  // of n_ktiles
+    uint8_t *cls;                  // paired mode: a byte for every read of n_tiles whole tiles (no bound in the kernels)
+    int32_t *kpos, *counts;
+    int min_mapq, min_shift, threshold;
+    double binsize;
+    bool paired;
+    unsigned long long *stats;
+    int *kept_total;                // where k_cv_scan<0> leaves the number of kept reads
+    const CvCarry *carry;           // CARRY: the state the slices before left; NULL without
+    int closing;                    // CARRY: 1 for the empty slice of wc_convert_finish, which counts the open run
+};
+
+// the launch sequence of the file's head comment; CARRY: the instances that read the carry
+template <bool CARRY> int cv_launch(const CvPass &p) {
+    const int n_chrom = p.n_chrom, n = p.n, n_tiles = p.n_tiles, n_ktiles = p.n_ktiles;
+    const hipStream_t stream = p.stream;
+    const CvTab *tab = p.tab;
+    const CvCarry *cin = p.carry;
+    const CvTiles &t = p.tiles;
+    if (p.paired) {
+        hipLaunchKernelGGL(k_cv_elig<CARRY>, dim3(n_tiles), dim3(CV_BLOCK), 0, stream, p.flag, tab, n_chrom, n, cin, t.elast);
+        hipLaunchKernelGGL(k_cv_scan<1>, dim3(1), dim3(CV_SCAN_BLOCK), 0, stream, (const int *)t.elast, n_tiles, t.carry_e,
+                           (int *)nullptr);
+        hipLaunchKernelGGL((k_cv_flags<true, CARRY>), dim3(n_tiles), dim3(CV_BLOCK), 0, stream, p.pos, p.mapq, p.flag,
+                           p.mate_pos, tab, n_chrom, n, p.min_mapq, (const int *)t.carry_e, p.cls, t.keep, p.stats, cin);
+    } else {
+        hipLaunchKernelGGL(k_cv_tables<CARRY>, dim3(1), dim3(CV_BLOCK), 0, stream, p.pos, p.tab, n_chrom, cin);
+        hipLaunchKernelGGL((k_cv_flags<false, CARRY>), dim3(n_tiles), dim3(CV_BLOCK), 0, stream, p.pos, p.mapq,
+                           (const uint16_t *)nullptr, (const int32_t *)nullptr, tab, n_chrom, n, p.min_mapq,
+                           (const int *)nullptr, (uint8_t *)nullptr, t.keep, p.stats, cin);
+    }
+    hipLaunchKernelGGL(k_cv_scan<0>, dim3(1), dim3(CV_SCAN_BLOCK), 0, stream, (const int *)t.keep, n_tiles, t.off,
+                       p.kept_total);
+    if (p.paired)
+        hipLaunchKernelGGL((k_cv_compact<true, CARRY>), dim3(n_tiles), dim3(CV_BLOCK), 0, stream, p.pos, p.mapq,
+                           (const uint8_t *)p.cls, p.tab, n_chrom, n, p.min_mapq, (const int *)t.off, p.kpos, cin);
+    else
+        hipLaunchKernelGGL((k_cv_compact<false, CARRY>), dim3(n_tiles), dim3(CV_BLOCK), 0, stream, p.pos, p.mapq,
+                           (const uint8_t *)nullptr, p.tab, n_chrom, n, p.min_mapq, (const int *)t.off, p.kpos, cin);
+    hipLaunchKernelGGL(k_cv_heads<CARRY>, dim3(n_ktiles), dim3(CV_BLOCK), 0, stream, (const int32_t *)p.kpos, tab, n_chrom,
+                       p.min_shift, t.last, t.first, cin);
+    hipLaunchKernelGGL(k_cv_scan<1>, dim3(1), dim3(CV_SCAN_BLOCK), 0, stream, (const int *)t.last, n_ktiles, t.carry_last,
+                       (int *)nullptr);
+    hipLaunchKernelGGL(k_cv_scan<2>, dim3(1), dim3(CV_SCAN_BLOCK), 0, stream, (const int *)t.first, n_ktiles, t.carry_next,
+                       (int *)nullptr);
+    hipLaunchKernelGGL(k_cv_count<CARRY>, dim3(n_ktiles), dim3(CV_BLOCK), 0, stream, (const int32_t *)p.kpos, tab, n_chrom,
+                       p.min_shift, p.threshold, p.binsize, (const int *)t.carry_last, (const int *)t.carry_next, p.counts,
+                       p.stats, cin, p.closing);
+    WC_HIP(hipGetLastError());
+    return WC_OK;
+}
+
 // one slice through the kernels.  Its offsets table is so_host (HOST int64 [n_chrom + 1]) or, where that is NULL, so_dev
 // (DEVICE int [n_chrom + 1]) with n64 a bound of its last entry: the grids are sized by n64, the kernels take the
 // number of reads from the table.  closing: the empty slice of wc_convert_finish, which counts the open run
@@ -652,10 +717,9 @@ int cv_feed(wc_convert_run *run, hipStream_t stream, const int32_t *pos, const u
     const int n = (int)n64;
     const int n_tiles = (n + 1 + CV_TILE - 1) / CV_TILE;                              // read n is the end marker
     const int n_ktiles = (int)((n64 + run->pend_bound + 1 + CV_TILE - 1) / CV_TILE);  // kept reads behind the pending ones
-    const bool paired = run->paired;
     int rc;
     if ((rc = run->tiles.reserve(sizeof(int) * 8 * (size_t)n_ktiles))) return rc;
-    if (paired && (rc = run->cls.reserve((size_t)n_tiles * CV_TILE))) return rc;
+    if (run->paired && (rc = run->cls.reserve((size_t)n_tiles * CV_TILE))) return rc;
     const size_t kbytes = sizeof(int32_t) * (size_t)(n64 + keep_after + 1);
     if ((rc = cv_grow_keep(run->kpos[run->at], kbytes, sizeof(int32_t) * (size_t)run->pend_bound, stream))) return rc;
     if ((rc = run->kpos[run->at ^ 1].reserve(kbytes))) return rc;
@@ -663,10 +727,6 @@ int cv_feed(wc_convert_run *run, hipStream_t stream, const int32_t *pos, const u
     CvCarry *carry = run->carry.as<CvCarry>();
     int32_t *kpos = run->kpos[run->at].as<int32_t>(), *kpos_next = run->kpos[run->at ^ 1].as<int32_t>();
     unsigned long long *stats = run->out.as<unsigned long long>();
-    int32_t *counts = reinterpret_cast<int32_t *>(stats + 8);
-    int *tile_keep = run->tiles.as<int>(), *tile_off = tile_keep + n_ktiles, *tile_last = tile_off + n_ktiles;
-    int *tile_first = tile_last + n_ktiles, *carry_last = tile_first + n_ktiles, *carry_next = carry_last + n_ktiles;
-    int *tile_elast = carry_next + n_ktiles, *carry_e = tile_elast + n_ktiles;
     if (so_host) {                                      // ro; bo is there since wc_convert_begin
         CvRo table;
         for (int c = 0; c <= WC_CV_MAX_CHROM; ++c) table.ro[c] = c <= n_chrom ? (int)so_host[c] : 0;
@@ -674,47 +734,19 @@ int cv_feed(wc_convert_run *run, hipStream_t stream, const int32_t *pos, const u
     } else {
         WC_HIP(hipMemcpyAsync(tab->ro, so_dev, sizeof(int) * ((size_t)n_chrom + 1), hipMemcpyDeviceToDevice, stream));
     }
-    const CvCarry *cin = carry;
-    if (paired) {
-        hipLaunchKernelGGL(k_cv_elig<true>, dim3(n_tiles), dim3(CV_BLOCK), 0, stream, flag, (const CvTab *)tab, n_chrom, n, cin,
-                           tile_elast);
-        hipLaunchKernelGGL(k_cv_scan<1>, dim3(1), dim3(CV_SCAN_BLOCK), 0, stream, (const int *)tile_elast, n_tiles, carry_e,
-                           (int *)nullptr);
-        hipLaunchKernelGGL((k_cv_flags<true, true>), dim3(n_tiles), dim3(CV_BLOCK), 0, stream, pos, mapq, flag, mate_pos,
-                           (const CvTab *)tab, n_chrom, n, run->min_mapq, (const int *)carry_e, run->cls.as<uint8_t>(),
-                           tile_keep, stats, cin);
-    } else {
-        hipLaunchKernelGGL(k_cv_tables<true>, dim3(1), dim3(CV_BLOCK), 0, stream, pos, tab, n_chrom, cin);
-        hipLaunchKernelGGL((k_cv_flags<false, true>), dim3(n_tiles), dim3(CV_BLOCK), 0, stream, pos, mapq,
-                           (const uint16_t *)nullptr, (const int32_t *)nullptr, (const CvTab *)tab, n_chrom, n, run->min_mapq,
-                           (const int *)nullptr, (uint8_t *)nullptr, tile_keep, stats, cin);
-    }
-    hipLaunchKernelGGL(k_cv_scan<0>, dim3(1), dim3(CV_SCAN_BLOCK), 0, stream, (const int *)tile_keep, n_tiles, tile_off,
-                       &carry->m_slice);
-    if (paired)
-        hipLaunchKernelGGL((k_cv_compact<true, true>), dim3(n_tiles), dim3(CV_BLOCK), 0, stream, pos, mapq,
-                           (const uint8_t *)run->cls.as<uint8_t>(), tab, n_chrom, n, run->min_mapq, (const int *)tile_off, kpos,
-                           cin);
-    else
-        hipLaunchKernelGGL((k_cv_compact<false, true>), dim3(n_tiles), dim3(CV_BLOCK), 0, stream, pos, mapq,
-                           (const uint8_t *)nullptr, tab, n_chrom, n, run->min_mapq, (const int *)tile_off, kpos, cin);
-    hipLaunchKernelGGL(k_cv_heads<true>, dim3(n_ktiles), dim3(CV_BLOCK), 0, stream, (const int32_t *)kpos, (const CvTab *)tab,
-                       n_chrom, run->min_shift, tile_last, tile_first, cin);
-    hipLaunchKernelGGL(k_cv_scan<1>, dim3(1), dim3(CV_SCAN_BLOCK), 0, stream, (const int *)tile_last, n_ktiles, carry_last,
-                       (int *)nullptr);
-    hipLaunchKernelGGL(k_cv_scan<2>, dim3(1), dim3(CV_SCAN_BLOCK), 0, stream, (const int *)tile_first, n_ktiles, carry_next,
-                       (int *)nullptr);
-    hipLaunchKernelGGL(k_cv_count<true>, dim3(n_ktiles), dim3(CV_BLOCK), 0, stream, (const int32_t *)kpos, (const CvTab *)tab,
-                       n_chrom, run->min_shift, run->threshold, run->binsize, (const int *)carry_last, (const int *)carry_next,
-                       counts, stats, cin, closing ? 1 : 0);
-    if (paired)
+    const CvPass pass = {stream, pos, mapq, flag, mate_pos, tab, n_chrom, n, n_tiles, n_ktiles,
+                         cv_tiles(run->tiles.as<int>(), n_ktiles), run->cls.as<uint8_t>(), kpos,
+                         reinterpret_cast<int32_t *>(stats + 8), run->min_mapq, run->min_shift, run->threshold, run->binsize,
+                         run->paired, stats, &carry->m_slice, carry, closing ? 1 : 0};
+    if ((rc = cv_launch<true>(pass))) return rc;
+    if (run->paired)
         hipLaunchKernelGGL(k_cv_carry<true>, dim3(1), dim3(CV_BLOCK), 0, stream, pos, mate_pos, (const CvTab *)tab, n_chrom,
-                           run->threshold, (const int *)tile_last, n_ktiles, (const int *)tile_elast, n_tiles,
+                           run->threshold, (const int *)pass.tiles.last, n_ktiles, (const int *)pass.tiles.elast, n_tiles,
                            (const int32_t *)kpos, kpos_next, carry, stats);
     else
         hipLaunchKernelGGL(k_cv_carry<false>, dim3(1), dim3(CV_BLOCK), 0, stream, pos, (const int32_t *)nullptr,
-                           (const CvTab *)tab, n_chrom, run->threshold, (const int *)tile_last, n_ktiles, (const int *)nullptr,
-                           n_tiles, (const int32_t *)kpos, kpos_next, carry, stats);
+                           (const CvTab *)tab, n_chrom, run->threshold, (const int *)pass.tiles.last, n_ktiles,
+                           (const int *)nullptr, n_tiles, (const int32_t *)kpos, kpos_next, carry, stats);
     WC_HIP(hipGetLastError());
     run->at ^= 1;
     run->pend_bound = keep_after;
@@ -740,6 +772,48 @@ int cv_check_slice(wc_convert_run *run, const int64_t *so) {
     return WC_OK;
 }
 
+// The arguments of wc_convert_reads_ex_dev, of wc_convert_begin (read_offsets NULL: it takes no reads) and, with `host`,
+// what wc_convert_reads_ex must know before it stages the arrays (have_reads: pos and mapq; have_pair: flag and mate_pos)
+// and hands everything to the device form.  It sizes the staging by the tables' last entries: one below 0 is WC_E_LIMIT
+// there, with a text of its own, and WC_E_ARG (the table decreases) from the two others; tests/test_convert_refusals_gpu.py
+int cv_check_args(int n_chrom, double binsize, const int64_t *read_offsets, const int64_t *bin_offsets, bool host,
+                  bool have_reads, bool paired, bool have_pair) {
+    WC_CHECK(n_chrom >= 1 && n_chrom <= WC_CV_MAX_CHROM, WC_E_LIMIT, "convert: %d chromosomes (1..%d supported)", n_chrom,
+             WC_CV_MAX_CHROM);
+    const int64_t n = read_offsets ? read_offsets[n_chrom] : 0, bins = bin_offsets[n_chrom];
+    if (host) {
+        WC_CHECK(n >= 0 && bins >= 0 && n <= (int64_t)INT_MAX && bins <= (int64_t)INT_MAX, WC_E_LIMIT,
+                 "convert: %lld reads, %lld bins in one call", (long long)n, (long long)bins);
+    } else {
+        WC_CHECK(binsize > 0.0 && binsize <= DBL_MAX, WC_E_ARG, "convert: bin size %g is not a positive finite number", binsize);
+        WC_CHECK((!read_offsets || read_offsets[0] == 0) && bin_offsets[0] == 0, WC_E_ARG,
+                 "convert: the offset tables must start at 0");
+        for (int c = 0; c < n_chrom; ++c)
+            WC_CHECK((!read_offsets || read_offsets[c + 1] >= read_offsets[c]) && bin_offsets[c + 1] >= bin_offsets[c],
+                     WC_E_ARG, "convert: offsets of chromosome %d decrease", c);
+        WC_CHECK(n <= (int64_t)INT_MAX - 2 * CV_TILE, WC_E_LIMIT, "convert: %lld reads in one call (limit %d)", (long long)n,
+                 INT_MAX - 2 * CV_TILE);
+        WC_CHECK(bins <= (int64_t)INT_MAX, WC_E_LIMIT, "convert: %lld bins in one call", (long long)bins);
+    }
+    WC_CHECK(!read_offsets || n == 0 || have_reads, WC_E_ARG, "convert: NULL read arrays");
+    WC_CHECK(!read_offsets || !paired || have_pair, WC_E_ARG,
+             "convert: the paired mode needs the flag and mate position arrays");
+    return WC_OK;
+}
+
+// n reads from the four HOST arrays to device memory that the caller has reserved (flag_dev, mate_dev: NULL unless paired)
+int cv_stage(int64_t n, const int32_t *pos, const uint8_t *mapq, const uint16_t *flag, const int32_t *mate_pos,
+             int32_t *pos_dev, uint8_t *mapq_dev, uint16_t *flag_dev, int32_t *mate_dev) {
+    if (!n) return WC_OK;
+    WC_HIP(hipMemcpy(pos_dev, pos, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice));
+    WC_HIP(hipMemcpy(mapq_dev, mapq, (size_t)n, hipMemcpyHostToDevice));
+    if (mate_dev) {
+        WC_HIP(hipMemcpy(mate_dev, mate_pos, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice));
+        WC_HIP(hipMemcpy(flag_dev, flag, sizeof(uint16_t) * (size_t)n, hipMemcpyHostToDevice));
+    }
+    return WC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -751,34 +825,19 @@ int wc_convert_reads_ex_dev(wc_ctx *ctx, void *stream_, const int32_t *pos, cons
                             int threshold, int min_mapq, int demand_pair, const int64_t *bin_offsets, int32_t *counts_out,
                             int64_t *stats_out) {
     WC_CHECK(ctx && read_offsets && bin_offsets && counts_out && stats_out, WC_E_ARG, "convert: NULL argument");
-    WC_CHECK(n_chrom >= 1 && n_chrom <= WC_CV_MAX_CHROM, WC_E_LIMIT, "convert: %d chromosomes (1..%d supported)", n_chrom,
-             WC_CV_MAX_CHROM);
-    WC_CHECK(binsize > 0.0 && binsize <= DBL_MAX, WC_E_ARG, "convert: bin size %g is not a positive finite number", binsize);
-    WC_CHECK(read_offsets[0] == 0 && bin_offsets[0] == 0, WC_E_ARG, "convert: the offset tables must start at 0");
-    for (int c = 0; c < n_chrom; ++c)
-        WC_CHECK(read_offsets[c + 1] >= read_offsets[c] && bin_offsets[c + 1] >= bin_offsets[c], WC_E_ARG,
-                 "convert: offsets of chromosome %d decrease", c);
-    const int64_t n64 = read_offsets[n_chrom], bins64 = bin_offsets[n_chrom];
-    WC_CHECK(n64 <= (int64_t)INT_MAX - 2 * CV_TILE, WC_E_LIMIT, "convert: %lld reads in one call (limit %d)", (long long)n64,
-             INT_MAX - 2 * CV_TILE);
-    WC_CHECK(bins64 <= (int64_t)INT_MAX, WC_E_LIMIT, "convert: %lld bins in one call", (long long)bins64);
-    WC_CHECK(n64 == 0 || (pos && mapq), WC_E_ARG, "convert: NULL read arrays");
     const bool paired = demand_pair != 0;
-    WC_CHECK(!paired || (flag && mate_pos), WC_E_ARG, "convert: the paired mode needs the flag and mate position arrays");
+    int rc;
+    if ((rc = cv_check_args(n_chrom, binsize, read_offsets, bin_offsets, false, pos && mapq, paired, flag && mate_pos))) return rc;
     WC_HIP(hipSetDevice(ctx->device));
     hipStream_t stream = (hipStream_t)stream_;
     ConvertState &cv = ctx->cv;
-    const int n = (int)n64;
+    const int n = (int)read_offsets[n_chrom];
     const int n_tiles = (n + 1 + CV_TILE - 1) / CV_TILE;         // read n is the end marker that closes the koff table
-    int rc;
     if ((rc = cv.tab.reserve(sizeof(CvTab)))) return rc;
     if ((rc = cv.tiles.reserve(sizeof(int) * 8 * (size_t)n_tiles))) return rc;
     if ((rc = cv.kpos.reserve(sizeof(int32_t) * ((size_t)n + 1)))) return rc;
     if (paired && (rc = cv.cls.reserve((size_t)n_tiles * CV_TILE))) return rc;      // whole tiles: no bound in the kernels
     CvTab *tab = cv.tab.as<CvTab>();
-    int *tile_keep = cv.tiles.as<int>(), *tile_off = tile_keep + n_tiles, *tile_last = tile_off + n_tiles;
-    int *tile_first = tile_last + n_tiles, *carry_last = tile_first + n_tiles, *carry_next = carry_last + n_tiles;
-    int *tile_elast = carry_next + n_tiles, *carry_e = tile_elast + n_tiles;
     std::vector<int> host(2 * (WC_CV_MAX_CHROM + 1), 0);
     for (int c = 0; c <= n_chrom; ++c) {
         host[c] = (int)read_offsets[c];
@@ -786,44 +845,13 @@ int wc_convert_reads_ex_dev(wc_ctx *ctx, void *stream_, const int32_t *pos, cons
     }
     WC_HIP(hipMemcpyAsync(tab, host.data(), sizeof(int) * host.size(), hipMemcpyHostToDevice, stream));   // ro, bo
     WC_HIP(hipMemsetAsync(stats_out, 0, sizeof(int64_t) * 8, stream));
-    if (bins64) WC_HIP(hipMemsetAsync(counts_out, 0, sizeof(int32_t) * (size_t)bins64, stream));
+    if (bin_offsets[n_chrom]) WC_HIP(hipMemsetAsync(counts_out, 0, sizeof(int32_t) * (size_t)bin_offsets[n_chrom], stream));
     unsigned long long *stats = reinterpret_cast<unsigned long long *>(stats_out);
-    const CvCarry *whole = nullptr;                     // the whole input in one call: the instances without a carry
-    if (paired) {
-        hipLaunchKernelGGL(k_cv_elig<false>, dim3(n_tiles), dim3(CV_BLOCK), 0, stream, flag, (const CvTab *)tab, n_chrom, n,
-                           whole, tile_elast);
-        hipLaunchKernelGGL(k_cv_scan<1>, dim3(1), dim3(CV_SCAN_BLOCK), 0, stream, (const int *)tile_elast, n_tiles, carry_e,
-                           (int *)nullptr);
-        hipLaunchKernelGGL((k_cv_flags<true, false>), dim3(n_tiles), dim3(CV_BLOCK), 0, stream, pos, mapq, flag, mate_pos,
-                           (const CvTab *)tab, n_chrom, n, min_mapq, (const int *)carry_e, cv.cls.as<uint8_t>(), tile_keep,
-                           stats, whole);
-    } else {
-        hipLaunchKernelGGL(k_cv_tables<false>, dim3(1), dim3(CV_BLOCK), 0, stream, pos, tab, n_chrom, whole);
-        hipLaunchKernelGGL((k_cv_flags<false, false>), dim3(n_tiles), dim3(CV_BLOCK), 0, stream, pos, mapq,
-                           (const uint16_t *)nullptr, (const int32_t *)nullptr, (const CvTab *)tab, n_chrom, n, min_mapq,
-                           (const int *)nullptr, (uint8_t *)nullptr, tile_keep, stats, whole);
-    }
-    hipLaunchKernelGGL(k_cv_scan<0>, dim3(1), dim3(CV_SCAN_BLOCK), 0, stream, (const int *)tile_keep, n_tiles, tile_off,
-                       reinterpret_cast<int *>(stats + 5));       // [5]: kept reads (low word; the high word is zero)
-    if (paired)
-        hipLaunchKernelGGL((k_cv_compact<true, false>), dim3(n_tiles), dim3(CV_BLOCK), 0, stream, pos, mapq,
-                           (const uint8_t *)cv.cls.as<uint8_t>(), tab, n_chrom, n, min_mapq, (const int *)tile_off,
-                           cv.kpos.as<int32_t>(), whole);
-    else
-        hipLaunchKernelGGL((k_cv_compact<false, false>), dim3(n_tiles), dim3(CV_BLOCK), 0, stream, pos, mapq,
-                           (const uint8_t *)nullptr, tab, n_chrom, n, min_mapq, (const int *)tile_off, cv.kpos.as<int32_t>(),
-                           whole);
-    hipLaunchKernelGGL(k_cv_heads<false>, dim3(n_tiles), dim3(CV_BLOCK), 0, stream, (const int32_t *)cv.kpos.as<int32_t>(),
-                       (const CvTab *)tab, n_chrom, min_shift, tile_last, tile_first, whole);
-    hipLaunchKernelGGL(k_cv_scan<1>, dim3(1), dim3(CV_SCAN_BLOCK), 0, stream, (const int *)tile_last, n_tiles, carry_last,
-                       (int *)nullptr);
-    hipLaunchKernelGGL(k_cv_scan<2>, dim3(1), dim3(CV_SCAN_BLOCK), 0, stream, (const int *)tile_first, n_tiles, carry_next,
-                       (int *)nullptr);
-    hipLaunchKernelGGL(k_cv_count<false>, dim3(n_tiles), dim3(CV_BLOCK), 0, stream, (const int32_t *)cv.kpos.as<int32_t>(),
-                       (const CvTab *)tab, n_chrom, min_shift, threshold, binsize, (const int *)carry_last,
-                       (const int *)carry_next, counts_out, stats, whole, 0);
-    WC_HIP(hipGetLastError());
-    return WC_OK;
+    // the whole input in one call: the instances without a carry; [5]: kept reads (low word; the high word is zero)
+    const CvPass pass = {stream, pos, mapq, flag, mate_pos, tab, n_chrom, n, n_tiles, n_tiles,
+                         cv_tiles(cv.tiles.as<int>(), n_tiles), cv.cls.as<uint8_t>(), cv.kpos.as<int32_t>(), counts_out, min_mapq,
+                         min_shift, threshold, binsize, paired, stats, reinterpret_cast<int *>(stats + 5), nullptr, 0};
+    return cv_launch<false>(pass);
 }
 
 int wc_convert_reads_dev(wc_ctx *ctx, void *stream, const int32_t *pos, const uint8_t *mapq, const int64_t *read_offsets,
@@ -837,43 +865,26 @@ int wc_convert_reads_ex(wc_ctx *ctx, const int32_t *pos, const uint8_t *mapq, co
                         const int64_t *read_offsets, int n_chrom, double binsize, int min_shift, int threshold, int min_mapq,
                         int demand_pair, const int64_t *bin_offsets, int32_t *counts_out, int64_t *stats_out) {
     WC_CHECK(ctx && read_offsets && bin_offsets && counts_out && stats_out, WC_E_ARG, "convert: NULL argument");
-    WC_CHECK(n_chrom >= 1 && n_chrom <= WC_CV_MAX_CHROM, WC_E_LIMIT, "convert: %d chromosomes (1..%d supported)", n_chrom,
-             WC_CV_MAX_CHROM);
-    const int64_t n = read_offsets[n_chrom], bins = bin_offsets[n_chrom];
-    WC_CHECK(n >= 0 && bins >= 0 && n <= (int64_t)INT_MAX && bins <= (int64_t)INT_MAX, WC_E_LIMIT,
-             "convert: %lld reads, %lld bins in one call", (long long)n, (long long)bins);
-    WC_CHECK(n == 0 || (pos && mapq), WC_E_ARG, "convert: NULL read arrays");
     const bool paired = demand_pair != 0;
-    WC_CHECK(!paired || (flag && mate_pos), WC_E_ARG, "convert: the paired mode needs the flag and mate position arrays");
-    WC_HIP(hipSetDevice(ctx->device));
     int rc;
+    if ((rc = cv_check_args(n_chrom, binsize, read_offsets, bin_offsets, true, pos && mapq, paired, flag && mate_pos))) return rc;
+    const int64_t n = read_offsets[n_chrom], bins = bin_offsets[n_chrom];
+    WC_HIP(hipSetDevice(ctx->device));
     if ((rc = ctx->tmp_a.reserve(sizeof(int32_t) * (size_t)(n + 1)))) return rc;
     if ((rc = ctx->tmp_b.reserve((size_t)n + 1))) return rc;
     if ((rc = ctx->tmp_c.reserve(sizeof(int32_t) * (size_t)(bins + 1) + 64))) return rc;
     if (paired && (rc = ctx->tmp_d.reserve((sizeof(int32_t) + sizeof(uint16_t)) * (size_t)(n + 1)))) return rc;
     int64_t *stats_dev = ctx->tmp_c.as<int64_t>();               // 8 words, then the counts
-    int32_t *counts_dev = reinterpret_cast<int32_t *>(stats_dev + 8);
     int32_t *mate_dev = paired ? ctx->tmp_d.as<int32_t>() : nullptr;      // n + 1 mate positions, then the flags
     uint16_t *flag_dev = paired ? reinterpret_cast<uint16_t *>(mate_dev + n + 1) : nullptr;
-    if (n) {
-        WC_HIP(hipMemcpy(ctx->tmp_a.p, pos, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice));
-        WC_HIP(hipMemcpy(ctx->tmp_b.p, mapq, (size_t)n, hipMemcpyHostToDevice));
-        if (paired) {
-            WC_HIP(hipMemcpy(mate_dev, mate_pos, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice));
-            WC_HIP(hipMemcpy(flag_dev, flag, sizeof(uint16_t) * (size_t)n, hipMemcpyHostToDevice));
-        }
-    }
+    rc = cv_stage(n, pos, mapq, flag, mate_pos, ctx->tmp_a.as<int32_t>(), ctx->tmp_b.as<uint8_t>(), flag_dev, mate_dev);
+    if (rc) return rc;
     rc = wc_convert_reads_ex_dev(ctx, nullptr, ctx->tmp_a.as<int32_t>(), ctx->tmp_b.as<uint8_t>(), flag_dev, mate_dev,
                                  read_offsets, n_chrom, binsize, min_shift, threshold, min_mapq, demand_pair, bin_offsets,
-                                 counts_dev, stats_dev);
+                                 reinterpret_cast<int32_t *>(stats_dev + 8), stats_dev);
     if (rc) return rc;
     WC_HIP(hipDeviceSynchronize());
-    WC_HIP(hipMemcpy(stats_out, stats_dev, sizeof(int64_t) * 8, hipMemcpyDeviceToHost));
-    if (bins) WC_HIP(hipMemcpy(counts_out, counts_dev, sizeof(int32_t) * (size_t)bins, hipMemcpyDeviceToHost));
-    WC_CHECK(stats_out[4] == 0, WC_E_ARG,
-             "convert: %lld read(s) lie beyond their chromosome's last bin (a position past the header's length)",
-             (long long)stats_out[4]);
-    return WC_OK;
+    return wc::convert_result(nullptr, stats_dev, bins, counts_out, stats_out, true);
 }
 
 int wc_convert_reads(wc_ctx *ctx, const int32_t *pos, const uint8_t *mapq, const int64_t *read_offsets, int n_chrom,
@@ -887,14 +898,8 @@ int wc_convert_begin(wc_ctx *ctx, int n_chrom, double binsize, int min_shift, in
                      const int64_t *bin_offsets, wc_convert_run **out) {
     WC_CHECK(ctx && bin_offsets && out, WC_E_ARG, "convert: NULL argument");
     *out = nullptr;
-    WC_CHECK(n_chrom >= 1 && n_chrom <= WC_CV_MAX_CHROM, WC_E_LIMIT, "convert: %d chromosomes (1..%d supported)", n_chrom,
-             WC_CV_MAX_CHROM);
-    WC_CHECK(binsize > 0.0 && binsize <= DBL_MAX, WC_E_ARG, "convert: bin size %g is not a positive finite number", binsize);
-    WC_CHECK(bin_offsets[0] == 0, WC_E_ARG, "convert: the offset tables must start at 0");
-    for (int c = 0; c < n_chrom; ++c)
-        WC_CHECK(bin_offsets[c + 1] >= bin_offsets[c], WC_E_ARG, "convert: offsets of chromosome %d decrease", c);
-    WC_CHECK(bin_offsets[n_chrom] <= (int64_t)INT_MAX, WC_E_LIMIT, "convert: %lld bins in one call",
-             (long long)bin_offsets[n_chrom]);
+    int rc;
+    if ((rc = cv_check_args(n_chrom, binsize, nullptr, bin_offsets, false, false, false, false))) return rc;
     WC_HIP(hipSetDevice(ctx->device));
     wc_convert_run *run = new wc_convert_run;
     run->ctx = ctx;
@@ -905,17 +910,12 @@ int wc_convert_begin(wc_ctx *ctx, int n_chrom, double binsize, int min_shift, in
     run->min_mapq = min_mapq;
     run->paired = demand_pair != 0;
     run->bins = bin_offsets[n_chrom];
-    for (int c = 0; c <= n_chrom; ++c) run->bo.push_back((int)bin_offsets[c]);
     const size_t out_bytes = sizeof(int64_t) * 8 + sizeof(int32_t) * (size_t)run->bins;
-    CvCarry start;
-    start.cur = -1;
-    start.cur_n = 0;
-    start.last_pos = start.larp = start.pe = start.me = -1;
-    start.run_chrom = -1;
-    start.last_kept = start.n_pend = start.m_slice = start.max_pend = 0;
+    const CvCarry start = {/* cur, cur_n */ -1, 0, /* last_pos, larp, pe, me */ -1, -1, -1, -1, /* run_chrom */ -1,
+                           /* last_kept, n_pend, m_slice, max_pend */ 0, 0, 0, 0};
     std::vector<int> bo(WC_CV_MAX_CHROM + 1, 0);
-    for (int c = 0; c <= n_chrom; ++c) bo[(size_t)c] = run->bo[(size_t)c];
-    int rc = run->out.reserve(out_bytes);
+    for (int c = 0; c <= n_chrom; ++c) bo[(size_t)c] = (int)bin_offsets[c];
+    rc = run->out.reserve(out_bytes);
     if (!rc) rc = run->carry.reserve(sizeof(CvCarry));
     if (!rc) rc = run->tab.reserve(sizeof(CvTab));
     if (!rc && (hipMemset(run->out.p, 0, out_bytes) != hipSuccess ||
@@ -961,24 +961,14 @@ int wc_convert_feed(wc_convert_run *run, const int32_t *pos, const uint8_t *mapq
     if ((rc = run->st_mapq.reserve((size_t)n + 1))) return rc;
     if (run->paired && (rc = run->st_mate.reserve(sizeof(int32_t) * (size_t)(n + 1)))) return rc;
     if (run->paired && (rc = run->st_flag.reserve(sizeof(uint16_t) * (size_t)(n + 1)))) return rc;
-    if (n) {
-        WC_HIP(hipMemcpy(run->st_pos.p, pos, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice));
-        WC_HIP(hipMemcpy(run->st_mapq.p, mapq, (size_t)n, hipMemcpyHostToDevice));
-        if (run->paired) {
-            WC_HIP(hipMemcpy(run->st_mate.p, mate_pos, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice));
-            WC_HIP(hipMemcpy(run->st_flag.p, flag, sizeof(uint16_t) * (size_t)n, hipMemcpyHostToDevice));
-        }
-    }
-    rc = wc_convert_feed_dev(run, nullptr, run->st_pos.as<int32_t>(), run->st_mapq.as<uint8_t>(),
-                             run->paired ? run->st_flag.as<uint16_t>() : nullptr,
-                             run->paired ? run->st_mate.as<int32_t>() : nullptr, slice_offsets);
+    uint16_t *flag_dev = run->paired ? run->st_flag.as<uint16_t>() : nullptr;
+    int32_t *mate_dev = run->paired ? run->st_mate.as<int32_t>() : nullptr;
+    rc = cv_stage(n, pos, mapq, flag, mate_pos, run->st_pos.as<int32_t>(), run->st_mapq.as<uint8_t>(), flag_dev, mate_dev);
     if (rc) return rc;
-    int64_t outside = 0;                                // the host form waits for the slice and reads the status word
-    WC_HIP(hipMemcpy(&outside, run->out.as<int64_t>() + 4, sizeof(outside), hipMemcpyDeviceToHost));
-    WC_CHECK(outside == 0, WC_E_ARG,
-             "convert: %lld read(s) lie beyond their chromosome's last bin (a position past the header's length)",
-             (long long)outside);
-    return WC_OK;
+    rc = wc_convert_feed_dev(run, nullptr, run->st_pos.as<int32_t>(), run->st_mapq.as<uint8_t>(), flag_dev, mate_dev,
+                             slice_offsets);
+    if (rc) return rc;
+    return wc::convert_result(nullptr, run->out.as<int64_t>(), 0, nullptr, nullptr, false);      // waits for the slice
 }
 
 static int cv_close(wc_convert_run *run, hipStream_t stream) {
@@ -1008,13 +998,7 @@ int wc_convert_finish(wc_convert_run *run, int32_t *counts_out, int64_t *stats_o
     WC_CHECK(run && counts_out && stats_out, WC_E_ARG, "convert: NULL argument");
     int rc;
     if ((rc = cv_close(run, nullptr))) return rc;
-    const int64_t *stats = run->out.as<int64_t>();
-    WC_HIP(hipMemcpy(stats_out, stats, sizeof(int64_t) * 8, hipMemcpyDeviceToHost));
-    WC_CHECK(stats_out[4] == 0, WC_E_ARG,
-             "convert: %lld read(s) lie beyond their chromosome's last bin (a position past the header's length)",
-             (long long)stats_out[4]);
-    if (run->bins) WC_HIP(hipMemcpy(counts_out, stats + 8, sizeof(int32_t) * (size_t)run->bins, hipMemcpyDeviceToHost));
-    return WC_OK;
+    return wc::convert_result(nullptr, run->out.as<int64_t>(), run->bins, counts_out, stats_out, false);
 }
 
 int wc_convert_run_info(const wc_convert_run *run, int64_t out[8]) {
@@ -1024,6 +1008,12 @@ int wc_convert_run_info(const wc_convert_run *run, int64_t out[8]) {
     out[1] = run->device_bytes();
     out[2] = run->pend_bound;
     return WC_OK;
+}
+
+void wc_convert_end(wc_convert_run *run) {
+    if (!run) return;
+    (void)hipDeviceSynchronize();                       // the last slice's kernels still use the buffers
+    delete run;
 }
 
 }  // extern "C"
@@ -1046,14 +1036,21 @@ int convert_run_max_pending(const wc_convert_run *run, hipStream_t stream, int64
     return WC_OK;
 }
 
-}  // namespace wc
-
-extern "C" {
-
-void wc_convert_end(wc_convert_run *run) {
-    if (!run) return;
-    (void)hipDeviceSynchronize();                       // the last slice's kernels still use the buffers
-    delete run;
+int convert_result(hipStream_t stream, const int64_t *image_dev, int64_t bins, int32_t *counts_out, int64_t *stats_out,
+                   bool counts_when_refused) {
+    int64_t word = 0;
+    if (stats_out) WC_HIP(hipMemcpyAsync(stats_out, image_dev, sizeof(int64_t) * 8, hipMemcpyDeviceToHost, stream));
+    else WC_HIP(hipMemcpyAsync(&word, image_dev + 4, sizeof(word), hipMemcpyDeviceToHost, stream));
+    WC_HIP(hipStreamSynchronize(stream));
+    const int64_t outside = stats_out ? stats_out[4] : word;
+    if (counts_out && bins && (outside == 0 || counts_when_refused)) {
+        WC_HIP(hipMemcpyAsync(counts_out, image_dev + 8, sizeof(int32_t) * (size_t)bins, hipMemcpyDeviceToHost, stream));
+        WC_HIP(hipStreamSynchronize(stream));
+    }
+    WC_CHECK(outside == 0, WC_E_ARG,
+             "convert: %lld read(s) lie beyond their chromosome's last bin (a position past the header's length)",
+             (long long)outside);
+    return WC_OK;
 }
 
-}  // extern "C"
+}  // namespace wc

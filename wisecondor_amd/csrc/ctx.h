@@ -203,4 +203,12 @@ int sym_eigh_leading(wc_ctx *ctx, const double *matrix_dev, int64_t n, int n_pai
 int convert_feed_table_dev(wc_convert_run *run, hipStream_t stream, const int32_t *pos, const uint8_t *mapq,
                            const uint16_t *flag, const int32_t *mate_pos, const int *slice_offsets_dev, int64_t most);
 int convert_run_max_pending(const wc_convert_run *run, hipStream_t stream, int64_t *out);
+// A convert's result from its device image -- 8 counters, then `bins` counts -- to HOST memory, on `stream` and waiting
+// for it: the counters, the counts, and the refusal (WC_E_ARG) of a status word, counter 4, that is not 0.  Behind a
+// refusal the entries differ and both ways are kept: the whole calls (wc_convert_reads_ex, wc_convert_bam_dev) have always
+// written the counts all the same (counts_when_refused; tests/test_convert_bounded_gpu.py compares them), a run's finish
+// leaves counts_out alone, as include/wisecondor_hip.h says.  stats_out NULL: the status word alone is read and checked
+// (a run between two slices).
+int convert_result(hipStream_t stream, const int64_t *image_dev, int64_t bins, int32_t *counts_out, int64_t *stats_out,
+                   bool counts_when_refused);
 }  // namespace wc

@@ -496,26 +496,51 @@ def prepReference(samples, pcacomp=3, device=0, device_out=False, counts=None, c
 CONVERT_KEYS = [str(c) for c in range(1, 23)] + ['X', 'Y']
 
 
-class BamReads(object):
+class _Handle(object):
+    """An object of the library in `_handle`, released once by the library function the subclass names in `_close`:
+    close(), or leaving a `with` block."""
+    _handle = None
+    _close = None
+
+    def close(self):
+        if self._handle is not None:
+            getattr(_lib.load(), self._close)(self._handle)
+            self._handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def _read_header(info_fn, refs_fn, handle, offsets=False):
+    """The header of an opened reader: (info int64 [8], names, lengths) and, with `offsets`, the offsets [n_refs + 1].
+    `info_fn` fills the info vector ([0] references, [5] bytes of their names), `refs_fn` the names with a newline
+    between them, the lengths and the offsets."""
+    info = np.zeros(8, dtype=np.int64)
+    _lib.check(info_fn(handle, _lib.ptr(info)))
+    n_refs, name_bytes = int(info[0]), int(info[5])
+    names = ctypes.create_string_buffer(name_bytes + 1)
+    tables = [np.zeros(n_refs, dtype=np.int64)] + ([np.zeros(n_refs + 1, dtype=np.int64)] if offsets else [])
+    _lib.check(refs_fn(handle, ctypes.cast(names, ctypes.c_void_p), name_bytes + 1, *[_lib.ptr(t) for t in tables]))
+    return [info, names.raw[:name_bytes].decode('latin1').split('\n')[:n_refs]] + tables
+
+
+class BamReads(_Handle):
     """The placed records of a BAM file as the native reader (csrc/bamio.cpp) leaves them: `names`, `lengths`
     from the header, `offsets` [n_refs + 1] into `pos` (int32) / `mapq` (uint8) / `flag` (uint16) / `mate_pos` (int32,
     the next_pos field) -- views of the library's own memory, valid until close() -- and the record counts `mapped`,
     `unmapped`, `no_coordinate`."""
+    _close = 'wc_bam_close'
 
     def __init__(self, path, threads=8):
         lib = _lib.load()
         handle = ctypes.c_void_p()
         _lib.check(lib.wc_bam_open(os.fsencode(path), int(threads), ctypes.byref(handle)))
         self._handle = handle
-        info = np.zeros(8, dtype=np.int64)
-        _lib.check(lib.wc_bam_info(handle, _lib.ptr(info)))
-        n_refs, n_reads, self.mapped, self.unmapped, self.no_coordinate, name_bytes = (int(v) for v in info[:6])
-        names = ctypes.create_string_buffer(name_bytes + 1)
-        self.lengths = np.zeros(n_refs, dtype=np.int64)
-        self.offsets = np.zeros(n_refs + 1, dtype=np.int64)
-        _lib.check(lib.wc_bam_refs(handle, ctypes.cast(names, ctypes.c_void_p), name_bytes + 1, _lib.ptr(self.lengths),
-                                   _lib.ptr(self.offsets)))
-        self.names = names.raw[:name_bytes].decode('latin1').split('\n')[:n_refs]
+        info, self.names, self.lengths, self.offsets = _read_header(lib.wc_bam_info, lib.wc_bam_refs, handle, offsets=True)
+        n_reads, self.mapped, self.unmapped, self.no_coordinate = (int(v) for v in info[1:5])
         if n_reads:
             self.pos = np.ctypeslib.as_array(ctypes.cast(lib.wc_bam_pos(handle), ctypes.POINTER(ctypes.c_int32)), (n_reads,))
             self.mapq = np.ctypeslib.as_array(ctypes.cast(lib.wc_bam_mapq(handle), ctypes.POINTER(ctypes.c_uint8)), (n_reads,))
@@ -527,23 +552,16 @@ class BamReads(object):
             self.flag, self.mate_pos = np.zeros(0, dtype=np.uint16), np.zeros(0, dtype=np.int32)
 
     def close(self):
-        if self._handle is not None:
-            self.pos = self.mapq = self.flag = self.mate_pos = None
-            _lib.load().wc_bam_close(self._handle)
-            self._handle = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
+        self.pos = self.mapq = self.flag = self.mate_pos = None      # the views go before the memory they look at
+        _Handle.close(self)
 
 
-class BamFile(object):
+class BamFile(_Handle):
     """The host stage of the device reader (csrc/bamfile.cpp, no GPU needed): the whole file in pinned host memory, its
     BGZF block directory, and the BAM header from as many leading blocks as it needs: `names`, `lengths`, `n_blocks`,
     `inflated_bytes` (the sum of ISIZE), `compressed_bytes`, `first_record` (offset of the first record in the inflated
     stream).  Errors carry the codes BamReads raises for the same file."""
+    _close = 'wc_bamfile_close'
 
     def __init__(self, path, device=0):
         lib = _lib.load()
@@ -551,26 +569,10 @@ class BamFile(object):
         _lib.check(lib.wc_bamfile_open(os.fsencode(path), int(device), ctypes.byref(handle)))
         self._handle = handle
         self.path = path
-        info = np.zeros(8, dtype=np.int64)
-        _lib.check(lib.wc_bamfile_info(handle, _lib.ptr(info)))
-        n_refs, self.n_blocks, self.inflated_bytes, self.compressed_bytes, self.first_record, name_bytes = (int(v) for v in info[:6])
+        info, self.names, self.lengths = _read_header(lib.wc_bamfile_info, lib.wc_bamfile_refs, handle)
+        self.n_blocks, self.inflated_bytes, self.compressed_bytes, self.first_record = (int(v) for v in info[1:5])
         self.pinned = bool(info[6])
         self.pin_ms = float(info[7]) / 1e3          # of the pinned allocation, part of the open
-        names = ctypes.create_string_buffer(name_bytes + 1)
-        self.lengths = np.zeros(n_refs, dtype=np.int64)
-        _lib.check(lib.wc_bamfile_refs(handle, ctypes.cast(names, ctypes.c_void_p), name_bytes + 1, _lib.ptr(self.lengths)))
-        self.names = names.raw[:name_bytes].decode('latin1').split('\n')[:n_refs]
-
-    def close(self):
-        if self._handle is not None:
-            _lib.load().wc_bamfile_close(self._handle)
-            self._handle = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
 
 class DeviceArray(object):
@@ -588,17 +590,17 @@ class DeviceArray(object):
 BAM_DEVICE_BUDGET = 0
 
 
-class BamReadsDevice(object):
+class BamReadsDevice(_Handle):
     """BamReads with `pos` / `mapq` / `flag` / `mate_pos` born on the device (DeviceArray; csrc/bamgpu.hip: only the
     compressed bytes cross to the device, BGZF inflate and the record walk are kernels).  `source` is a path or an
     opened BamFile (which stays the caller's).  `budget`: device bytes the open may take (<= 0: BAM_DEVICE_BUDGET); a
     file that needs more raises with code E_LIMIT.  `stage_ms`: the open's stage times (wc_bam_dev_times)."""
+    _close = 'wc_bam_dev_close'
 
     def __init__(self, source, device=0, budget=0):
         lib = _lib.load()
         own = not isinstance(source, BamFile)
         bamfile = BamFile(source, device=device) if own else source
-        self._handle = None
         try:
             handle = ctypes.c_void_p()
             _lib.check(lib.wc_bam_open_dev(_lib.context(device), None, bamfile._handle,
@@ -612,15 +614,10 @@ class BamReadsDevice(object):
         """The attributes of an opened wc_bam_dev handle."""
         lib = _lib.load()
         self._handle = handle
-        info = np.zeros(8, dtype=np.int64)
-        _lib.check(lib.wc_bam_dev_info(handle, _lib.ptr(info)))
-        n_refs, n_reads, self.mapped, self.unmapped, self.no_coordinate, name_bytes, self.device_bytes = (int(v) for v in info[:7])
-        names = ctypes.create_string_buffer(name_bytes + 1)
-        self.lengths = np.zeros(n_refs, dtype=np.int64)
-        self.offsets = np.zeros(n_refs + 1, dtype=np.int64)
-        _lib.check(lib.wc_bam_dev_refs(handle, ctypes.cast(names, ctypes.c_void_p), name_bytes + 1, _lib.ptr(self.lengths),
-                                       _lib.ptr(self.offsets)))
-        self.names = names.raw[:name_bytes].decode('latin1').split('\n')[:n_refs]
+        info, self.names, self.lengths, self.offsets = _read_header(lib.wc_bam_dev_info, lib.wc_bam_dev_refs, handle,
+                                                                    offsets=True)
+        n_reads, self.mapped, self.unmapped, self.no_coordinate = (int(v) for v in info[1:5])
+        self.device_bytes = int(info[6])
         self.n_reads = n_reads
         self.pos = DeviceArray(self, lib.wc_bam_dev_pos(handle), n_reads, np.int32)
         self.mapq = DeviceArray(self, lib.wc_bam_dev_mapq(handle), n_reads, np.uint8)
@@ -639,16 +636,8 @@ class BamReadsDevice(object):
         return out
 
     def close(self):
-        if self._handle is not None:
-            self.pos = self.mapq = self.flag = self.mate_pos = None
-            _lib.load().wc_bam_dev_close(self._handle)
-            self._handle = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
+        self.pos = self.mapq = self.flag = self.mate_pos = None      # the views go before the memory they look at
+        _Handle.close(self)
 
 
 #: compressed bytes per chunk of BamReadsStream; 0: the library's default (wc_bam_stream_default_chunk)
@@ -667,7 +656,6 @@ class BamReadsStream(BamReadsDevice):
 
     def __init__(self, path, device=0, chunk=0):
         lib = _lib.load()
-        self._handle = None
         handle = ctypes.c_void_p()
         _lib.check(lib.wc_bam_stream_dev(_lib.context(device), None, os.fsencode(path),
                                          int(chunk) if chunk > 0 else int(BAM_STREAM_CHUNK), ctypes.byref(handle)))
@@ -680,24 +668,20 @@ class BamReadsStream(BamReadsDevice):
         self.stream_info = dict(zip(STREAM_INFO_KEYS, (int(v) for v in info)))
 
 
-class BamChunks(object):
+class BamChunks(_Handle):
     """The host stage of the streamed reader (csrc/bamfile.cpp, no GPU needed): the header (`names`, `lengths`,
     `first_record`), then iteration over the chunks as dicts (first_block, blocks, compressed_bytes, inflated_bytes,
     file_offset, last).  Errors carry the codes of BamFile; a defect of a block is raised when its chunk is reached."""
+    _close = 'wc_bamchunks_close'
 
     def __init__(self, path, device=0, chunk=0):
         lib = _lib.load()
         handle = ctypes.c_void_p()
         _lib.check(lib.wc_bamchunks_open(os.fsencode(path), int(device), int(chunk), ctypes.byref(handle)))
         self._handle = handle
-        info = np.zeros(8, dtype=np.int64)
-        _lib.check(lib.wc_bamchunks_info(handle, _lib.ptr(info)))
-        n_refs, _, _, self.compressed_bytes, self.first_record, name_bytes = (int(v) for v in info[:6])
+        info, self.names, self.lengths = _read_header(lib.wc_bamchunks_info, lib.wc_bamchunks_refs, handle)
+        self.compressed_bytes, self.first_record = int(info[3]), int(info[4])
         self.pinned, self.host_bytes = bool(info[6]), int(info[7])
-        names = ctypes.create_string_buffer(name_bytes + 1)
-        self.lengths = np.zeros(n_refs, dtype=np.int64)
-        _lib.check(lib.wc_bamchunks_refs(handle, ctypes.cast(names, ctypes.c_void_p), name_bytes + 1, _lib.ptr(self.lengths)))
-        self.names = names.raw[:name_bytes].decode('latin1').split('\n')[:n_refs]
 
     def __iter__(self):
         return self
@@ -709,17 +693,6 @@ class BamChunks(object):
             raise StopIteration
         return {'first_block': int(out[1]), 'blocks': int(out[2]), 'compressed_bytes': int(out[3]),
                 'inflated_bytes': int(out[4]), 'file_offset': int(out[5]), 'last': bool(out[6])}
-
-    def close(self):
-        if self._handle is not None:
-            _lib.load().wc_bamchunks_close(self._handle)
-            self._handle = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
 
 #: the reader convertBam and convertbatch open a file with: 'device' (BamReadsDevice; the host reader only for a file
@@ -752,6 +725,58 @@ def convert_chromosome_key(name):
     return key if key in CONVERT_KEYS else None
 
 
+class _ConvertPlan(object):
+    """What `convert` makes of the references `names` / `lengths` (header order) at `binsize`: `picked`, the (header
+    index, sample key) of every processed chromosome; `refs`, those indices (int32); `n_bins` of each and `bin_offsets`
+    [len(picked) + 1] into the flat counts of a call."""
+
+    def __init__(self, names, lengths, binsize):
+        picked = [(r, convert_chromosome_key(name)) for r, name in enumerate(names)]
+        self.picked = [(r, key) for r, key in picked if key is not None]
+        self.refs = np.asarray([r for r, _ in self.picked], dtype=np.int32)
+        self.n_bins = [int(int(lengths[r]) / float(binsize) + 1) for r in self.refs]
+        self.bin_offsets = np.concatenate([[0], np.cumsum(self.n_bins)]).astype(np.int64)
+        self._listing = [(names[r], int(lengths[r])) for r in self.refs]
+
+    def describe(self):
+        """convertBam's line per processed chromosome"""
+        for (name, length), bins in zip(self._listing, self.n_bins):
+            print(name, 'length:', length, 'bins:', bins)
+
+    def new_counts(self):
+        return np.zeros(int(self.bin_offsets[-1]), dtype=np.int32)
+
+    def sample(self, counts):
+        """The sample dict of a call's flat counts (copies); a chromosome that is not in the header stays None."""
+        chromosomes = dict((key, None) for key in CONVERT_KEYS)
+        for i, (_, key) in enumerate(self.picked):
+            chromosomes[key] = counts[self.bin_offsets[i]:self.bin_offsets[i + 1]].copy()
+        return chromosomes
+
+    @staticmethod
+    def counters(stats):
+        """The four filter counters and pair_fail out of a call's stats."""
+        return {'filter_rmdup': int(stats[0]), 'filter_mapq': int(stats[1]), 'pre_retro': int(stats[2]),
+                'post_retro': int(stats[3]), 'pair_fail': int(stats[6])}
+
+    def spans(self, offsets):
+        """[lo, hi) of every processed chromosome in arrays that reference r owns [offsets[r], offsets[r+1]) of; then the
+        table of the same reads set side by side."""
+        spans = [(int(offsets[r]), int(offsets[r + 1])) for r in self.refs]
+        return spans, np.concatenate([[0], np.cumsum([hi - lo for lo, hi in spans])]).astype(np.int64)
+
+    @staticmethod
+    def contiguous(spans):
+        return all(spans[i][1] == spans[i + 1][0] for i in range(len(spans) - 1))
+
+    @staticmethod
+    def gather(array, spans, dtype):
+        """The spans of a host array side by side, C-contiguous: a slice without a copy in the usual header order."""
+        a = np.asarray(array)
+        a = a[spans[0][0]:spans[-1][1]] if _ConvertPlan.contiguous(spans) else np.concatenate([a[lo:hi] for lo, hi in spans])
+        return np.ascontiguousarray(a, dtype=dtype)
+
+
 def convertReads(names, lengths, offsets, pos, mapq, binsize=1000000, minShift=4, threshold=4, device=0, verbose=False,
                  flag=None, mate_pos=None, minMapq=1, demandPair=False):
     """convertBam's filters and binning (wisetools.py:143-206) on reads that are already in arrays: references
@@ -765,18 +790,13 @@ def convertReads(names, lengths, offsets, pos, mapq, binsize=1000000, minShift=4
     demandPair = bool(demandPair)
     if demandPair and (flag is None or mate_pos is None):
         raise ValueError('convertReads: demandPair needs the flag and mate_pos arrays')
-    chromosomes = dict((key, None) for key in CONVERT_KEYS)
-    picked = [(r, convert_chromosome_key(name)) for r, name in enumerate(names)]
-    picked = [(r, key) for r, key in picked if key is not None]
-    stats = np.zeros(8, dtype=np.int64)
-    if picked:
-        spans = [(int(offsets[r]), int(offsets[r + 1])) for r, _ in picked]
-        n_bins = [int(int(lengths[r]) / float(binsize) + 1) for r, _ in picked]
+    plan = _ConvertPlan(names, lengths, binsize)
+    counts, stats = plan.new_counts(), np.zeros(8, dtype=np.int64)
+    if plan.picked:
         if verbose:
-            for (r, _), bins in zip(picked, n_bins):
-                print(names[r], 'length:', int(lengths[r]), 'bins:', bins)
-        bin_offsets = np.concatenate([[0], np.cumsum(n_bins)]).astype(np.int64)
-        counts = np.zeros(int(bin_offsets[-1]), dtype=np.int32)
+            plan.describe()
+        params = (float(binsize), int(minShift), int(threshold), int(minMapq), int(demandPair), _lib.ptr(plan.bin_offsets),
+                  _lib.ptr(counts), _lib.ptr(stats))
         if isinstance(pos, DeviceArray):
             # the call works on the reader's own arrays and offsets: anything else would be silently ignored
             reader = pos.reader
@@ -786,34 +806,19 @@ def convertReads(names, lengths, offsets, pos, mapq, binsize=1000000, minShift=4
                 raise ValueError('convertReads: device flag / mate_pos must belong to the same BamReadsDevice')
             if not np.array_equal(np.asarray(offsets, dtype=np.int64), reader.offsets):
                 raise ValueError('convertReads: with device arrays `offsets` must be the reader\'s own')
-            refs = np.asarray([r for r, _ in picked], dtype=np.int32)
-            _lib.check(lib.wc_convert_bam_dev(_lib.context(device), None, pos.reader._handle, _lib.ptr(refs), len(picked),
-                                              float(binsize), int(minShift), int(threshold), int(minMapq), int(demandPair),
-                                              _lib.ptr(bin_offsets), _lib.ptr(counts), _lib.ptr(stats)))
+            _lib.check(lib.wc_convert_bam_dev(_lib.context(device), None, reader._handle, _lib.ptr(plan.refs), len(plan.picked),
+                                              *params))
         else:
-            if all(spans[i][1] == spans[i + 1][0] for i in range(len(spans) - 1)):
-                def gather(a):
-                    return a[spans[0][0]:spans[-1][1]]                              # no copy: the usual header order
-            else:
-                def gather(a):
-                    return np.concatenate([a[lo:hi] for lo, hi in spans])
-            p = np.ascontiguousarray(gather(pos), dtype=np.int32)
-            q = np.ascontiguousarray(gather(mapq), dtype=np.uint8)
-            f = np.ascontiguousarray(gather(np.asarray(flag)), dtype=np.uint16) if demandPair else None
-            m = np.ascontiguousarray(gather(np.asarray(mate_pos)), dtype=np.int32) if demandPair else None
-            read_offsets = np.concatenate([[0], np.cumsum([b - a for a, b in spans])]).astype(np.int64)
-            _lib.check(lib.wc_convert_reads_ex(_lib.context(device), _lib.ptr(p), _lib.ptr(q),
-                                               _lib.ptr(f) if demandPair else None, _lib.ptr(m) if demandPair else None,
-                                               _lib.ptr(read_offsets), len(picked), float(binsize), int(minShift),
-                                               int(threshold), int(minMapq), int(demandPair), _lib.ptr(bin_offsets),
-                                               _lib.ptr(counts), _lib.ptr(stats)))
-        for i, (_, key) in enumerate(picked):
-            chromosomes[key] = counts[bin_offsets[i]:bin_offsets[i + 1]].copy()
-    return chromosomes, {'filter_rmdup': int(stats[0]), 'filter_mapq': int(stats[1]), 'pre_retro': int(stats[2]),
-                         'post_retro': int(stats[3]), 'pair_fail': int(stats[6])}
+            spans, read_offsets = plan.spans(offsets)
+            p, q = plan.gather(pos, spans, np.int32), plan.gather(mapq, spans, np.uint8)
+            f = plan.gather(flag, spans, np.uint16) if demandPair else None
+            m = plan.gather(mate_pos, spans, np.int32) if demandPair else None
+            _lib.check(lib.wc_convert_reads_ex(_lib.context(device), _lib.ptr(p), _lib.ptr(q), _lib.ptr(f), _lib.ptr(m),
+                                               _lib.ptr(read_offsets), len(plan.picked), *params))
+    return plan.sample(counts), plan.counters(stats)
 
 
-class ConvertRun(object):
+class ConvertRun(_Handle):
     """convertReads in resumable form (wc_convert_begin / feed / finish): the reads of the references `names` /
     `lengths` (header order) arrive in slices, in file order; every slice is filtered and binned as it arrives and only
     a small carry stays on the device, so the working memory follows the largest slice, not the read count.
@@ -821,17 +826,15 @@ class ConvertRun(object):
     (references that are not processed are skipped); with `device_arrays` true the four are device addresses (ints)
     and the call returns as soon as the slice's kernels are enqueued on `stream`.  `finish()` returns what
     convertReads returns for the concatenation of the slices."""
+    _close = 'wc_convert_end'
 
     def __init__(self, names, lengths, binsize=1000000, minShift=4, threshold=4, device=0, minMapq=1, demandPair=False):
         lib = _lib.load()
-        self._handle = None
         self.demandPair = bool(demandPair)
-        picked = [(r, convert_chromosome_key(name)) for r, name in enumerate(names)]
-        self.picked = [(r, key) for r, key in picked if key is not None]
+        self.plan = _ConvertPlan(names, lengths, binsize)
+        self.picked, self.bin_offsets = self.plan.picked, self.plan.bin_offsets
         if not self.picked:
             raise ValueError('ConvertRun: none of the references is a processed chromosome')
-        n_bins = [int(int(lengths[r]) / float(binsize) + 1) for r, _ in self.picked]
-        self.bin_offsets = np.concatenate([[0], np.cumsum(n_bins)]).astype(np.int64)
         handle = ctypes.c_void_p()
         _lib.check(lib.wc_convert_begin(_lib.context(device), len(self.picked), float(binsize), int(minShift), int(threshold),
                                         int(minMapq), int(self.demandPair), _lib.ptr(self.bin_offsets), ctypes.byref(handle)))
@@ -841,11 +844,9 @@ class ConvertRun(object):
         lib = _lib.load()
         if self.demandPair and (flag is None or mate_pos is None):
             raise ValueError('ConvertRun.feed: demandPair needs the flag and mate_pos arrays')
-        spans = [(int(offsets[r]), int(offsets[r + 1])) for r, _ in self.picked]
-        slice_offsets = np.concatenate([[0], np.cumsum([b - a for a, b in spans])]).astype(np.int64)
-        contiguous = all(spans[i][1] == spans[i + 1][0] for i in range(len(spans) - 1))
+        spans, slice_offsets = self.plan.spans(offsets)
         if device_arrays:
-            if not contiguous:
+            if not self.plan.contiguous(spans):
                 raise ValueError('ConvertRun.feed: device arrays must hold the processed references side by side')
             lo = spans[0][0]
             args = [ctypes.c_void_p(int(pos) + 4 * lo), ctypes.c_void_p(int(mapq) + lo),
@@ -854,14 +855,9 @@ class ConvertRun(object):
             _lib.check(lib.wc_convert_feed_dev(self._handle, ctypes.c_void_p(stream) if stream else None, *args,
                                                _lib.ptr(slice_offsets)))
             return
-
-        def gather(a, dtype):
-            a = np.asarray(a)
-            a = a[spans[0][0]:spans[-1][1]] if contiguous else np.concatenate([a[lo:hi] for lo, hi in spans])
-            return np.ascontiguousarray(a, dtype=dtype)
-        p, q = gather(pos, np.int32), gather(mapq, np.uint8)
-        f = gather(flag, np.uint16) if self.demandPair else None
-        m = gather(mate_pos, np.int32) if self.demandPair else None
+        p, q = self.plan.gather(pos, spans, np.int32), self.plan.gather(mapq, spans, np.uint8)
+        f = self.plan.gather(flag, spans, np.uint16) if self.demandPair else None
+        m = self.plan.gather(mate_pos, spans, np.int32) if self.demandPair else None
         _lib.check(lib.wc_convert_feed(self._handle, _lib.ptr(p), _lib.ptr(q), _lib.ptr(f), _lib.ptr(m),
                                        _lib.ptr(slice_offsets)))
 
@@ -872,25 +868,9 @@ class ConvertRun(object):
         return {'slices': int(out[0]), 'device_bytes': int(out[1]), 'carry_bound': int(out[2])}
 
     def finish(self):
-        counts = np.zeros(int(self.bin_offsets[-1]), dtype=np.int32)
-        stats = np.zeros(8, dtype=np.int64)
+        counts, stats = self.plan.new_counts(), np.zeros(8, dtype=np.int64)
         _lib.check(_lib.load().wc_convert_finish(self._handle, _lib.ptr(counts), _lib.ptr(stats)))
-        chromosomes = dict((key, None) for key in CONVERT_KEYS)
-        for i, (_, key) in enumerate(self.picked):
-            chromosomes[key] = counts[self.bin_offsets[i]:self.bin_offsets[i + 1]].copy()
-        return chromosomes, {'filter_rmdup': int(stats[0]), 'filter_mapq': int(stats[1]), 'pre_retro': int(stats[2]),
-                             'post_retro': int(stats[3]), 'pair_fail': int(stats[6])}
-
-    def close(self):
-        if self._handle is not None:
-            _lib.load().wc_convert_end(self._handle)
-            self._handle = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
+        return self.plan.sample(counts), self.plan.counters(stats)
 
 
 def convertBamReads(bam, binsize=1000000, minShift=4, threshold=4, device=0, verbose=False, mapq=1, demandPair=False):
@@ -915,34 +895,25 @@ def convertBamBounded(bamfile, binsize=1000000, minShift=4, threshold=4, device=
     number of reads is not limited.  The same (chromosomes, qual_info).  `info`: a dict that receives BOUNDED_INFO_KEYS."""
     lib = _lib.load()
     with BamChunks(bamfile, device=-1, chunk=65536) as header:      # the header alone (host stage, ordinary memory)
-        names, lengths = header.names, header.lengths
-    chromosomes = dict((key, None) for key in CONVERT_KEYS)
-    picked = [(r, convert_chromosome_key(name)) for r, name in enumerate(names)]
-    picked = [(r, key) for r, key in picked if key is not None]
-    if not picked:
+        plan = _ConvertPlan(header.names, header.lengths, binsize)
+    if not plan.picked:
         # nothing to bin: the reader alone gives the record counts (and the file's errors)
         with BamReadsStream(bamfile, device=device, chunk=chunk) as bam:
             return convertBamReads(bam, binsize, minShift, threshold, device=device, mapq=mapq, demandPair=demandPair)
-    n_bins = [int(int(lengths[r]) / float(binsize) + 1) for r, _ in picked]
     if verbose:
-        for (r, _), bins in zip(picked, n_bins):
-            print(names[r], 'length:', int(lengths[r]), 'bins:', bins)
-    bin_offsets = np.concatenate([[0], np.cumsum(n_bins)]).astype(np.int64)
-    counts = np.zeros(int(bin_offsets[-1]), dtype=np.int32)
-    stats = np.zeros(8, dtype=np.int64)
+        plan.describe()
+    counts, stats = plan.new_counts(), np.zeros(8, dtype=np.int64)
     out = np.zeros(16, dtype=np.int64)
-    refs = np.asarray([r for r, _ in picked], dtype=np.int32)
     _lib.check(lib.wc_convert_bam_stream_dev(_lib.context(device), None, os.fsencode(bamfile),
-                                             int(chunk) if chunk > 0 else int(BAM_STREAM_CHUNK), _lib.ptr(refs), len(picked),
-                                             float(binsize), int(minShift), int(threshold), int(mapq), int(bool(demandPair)),
-                                             _lib.ptr(bin_offsets), _lib.ptr(counts), _lib.ptr(stats), _lib.ptr(out)))
-    for i, (_, key) in enumerate(picked):
-        chromosomes[key] = counts[bin_offsets[i]:bin_offsets[i + 1]].copy()
+                                             int(chunk) if chunk > 0 else int(BAM_STREAM_CHUNK), _lib.ptr(plan.refs),
+                                             len(plan.picked), float(binsize), int(minShift), int(threshold), int(mapq),
+                                             int(bool(demandPair)), _lib.ptr(plan.bin_offsets), _lib.ptr(counts),
+                                             _lib.ptr(stats), _lib.ptr(out)))
     if info is not None:
         info.update(zip(BOUNDED_INFO_KEYS, (int(v) for v in out[:8])))
-    return chromosomes, {'mapped': int(out[8]), 'unmapped': int(out[9]), 'no_coordinate': int(out[10]),
-                         'filter_rmdup': int(stats[0]), 'filter_mapq': int(stats[1]), 'pre_retro': int(stats[2]),
-                         'post_retro': int(stats[3]), 'pair_fail': int(stats[6])}
+    qual_info = {'mapped': int(out[8]), 'unmapped': int(out[9]), 'no_coordinate': int(out[10])}
+    qual_info.update(plan.counters(stats))
+    return plan.sample(counts), qual_info
 
 
 def convertBam(bamfile, binsize=1000000, minShift=4, threshold=4, threads=8, device=0, mapq=1, demandPair=False):
