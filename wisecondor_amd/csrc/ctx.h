@@ -25,6 +25,10 @@ struct NewrefState {
     wc::DevBuf keys1, thr, cnt, list, tiles;
     wc::DevBuf fb_rows, fb_count, fb_scratch, stats, tiles0, pw_prog, pairs, x64, m2;
     bool fb_dirty = true;       // fb_count holds a finished pass's counts (k_convert zeroes it for the next job)
+    // m2[1 + bad_slot] is the smallest norm among the rows with a clamped value (+inf: none) of the prepared job;
+    // bad_spare_clean: the other slot holds +inf, left there by the one-launch prepare for the prepare after it
+    int bad_slot = 0;
+    bool bad_spare_clean = false;
     int64_t s_pad = 0;      // samples padded to whole 16-sample chunks (x64 row stride)
     bool exact_only = false; // refsize beyond the candidate lists' design size: every row takes the exact path
     wc::DevBuf cand_word;    // per row: row | slack code << index_bits, the low word of the row's entries in other rows' lists

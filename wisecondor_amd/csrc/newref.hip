@@ -162,37 +162,38 @@ __device__ __forceinline__ float slack_of_word(unsigned int word, unsigned int i
 // row gets infinite bounds -- never listed, its own row takes the exact path -- and leaves the smallest
 // norm among such rows in *bad_norm; k_pick certifies a row only if (|a_bad| - |a_i|)^2, a lower bound of
 // its distance to any of them, stays above U.
-__global__ __launch_bounds__(256) void k_convert(const double *__restrict__ X, int64_t B, int64_t S,
-                                                 int64_t Bpad,
-                                                 const double *__restrict__ mean, double beta, double tau,
-                                                 const int64_t *__restrict__ chrom_off, int n_chrom,
-                                                 unsigned short *__restrict__ A16,
-                                                 int64_t Kpad16, float *__restrict__ norm_lo,
-                                                 float *__restrict__ norm_hi, int *__restrict__ chrom_of_row,
-                                                 int2 *__restrict__ chrom_range,
-                                                 const int *__restrict__ sample_slot,
-                                                 unsigned short *__restrict__ S16, float *__restrict__ s_norm_lo,
-                                                 int *__restrict__ s_chrom, int2 *__restrict__ s_range,
-                                                 float *__restrict__ thr, int *__restrict__ cnt,
-                                                 int *__restrict__ row_stat,
-                                                 double *__restrict__ X64, int64_t Sp, float *__restrict__ m2_out,
-                                                 int *__restrict__ bad_norm, int *__restrict__ fb_zero, int n_fb_zero,
-                                                 unsigned int *__restrict__ cand_word, int index_bits) {
+// The row body of k_convert (NT = 256 threads, centre and scale from global memory: `mean`, the scale terms S doubles
+// on) and of k_prepare_fused (LDS: `mean` points there, the scale terms 128 doubles on).
+template <bool CENTRE_IN_LDS, int NT>
+__device__ __forceinline__ void convert_row(const double *__restrict__ X, int64_t B, int64_t S, int64_t Bpad,
+                                            const double *mean, double beta, double tau,
+                                            const int64_t *__restrict__ chrom_off, int n_chrom,
+                                            unsigned short *__restrict__ A16, int64_t Kpad16,
+                                            float *__restrict__ norm_lo, float *__restrict__ norm_hi,
+                                            int *__restrict__ chrom_of_row, int2 *__restrict__ chrom_range,
+                                            const int *__restrict__ sample_slot, unsigned short *__restrict__ S16,
+                                            float *__restrict__ s_norm_lo, int *__restrict__ s_chrom,
+                                            int2 *__restrict__ s_range, float *__restrict__ thr, int *__restrict__ cnt,
+                                            int *__restrict__ row_stat, double *__restrict__ X64, int64_t Sp,
+                                            float *__restrict__ m2_out, int *__restrict__ bad_norm,
+                                            int *__restrict__ fb_zero, int n_fb_zero,
+                                            unsigned int *__restrict__ cand_word, int index_bits) {
     // Half a wave per row (lane hl of 32, `half` picks the row): a row's life here is a few dependent round trips,
     // and with a wave per row the 11 087 rows of a 250 kb problem were 1.35 rounds of what fits the chip -- two rounds
     // of ~5 us.  Two rows per wave make it one.
     const int lane = threadIdx.x & 63, hl = lane & 31, half = lane >> 5;
-    const int64_t row = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 2 + half;
+    const int64_t row = ((int64_t)blockIdx.x * (NT / 64) + (threadIdx.x >> 6)) * 2 + half;
     // the exact path's counter and tickets of the job that starts here (was a memset launch in front of
     // the pick stage of every pass)
     if (blockIdx.x == 0)
-        for (int i = threadIdx.x; i < n_fb_zero; i += 256) fb_zero[i] = 0;
+        for (int i = threadIdx.x; i < n_fb_zero; i += NT) fb_zero[i] = 0;
     if (row >= Bpad) return;                   // (Bpad is a multiple of 128: whole waves)
     // The half wave reads its row ONCE, samples hl + 32 i in blocks of CB: every load of a block -- the row's values,
     // mean[s] and the scale terms mean[S + s] -- is an unconditional load of a selected index (element 0 always exists)
     // issued before the block's first use, so a block is one memory round trip.  (One load and one wait per iteration
     // of three loops, two of which read again what the first had read, were twelve dependent trips at 100 samples.)
     constexpr int CB = 4;
+    const int64_t scale_off = CENTRE_IN_LDS ? 128 : S;
     const int64_t xrow = (row < B ? row : 0) * S;
     auto load_x = [&](int64_t s0, double (&xv)[CB], double (&mv)[CB]) {
 #pragma unroll
@@ -212,7 +213,7 @@ __global__ __launch_bounds__(256) void k_convert(const double *__restrict__ X, i
 #pragma unroll
         for (int j = 0; j < CB; ++j) {
             const int64_t s = s0 + 32 * j;
-            sv[j] = mean[S + (s < S ? s : 0)];
+            sv[j] = mean[scale_off + (s < S ? s : 0)];
         }
     };
     // the first block of the row and of the centre rides with the first block of the scale terms, the row's sample
@@ -337,6 +338,104 @@ __global__ __launch_bounds__(256) void k_convert(const double *__restrict__ X, i
         row_stat[row] = (int)0xFEFEFEFE;
     }
 }
+
+#define WC_CONVERT_PARAMS                                                                                            \
+    const double *__restrict__ X, int64_t B, int64_t S, int64_t Bpad, const double *__restrict__ mean, double beta, \
+        double tau, const int64_t *__restrict__ chrom_off, int n_chrom, unsigned short *__restrict__ A16,           \
+        int64_t Kpad16, float *__restrict__ norm_lo, float *__restrict__ norm_hi, int *__restrict__ chrom_of_row,   \
+        int2 *__restrict__ chrom_range, const int *__restrict__ sample_slot, unsigned short *__restrict__ S16,      \
+        float *__restrict__ s_norm_lo, int *__restrict__ s_chrom, int2 *__restrict__ s_range,                       \
+        float *__restrict__ thr, int *__restrict__ cnt, int *__restrict__ row_stat, double *__restrict__ X64,       \
+        int64_t Sp, float *__restrict__ m2_out, int *__restrict__ bad_norm, int *__restrict__ fb_zero,              \
+        int n_fb_zero, unsigned int *__restrict__ cand_word, int index_bits
+#define WC_CONVERT_ARGS(mean_)                                                                                        \
+    X, B, S, Bpad, mean_, beta, tau, chrom_off, n_chrom, A16, Kpad16, norm_lo, norm_hi, chrom_of_row, chrom_range,   \
+        sample_slot, S16, s_norm_lo, s_chrom, s_range, thr, cnt, row_stat, X64, Sp, m2_out, bad_norm, fb_zero,       \
+        n_fb_zero, cand_word, index_bits
+
+// centre and scale from `mean` (k_col_centre's 2 S numbers); more than 128 samples
+__global__ __launch_bounds__(256) void k_convert(WC_CONVERT_PARAMS) {
+    convert_row<false, 256>(WC_CONVERT_ARGS(mean));
+}
+
+// Up to 128 samples: prepare in ONE launch.  Every workgroup derives centre and scale itself, in LDS, from the same
+// n_crows <= CR sampled rows (rows q * crow_step) with k_col_centre's three passes -- the same loads, the same sums in
+// the same order, so the same bits in every workgroup (rows compared with each other must share a centre) -- and then
+// converts its NT / 32 rows as k_convert does.  k_col_centre was a dependent launch of two workgroups for 2 S numbers
+// that any later stage tolerates in any reasonable value; the CR rows are 25 KB at 100 samples, read from L2 by all but
+// the first workgroups.  Thread = sample (threadIdx & 127) x row phase (threadIdx >> 7), CR / (NT / 128) rows each, ONE
+// batch of unconditional loads of selected indices; the row's own loads follow the centre (requested with it they made
+// the pass slower: EXPERIMENTS.md).  Workgroup 0 writes `mean_out` for the callers that read the centres back.
+// *bad_norm must be +inf at entry (k_col_centre reset it itself, this kernel's rows take minima into it from the
+// start); the kernel leaves *bad_spare, the slot of the prepare before this one, at +inf for the prepare after it.
+constexpr int FUSED_CENTRE_ROWS = 32;
+constexpr int FUSED_MAX_SAMPLES = 128;
+constexpr int FUSED_THREADS = 512;      // 16 rows per workgroup: the centre phase is done 693 times at cfg2, not 1 386
+constexpr int FUSED_WGS_PER_CU = 3;     // cfg2: 693 workgroups on 256 CUs are one round
+template <int CR, int NT>
+__global__ __launch_bounds__(NT, FUSED_WGS_PER_CU) void k_prepare_fused(WC_CONVERT_PARAMS, double *__restrict__ mean_out,
+                                                                       int64_t n_crows, int64_t crow_step,
+                                                                       int *__restrict__ bad_spare) {
+    constexpr int NPH = NT / 128, PER = CR / NPH;   // row phases, sampled rows per thread
+    static_assert(CR % NPH == 0, "whole rows per phase");
+    __shared__ float sh_part[2][2][NPH][128];   // [pass parity][sum, count][row phase][sample]
+    __shared__ double sh_cs[2 * 128];           // centre, then scale (mean absolute deviation), per sample
+    // (the row phase is the same for a whole wave: as a scalar it leaves the sampled rows' addresses in scalar registers)
+    const int tx = threadIdx.x & 127, ty = __builtin_amdgcn_readfirstlane(threadIdx.x >> 7);
+    if (blockIdx.x == 0 && threadIdx.x == 0) *bad_spare = 0x7F800000;
+    double val[PER];
+    {
+        const unsigned int sc = tx < S ? tx : 0;
+#pragma unroll
+        for (int e = 0; e < PER; ++e) {
+            const int64_t q = ty + NPH * e;
+            const double *__restrict__ xq = X + ((q < n_crows ? q : 0) * crow_step) * S;
+            val[e] = xq[sc];
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < PER; ++e) asm volatile("" : "+v"(val[e]));
+    // The three passes in float32: a centre needs no more (the values are centred in float64, whatever it is), and the
+    // phase is repeated by every workgroup -- in float64 its arithmetic cost what the launch it replaces did.  A value
+    // beyond the float32 range counts as not finite.
+    float fv[PER];
+#pragma unroll
+    for (int e = 0; e < PER; ++e) fv[e] = (tx < S && ty + NPH * e < n_crows) ? (float)val[e] : NAN;
+    float c = 0.f, rad = 0.f, mad = 0.f;
+    for (int pass = 0; pass < 3; ++pass) {
+        float sum = 0.f, n = 0.f;
+#pragma unroll
+        for (int e = 0; e < PER; ++e) {
+            const float v = fv[e];
+            const bool ok = isfinite(v) && (pass != 2 || fabsf(v - c) <= rad);
+            sum += ok ? ((pass == 1) ? fabsf(v - c) : v) : 0.f;
+            n += ok ? 1.f : 0.f;
+        }
+        // (pass 2 writes the block of pass 0 again: every thread has read that one before the barrier of pass 1)
+        float (*part)[NPH][128] = sh_part[pass & 1];
+        part[0][ty][tx] = sum;
+        part[1][ty][tx] = n;
+        wc_sync();
+        float a = 0.f, b = 0.f;
+#pragma unroll
+        for (int r = 0; r < NPH; ++r) { a += part[0][r][tx]; b += part[1][r][tx]; }
+        const float v = b > 0.f ? a / b : 0.f;
+        if (pass == 1) { mad = v; rad = 8.f * v; }
+        else c = v;
+    }
+    if (ty == 0) {
+        sh_cs[tx] = (double)c;
+        sh_cs[128 + tx] = (double)mad;
+        if (blockIdx.x == 0 && tx < S) {
+            mean_out[tx] = (double)c;
+            mean_out[S + tx] = (double)mad;
+        }
+    }
+    wc_sync();
+    convert_row<true, NT>(WC_CONVERT_ARGS((const double *)sh_cs));
+}
+#undef WC_CONVERT_PARAMS
+#undef WC_CONVERT_ARGS
 
 // Sample slots beyond the real rows (problems with fewer bins than sample columns): zero
 // rows that can never be candidates.
@@ -2516,22 +2615,50 @@ int wc_newref_prepare_dev(wc_ctx *ctx, void *stream_, const double *corrected, i
     }
 
     double *mean2 = st.col_mean.as<double>();
-    {
+    if (n_samples <= FUSED_MAX_SAMPLES) {
+        // one launch.  The smallest norm of a clamped row lives in one of two slots, m2[1] and m2[2]: the fused kernel
+        // takes minima into one from its first workgroup on, so it cannot reset that one itself; it resets the OTHER,
+        // which no kernel of this job reads, for the prepare after this one.  bad_spare_clean says that it has; a
+        // prepare that does not find it (the first of a context) sets its slot from the host.
+        const int slot = 1 - st.bad_slot;
+        int *bad = st.m2.as<int>() + 1 + slot, *spare = st.m2.as<int>() + 1 + st.bad_slot;
+        if (!st.bad_spare_clean) WC_HIP(hipMemsetD32Async((hipDeviceptr_t)bad, 0x7F800000, 1, stream));
+        // the sampled rows: every fourth of the 128 strided rows k_col_centre takes (a row that is none of those is
+        // none of these); with fewer than 128 bins, FUSED_CENTRE_ROWS of them evenly
+        const int64_t n_crows = std::min<int64_t>(n_bins, FUSED_CENTRE_ROWS);
+        const int64_t crow_step = n_bins >= 128 ? (128 / FUSED_CENTRE_ROWS) * (n_bins / 128) : n_bins / n_crows;
+        hipLaunchKernelGGL((k_prepare_fused<FUSED_CENTRE_ROWS, FUSED_THREADS>),
+                           dim3((unsigned)(st.bins_pad / (FUSED_THREADS / 32))), dim3(FUSED_THREADS),
+                           0, stream, corrected, n_bins, n_samples, st.bins_pad, (const double *)nullptr,
+                           (double)st.beta, st.tau, st.chrom_off_dev.as<int64_t>(), n_chrom,
+                           st.a16.as<unsigned short>(), st.k_pad16, st.norm_lo.as<float>(), st.norm_hi.as<float>(),
+                           st.chrom_of_row.as<int>(), st.chrom_range.as<int2>(),
+                           (const int *)st.sample_slot.as<int>(), st.s16.as<unsigned short>(),
+                           st.s_norm_lo.as<float>(), st.s_chrom.as<int>(), st.s_range.as<int2>(), st.thr.as<float>(),
+                           st.cnt.as<int>(), st.stats.as<int>(), st.x64_pad ? st.x64.as<double>() : (double *)nullptr,
+                           st.s_pad, st.m2.as<float>(), bad, st.fb_count.as<int>(), 4,
+                           st.cand_word.as<unsigned int>(), st.index_bits, mean2, n_crows, crow_step, spare);
+        WC_HIP(hipGetLastError());
+        st.bad_slot = slot;
+        st.bad_spare_clean = true;
+    } else {
+        // more samples than the fused kernel holds per workgroup: the centres first, in a launch of their own
+        // (k_col_centre resets the slot in use itself; the spare one stays as it is)
         int64_t n_rows = std::min<int64_t>(n_bins, 128);
         int64_t row_step = n_bins / n_rows;
+        int *bad = st.m2.as<int>() + 1 + st.bad_slot;
         hipLaunchKernelGGL(k_col_centre, dim3((unsigned)((n_samples + 63) / 64)), dim3(1024), 0, stream, corrected,
-                           n_bins, n_samples, n_rows, row_step, mean2, st.m2.as<int>() + 1);
+                           n_bins, n_samples, n_rows, row_step, mean2, bad);
+        hipLaunchKernelGGL(k_convert, dim3((unsigned)(st.bins_pad / 8)), dim3(256), 0, stream, corrected, n_bins,
+                           n_samples, st.bins_pad, (const double *)mean2, (double)st.beta, st.tau,
+                           st.chrom_off_dev.as<int64_t>(), n_chrom, st.a16.as<unsigned short>(),
+                           st.k_pad16, st.norm_lo.as<float>(), st.norm_hi.as<float>(), st.chrom_of_row.as<int>(),
+                           st.chrom_range.as<int2>(), (const int *)st.sample_slot.as<int>(),
+                           st.s16.as<unsigned short>(), st.s_norm_lo.as<float>(), st.s_chrom.as<int>(),
+                           st.s_range.as<int2>(), st.thr.as<float>(), st.cnt.as<int>(), st.stats.as<int>(),
+                           st.x64_pad ? st.x64.as<double>() : (double *)nullptr, st.s_pad, st.m2.as<float>(),
+                           bad, st.fb_count.as<int>(), 4, st.cand_word.as<unsigned int>(), st.index_bits);
     }
-
-    hipLaunchKernelGGL(k_convert, dim3((unsigned)(st.bins_pad / 8)), dim3(256), 0, stream, corrected, n_bins,
-                       n_samples, st.bins_pad, (const double *)mean2, (double)st.beta, st.tau,
-                       st.chrom_off_dev.as<int64_t>(), n_chrom, st.a16.as<unsigned short>(),
-                       st.k_pad16, st.norm_lo.as<float>(), st.norm_hi.as<float>(), st.chrom_of_row.as<int>(),
-                       st.chrom_range.as<int2>(), (const int *)st.sample_slot.as<int>(),
-                       st.s16.as<unsigned short>(), st.s_norm_lo.as<float>(), st.s_chrom.as<int>(),
-                       st.s_range.as<int2>(), st.thr.as<float>(), st.cnt.as<int>(), st.stats.as<int>(),
-                       st.x64_pad ? st.x64.as<double>() : (double *)nullptr, st.s_pad, st.m2.as<float>(),
-                       st.m2.as<int>() + 1, st.fb_count.as<int>(), 4, st.cand_word.as<unsigned int>(), st.index_bits);
     st.fb_dirty = false;
     if (M > n_bins)
         hipLaunchKernelGGL(k_pad_samples, dim3((unsigned)(M - n_bins)), dim3(256), 0, stream, st.k_pad16, n_bins,
@@ -2756,7 +2883,7 @@ static void finish_args(NewrefState &st, int64_t row_begin, int64_t row_end, int
     a.dist_out = dist_out;
     a.fb_rows = st.fb_rows.as<int>();
     a.fb_count = st.fb_count.as<int>();
-    a.bad_norm = st.m2.as<float>() + 1;
+    a.bad_norm = st.m2.as<float>() + 1 + st.bad_slot;
     a.row_stat = st.stats.as<int>();
     a.sum_order = st.sum_order;
     a.lone_mask = 0ull;
