@@ -933,6 +933,55 @@ int wc_sensitivity_batch_dev(wc_ctx *ctx, void *stream, const wc_reference *ref,
                              int min_ref_bins, int repeats, double min_effect, const int32_t *chromosomes_host, int n_sel, int max_calls,
                              int32_t *rec_i, double *rec_f, double *calls, int32_t *n_calls);
 
+/* ---- sensitivity: reproducible binomial draws on the device ---------------------------------------------
+ * The generator is Philox4x32-10 (Random123: multipliers 0xD2511F53, 0xCD9E8D57, key increments 0x9E3779B9, 0xBB67AE85, ten
+ *   rounds) under the key (seed low 32 bits, seed high 32 bits).  B(c, f), c >= 0 reads and f parts per million
+ *   (0 .. 1 000 000): read r (0 <= r < c) is kept when its 32-bit word, as 64 bits, is below T = (f << 32) div 1 000 000;
+ *   B counts the kept reads (f = 1 000 000 keeps all, f = 0 none).  Read r takes word r & 3 of the block with counter
+ *   (c0 = bin within its chromosome, c1 = chromosome (1-based) | tag << 16, c2 = r >> 2, c3 = row id).  Tag 1 is thinning,
+ *   tag 2 the spike.  The counter names chromosome and bin, never a flat index or a batch position.
+ * wc_philox4x32_host (no GPU needed): out [n, 4] = the block of counters [n, 4] under keys [n, 2], all uint32 HOST.
+ * wc_philox4x32: the same by the device function, through a kernel; HOST pointers, synchronising, n >= 1.
+ * wc_philox_spin_dev (a measuring aid): every one of `lanes` lanes (a multiple of 256, at most 2^30) runs `blocks` (at most
+ *   2^24) blocks over registers and stores the exclusive-or of their words to out [lanes] uint32 (DEVICE); enqueued on
+ *   `stream`.  The rate of the rounds with no memory in the loop: what the thinning kernel's rate is held against.
+ * wc_thin_counts_dev: out [n_keep, n_base, n_total] int32 (DEVICE) of base [n_base, n_total] int32 (DEVICE): depth d holds
+ *   B(c, keep_ppm[d]) with tag 1 and row id b in every bin of base row b; counts below 0 are copied.  The depth is NOT in
+ *   the counter: all depths of a base row use the same words, so a bin's count never rises as keep_ppm falls, and a
+ *   depth of 1 000 000 is a copy.  Checked on the host first, the first bad argument named (WC_E_ARG): n_base >= 1,
+ *   1 .. WC_MAX_CHROM (64) chromosomes of >= 0 bins and fewer than 2^31 - 8 in a row, n_keep 1 .. 8, every keep_ppm
+ *   1 .. 1 000 000 (HOST int32).  A bin with more than 2^24 reads is refused with WC_E_LIMIT, the base row and the flat bin
+ *   named and NOTHING written to out: a kernel looks for one first and the call waits on `stream` for its status word
+ *   (the call's one wait); the thinning itself is enqueued and not waited for.  base and out must not overlap.
+ * wc_thin_counts: the same from HOST pointers, synchronising.
+ * wc_thin_wave_cutoff: the reads from which the thinning kernel's wave takes a bin together instead of leaving it to its
+ *   lane (for tests that stand on either side of it; the result does not depend on which form ran).
+ * wc_spike_counts_ex_dev / wc_spike_counts_ex: wc_spike_counts_dev / wc_spike_counts with the rule chosen.  draw == 0: the
+ *   deterministic rule above, bit for bit (seed and trial0 are not looked at beyond their check).  draw == 1: the binomial
+ *   spike: with m = 1 000 000 + ppm, whole = m div 1 000 000 and frac = m mod 1 000 000, a count c >= 0 inside the span
+ *   becomes min(2^31 - 1, c * whole + B(c, frac)) with tag 2 and row id trial0 + i for plan row i, so a plan cut into
+ *   batches gives the uncut plan's rows when every batch passes its global offset.  Its expectation is the deterministic
+ *   rule's value, and a ppm that is a multiple of 1 000 000 gives that rule's bits.  WC_E_ARG for draw outside {0, 1},
+ *   trial0 < 0 or trial0 + n_trials > 2^32.  A span bin costs ceil(c / 4) blocks spread over a wave.
+ * wc_sensitivity_batch_ex_dev: wc_sensitivity_batch_dev likewise.  The first names call these with draw = 0.          */
+int wc_philox4x32_host(const uint32_t *counters, const uint32_t *keys, int64_t n, uint32_t *out);
+int wc_philox4x32(wc_ctx *ctx, const uint32_t *counters, const uint32_t *keys, int64_t n, uint32_t *out);
+int wc_philox_spin_dev(wc_ctx *ctx, void *stream, int64_t lanes, int64_t blocks, uint64_t seed, uint32_t *out);
+int wc_thin_counts_dev(wc_ctx *ctx, void *stream, const int32_t *base, int64_t n_base, const int64_t *chrom_sizes_host, int n_chrom,
+                       const int32_t *keep_ppm_host, int n_keep, uint64_t seed, int32_t *out);
+int wc_thin_counts(wc_ctx *ctx, const int32_t *base, int64_t n_base, const int64_t *chrom_sizes, int n_chrom, const int32_t *keep_ppm, int n_keep,
+                   uint64_t seed, int32_t *out);
+int wc_thin_wave_cutoff(void);
+int wc_spike_counts_ex_dev(wc_ctx *ctx, void *stream, const int32_t *base, int64_t n_base, const int64_t *chrom_sizes_host, int n_chrom,
+                           const int32_t *plan_host, int64_t n_trials, int draw, uint64_t seed, int64_t trial0, int32_t *out, int64_t *saturated);
+int wc_spike_counts_ex(wc_ctx *ctx, const int32_t *base, int64_t n_base, const int64_t *chrom_sizes, int n_chrom, const int32_t *plan,
+                       int64_t n_trials, int draw, uint64_t seed, int64_t trial0, int32_t *out, int64_t *saturated);
+int wc_sensitivity_batch_ex_dev(wc_ctx *ctx, void *stream, const wc_reference *ref, const int32_t *base, int64_t n_base,
+                                const int64_t *chrom_sizes_host, int n_chrom, const int32_t *plan_host, int64_t n_trials, int draw, uint64_t seed,
+                                int64_t trial0, double threshold, int min_ref_bins, int repeats, double min_effect,
+                                const int32_t *chromosomes_host, int n_sel, int max_calls, int32_t *rec_i, double *rec_f, double *calls,
+                                int32_t *n_calls);
+
 #ifdef __cplusplus
 }
 #endif

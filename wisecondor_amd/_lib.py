@@ -169,6 +169,16 @@ SIGNATURES = {
     "wc_spike_score": (_i32, [_vp, _vp, _i64, _vp, _vp, _i32, _vp, _vp]),
     "wc_sensitivity_batch_dev": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _i32, _vp, _i64, _dbl, _i32, _i32, _dbl, _vp, _i32, _i32,
                                         _vp, _vp, _vp, _vp]),
+    "wc_philox4x32_host": (_i32, [_vp, _vp, _i64, _vp]),
+    "wc_philox4x32": (_i32, [_vp, _vp, _vp, _i64, _vp]),
+    "wc_philox_spin_dev": (_i32, [_vp, _vp, _i64, _i64, _c.c_uint64, _vp]),
+    "wc_thin_counts_dev": (_i32, [_vp, _vp, _vp, _i64, _vp, _i32, _vp, _i32, _c.c_uint64, _vp]),
+    "wc_thin_counts": (_i32, [_vp, _vp, _i64, _vp, _i32, _vp, _i32, _c.c_uint64, _vp]),
+    "wc_thin_wave_cutoff": (_i32, []),
+    "wc_spike_counts_ex_dev": (_i32, [_vp, _vp, _vp, _i64, _vp, _i32, _vp, _i64, _i32, _c.c_uint64, _i64, _vp, _vp]),
+    "wc_spike_counts_ex": (_i32, [_vp, _vp, _i64, _vp, _i32, _vp, _i64, _i32, _c.c_uint64, _i64, _vp, _vp]),
+    "wc_sensitivity_batch_ex_dev": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _i32, _vp, _i64, _i32, _c.c_uint64, _i64, _dbl, _i32, _i32, _dbl,
+                                           _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
 }
 
 SUM_PAIRWISE = 0

@@ -15,23 +15,17 @@
 //                  matches when its chromosome is the trial's, its z has the effect's sign and it overlaps the span by a bin
 //                  at least.  Counts and sums by a wave reduction, the best call (largest overlap, earliest row) by an
 //                  arg-max; lane 0 copies that row's doubles.  Sums are kept in 64 bits and stored clipped to 2^31 - 1.
-// Nothing synchronises inside a workgroup and no kernel uses LDS.
+// Nothing synchronises inside a workgroup and no kernel uses LDS.  The host's half (checked rows, upload, launches) is
+// declared in spike.h: draw.hip, which holds the binomial spike and the _ex entry points, calls it too.
 #include <limits.h>
 
-#include "ctx.h"
+#include "spike.h"
 
 namespace {
 
 const int SP_T = 256;                   // lanes per workgroup
 const int SP_U = 4;                     // quads per lane in k_spike
 const int SP_PPM_MIN = -1000000, SP_PPM_MAX = 100000000;
-
-struct SpRow {                          // 32 bytes: a checked plan row as the kernels read it
-    long long src;                      // the base row's first element
-    int lo, hi;                         // the span as flat bins of a row, hi exclusive (lo == hi: a control trial)
-    int ppm, chrom, first, bins;        // chrom 1-based
-};
-static_assert(sizeof(SpRow) == 32, "a plan row is two 16-byte loads");
 
 __device__ __forceinline__ int sp_value(int c, int ppm, int &clipped) {
     if (c < 0) return c;
@@ -145,7 +139,9 @@ __global__ __launch_bounds__(SP_T) void k_spike_score(const SpRow *__restrict__ 
     rf[1] = have ? b[4] : (double)NAN;
 }
 
-// ---- the host's half ----------------------------------------------------------------------------------------------------
+}  // namespace
+
+// ---- the host's half (spike.h: draw.hip calls it too) -------------------------------------------------------------------
 // every plan row checked (the first bad one named) and turned into a SpRow; chrom_sizes == NULL: the score's checks alone
 int sp_rows(const char *who, const int32_t *plan, int64_t n_trials, int64_t n_base, const int64_t *chrom_sizes, int n_chrom,
             std::vector<SpRow> &rows, int64_t *n_total_out) {
@@ -207,14 +203,14 @@ int sp_upload(wc_ctx *ctx, hipStream_t stream, const std::vector<SpRow> &rows) {
 }
 
 int sp_spike_launch(wc_ctx *ctx, hipStream_t stream, const int32_t *base, int64_t n_total, int64_t n_trials, int32_t *out,
-                    unsigned long long *saturated_dev) {
+                    unsigned long long *saturated_dev, size_t slot) {
     WC_CHECK(((uintptr_t)base & 3) == 0 && ((uintptr_t)out & 3) == 0, WC_E_ARG, "spike: counts not aligned to four bytes");
     WC_CHECK(n_trials <= INT_MAX, WC_E_LIMIT, "spike: more than 2^31 - 1 trials per call");
     if (saturated_dev) WC_HIP(hipMemsetAsync(saturated_dev, 0, sizeof(unsigned long long), stream));
     const int64_t quads = n_total / 4 + 2;
     const dim3 grid((unsigned)n_trials, (unsigned)((quads + SP_T * SP_U - 1) / (SP_T * SP_U)));
     hipLaunchKernelGGL(k_spike, grid, dim3(SP_T), 0, stream, (const int *)base, (long long)n_total,
-                       (const SpRow *)ctx->sp_plan.as<SpRow>(), (long long)n_trials, (int *)out, (int)(((uintptr_t)out >> 2) & 3),
+                       (const SpRow *)ctx->sp_plan.as<SpRow>() + slot, (long long)n_trials, (int *)out, (int)(((uintptr_t)out >> 2) & 3),
                        saturated_dev);
     WC_HIP(hipGetLastError());
     return WC_OK;
@@ -230,43 +226,17 @@ int sp_score_launch(wc_ctx *ctx, hipStream_t stream, int64_t n_trials, const dou
     return WC_OK;
 }
 
-}  // namespace
-
 extern "C" {
 
-int wc_spike_counts_dev(wc_ctx *ctx, void *stream_, const int32_t *base, int64_t n_base, const int64_t *chrom_sizes_host, int n_chrom,
+// the deterministic rule under its first names: the _ex entry points (draw.hip) with draw = 0
+int wc_spike_counts_dev(wc_ctx *ctx, void *stream, const int32_t *base, int64_t n_base, const int64_t *chrom_sizes_host, int n_chrom,
                         const int32_t *plan_host, int64_t n_trials, int32_t *out, int64_t *saturated) {
-    WC_CHECK(ctx && base && out && chrom_sizes_host, WC_E_ARG, "spike: NULL argument");
-    hipStream_t stream = (hipStream_t)stream_;
-    std::vector<SpRow> rows;
-    int64_t n_total = 0;
-    int rc;
-    if ((rc = sp_rows("spike", plan_host, n_trials, n_base, chrom_sizes_host, n_chrom, rows, &n_total))) return rc;
-    WC_HIP(hipSetDevice(ctx->device));
-    if ((rc = sp_upload(ctx, stream, rows))) return rc;
-    return sp_spike_launch(ctx, stream, base, n_total, n_trials, out, (unsigned long long *)saturated);
+    return wc_spike_counts_ex_dev(ctx, stream, base, n_base, chrom_sizes_host, n_chrom, plan_host, n_trials, 0, 0, 0, out, saturated);
 }
 
 int wc_spike_counts(wc_ctx *ctx, const int32_t *base, int64_t n_base, const int64_t *chrom_sizes, int n_chrom, const int32_t *plan,
                     int64_t n_trials, int32_t *out, int64_t *saturated) {
-    WC_CHECK(ctx && base && out && chrom_sizes, WC_E_ARG, "spike: NULL argument");
-    std::vector<SpRow> rows;
-    int64_t n_total = 0;
-    int rc;
-    if ((rc = sp_rows("spike", plan, n_trials, n_base, chrom_sizes, n_chrom, rows, &n_total))) return rc;
-    WC_HIP(hipSetDevice(ctx->device));
-    const size_t in_bytes = sizeof(int32_t) * (size_t)(n_base * n_total), out_bytes = sizeof(int32_t) * (size_t)(n_trials * n_total);
-    if ((rc = ctx->tmp_a.reserve(in_bytes)) || (rc = ctx->tmp_b.reserve(out_bytes)) || (rc = ctx->tmp_c.reserve(8)) ||
-        (rc = sp_upload(ctx, nullptr, rows)))
-        return rc;
-    WC_HIP(hipMemcpy(ctx->tmp_a.p, base, in_bytes, hipMemcpyHostToDevice));
-    if ((rc = sp_spike_launch(ctx, nullptr, ctx->tmp_a.as<int32_t>(), n_total, n_trials, ctx->tmp_b.as<int32_t>(),
-                              ctx->tmp_c.as<unsigned long long>())))
-        return rc;
-    WC_HIP(hipDeviceSynchronize());
-    WC_HIP(hipMemcpy(out, ctx->tmp_b.p, out_bytes, hipMemcpyDeviceToHost));
-    if (saturated) WC_HIP(hipMemcpy(saturated, ctx->tmp_c.p, 8, hipMemcpyDeviceToHost));
-    return WC_OK;
+    return wc_spike_counts_ex(ctx, base, n_base, chrom_sizes, n_chrom, plan, n_trials, 0, 0, 0, out, saturated);
 }
 
 int wc_spike_score_dev(wc_ctx *ctx, void *stream_, const int32_t *plan_host, int64_t n_trials, const double *calls, const int32_t *n_calls,
@@ -305,42 +275,12 @@ int wc_spike_score(wc_ctx *ctx, const int32_t *plan, int64_t n_trials, const dou
     return WC_OK;
 }
 
-int wc_sensitivity_batch_dev(wc_ctx *ctx, void *stream_, const wc_reference *ref, const int32_t *base, int64_t n_base,
+int wc_sensitivity_batch_dev(wc_ctx *ctx, void *stream, const wc_reference *ref, const int32_t *base, int64_t n_base,
                              const int64_t *chrom_sizes_host, int n_chrom, const int32_t *plan_host, int64_t n_trials, double threshold,
                              int min_ref_bins, int repeats, double min_effect, const int32_t *chromosomes_host, int n_sel, int max_calls,
                              int32_t *rec_i, double *rec_f, double *calls, int32_t *n_calls) {
-    WC_CHECK(ctx && ref && base && chrom_sizes_host && rec_i && rec_f, WC_E_ARG, "sensitivity: NULL argument");
-    WC_CHECK(max_calls >= 1 && n_sel >= 0, WC_E_ARG, "sensitivity: max_calls = %d, %d chromosomes selected", max_calls, n_sel);
-    WC_CHECK(n_trials <= 60000 && n_trials * std::max(n_sel, 1) <= 60000, WC_E_LIMIT,
-             "sensitivity: trials x chromosomes = %lld exceeds 60000 per call; split the plan", (long long)(n_trials * std::max(n_sel, 1)));
-    hipStream_t stream = (hipStream_t)stream_;
-    std::vector<SpRow> rows;
-    int64_t n_total = 0;
-    int rc;
-    if ((rc = sp_rows("sensitivity", plan_host, n_trials, n_base, chrom_sizes_host, n_chrom, rows, &n_total))) return rc;
-    WC_HIP(hipSetDevice(ctx->device));
-    TestState &ts = ctx->ts;
-    // the spiked rows and everything the test writes besides the calls live in the workspaces of the host-array test
-    if ((rc = ts.counts.reserve(sizeof(int32_t) * (size_t)(n_trials * n_total))) ||
-        (rc = ts.res_z.reserve(sizeof(double) * (size_t)(n_trials * n_total))) ||
-        (rc = ts.res_r.reserve(sizeof(double) * (size_t)(n_trials * n_total))) ||
-        (rc = ts.cwz.reserve(sizeof(double) * (size_t)(n_trials * std::max(n_sel, 1)))) || (rc = ts.n.reserve(sizeof(double) * (size_t)n_trials)))
-        return rc;
-    if (!calls) {
-        if ((rc = ts.calls.reserve(sizeof(double) * (size_t)n_trials * max_calls * 5))) return rc;
-        calls = ts.calls.as<double>();
-    }
-    if (!n_calls) {
-        if ((rc = ts.n_calls.reserve(sizeof(int32_t) * (size_t)n_trials))) return rc;
-        n_calls = ts.n_calls.as<int32_t>();
-    }
-    if ((rc = sp_upload(ctx, stream, rows)) || (rc = sp_spike_launch(ctx, stream, base, n_total, n_trials, ts.counts.as<int32_t>(), nullptr)))
-        return rc;
-    if ((rc = wc_test_batch_dev(ctx, stream_, ref, ts.counts.as<int32_t>(), n_trials, threshold, min_ref_bins, repeats, min_effect,
-                                chromosomes_host, n_sel, max_calls, ts.res_z.as<double>(), ts.res_r.as<double>(), ts.cwz.as<double>(), calls,
-                                n_calls, ts.n.as<double>())))
-        return rc;
-    return sp_score_launch(ctx, stream, n_trials, calls, n_calls, max_calls, rec_i, rec_f);
+    return wc_sensitivity_batch_ex_dev(ctx, stream, ref, base, n_base, chrom_sizes_host, n_chrom, plan_host, n_trials, 0, 0, 0, threshold,
+                                       min_ref_bins, repeats, min_effect, chromosomes_host, n_sel, max_calls, rec_i, rec_f, calls, n_calls);
 }
 
 }  // extern "C"

@@ -15,7 +15,8 @@ sub-command (the same panels as vector PDF pages, the content stream written on 
 sub-command (result files to lossless JSON, the numbers' digits made on the GPU) and the `exporttracks` sub-command
 (result files to bedGraph tracks and BED calls for genome browsers, the text and its BGZF blocks made on the GPU) and
 the `sensitivity` sub-command (aberrations planted into healthy samples on the GPU, tested and judged there: how often
-a reference finds a span of a given length and effect).
+a reference finds a span of a given length and effect, at the samples' read depth or thinned to fractions of it) and
+the `downsample` sub-command (a converted sample thinned to a fraction of its reads on the GPU).
 `plot` itself stays refused: its default output is a matplotlib PDF, which this build does not make.
 """
 import argparse
@@ -644,7 +645,10 @@ def toolSensitivity(args):
     are planted at -trials random places into every healthy sample with every effect, each spiked copy is tested as
     `test` tests a sample, and every trial's calls are judged against what was planted, all on the GPU
     (wt.sensitivity_batch).  Writes out.npz (the plan, a record per trial, the table) and out.tsv (the table), and prints
-    the table.  Everything that can be refused is refused before the GPU is touched: exit status 2."""
+    the table.  -depths thins the samples on the GPU to every fraction of their reads and repeats the grid per depth
+    (the table gains a leading depth_ppm column and a control line per depth); -draw plants Binomial spikes instead of
+    the rounded product; -seed keys both.  Everything that can be refused is refused before the GPU is touched: exit
+    status 2."""
     from . import ingest, sensitivity
     try:
         stored = _open_npz(args.reference)
@@ -656,8 +660,10 @@ def toolSensitivity(args):
             own = _open_npz(path)['arguments'].item()['binsize']
             if own == 0 or binsize < own or binsize % own > 0:
                 raise ValueError('%s was binned at %s, which does not scale to the reference\'s %s' % (path, own, binsize))
+        depths_ppm = sensitivity.parseDepths(args.depths) if hasattr(args, 'depths') else None
+        draw = bool(getattr(args, 'draw', False))
         plan = sensitivity.makePlan(stored, len(args.infiles), lengths_bins, effects_ppm, args.trials,
-                                    chromosomes=list(args.chromosomes), seed=args.seed)
+                                    chromosomes=list(args.chromosomes), seed=args.seed, n_depths=len(depths_ppm) if depths_ppm else 1)
     except ValueError as exc:
         print('ERROR:', exc)
         sys.exit(2)
@@ -668,18 +674,74 @@ def toolSensitivity(args):
     began = time.time()
     rec_i, rec_f = sensitivity.sensitivity_batch(reference, samples, plan, cut, minrefbins=args.minrefbins, repeats=args.repeats,
                                                  chromosomes=list(args.chromosomes), mineffectsize=args.mineffectsize,
-                                                 batch=args.batch)
+                                                 batch=args.batch, depths_ppm=depths_ppm, draw=draw, seed=args.seed)
     print('%d trials took %.3f s' % (len(plan), time.time() - began))
-    table = sensitivity.sensitivityTable(plan, rec_i, rec_f, lengths_bins, effects_ppm, minoverlap=args.minoverlap)
+    table = sensitivity.sensitivityTable(plan, rec_i, rec_f, lengths_bins, effects_ppm, minoverlap=args.minoverlap,
+                                         depths_ppm=depths_ppm, n_samples=len(args.infiles))
     text = sensitivity.tableText(table)
     npz_path, tsv_path = sensitivityOutputs(args.outfile)
+    # (depths_ppm and draw are members only when one of the two options is given: without them the file is what it always was)
+    extra = dict(depths_ppm=np.array(depths_ppm if depths_ppm else [1000000], dtype=np.int64),
+                 draw=np.bool_(draw)) if depths_ppm or draw else {}
     write_npz(npz_path, arguments=vars(args), runtime=getRuntime(), binsize=binsize, threshold_z=cut,
               samples=np.array([str(p) for p in args.infiles]), lengths_bins=np.array(lengths_bins, dtype=np.int64),
-              effects_ppm=np.array(effects_ppm, dtype=np.int64), plan=plan, rec_i=rec_i, rec_f=rec_f, table=table)
+              effects_ppm=np.array(effects_ppm, dtype=np.int64), plan=plan, rec_i=rec_i, rec_f=rec_f, table=table, **extra)
     with open(tsv_path, 'w') as handle:
         handle.write(text)
     print(text, end='')
     reference.close()
+
+
+# ------------------------------------------------------------------ downsample ----
+def toolDownsample(args):
+    """`downsample in.npz out.npz (-fraction F | -reads N)` (build-only): a converted sample thinned on the GPU to a
+    fraction of its reads, every read kept with probability keep_ppm / 10^6 (sensitivity.thinCounts: chromosome int(key),
+    row id 0, the file's own bin size).  -reads N keeps min(10^6, N * 10^6 // total) ppm: the kept total is a draw around
+    N, not N.  `arguments` are those of the input plus the options given here, `quality` is copied with the kept total
+    under 'downsampled'.  Refusals come before the GPU is touched: exit status 2."""
+    from . import sensitivity
+    try:
+        stored = _open_npz(args.infile)
+        sample = stored['sample'].item()
+        numbers = {}
+        for key in sample:
+            try:
+                numbers[key] = int(key)
+            except ValueError:
+                raise ValueError('chromosome key %r is not a number' % (key,))
+            if not 1 <= numbers[key] <= 64:
+                raise ValueError('chromosome key %r is outside 1 .. 64' % (key,))
+        if not numbers:
+            raise ValueError('%s holds no chromosome' % args.infile)
+        total = int(sum(int(np.asarray(sample[key]).clip(0).sum()) for key in sample))
+        if hasattr(args, 'fraction'):
+            if not 0 < args.fraction <= 1 or int(round(args.fraction * 1e6)) < 1:
+                raise ValueError('-fraction %r is out of range (a fraction in (0, 1] of 1 ppm at least)' % args.fraction)
+            keep_ppm = int(round(args.fraction * 1e6))
+        else:
+            if args.reads < 1 or total < 1:
+                raise ValueError('-reads %d of %d reads' % (args.reads, total))
+            keep_ppm = min(1000000, (args.reads * 1000000) // total)
+            if keep_ppm < 1:
+                raise ValueError('-reads %d of %d reads is less than 1 ppm' % (args.reads, total))
+    except ValueError as exc:
+        print('ERROR:', exc)
+        sys.exit(2)
+    sizes = np.zeros(max(numbers.values()), dtype=np.int64)
+    for key, number in numbers.items():
+        sizes[number - 1] = len(sample[key])
+    offs = np.concatenate([[0], np.cumsum(sizes)])
+    image = np.zeros((1, int(offs[-1])), dtype=np.int32)
+    for key, number in numbers.items():
+        image[0, offs[number - 1]:offs[number]] = sample[key]
+    thinned = sensitivity.thinCounts(image, sizes, [keep_ppm], seed=args.seed)[0, 0]
+    out = {key: thinned[offs[number - 1]:offs[number]].astype(np.asarray(sample[key]).dtype) for key, number in numbers.items()}
+    arguments = dict(stored['arguments'].item())
+    arguments.update({name: value for name, value in vars(args).items() if name in ('fraction', 'reads', 'seed')})
+    quality = dict(stored['quality'].item())
+    quality['downsampled'] = int(thinned.clip(0).sum())
+    write_npz(args.outfile, arguments=arguments, runtime=getRuntime(), sample=out, quality=quality)
+    print('kept %d of %d reads (%d ppm)' % (quality['downsampled'], total, keep_ppm))
 
 
 # ---------------------------------------------------------------------- parser ----
@@ -888,13 +950,30 @@ def buildParser():
                    help='changes in read depth in percent, comma separated, -100 .. 10000 (2.5,5,10,-2.5,-5,-10); a list that '
                         'begins with a negative value is written -effects=-5,5')
     p.add_argument('-trials', type=int, default=20, help='placements per sample and length')
-    p.add_argument('-seed', type=int, default=1, help='seed of the placements')
+    p.add_argument('-seed', type=int, default=1, help='seed of the placements, and the key of the draws of -depths and -draw')
+    # build-only additions; SUPPRESS keeps them out of the namespace (and the `arguments` of out.npz) unless they are given
+    p.add_argument('-depths', type=str, default=argparse.SUPPRESS,
+                   help='fractions of the read depth in (0, 1], comma separated, at most 8 (1,0.5,0.25): the samples are thinned '
+                        'on the GPU to each and the grid runs at every depth')
+    p.add_argument('-draw', action='store_true', default=argparse.SUPPRESS,
+                   help='plant Binomial spikes (a real aberration\'s sampling noise) instead of the rounded product')
     p.add_argument('-minoverlap', type=float, default=0.5,
                    help='a trial counts as detected when its matching calls cover this share of the span')
     p.add_argument('-batch', type=int, default=1024, help='trials per GPU batch')
     for flag, settings in _TEST_OPTIONS:
         p.add_argument(flag, **settings)
     p.set_defaults(func=toolSensitivity)
+
+    p = sub.add_parser('downsample', description='thin a converted sample to a fraction of its reads on the GPU (build-only)')
+    p.add_argument('infile', type=str, help='converted sample (.npz)')
+    p.add_argument('outfile', type=str, help='thinned sample to write (.npz)')
+    how = p.add_mutually_exclusive_group(required=True)
+    how.add_argument('-fraction', type=float, default=argparse.SUPPRESS, help='keep every read with this probability, in (0, 1]')
+    how.add_argument('-reads', type=int, default=argparse.SUPPRESS,
+                     help='keep every read with probability N / (the file\'s reads), in whole ppm: the kept total is a draw around N, '
+                          'not N')
+    p.add_argument('-seed', type=int, default=1, help='key of the draws')
+    p.set_defaults(func=toolDownsample)
     return parser
 
 

@@ -1686,9 +1686,14 @@ def export_tracks_batch(results, only=None, gz=False, nozero=False, prefix='chr'
 # ---------------------------------------------------------------------------
 # sensitivity: thin mirrors of sensitivity.py, which imports this module
 # ---------------------------------------------------------------------------
-def spikeCounts(base, chrom_sizes, plan, device=0):
+def spikeCounts(base, chrom_sizes, plan, device=0, draw=False, seed=1, trial0=0):
     from . import sensitivity
-    return sensitivity.spikeCounts(base, chrom_sizes, plan, device=device)
+    return sensitivity.spikeCounts(base, chrom_sizes, plan, device=device, draw=draw, seed=seed, trial0=trial0)
+
+
+def thinCounts(base, chrom_sizes, keep_ppm, seed=1, device=0):
+    from . import sensitivity
+    return sensitivity.thinCounts(base, chrom_sizes, keep_ppm, seed=seed, device=device)
 
 
 def scoreTrials(plan, calls, n_calls, device=0):
@@ -1696,14 +1701,16 @@ def scoreTrials(plan, calls, n_calls, device=0):
     return sensitivity.scoreTrials(plan, calls, n_calls, device=device)
 
 
-def makePlan(reference, n_samples, lengths_bins, effects_ppm, trials, chromosomes=None, seed=1):
+def makePlan(reference, n_samples, lengths_bins, effects_ppm, trials, chromosomes=None, seed=1, n_depths=1):
     from . import sensitivity
-    return sensitivity.makePlan(reference, n_samples, lengths_bins, effects_ppm, trials, chromosomes=chromosomes, seed=seed)
+    return sensitivity.makePlan(reference, n_samples, lengths_bins, effects_ppm, trials, chromosomes=chromosomes, seed=seed,
+                                n_depths=n_depths)
 
 
-def sensitivityTable(plan, rec_i, rec_f, lengths_bins, effects_ppm, minoverlap=0.5):
+def sensitivityTable(plan, rec_i, rec_f, lengths_bins, effects_ppm, minoverlap=0.5, depths_ppm=None, n_samples=None):
     from . import sensitivity
-    return sensitivity.sensitivityTable(plan, rec_i, rec_f, lengths_bins, effects_ppm, minoverlap=minoverlap)
+    return sensitivity.sensitivityTable(plan, rec_i, rec_f, lengths_bins, effects_ppm, minoverlap=minoverlap, depths_ppm=depths_ppm,
+                                        n_samples=n_samples)
 
 
 def sensitivity_batch(reference, samples, plan, threshold, **options):
