@@ -982,6 +982,49 @@ int wc_sensitivity_batch_ex_dev(wc_ctx *ctx, void *stream, const wc_reference *r
                                 const int32_t *chromosomes_host, int n_sel, int max_calls, int32_t *rec_i, double *rec_f, double *calls,
                                 int32_t *n_calls);
 
+/* ---- crossval: the held-out z-scores of a healthy cohort, judged on the device --------------------------
+ * wc_crossval_stats_dev: Z [n_samples, row_stride] float64 (DEVICE; n_total = sum(chrom_sizes) <= row_stride bins of a row
+ *   are read: the dense layout wc_test_batch_dev leaves), thr and asdef [n_samples] float64 (DEVICE: the per-bin |z| cut
+ *   and the asdef of every sample), calls [n_samples, max_calls, 5] float64 rows [chrom, start, end, z, effect] and n_calls
+ *   [n_samples] int32 (DEVICE; rows at and behind n_calls[i] are not read, n_calls is taken as clipped to 0 .. max_calls).
+ *   chrom_sizes, sel (the selected chromosomes, 1-based, each once) and lengths (the window lengths) are HOST memory.
+ *   With z = Z[i][b], i ascending:
+ *   Classes: a bin is TESTED when z != 0 (so +0.0 and -0.0, the fill of masked and removed bins, are untested and NaN is
+ *     tested), NONFINITE when tested and not finite, else FINITE.
+ *   bins_i [n_total, 6] int32: {tested, nonfinite, over_hi (finite and z >= thr[i]), over_lo (finite and z <= -thr[i]),
+ *     in_gain, in_loss}: the call rows whose [start, end] (inclusive, the chromosome's own bins) covers the bin, a row with
+ *     z > 0 a gain and one with z < 0 a loss.
+ *   bins_f [n_total, 2] float64: {sum z, sum z * z} over the bin's finite samples, added one sample after the other in
+ *     ascending i from 0.0, every product rounded before it is added (no fused multiply-add).
+ *   rec_i [n_samples, 8] int32: {0 (the caller's: the sample's fold), n_calls, tested, nonfinite, over_hi, over_lo,
+ *     call_bins = sum(end - start + 1), rows_skipped}, the sums formed in 64 bits and stored clipped to 2^31 - 1.
+ *   rec_f [n_samples, 4] float64: {asdef[i], thr[i], the largest finite z, the smallest finite z}; the last two are NaN
+ *     when the sample has no finite z.
+ *   Windows: for sample i and selected chromosome c, t = the chromosome's tested values in bin order, n of them.  A row with
+ *     a nonfinite value is skipped and counted in rows_skipped.  Otherwise P[0] = 0, P[j + 1] = P[j] + t[j], sequentially,
+ *     and for every length L and every a in 0 .. n - L: w = (P[a + L] - P[a]) / sqrt((double)L).
+ *   win_n [n_samples, n_lengths] int64: windows per sample and length.
+ *   win_i [n_lengths, 4] int64: {rows (not skipped, with a window of this length at least: n >= L), windows,
+ *     hi (w >= thr[i]), lo (w <= -thr[i])}.
+ *   win_hist [n_lengths, 130] int64: slot 0 for w < -16, slot 129 for w >= 16 or NaN, else 1 + (int)floor((w + 16.0) * 4.0).
+ *   Refused with WC_E_ARG before any output is written: NULL pointers, n_samples < 1, a layout outside 1 .. WC_MAX_CHROM
+ *     chromosomes of fewer than 2^31 - 8 bins in a row, row_stride < n_total, max_calls < 1, n_sel outside 1 .. n_chrom, a
+ *     selected chromosome outside 1 .. n_chrom or named twice, n_lengths outside 1 .. 16, a length < 1 or not above the one
+ *     before it -- and a call row whose chromosome is no whole number in 1 .. n_chrom or whose span is not whole numbers
+ *     0 <= start <= end < the chromosome's bins: a kernel looks for one and the call waits on `stream` for its status word
+ *     (the call's one wait; the first such row is named), so a call row is never clipped silently and never indexed.  The
+ *     rest is enqueued and not waited for.  One call in flight per context.
+ * wc_crossval_stats: the same from HOST pointers, synchronising.                                                          */
+int wc_crossval_stats_dev(wc_ctx *ctx, void *stream, const double *Z, int64_t row_stride, int64_t n_samples,
+                          const int64_t *chrom_sizes_host, int n_chrom, const double *thr, const double *asdef, const double *calls,
+                          const int32_t *n_calls, int max_calls, const int32_t *sel_host, int n_sel, const int32_t *lengths_host,
+                          int n_lengths, int32_t *bins_i, double *bins_f, int32_t *rec_i, double *rec_f, int64_t *win_n, int64_t *win_i,
+                          int64_t *win_hist);
+int wc_crossval_stats(wc_ctx *ctx, const double *Z, int64_t row_stride, int64_t n_samples, const int64_t *chrom_sizes, int n_chrom,
+                      const double *thr, const double *asdef, const double *calls, const int32_t *n_calls, int max_calls, const int32_t *sel,
+                      int n_sel, const int32_t *lengths, int n_lengths, int32_t *bins_i, double *bins_f, int32_t *rec_i, double *rec_f,
+                      int64_t *win_n, int64_t *win_i, int64_t *win_hist);
+
 #ifdef __cplusplus
 }
 #endif

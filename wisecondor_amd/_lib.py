@@ -179,6 +179,10 @@ SIGNATURES = {
     "wc_spike_counts_ex": (_i32, [_vp, _vp, _i64, _vp, _i32, _vp, _i64, _i32, _c.c_uint64, _i64, _vp, _vp]),
     "wc_sensitivity_batch_ex_dev": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _i32, _vp, _i64, _i32, _c.c_uint64, _i64, _dbl, _i32, _i32, _dbl,
                                            _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "wc_crossval_stats_dev": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _i32,
+                                     _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "wc_crossval_stats": (_i32, [_vp, _vp, _i64, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _i32,
+                                 _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 SUM_PAIRWISE = 0

@@ -102,6 +102,7 @@ struct wc_ctx {
     wc::DevBuf js_slots, js_tiles;          // export.hip: the values' decimal digits between the passes; the tiles' sums and offsets
     wc::DevBuf sp_plan;                     // spike.hip: the checked plan rows of the call in flight
     wc::DevBuf dr_tab;                      // draw.hip: the thinning's status word and chromosome offsets
+    wc::DevBuf cx_tab, cx_prefix, cx_rows;  // crossval.hip: the call's tables and status word; the prefix sums P; tested values per row
     // plot.hip: display lists and their counts, the small tables of a call (and the host block they are copied from),
     // the scanline images, the Adler-32 block sums, the status word
     wc::DevBuf pl_list, pl_counts, pl_tab, pl_img, pl_part, pl_status;
@@ -171,7 +172,7 @@ struct wc_ctx {
                 &ts.reg_flag, &ts.rs, &ts.jobs_a, &ts.jobs_b, &ts.job_cnt, &ts.partial, &ts.cbound, &ts.cuts, &ts.job_res, &ts.hot,
                 &ts.cand, &ts.cand_cnt, &ts.seg, &ts.out_val, &ts.out_x, &ts.out_y, &ts.out_n,
                 &ts.whole, &ts.effect, &ts.misc, &ts.misc2, &ts.reduce_tmp, &ts.win_bits, &ts.bit_off, &ts.pairs_a, &ts.pairs_b, &ts.cut_vals, &ts.prof_work, &ts.sd_fail, &ts.walk_hot, &prep.eig_ws,
-                &cv.tab, &cv.tiles, &cv.kpos, &cv.cls, &df_scratch, &df_meta, &js_slots, &js_tiles, &sp_plan, &dr_tab, &pl_list, &pl_counts, &pl_tab, &pl_img, &pl_part, &pl_status};
+                &cv.tab, &cv.tiles, &cv.kpos, &cv.cls, &df_scratch, &df_meta, &js_slots, &js_tiles, &sp_plan, &dr_tab, &cx_tab, &cx_prefix, &cx_rows, &pl_list, &pl_counts, &pl_tab, &pl_img, &pl_part, &pl_status};
     }
 };
 

@@ -16,7 +16,9 @@ sub-command (result files to lossless JSON, the numbers' digits made on the GPU)
 (result files to bedGraph tracks and BED calls for genome browsers, the text and its BGZF blocks made on the GPU) and
 the `sensitivity` sub-command (aberrations planted into healthy samples on the GPU, tested and judged there: how often
 a reference finds a span of a given length and effect, at the samples' read depth or thinned to fractions of it) and
-the `downsample` sub-command (a converted sample thinned to a fraction of its reads on the GPU).
+the `downsample` sub-command (a converted sample thinned to a fraction of its reads on the GPU) and the `crossval`
+sub-command (every healthy sample tested against a reference built without its fold, the held-out z-scores judged on
+the GPU).
 `plot` itself stays refused: its default output is a matplotlib PDF, which this build does not make.
 """
 import argparse
@@ -692,6 +694,84 @@ def toolSensitivity(args):
     reference.close()
 
 
+# -------------------------------------------------------------------- crossval ----
+def crossvalOutputs(outfile):
+    """(out.npz, out_samples.tsv, out_windows.tsv) of the `out` argument (a trailing .npz is taken as part of none)."""
+    stem = outfile[:-4] if outfile.endswith('.npz') else outfile
+    return stem + '.npz', stem + '_samples.tsv', stem + '_windows.tsv'
+
+
+def crossvalPlan(args):
+    """What `crossval` can refuse before the GPU is touched, as ValueError: fewer than 5 files, a bad fold count, bad
+    -windows, no chromosome, bin sizes that do not scale.  Returns (fold_of, window lengths, the bin size the files are
+    read at)."""
+    from . import crossval
+    n = len(args.infiles)
+    if n < 5:
+        raise ValueError('crossval needs 5 healthy samples at least, got %d' % n)
+    fold_of = crossval.foldPlan(n, n if args.loo else args.folds, seed=args.seed)
+    windows = crossval.parseWindows(args.windows)
+    if not args.chromosomes or args.refsize < 1:
+        raise ValueError('crossval needs -refsize >= 1 and at least one chromosome')
+    if args.results is not None:
+        from . import ingest
+        ingest.output_names(args.infiles, args.results)        # two inputs with one leaf name would share a result file
+    own =[_open_npz(path)['arguments'].item()['binsize'] for path in args.infiles]
+    if args.binsize is None:
+        if len(set(float(v) for v in own)) > 1:
+            raise ValueError('the input samples were binned at different sizes %s: give -binsize to merge them to a common size'
+                             % sorted(set(float(v) for v in own)))
+        return fold_of, windows, own[0]
+    for path, size in zip(args.infiles, own):
+        if size == 0 or args.binsize < size or args.binsize % size > 0:
+            raise ValueError('%s was binned at %s, which does not scale to -binsize %s' % (path, size, args.binsize))
+    return fold_of, windows, args.binsize
+
+
+def toolCrossval(args):
+    """`crossval healthy... out [-folds N | -loo]` (build-only): every healthy sample is tested against a reference built
+    from the samples of the other folds, as `newref` builds and `test` tests, and the held-out z-scores of the whole cohort
+    are judged on the GPU (crossval.crossval_batch).  Writes out.npz (every array of the run), out_samples.tsv (a line per
+    sample: the samples with calls are what to look at) and out_windows.tsv (a line per window length: how often
+    sum(z) / sqrt(L) of healthy held-out data passes the threshold, and how wide it is spread); with -results DIR also a
+    `test`-format file per held-out sample, DIR/<stem>_test.npz.  Everything that can be refused is refused before the GPU
+    is touched: exit status 2."""
+    from . import crossval
+    try:
+        fold_of, windows, binsize = crossvalPlan(args)
+    except ValueError as exc:
+        print('ERROR:', exc)
+        sys.exit(2)
+    from . import ingest
+    counts, chrom_sizes, _ = ingest.load_counts(args.infiles, args.binsize, threads=min(16, os.cpu_count() or 1), verbose=True)
+    began = time.time()
+    result = crossval.crossval_batch(counts, chrom_sizes, fold_of, binsize, refsize=args.refsize, multitest=args.multitest,
+                                     minzscore=args.minzscore, minrefbins=args.minrefbins, repeats=args.repeats,
+                                     chromosomes=list(args.chromosomes), mineffectsize=args.mineffectsize, windows=windows,
+                                     keep_results=args.results is not None)
+    print('%d folds over %d samples took %.3f s' % (int(fold_of.max()) + 1, len(fold_of), time.time() - began))
+    npz_path, samples_path, windows_path = crossvalOutputs(args.outfile)
+    table = crossval.windowsTable(windows, result['win_n'], result['win_i'], result['win_hist'], result['rec_f'][:, 1])
+    stored = {key: value for key, value in result.items() if key not in ('Z', 'R', 'results_cwz')}
+    write_npz(npz_path, arguments=vars(args), runtime=getRuntime(), binsize=binsize, samples=np.array([str(p) for p in args.infiles]),
+              chromosome_sizes=np.array(chrom_sizes, dtype=np.int64), windows=np.array(windows, dtype=np.int64), **stored)
+    with open(samples_path, 'w') as handle:
+        handle.write(crossval.samplesText([os.path.basename(str(p)) for p in args.infiles], result['rec_i'], result['rec_f']))
+    text = crossval.windowsText(table)
+    with open(windows_path, 'w') as handle:
+        handle.write(text)
+    print(text, end='')
+    with_calls = np.flatnonzero(result['rec_i'][:, 1] > 0)
+    print('%d of %d held-out samples carry a call%s' % (len(with_calls), len(fold_of),
+                                                       ': ' + ', '.join(os.path.basename(str(args.infiles[i])) for i in with_calls)
+                                                       if len(with_calls) else ''))
+    if args.results is not None:
+        os.makedirs(args.results, exist_ok=True)
+        names = ingest.output_names(args.infiles, args.results)
+        for name, fold, held in zip(names, fold_of, crossval.heldOutResults(result, chrom_sizes)):
+            writeTestOutput(name, args, binsize, held, result['threshold'][fold])
+
+
 # ------------------------------------------------------------------ downsample ----
 def toolDownsample(args):
     """`downsample in.npz out.npz (-fraction F | -reads N)` (build-only): a converted sample thinned on the GPU to a
@@ -963,6 +1043,25 @@ def buildParser():
     for flag, settings in _TEST_OPTIONS:
         p.add_argument(flag, **settings)
     p.set_defaults(func=toolSensitivity)
+
+    p = sub.add_parser('crossval', description='test every healthy sample against a reference built without its fold and judge the '
+                                               'held-out z-scores on the GPU (build-only)')
+    p.add_argument('infiles', type=str, nargs='+', help='converted healthy samples (.npz), 5 at least')
+    p.add_argument('outfile', type=str, help='out: out.npz, out_samples.tsv and out_windows.tsv are written')
+    how = p.add_mutually_exclusive_group()
+    how.add_argument('-folds', type=int, default=10, help='folds of the cohort (default 10)')
+    how.add_argument('-loo', action='store_true', help='leave one out: as many folds as files')
+    p.add_argument('-seed', type=int, default=1, help='seed of the fold plan')
+    p.add_argument('-refsize', type=int, default=100, help='reference bins kept per target bin')
+    p.add_argument('-binsize', type=int, default=None,
+                   help='merge sample bins to this size first (a multiple of their own size)')
+    p.add_argument('-windows', type=str, default='1,2,5,10,20,50,100',
+                   help='window lengths in bins, comma separated, ascending, at most 16')
+    p.add_argument('-results', type=str, default=None,
+                   help='directory receiving <sample>_test.npz, the held-out result of every sample in the format of test')
+    for flag, settings in _TEST_OPTIONS:
+        p.add_argument(flag, **settings)
+    p.set_defaults(func=toolCrossval)
 
     p = sub.add_parser('downsample', description='thin a converted sample to a fraction of its reads on the GPU (build-only)')
     p.add_argument('infile', type=str, help='converted sample (.npz)')
