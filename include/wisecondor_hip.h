@@ -219,13 +219,21 @@ int wc_write_test_results(int n_files, int n_threads, const char *const *out_pat
  * outputs), _finish takes such pairs -- from _eig or from the caller's own LAPACK on gram_out.
  * wc_sym_eigh_leading_dev is the same solver on any device-resident symmetric float64 matrix
  * (left untouched).
+ * What _gram leaves for _eig and _finish* lives in workspaces of the prep step's own: any other entry
+ * point may run on the context between the steps, and _finish* may be called any number of times (with
+ * other pairs or component counts too) after one _gram; each computes from that _gram's data.  Only the
+ * next _gram (or wc_newref_prep, which calls it) replaces the state.  Before the first _gram of a
+ * context, or after one that failed, _eig and _finish* return WC_E_ARG ("wc_newref_prep_gram has not
+ * run") and write no output.
  */
+/* Leaves the state described above; an error return leaves none (_eig / _finish* then refuse). */
 int wc_newref_prep_gram(wc_ctx *ctx, const int32_t *counts, int64_t n_samples, int64_t n_total_bins,
                         const int64_t *chromosome_bins, int n_chrom, uint8_t *mask_out,
                         int64_t *masked_chrom_bins_out, int64_t *n_masked_out, double *gram_out);
 int wc_newref_prep_eig(wc_ctx *ctx, int n_pairs, double *eigvals_out, double *eigvecs_out);
 int wc_sym_eigh_leading_dev(wc_ctx *ctx, const double *matrix_dev, int64_t n, int n_pairs, double *eigvals_out,
                             double *eigvecs_out);
+/* Reads the state of the context's last wc_newref_prep_gram, whatever ran in between; repeatable. */
 int wc_newref_prep_finish(wc_ctx *ctx, int n_comp, const double *eigvecs, const double *eigvals,
                           double *masked_data_out, double *corrected_t_out, double *pca_components_out,
                           double *pca_mean_out);
@@ -233,7 +241,8 @@ int wc_newref_prep_finish(wc_ctx *ctx, int n_comp, const double *eigvecs, const 
  * trip through the host).  corrected_bs_dev [n_masked, n_samples] row-major device memory holding the
  * values of the reference's Fortran-ordered correctedData (wisetools.py:101: pass WC_SUM_SEQUENTIAL
  * to newref); masked_dev [n_masked, n_samples] device memory; pca_components_out / pca_mean_out host
- * memory.  Every output may be NULL. */
+ * memory.  Every output may be NULL.  Like wc_newref_prep_finish it reads the state of the context's last
+ * wc_newref_prep_gram, whatever ran in between, and may be repeated. */
 int wc_newref_prep_finish_dev(wc_ctx *ctx, int n_comp, const double *eigvecs, const double *eigvals,
                               double *masked_dev, double *corrected_bs_dev, double *pca_components_out,
                               double *pca_mean_out);
@@ -616,6 +625,11 @@ int wc_test_profile(wc_ctx *ctx, int enable);
 /* Development aid: phase stamps (shader clock) of the latency-mode kernels' workgroup
  * `block_plus_one - 1` (0: off); returns the 64 stamps of the calls since the last request. */
 int wc_debug_times(wc_ctx *ctx, int block_plus_one, unsigned long long *out64);
+/* Development aid: the process-wide count of workspace (re)allocations -- every device workspace of every context
+ * that was allocated, grown or released, and every context's pinned host block that moved.  Read only.  A repeated
+ * call of an unchanged shape leaves it unchanged (such calls only enqueue kernels); the latency-mode graph of the
+ * test path is dropped and captured again once it differs from its value at capture time. */
+unsigned long long wc_realloc_epoch(void);
 int wc_test_profile_read(wc_ctx *ctx, double out[8]);
 
 /* ---- result files: raw deflate and CRC-32 on the device (testbatch -encoder gpu) ------------

@@ -160,6 +160,7 @@ SIGNATURES = {
                              _vp, _vp, _vp, _vp, _vp, _vp]),
     "wc_test_profile": (_i32, [_vp, _i32]),
     "wc_debug_times": (_i32, [_vp, _i32, _vp]),
+    "wc_realloc_epoch": (_c.c_ulonglong, []),
     "wc_test_profile_read": (_i32, [_vp, _vp]),
     "wc_test_batch_dev": (_i32, [_vp, _vp, _vp, _vp, _i64, _dbl, _i32, _i32, _dbl, _vp, _i32, _i32,
                                  _vp, _vp, _vp, _vp, _vp, _vp]),

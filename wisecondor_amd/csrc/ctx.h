@@ -78,11 +78,17 @@ struct TestState {
     }
 };
 
-// state carried from wc_newref_prep_gram to wc_newref_prep_finish
+// state carried from wc_newref_prep_gram to wc_newref_prep_finish.  The arrays are the prep step's own: no other
+// entry point writes them, so _eig and _finish* compute from what _gram left whatever ran on the context in between.
 struct PrepState {
     int64_t S = 0, Btot = 0, B = 0;
     bool ready = false;
     wc::DevBuf eig_ws;          // eigh.hip: working copy, reflectors, tridiagonal, vectors
+    wc::DevBuf counts, totals, sel;     // the counts [S, Btot], the samples' totals, the kept bins' places
+    wc::DevBuf raw, data, xt, xc;       // maskedData [B, S]; tdata, centred and corrected_t [S, B]
+    wc::DevBuf z;                       // Gram matrix [S, S] | scaled eigenvectors [8, S] | components [8, B] | mean [B]
+    wc::DevBuf proj;                    // projection [S, 8]
+    wc::DevBuf misc, zt;                // the Gram tiles' list; their slices' partial tiles
 };
 
 // workspaces of `convert` (convert.hip): the small tables, the per-tile words, the kept positions, and in paired mode
@@ -137,9 +143,12 @@ struct wc_ctx {
     bool side2_pending = false;
     bool side_fresh = false;               // the side stream was forked from the launch stream and NOTHING has been enqueued on the
                                            // launch stream since: the next side_begin needs no second event record + wait
-    // small pinned host block for count read-backs (a pageable destination costs a staged copy)
+    // small pinned host block for count read-backs (a pageable destination costs a staged copy).  The latency-mode
+    // graph of the test path bakes this block's address in (k_assemble_calls' host_status), so a block that moves
+    // counts as a reallocation like a DevBuf's: whoever cached the address compares wc::realloc_epoch().
     int ensure_pinned(size_t bytes) {
         if (pinned_bytes >= bytes) return WC_OK;
+        ++wc::realloc_epoch();
         if (pinned) (void)hipHostFree(pinned);
         pinned = nullptr;
         pinned_bytes = 0;
@@ -171,7 +180,8 @@ struct wc_ctx {
                 &ts.sel, &ts.res_z, &ts.res_r, &ts.cwz, &ts.calls, &ts.n_calls, &ts.zs, &ts.rs2, &ts.ns2, &ts.sds, &ts.sub, &ts.tmin, &ts.tmax, &ts.tmin2, &ts.tmax2, &ts.cell_state, &ts.cell_rec, &ts.prefix, &ts.reg_abs,
                 &ts.reg_flag, &ts.rs, &ts.jobs_a, &ts.jobs_b, &ts.job_cnt, &ts.partial, &ts.cbound, &ts.cuts, &ts.job_res, &ts.hot,
                 &ts.cand, &ts.cand_cnt, &ts.seg, &ts.out_val, &ts.out_x, &ts.out_y, &ts.out_n,
-                &ts.whole, &ts.effect, &ts.misc, &ts.misc2, &ts.reduce_tmp, &ts.win_bits, &ts.bit_off, &ts.pairs_a, &ts.pairs_b, &ts.cut_vals, &ts.prof_work, &ts.sd_fail, &ts.walk_hot, &prep.eig_ws,
+                &ts.whole, &ts.effect, &ts.misc, &ts.misc2, &ts.reduce_tmp, &ts.win_bits, &ts.bit_off, &ts.pairs_a, &ts.pairs_b, &ts.cut_vals, &ts.prof_work, &ts.sd_fail, &ts.walk_hot, &prep.eig_ws, &prep.counts, &prep.totals, &prep.sel, &prep.raw, &prep.data,
+                &prep.xt, &prep.xc, &prep.z, &prep.proj, &prep.misc, &prep.zt,
                 &cv.tab, &cv.tiles, &cv.kpos, &cv.cls, &df_scratch, &df_meta, &js_slots, &js_tiles, &sp_plan, &dr_tab, &cx_tab, &cx_prefix, &cx_rows, &pl_list, &pl_counts, &pl_tab, &pl_img, &pl_part, &pl_status};
     }
 };

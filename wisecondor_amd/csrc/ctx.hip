@@ -64,6 +64,8 @@ void wc_destroy(wc_ctx *ctx) {
     delete ctx;
 }
 
+unsigned long long wc_realloc_epoch(void) { return wc::realloc_epoch().load(); }
+
 void wc_get_part(int64_t partnum, int64_t outof, int64_t bincount, int64_t *start, int64_t *end) {
     // wisetools.py:358-361: int(bincount / float(outof) * partnum)
     double per = (double)bincount / (double)outof;

@@ -400,19 +400,18 @@ int wc_newref_prep_gram(wc_ctx *ctx, const int32_t *counts, int64_t n_samples, i
     WC_CHECK(n_samples > 0 && n_total_bins > 0 && n_chrom > 0 && n_chrom <= WC_MAX_CHROM, WC_E_ARG, "prep: bad shape");
     WC_CHECK(n_samples <= 4096, WC_E_LIMIT, "prep: more than 4096 samples not supported");
     WC_HIP(hipSetDevice(ctx->device));
-    PrepState &g_prep = ctx->prep;
-    g_prep.ready = false;
+    PrepState &ps = ctx->prep;
+    ps.ready = false;
     const int64_t S = n_samples, Btot = n_total_bins;
-    TestState &ts = ctx->ts;
     int rc;
-    if ((rc = ts.counts.reserve(sizeof(int) * S * Btot))) return rc;
-    if ((rc = ts.totals.reserve(sizeof(double) * S))) return rc;
+    if ((rc = ps.counts.reserve(sizeof(int) * S * Btot))) return rc;
+    if ((rc = ps.totals.reserve(sizeof(double) * S))) return rc;
     if ((rc = ctx->tmp_d.reserve(Btot))) return rc;
-    WC_HIP(hipMemcpy(ts.counts.p, counts, sizeof(int) * S * Btot, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_prep_totals, dim3((unsigned)S), dim3(256), 0, nullptr, (const int *)ts.counts.as<int>(), Btot,
-                       ts.totals.as<double>());
+    WC_HIP(hipMemcpy(ps.counts.p, counts, sizeof(int) * S * Btot, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_prep_totals, dim3((unsigned)S), dim3(256), 0, nullptr, (const int *)ps.counts.as<int>(), Btot,
+                       ps.totals.as<double>());
     hipLaunchKernelGGL(k_prep_mask, dim3((unsigned)cdiv(Btot, 256)), dim3(256), 0, nullptr,
-                       (const int *)ts.counts.as<int>(), S, Btot, (const double *)ts.totals.as<double>(),
+                       (const int *)ps.counts.as<int>(), S, Btot, (const double *)ps.totals.as<double>(),
                        ctx->tmp_d.as<unsigned char>());
     WC_HIP(hipDeviceSynchronize());
     WC_HIP(hipMemcpy(mask_out, ctx->tmp_d.p, Btot, hipMemcpyDeviceToHost));
@@ -430,16 +429,15 @@ int wc_newref_prep_gram(wc_ctx *ctx, const int32_t *counts, int64_t n_samples, i
     const int64_t B = (int64_t)m2g.size();
     *n_masked_out = B;
     WC_CHECK(B > 0, WC_E_ARG, "prep: every bin is empty");
-    if ((rc = ts.sel.reserve(sizeof(int) * B))) return rc;
-    if ((rc = ts.raw.reserve(sizeof(double) * B * S))) return rc;     // maskedData [B, S]
-    if ((rc = ts.data.reserve(sizeof(double) * B * S))) return rc;    // tdata [S, B]
-    if ((rc = ts.xt.reserve(sizeof(double) * B * S))) return rc;      // centred [S, B]
-    if ((rc = ts.xc.reserve(sizeof(double) * B * S))) return rc;      // corrected_t [S, B]
-    if ((rc = ts.z.reserve(sizeof(double) * (S * S + 8 * S + 8 * B + B)))) return rc;
-    if ((rc = ts.proj.reserve(sizeof(double) * 8 * S))) return rc;
-    double *G = ts.z.as<double>(), *mean = G + S * S + 8 * S + 8 * B;
-    ts.sel_host.clear();      // the test path caches its chromosome selection in this buffer: not valid any more
-    WC_HIP(hipMemcpy(ts.sel.p, m2g.data(), sizeof(int) * B, hipMemcpyHostToDevice));
+    if ((rc = ps.sel.reserve(sizeof(int) * B))) return rc;
+    if ((rc = ps.raw.reserve(sizeof(double) * B * S))) return rc;     // maskedData [B, S]
+    if ((rc = ps.data.reserve(sizeof(double) * B * S))) return rc;    // tdata [S, B]
+    if ((rc = ps.xt.reserve(sizeof(double) * B * S))) return rc;      // centred [S, B]
+    if ((rc = ps.xc.reserve(sizeof(double) * B * S))) return rc;      // corrected_t [S, B]
+    if ((rc = ps.z.reserve(sizeof(double) * (S * S + 8 * S + 8 * B + B)))) return rc;
+    if ((rc = ps.proj.reserve(sizeof(double) * 8 * S))) return rc;
+    double *G = ps.z.as<double>(), *mean = G + S * S + 8 * S + 8 * B;
+    WC_HIP(hipMemcpy(ps.sel.p, m2g.data(), sizeof(int) * B, hipMemcpyHostToDevice));
     {
         int nbins = 32;                             // bins per workgroup: a power of two, tile <= 96 KB of LDS
         while (nbins > 1 && (int64_t)nbins * (S | 1) * 8 > 96 * 1024) nbins >>= 1;
@@ -448,9 +446,9 @@ int wc_newref_prep_gram(wc_ctx *ctx, const int32_t *counts, int64_t n_samples, i
             WC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_prep_norm_centre),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(k_prep_norm_centre, dim3((unsigned)cdiv(B, nbins)), dim3(256), lds, nullptr,
-                           (const int *)ts.counts.as<int>(), S, Btot, (const int *)ts.sel.as<int>(), B,
-                           (const double *)ts.totals.as<double>(), nbins, ts.raw.as<double>(), ts.data.as<double>(), mean,
-                           ts.xt.as<double>());
+                           (const int *)ps.counts.as<int>(), S, Btot, (const int *)ps.sel.as<int>(), B,
+                           (const double *)ps.totals.as<double>(), nbins, ps.raw.as<double>(), ps.data.as<double>(), mean,
+                           ps.xt.as<double>());
     }
     {
         // lower triangle of 64 x 64 tiles x bin slices: about 2 000 workgroups, slices of whole panels
@@ -463,19 +461,19 @@ int wc_newref_prep_gram(wc_ctx *ctx, const int32_t *counts, int64_t n_samples, i
         int64_t per = round_up(cdiv(B, n_slices), SY_KB);
         per = std::max<int64_t>(per, 4 * SY_KB);
         n_slices = cdiv(B, per);
-        if ((rc = ts.misc.reserve(sizeof(int2) * n_tiles + 16))) return rc;
-        if ((rc = ts.zt.reserve(sizeof(double) * n_slices * n_tiles * SY_T * SY_T))) return rc;
-        WC_HIP(hipMemcpy(ts.misc.p, tiles.data(), sizeof(int2) * n_tiles, hipMemcpyHostToDevice));
+        if ((rc = ps.misc.reserve(sizeof(int2) * n_tiles + 16))) return rc;
+        if ((rc = ps.zt.reserve(sizeof(double) * n_slices * n_tiles * SY_T * SY_T))) return rc;
+        WC_HIP(hipMemcpy(ps.misc.p, tiles.data(), sizeof(int2) * n_tiles, hipMemcpyHostToDevice));
         hipLaunchKernelGGL(k_prep_syrk, dim3((unsigned)n_tiles, (unsigned)n_slices), dim3(256), 0, nullptr,
-                           (const double *)ts.xt.as<double>(), S, B, (const int2 *)ts.misc.as<int2>(), per,
-                           ts.zt.as<double>());
+                           (const double *)ps.xt.as<double>(), S, B, (const int2 *)ps.misc.as<int2>(), per,
+                           ps.zt.as<double>());
         hipLaunchKernelGGL(k_prep_gram_reduce, dim3((unsigned)n_tiles, SY_T * SY_T / 256), dim3(256), 0, nullptr,
-                           (const double *)ts.zt.as<double>(), (const int2 *)ts.misc.as<int2>(), n_tiles,
+                           (const double *)ps.zt.as<double>(), (const int2 *)ps.misc.as<int2>(), n_tiles,
                            (int)n_slices, S, G);
     }
     WC_HIP(hipDeviceSynchronize());
     if (gram_out) WC_HIP(hipMemcpy(gram_out, G, sizeof(double) * S * S, hipMemcpyDeviceToHost));
-    g_prep.S = S; g_prep.Btot = Btot; g_prep.B = B; g_prep.ready = true;
+    ps.S = S; ps.Btot = Btot; ps.B = B; ps.ready = true;
     return WC_OK;
 }
 
@@ -485,22 +483,21 @@ int wc_newref_prep_eig(wc_ctx *ctx, int n_pairs, double *eigvals_out, double *ei
     WC_CHECK(ctx && eigvals_out && eigvecs_out, WC_E_ARG, "prep: NULL argument");
     WC_CHECK(ctx->prep.ready, WC_E_ARG, "prep: wc_newref_prep_gram has not run");
     WC_HIP(hipSetDevice(ctx->device));
-    return wc::sym_eigh_leading(ctx, ctx->ts.z.as<double>(), ctx->prep.S, n_pairs, eigvals_out, eigvecs_out);
+    return wc::sym_eigh_leading(ctx, ctx->prep.z.as<double>(), ctx->prep.S, n_pairs, eigvals_out, eigvecs_out);
 }
 
-// Device part of the finish step: components (sign fixed), projection, corrected_t [S, B] in ts.xc.
-// Leaves maskedData in ts.raw, components / mean in ts.z; *hc points at the host copy of the components in the
+// Device part of the finish step: components (sign fixed), projection, corrected_t [S, B] in ps.xc.
+// Leaves maskedData in ps.raw, components / mean in ps.z; *hc points at the host copy of the components in the
 // context's pinned block (valid once the caller has synchronised; owned by the context, so an error return
 // between the copy's launch and that synchronisation leaves nothing dangling).
 static int prep_finish_body(wc_ctx *ctx, int n_comp, const double *eigvecs, const double *eigvals,
                             const double **hc, bool want_t) {
-    PrepState &g_prep = ctx->prep;
-    WC_CHECK(g_prep.ready, WC_E_ARG, "prep: wc_newref_prep_gram has not run");
-    const int64_t S = g_prep.S, B = g_prep.B;
+    PrepState &ps = ctx->prep;
+    WC_CHECK(ps.ready, WC_E_ARG, "prep: wc_newref_prep_gram has not run");
+    const int64_t S = ps.S, B = ps.B;
     WC_CHECK(n_comp >= 1 && n_comp <= 8 && n_comp <= S, WC_E_ARG, "prep: 1..8 components supported");
     WC_HIP(hipSetDevice(ctx->device));
-    TestState &ts = ctx->ts;
-    double *G = ts.z.as<double>(), *w = G + S * S, *comp = w + 8 * S, *mean = comp + 8 * B;
+    double *G = ps.z.as<double>(), *w = G + S * S, *comp = w + 8 * S, *mean = comp + 8 * B;
     std::vector<double> hw((size_t)8 * S, 0.0);
     for (int c = 0; c < n_comp; ++c) {
         WC_CHECK(eigvals[c] > 0.0, WC_E_ARG, "prep: data has rank below %d", n_comp);
@@ -509,10 +506,10 @@ static int prep_finish_body(wc_ctx *ctx, int n_comp, const double *eigvecs, cons
     }
     WC_HIP(hipMemcpy(w, hw.data(), sizeof(double) * 8 * S, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(k_prep_components, dim3((unsigned)cdiv(B, 64)), dim3(1024), 0, nullptr,
-                       (const double *)ts.xt.as<double>(), S, B, (const double *)w, n_comp, comp);
+                       (const double *)ps.xt.as<double>(), S, B, (const double *)w, n_comp, comp);
     hipLaunchKernelGGL(k_prep_sign, dim3((unsigned)n_comp), dim3(1024), 0, nullptr, comp, B);
-    hipLaunchKernelGGL(k_prep_transform, dim3((unsigned)S), dim3(1024), 0, nullptr, (const double *)ts.xt.as<double>(),
-                       B, (const double *)comp, n_comp, ts.proj.as<double>());
+    hipLaunchKernelGGL(k_prep_transform, dim3((unsigned)S), dim3(1024), 0, nullptr, (const double *)ps.xt.as<double>(),
+                       B, (const double *)comp, n_comp, ps.proj.as<double>());
     // the host copy of the components travels while the rest runs (the callers synchronise): pinned memory, so the
     // copy really is asynchronous
     {
@@ -523,9 +520,9 @@ static int prep_finish_body(wc_ctx *ctx, int n_comp, const double *eigvecs, cons
     WC_HIP(hipMemcpyAsync(ctx->pinned, comp, sizeof(double) * n_comp * B, hipMemcpyDeviceToHost, nullptr));
     if (want_t) {
         dim3 gb((unsigned)cdiv(B, 256), (unsigned)S);
-        hipLaunchKernelGGL(k_prep_correct, gb, dim3(256), 0, nullptr, (const double *)ts.data.as<double>(), B,
-                           (const double *)mean, (const double *)comp, n_comp, (const double *)ts.proj.as<double>(),
-                           ts.xc.as<double>());
+        hipLaunchKernelGGL(k_prep_correct, gb, dim3(256), 0, nullptr, (const double *)ps.data.as<double>(), B,
+                           (const double *)mean, (const double *)comp, n_comp, (const double *)ps.proj.as<double>(),
+                           ps.xc.as<double>());
     }
     WC_HIP(hipGetLastError());
     return WC_OK;
@@ -539,12 +536,12 @@ int wc_newref_prep_finish(wc_ctx *ctx, int n_comp, const double *eigvecs, const 
     const double *hc = nullptr;
     int rc = prep_finish_body(ctx, n_comp, eigvecs, eigvals, &hc, true);
     if (rc) return rc;
-    TestState &ts = ctx->ts;
+    PrepState &ps = ctx->prep;
     const int64_t S = ctx->prep.S, B = ctx->prep.B;
-    const double *mean = ts.z.as<double>() + S * S + 8 * S + 8 * B;
+    const double *mean = ps.z.as<double>() + S * S + 8 * S + 8 * B;
     WC_HIP(hipDeviceSynchronize());
-    WC_HIP(hipMemcpy(masked_data_out, ts.raw.p, sizeof(double) * B * S, hipMemcpyDeviceToHost));
-    WC_HIP(hipMemcpy(corrected_t_out, ts.xc.p, sizeof(double) * B * S, hipMemcpyDeviceToHost));
+    WC_HIP(hipMemcpy(masked_data_out, ps.raw.p, sizeof(double) * B * S, hipMemcpyDeviceToHost));
+    WC_HIP(hipMemcpy(corrected_t_out, ps.xc.p, sizeof(double) * B * S, hipMemcpyDeviceToHost));
     memcpy(pca_components_out, hc, sizeof(double) * n_comp * B);
     WC_HIP(hipMemcpy(pca_mean_out, mean, sizeof(double) * B, hipMemcpyDeviceToHost));
     return WC_OK;
@@ -561,16 +558,16 @@ int wc_newref_prep_finish_dev(wc_ctx *ctx, int n_comp, const double *eigvecs, co
     const double *hc = nullptr;
     int rc = prep_finish_body(ctx, n_comp, eigvecs, eigvals, &hc, false);
     if (rc) return rc;
-    TestState &ts = ctx->ts;
+    PrepState &ps = ctx->prep;
     const int64_t S = ctx->prep.S, B = ctx->prep.B;
-    const double *comp = ts.z.as<double>() + S * S + 8 * S, *mean = comp + 8 * B;
+    const double *comp = ps.z.as<double>() + S * S + 8 * S, *mean = comp + 8 * B;
     if (corrected_bs_dev) {
         dim3 g((unsigned)cdiv(B, 32), (unsigned)cdiv(S, 32));
-        hipLaunchKernelGGL(k_prep_correct_bs, g, dim3(256), 0, nullptr, (const double *)ts.data.as<double>(), S, B,
-                           mean, comp, n_comp, (const double *)ts.proj.as<double>(), corrected_bs_dev);
+        hipLaunchKernelGGL(k_prep_correct_bs, g, dim3(256), 0, nullptr, (const double *)ps.data.as<double>(), S, B,
+                           mean, comp, n_comp, (const double *)ps.proj.as<double>(), corrected_bs_dev);
     }
     if (masked_dev)
-        WC_HIP(hipMemcpyAsync(masked_dev, ts.raw.p, sizeof(double) * B * S, hipMemcpyDeviceToDevice, nullptr));
+        WC_HIP(hipMemcpyAsync(masked_dev, ps.raw.p, sizeof(double) * B * S, hipMemcpyDeviceToDevice, nullptr));
     if (pca_mean_out) WC_HIP(hipMemcpy(pca_mean_out, mean, sizeof(double) * B, hipMemcpyDeviceToHost));
     WC_HIP(hipDeviceSynchronize());
     if (pca_components_out) memcpy(pca_components_out, hc, sizeof(double) * n_comp * B);   // (its copy has landed)
