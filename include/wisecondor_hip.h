@@ -230,6 +230,12 @@ int wc_write_test_results(int n_files, int n_threads, const char *const *out_pat
 int wc_newref_prep_gram(wc_ctx *ctx, const int32_t *counts, int64_t n_samples, int64_t n_total_bins,
                         const int64_t *chromosome_bins, int n_chrom, uint8_t *mask_out,
                         int64_t *masked_chrom_bins_out, int64_t *n_masked_out, double *gram_out);
+/* wc_newref_prep_gram with a blacklist: drop_host [n_total_bins] uint8 (HOST, may be NULL).  Once the zero mask has reached
+ * the host, mask_out[g] is cleared where drop_host[g] is set; the masked layout and everything behind it follow that mask, so
+ * a dropped bin is treated as a bin that is empty in every sample.  Nothing else differs; NULL is wc_newref_prep_gram. */
+int wc_newref_prep_gram_ex(wc_ctx *ctx, const int32_t *counts, int64_t n_samples, int64_t n_total_bins,
+                           const int64_t *chromosome_bins, int n_chrom, uint8_t *mask_out,
+                           int64_t *masked_chrom_bins_out, int64_t *n_masked_out, double *gram_out, const uint8_t *drop_host);
 int wc_newref_prep_eig(wc_ctx *ctx, int n_pairs, double *eigvals_out, double *eigvecs_out);
 int wc_sym_eigh_leading_dev(wc_ctx *ctx, const double *matrix_dev, int64_t n, int n_pairs, double *eigvals_out,
                             double *eigvecs_out);
@@ -1038,6 +1044,27 @@ int wc_crossval_stats(wc_ctx *ctx, const double *Z, int64_t row_stride, int64_t 
                       const double *thr, const double *asdef, const double *calls, const int32_t *n_calls, int max_calls, const int32_t *sel,
                       int n_sel, const int32_t *lengths, int n_lengths, int32_t *bins_i, double *bins_f, int32_t *rec_i, double *rec_f,
                       int64_t *win_n, int64_t *win_i, int64_t *win_hist);
+
+/* ---- robust column statistics: the median and the median absolute deviation of every column ------------
+ * wc_column_robust_dev: Z [n_rows, row_stride] float64 (DEVICE; n_cols <= row_stride columns of a row are read), col_i
+ *   [n_cols, 2] int32 and col_f [n_cols, 2] float64 (DEVICE).  For column b, with z = Z[i * row_stride + b], i = 0 .. n_rows - 1:
+ *   Classes: crossval's.  TESTED when z != 0 (so +0.0 and -0.0 are untested and NaN is tested), NONFINITE when tested and
+ *     not finite, else FINITE.
+ *   col_i[b] = {finite, nonfinite}.
+ *   Median: v = the column's FINITE values, n of them, s = the same in ascending order.  med(s) = s[(n - 1) / 2] for odd n and
+ *     (s[n / 2 - 1] + s[n / 2]) / 2.0 for even n, the sum rounded first.
+ *   col_f[b][0] = med(s), NaN when n == 0.
+ *   col_f[b][1] = med of d_i = fabs(v_i - col_f[b][0]), every difference rounded, sorted ascending; NaN when n == 0 or the
+ *     median is not finite (the two middle values overflowed).  d can be zero, and then +0.0; it can be +inf.
+ *   For nonzero finite input this is np.median(v) and np.median(np.abs(v - np.median(v))) bit for bit.  The selection is
+ *   exact (a radix selection over the values' bits): no sum enters but the one of the middle pair.
+ *   Refused before anything is written: WC_E_ARG for NULL pointers, n_rows < 1, n_cols < 1 (or above 2^31 - 1),
+ *     row_stride < n_cols; WC_E_LIMIT for n_rows > 8192.  The work is enqueued on `stream` and not waited for.
+ * wc_column_robust: the same from HOST pointers, synchronising (of Z's last row only n_cols values are read).           */
+int wc_column_robust_dev(wc_ctx *ctx, void *stream, const double *Z, int64_t row_stride, int64_t n_rows, int64_t n_cols,
+                         int32_t *col_i, double *col_f);
+int wc_column_robust(wc_ctx *ctx, const double *Z, int64_t row_stride, int64_t n_rows, int64_t n_cols, int32_t *col_i,
+                     double *col_f);
 
 #ifdef __cplusplus
 }

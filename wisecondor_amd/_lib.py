@@ -141,6 +141,7 @@ SIGNATURES = {
     "wc_convert_run_info": (_i32, [_vp, _vp]),
     "wc_convert_end": (None, [_vp]),
     "wc_newref_prep_gram": (_i32, [_vp, _vp, _i64, _i64, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "wc_newref_prep_gram_ex": (_i32, [_vp, _vp, _i64, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "wc_newref_prep_eig": (_i32, [_vp, _i32, _vp, _vp]),
     "wc_sym_eigh_leading_dev": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp]),
     "wc_newref_prep_finish": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -184,6 +185,8 @@ SIGNATURES = {
                                      _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "wc_crossval_stats": (_i32, [_vp, _vp, _i64, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _i32,
                                  _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "wc_column_robust_dev": (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp]),
+    "wc_column_robust": (_i32, [_vp, _vp, _i64, _i64, _i64, _vp, _vp]),
 }
 
 SUM_PAIRWISE = 0

@@ -12,7 +12,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libwisecondor_hip.so")
-SOURCES = ["ctx.hip", "newref.hip", "testpath.hip", "prep.hip", "eigh.hip", "convert.hip", "bamgpu.hip", "deflate.hip", "plot.hip", "pdf.hip", "export.hip", "tracks.hip", "spike.hip", "draw.hip", "crossval.hip", "npzio.cpp", "bamio.cpp",
+SOURCES = ["ctx.hip", "newref.hip", "testpath.hip", "prep.hip", "eigh.hip", "convert.hip", "bamgpu.hip", "deflate.hip", "plot.hip", "pdf.hip", "export.hip", "tracks.hip", "spike.hip", "draw.hip", "crossval.hip", "robust.hip", "npzio.cpp", "bamio.cpp",
            "bamfile.cpp"]   # npzio.cpp, bamio.cpp, bamfile.cpp: host only (zip / pickle / zlib; BGZF / BAM)
 # -fno-slp-vectorize: the SLP vectoriser pairs float32 operations into v_pk_add_f32 /
 # v_pk_fma_f32; an in-place pair whose low half reads the destination's high half

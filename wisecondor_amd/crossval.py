@@ -7,6 +7,8 @@ fold the kernels of csrc/crossval.hip judge all rows in cohort order: per sample
 (wc_crossval_stats_dev; include/wisecondor_hip.h has the rules).  The fold plan and the tables are host work on small
 arrays.
 """
+import math
+
 import numpy as np
 
 from . import _lib
@@ -19,6 +21,7 @@ MAX_LENGTHS = 16
 HIST_SLOTS = 130                  # win_hist: slot 0 below -16, 1 .. 128 quarter units of [-16, 16), 129 at 16, above, or NaN
 DEFAULT_WINDOWS = (1, 2, 5, 10, 20, 50, 100)
 SAMPLE_COLUMNS = ('sample', 'fold', 'calls', 'call_bins', 'tested', 'over_hi', 'over_lo', 'asdef', 'max_z', 'min_z')
+BIN_COLUMNS = ('chromosome', 'start', 'end', 'tested', 'nonfinite', 'median', 'spread', 'mean', 'sd', 'listed')
 WINDOW_COLUMNS = ('length', 'rows', 'windows', 'hi', 'lo', 'rate', 'expected', 'spread')
 #: the two quantiles whose half distance is a normal distribution's standard deviation
 SPREAD_QUANTILES = (0.1587, 0.8413)
@@ -103,7 +106,8 @@ def crossvalStats(Z, chrom_sizes, thr, asdef, calls, n_calls, chromosomes=None, 
 
 
 def crossval_batch(counts, chrom_sizes, fold_of, binsize, refsize=100, multitest=1000, minzscore=None, minrefbins=25, repeats=5,
-                   chromosomes=None, mineffectsize=0, windows=DEFAULT_WINDOWS, keep_results=False, device=0, stage_ms=None):
+                   chromosomes=None, mineffectsize=0, windows=DEFAULT_WINDOWS, keep_results=False, device=0, stage_ms=None,
+                   drop=None, robust=False):
     """Every sample of counts (int32 [n, n_total], the image of ingest.load_counts / wt.samples_to_counts in the layout
     chrom_sizes, which every fold uses) tested against a reference built from the samples of the other folds, and the
     held-out results judged on the device.  fold_of: foldPlan's array.  Folds run in ascending fold number; nothing in a
@@ -115,8 +119,12 @@ def crossval_batch(counts, chrom_sizes, fold_of, binsize, refsize=100, multitest
     bins_i, bins_f, win_n, win_i, win_hist (wc_crossval_stats_dev; rec_i's first column is the fold).  With keep_results
     also Z, R float64 [n, n_total] and results_cwz [n, selected chromosomes].
 
+    drop: a blacklist (blacklist.readBlacklist), handed to every fold's wt.prepReference.  robust: after the judging
+    wc_column_robust_dev runs once over Z on the same stream, and the result gains robust_i int32 [n_total, 2] {finite,
+    nonfinite} and robust_f float64 [n_total, 2] {median, mad} (stage_ms: 'robust').  Without it no key and no launch is new.
+
     stage_ms (a dict, for the measuring tool): receives device-event times in ms summed over the folds under 'gather',
-    'prep', 'newref', 'reference', 'test' and 'stats'; the events synchronise, so the run is slower with it."""
+    'prep', 'newref', 'reference', 'test', 'stats' and, with robust, 'robust'; the events synchronise, so the run is slower with it."""
     import torch
     from .distributed import NewrefJob
     from .wisecondor import zThreshold
@@ -165,7 +173,7 @@ def crossval_batch(counts, chrom_sizes, fold_of, binsize, refsize=100, multitest
             tested = image.index_select(0, held_dev)
             mark('gather')
             _, _, mask, corrected, components, mean, masked_sizes = wt.prepReference(None, device=device, device_out=True, counts=training,
-                                                                                     chrom_bins=sizes)
+                                                                                     chrom_bins=sizes, drop=drop)
             mark('prep')
             job = NewrefJob(ctx, corrected, np.ascontiguousarray(masked_sizes, dtype=np.int64), int(refsize), _lib.SUM_SEQUENTIAL)
             indexes, distances = job.run()
@@ -216,7 +224,14 @@ def crossval_batch(counts, chrom_sizes, fold_of, binsize, refsize=100, multitest
                                              asdef.data_ptr(), calls.data_ptr(), n_calls.data_ptr(), max_calls, _lib.ptr(sel), len(sel),
                                              _lib.ptr(lengths), len(lengths), *[out[key].data_ptr() for key in STATS_KEYS]))
         mark('stats')
+        if robust:
+            robust_i = torch.zeros((n_total, 2), dtype=torch.int32, device=dev)
+            robust_f = torch.zeros((n_total, 2), **f64)
+            _lib.check(lib.wc_column_robust_dev(ctx, stream, Z.data_ptr(), n_total, n, n_total, robust_i.data_ptr(), robust_f.data_ptr()))
+            mark('robust')
         result = {key: out[key].cpu().numpy() for key in STATS_KEYS}
+        if robust:
+            result.update(robust_i=robust_i.cpu().numpy(), robust_f=robust_f.cpu().numpy())
         counts_of = n_calls.cpu().numpy()
         rows_of = calls.cpu().numpy()
         if stage_ms is not None:
@@ -261,6 +276,32 @@ def samplesText(names, rec_i, rec_f):
     out = ['\t'.join(SAMPLE_COLUMNS)]
     for name, ri, rf in zip(names, rec_i, rec_f):
         out.append('\t'.join([str(name)] + [str(int(ri[k])) for k in (0, 1, 6, 2, 4, 5)] + [repr(float(rf[k])) for k in (0, 2, 3)]))
+    return '\n'.join(out) + '\n'
+
+
+def binsText(chrom_sizes, binsize, bins_i, bins_f, robust_f, listed):
+    """The per-bin table of -robust as tab separated text, a line per bin of the layout, columns BIN_COLUMNS: the bin's
+    chromosome, start and end in base pairs; tested and nonfinite (bins_i); median and spread = 1.4826 * mad (robust_f);
+    mean and sd, formed here from bins_f's sums over the bin's n finite samples (sd = sqrt((sum z * z - n * mean * mean) /
+    (n - 1)), clipped at 0), NaN below two; listed as 0 or 1.  Doubles as repr writes them."""
+    from .blacklist import spreadOf
+    bins_i = np.asarray(bins_i).reshape(-1, 6)
+    bins_f = np.asarray(bins_f, dtype=np.float64).reshape(-1, 2)
+    robust_f = np.asarray(robust_f, dtype=np.float64).reshape(-1, 2)
+    spread = spreadOf(robust_f)
+    out = ['\t'.join(BIN_COLUMNS)]
+    b = 0
+    for c, size in enumerate(int(v) for v in chrom_sizes):
+        for g in range(size):
+            n = int(bins_i[b, 0]) - int(bins_i[b, 1])
+            mean = sd = float('nan')
+            if n >= 2:
+                mean = float(bins_f[b, 0]) / n
+                sd = math.sqrt(max(0.0, (float(bins_f[b, 1]) - n * mean * mean) / (n - 1)))
+            out.append('\t'.join([str(c + 1), str(g * int(binsize)), str((g + 1) * int(binsize)), str(int(bins_i[b, 0])),
+                                  str(int(bins_i[b, 1])), repr(float(robust_f[b, 0])), repr(float(spread[b])), repr(mean), repr(sd),
+                                  str(int(bool(listed[b])))]))
+            b += 1
     return '\n'.join(out) + '\n'
 
 

@@ -395,6 +395,13 @@ extern "C" {
 int wc_newref_prep_gram(wc_ctx *ctx, const int32_t *counts, int64_t n_samples, int64_t n_total_bins,
                         const int64_t *chromosome_bins, int n_chrom, uint8_t *mask_out,
                         int64_t *masked_chrom_bins_out, int64_t *n_masked_out, double *gram_out) {
+    return wc_newref_prep_gram_ex(ctx, counts, n_samples, n_total_bins, chromosome_bins, n_chrom, mask_out, masked_chrom_bins_out,
+                                  n_masked_out, gram_out, nullptr);
+}
+
+int wc_newref_prep_gram_ex(wc_ctx *ctx, const int32_t *counts, int64_t n_samples, int64_t n_total_bins,
+                           const int64_t *chromosome_bins, int n_chrom, uint8_t *mask_out,
+                           int64_t *masked_chrom_bins_out, int64_t *n_masked_out, double *gram_out, const uint8_t *drop_host) {
     WC_CHECK(ctx && counts && chromosome_bins && mask_out && masked_chrom_bins_out && n_masked_out,
              WC_E_ARG, "prep: NULL argument");           // gram_out may be NULL: the matrix stays in HBM for wc_newref_prep_eig
     WC_CHECK(n_samples > 0 && n_total_bins > 0 && n_chrom > 0 && n_chrom <= WC_MAX_CHROM, WC_E_ARG, "prep: bad shape");
@@ -415,6 +422,9 @@ int wc_newref_prep_gram(wc_ctx *ctx, const int32_t *counts, int64_t n_samples, i
                        ctx->tmp_d.as<unsigned char>());
     WC_HIP(hipDeviceSynchronize());
     WC_HIP(hipMemcpy(mask_out, ctx->tmp_d.p, Btot, hipMemcpyDeviceToHost));
+    if (drop_host)                                       // the blacklist: a dropped bin is masked like an empty one
+        for (int64_t g = 0; g < Btot; ++g)
+            if (drop_host[g]) mask_out[g] = 0;
     std::vector<int> m2g;
     int64_t at = 0;
     for (int c = 0; c < n_chrom; ++c) {

@@ -364,6 +364,18 @@ def select_all_rows(prepfile, refsize, device=0, rank=0, world=1, gather=True):
 
 
 # --------------------------------------------------------------- newref: tools ----
+def readBlacklistOption(args, chrom_sizes, binsize):
+    """The bins `-blacklist FILE` drops at the layout chrom_sizes of `binsize` bp bins (blacklist.readBlacklist), or None
+    without the option.  Prints how many bins are dropped and how many lines were ignored."""
+    if getattr(args, 'blacklist', None) is None:
+        return None
+    from . import blacklist
+    drop, ignored = blacklist.readBlacklist(args.blacklist, chrom_sizes, binsize)
+    print('Blacklist %s: %d of %d bins dropped, %d lines ignored (not chromosome 1 .. 22)'
+          % (args.blacklist, int(drop.sum()), len(drop), ignored))
+    return drop
+
+
 def toolNewrefPrep(args, temporary=False):
     """`newrefprep`: sample files -> prep file (normalise, mask all-zero bins, PCA-correct).
 
@@ -380,8 +392,13 @@ def toolNewrefPrep(args, temporary=False):
     binsize = args.binsize if args.binsize is not None else next(iter(binsizes))
 
     n_given = counts.shape[0]
+    try:
+        drop = readBlacklistOption(args, chrom_bins_in, binsize)
+    except (ValueError, OSError) as exc:
+        print('ERROR:', exc)
+        sys.exit(1)
     masked, chrom_bins, mask, corrected, components, mean, masked_bins = wt.prepReference(
-        None, counts=counts, chrom_bins=chrom_bins_in)
+        None, counts=counts, chrom_bins=chrom_bins_in, drop=drop)
     print('Zero mask on the GPU: %d bins x %d samples -> %d bins kept, 3 PCA components removed'
           % (len(mask), n_given, masked.shape[0]))
     running = np.cumsum(masked_bins)
@@ -396,6 +413,8 @@ def toolNewrefPrep(args, temporary=False):
                   correctedData=corrected,
                   pca_components=components,
                   pca_mean=mean)
+    if drop is not None:
+        stored['blacklist'] = drop
     write_npz(args.prepfile, temporary, **stored)
     return stored
 
@@ -431,6 +450,8 @@ def toolNewrefPost(args):
     width = max(b.shape[1] for b in idx_blocks if b.ndim == 2) if any(b.ndim == 2 for b in idx_blocks) else 0
     idx_blocks = [b.reshape(-1, width) for b in idx_blocks]
     dst_blocks = [b.reshape(-1, width) for b in dst_blocks]
+    # (a prep file made with -blacklist carries the dropped bins; the reference file then does too)
+    extra = dict(blacklist=prep['blacklist']) if 'blacklist' in prep.files else {}
     write_npz(args.outfile,
               arguments=vars(args),
               runtime=getRuntime(),
@@ -441,7 +462,8 @@ def toolNewrefPost(args):
               mask=prep['mask'],
               masked_sizes=prep['maskedChromBins'],
               pca_components=prep['pca_components'],
-              pca_mean=prep['pca_mean'])
+              pca_mean=prep['pca_mean'],
+              **extra)
 
 
 def toolNewref(args):
@@ -701,6 +723,27 @@ def crossvalOutputs(outfile):
     return stem + '.npz', stem + '_samples.tsv', stem + '_windows.tsv'
 
 
+def crossvalBinsOutput(outfile):
+    """out_bins.tsv of the `out` argument: the per-bin table of -robust."""
+    return crossvalOutputs(outfile)[0][:-4] + '_bins.tsv'
+
+
+def crossvalRobustPlan(args):
+    """The -robust family of `crossval` as (robust, criteria): criteria is None without -maxspread, else the keyword
+    arguments of blacklist.listedBins.  ValueError: -makeblacklist without -maxspread, -maxshift or -mincover without
+    -maxspread, a criterion that is no number of its range."""
+    given = {name: getattr(args, name) for name in ('maxspread', 'maxshift', 'mincover') if hasattr(args, name)}
+    if 'maxspread' not in given:
+        if hasattr(args, 'makeblacklist'):
+            raise ValueError('-makeblacklist needs -maxspread: which spread is too wide is the cohort\'s to say')
+        if given:
+            raise ValueError('-%s goes with -maxspread' % sorted(given)[0])
+        return hasattr(args, 'robust'), None
+    if not given['maxspread'] > 0 or not given.get('maxshift', 1.0) > 0 or not 0 <= given.get('mincover', 0.5) <= 1:
+        raise ValueError('-maxspread and -maxshift are above 0 and -mincover lies in 0 .. 1')
+    return True, dict(maxspread=given['maxspread'], maxshift=given.get('maxshift'), mincover=given.get('mincover', 0.5))
+
+
 def crossvalPlan(args):
     """What `crossval` can refuse before the GPU is touched, as ValueError: fewer than 5 files, a bad fold count, bad
     -windows, no chromosome, bin sizes that do not scale.  Returns (fold_of, window lengths, the bin size the files are
@@ -711,6 +754,7 @@ def crossvalPlan(args):
         raise ValueError('crossval needs 5 healthy samples at least, got %d' % n)
     fold_of = crossval.foldPlan(n, n if args.loo else args.folds, seed=args.seed)
     windows = crossval.parseWindows(args.windows)
+    crossvalRobustPlan(args)
     if not args.chromosomes or args.refsize < 1:
         raise ValueError('crossval needs -refsize >= 1 and at least one chromosome')
     if args.results is not None:
@@ -735,26 +779,53 @@ def toolCrossval(args):
     sample: the samples with calls are what to look at) and out_windows.tsv (a line per window length: how often
     sum(z) / sqrt(L) of healthy held-out data passes the threshold, and how wide it is spread); with -results DIR also a
     `test`-format file per held-out sample, DIR/<stem>_test.npz.  Everything that can be refused is refused before the GPU
-    is touched: exit status 2."""
+    is touched: exit status 2.
+
+    -blacklist FILE drops the file's bins from every fold's reference, as `newref -blacklist` does.  -robust adds the per-bin
+    median and median absolute deviation of the held-out z-scores (wc_column_robust_dev) to out.npz and writes
+    out_bins.tsv; -makeblacklist FILE -maxspread S [-maxshift M] [-mincover C] also writes the bins blacklist.listedBins
+    lists as a BED file."""
     from . import crossval
     try:
         fold_of, windows, binsize = crossvalPlan(args)
+        robust, criteria = crossvalRobustPlan(args)
     except ValueError as exc:
         print('ERROR:', exc)
         sys.exit(2)
     from . import ingest
     counts, chrom_sizes, _ = ingest.load_counts(args.infiles, args.binsize, threads=min(16, os.cpu_count() or 1), verbose=True)
+    try:
+        drop = readBlacklistOption(args, chrom_sizes, binsize)
+    except (ValueError, OSError) as exc:
+        print('ERROR:', exc)
+        sys.exit(2)
+    extra = dict(drop=drop) if drop is not None else {}
+    if robust:
+        extra['robust'] = True
     began = time.time()
     result = crossval.crossval_batch(counts, chrom_sizes, fold_of, binsize, refsize=args.refsize, multitest=args.multitest,
                                      minzscore=args.minzscore, minrefbins=args.minrefbins, repeats=args.repeats,
                                      chromosomes=list(args.chromosomes), mineffectsize=args.mineffectsize, windows=windows,
-                                     keep_results=args.results is not None)
+                                     keep_results=args.results is not None, **extra)
     print('%d folds over %d samples took %.3f s' % (int(fold_of.max()) + 1, len(fold_of), time.time() - began))
     npz_path, samples_path, windows_path = crossvalOutputs(args.outfile)
     table = crossval.windowsTable(windows, result['win_n'], result['win_i'], result['win_hist'], result['rec_f'][:, 1])
     stored = {key: value for key, value in result.items() if key not in ('Z', 'R', 'results_cwz')}
+    if drop is not None:
+        stored['blacklist'] = drop
     write_npz(npz_path, arguments=vars(args), runtime=getRuntime(), binsize=binsize, samples=np.array([str(p) for p in args.infiles]),
               chromosome_sizes=np.array(chrom_sizes, dtype=np.int64), windows=np.array(windows, dtype=np.int64), **stored)
+    if robust:
+        from . import blacklist
+        listed = np.zeros(len(result['robust_i']), dtype=bool)
+        if criteria is not None:
+            listed = blacklist.listedBins(result['robust_i'], result['robust_f'], len(fold_of), **criteria)
+        with open(crossvalBinsOutput(args.outfile), 'w') as handle:
+            handle.write(crossval.binsText(chrom_sizes, binsize, result['bins_i'], result['bins_f'], result['robust_f'], listed))
+        if hasattr(args, 'makeblacklist'):
+            note = ' '.join('%s=%r' % (key, value) for key, value in sorted(criteria.items()) if value is not None)
+            runs = blacklist.writeBlacklist(args.makeblacklist, listed, chrom_sizes, binsize, note=note)
+            print('Blacklist %s: %d bins in %d runs listed' % (args.makeblacklist, int(listed.sum()), runs))
     with open(samples_path, 'w') as handle:
         handle.write(crossval.samplesText([os.path.basename(str(p)) for p in args.infiles], result['rec_i'], result['rec_f']))
     text = crossval.windowsText(table)
@@ -835,6 +906,12 @@ def _not_in_this_build(args):
 def _chromosome_list(text):
     return [int(token) for token in text.split(',')]
 
+
+#: `-blacklist` of newref, newrefprep and crossval (build-only).  SUPPRESS keeps it out of the namespace, and so out of the
+#: `arguments` of the written files and of `report`'s text, unless it is given
+_BLACKLIST_OPTION = dict(type=str, default=argparse.SUPPRESS,
+                         help='BED file (base pairs, chr1 .. chr22 or 1 .. 22) of regions to leave out of the reference: a bin '
+                              'that meets one is masked like a bin without reads')
 
 #: options shared by `test` and `testbatch`: (flag, argparse settings)
 _TEST_OPTIONS = (
@@ -971,6 +1048,7 @@ def buildParser():
                         'number of visible GPUs, of GPU processes')
     p.add_argument('-parts', type=int, default=1, help='number of part files when larger than -cpus')
     p.add_argument('-gpus', type=int, default=None, help='GPU processes to use (build-only option)')
+    p.add_argument('-blacklist', **_BLACKLIST_OPTION)
     p.set_defaults(func=toolNewref)
 
     p = sub.add_parser('newrefprep', description='Step 1 of a split reference build: the prep file')
@@ -978,6 +1056,7 @@ def buildParser():
     p.add_argument('prepfile', type=str, help='prep file to write (.npz)')
     p.add_argument('-binsize', type=int, default=None,
                    help='merge sample bins to this size first (a multiple of their own size)')
+    p.add_argument('-blacklist', **_BLACKLIST_OPTION)
     p.set_defaults(func=toolNewrefPrep)
 
     p = sub.add_parser('newrefpart', description='Step 2 of a split reference build: one part')
@@ -1061,6 +1140,17 @@ def buildParser():
                    help='directory receiving <sample>_test.npz, the held-out result of every sample in the format of test')
     for flag, settings in _TEST_OPTIONS:
         p.add_argument(flag, **settings)
+    p.add_argument('-blacklist', **_BLACKLIST_OPTION)
+    # build-only additions; SUPPRESS keeps them out of the namespace (and the `arguments` of out.npz) unless they are given
+    p.add_argument('-robust', action='store_true', default=argparse.SUPPRESS,
+                   help='per bin the median and the median absolute deviation of the held-out z-scores, from the GPU: two more '
+                        'arrays in out.npz, and out_bins.tsv')
+    p.add_argument('-makeblacklist', type=str, default=argparse.SUPPRESS,
+                   help='BED file to write: the bins whose robust spread lies above -maxspread (implies -robust, needs -maxspread)')
+    p.add_argument('-maxspread', type=float, default=argparse.SUPPRESS, help='list a bin when 1.4826 * mad of its z-scores is above this')
+    p.add_argument('-maxshift', type=float, default=argparse.SUPPRESS, help='and when the |median| of its z-scores is above this')
+    p.add_argument('-mincover', type=float, default=argparse.SUPPRESS,
+                   help='but only bins that this share of the samples tested with a finite z (default 0.5)')
     p.set_defaults(func=toolCrossval)
 
     p = sub.add_parser('downsample', description='thin a converted sample to a fraction of its reads on the GPU (build-only)')

@@ -429,7 +429,7 @@ def _pinned(shape):
         return np.empty(shape)
 
 
-def prepReference(samples, pcacomp=3, device=0, device_out=False, counts=None, chrom_bins=None):
+def prepReference(samples, pcacomp=3, device=0, device_out=False, counts=None, chrom_bins=None, drop=None):
     """toNumpyArray + trainPCA (wisetools.py:240-264, 89-101) with the bins-sized work on the GPU.
 
     The Gram matrix of the centred [samples, bins] data comes from the GPU (float64 matrix
@@ -447,6 +447,10 @@ def prepReference(samples, pcacomp=3, device=0, device_out=False, counts=None, c
 
     counts / chrom_bins: the samples already as the dense int32 [samples, bins] matrix of
     samples_to_counts (a caller that ingests many files keeps them that way); `samples` is ignored.
+
+    drop: a blacklist, one value per bin of the layout (blacklist.readBlacklist).  A bin whose value is set leaves the mask
+    as a bin that is empty in every sample does, and every later stage follows the mask (wc_newref_prep_gram_ex).
+    ValueError for another length.
     """
     lib = _lib.load()
     ctx = _lib.context(device)
@@ -463,9 +467,13 @@ def prepReference(samples, pcacomp=3, device=0, device_out=False, counts=None, c
     n_b = ctypes.c_int64()
     on_gpu = _eig_on_gpu(n_s, pcacomp)
     gram = None if on_gpu else np.empty((n_s, n_s))
-    _lib.check(lib.wc_newref_prep_gram(ctx, _lib.ptr(counts), n_s, n_total, _lib.ptr(sizes), len(sizes),
-                                       _lib.ptr(mask), _lib.ptr(mbins), ctypes.byref(n_b),
-                                       None if on_gpu else _lib.ptr(gram)))
+    if drop is not None:
+        drop = np.ascontiguousarray(np.asarray(drop).reshape(-1) != 0, dtype=np.uint8)
+        if len(drop) != n_total:
+            raise ValueError('a blacklist of %d bins for a layout of %d' % (len(drop), n_total))
+    _lib.check(lib.wc_newref_prep_gram_ex(ctx, _lib.ptr(counts), n_s, n_total, _lib.ptr(sizes), len(sizes),
+                                          _lib.ptr(mask), _lib.ptr(mbins), ctypes.byref(n_b),
+                                          None if on_gpu else _lib.ptr(gram), _lib.ptr(drop)))
     if on_gpu:          # the Gram matrix never leaves HBM
         evals, evecs = np.empty(pcacomp), np.empty((pcacomp, n_s))
         _lib.check(lib.wc_newref_prep_eig(ctx, int(pcacomp), _lib.ptr(evals), _lib.ptr(evecs)))
