@@ -133,6 +133,11 @@ int wc_newref_export_raw_dev(wc_ctx *ctx, void *stream, int64_t row_begin, int64
 int wc_newref_index_bits(wc_ctx *ctx);
 int wc_newref_set_index_bits(wc_ctx *ctx, int bits);
 int wc_slack_code_host(const float *slack, int64_t n, int code_bits, uint32_t *code_out, float *decoded_out);
+/* For tests: the 32-bit image of a row's float64-ordered distance keys on which k_rescore ranks the row's pairs
+ * (csrc/common.h, order_key32), on the host.  key[n] are the row's keys (~0 = no distance); min_hi_out = the smallest
+ * high word among them, image_out[i] = min((key[i] - (min_hi << 32)) >> shift, 0xFFFFFFFE), 0xFFFFFFFF for ~0.
+ * shift 0..32, or -1 for the kernel's own.                                                                        */
+int wc_order_key_host(const uint64_t *key, int64_t n, int shift, uint32_t *image_out, uint32_t *min_hi_out);
 int wc_newref_finish_dev(wc_ctx *ctx, void *stream, int64_t row_begin, int64_t row_end,
                          int32_t *idx_out, double *dist_out);
 /* stage D in its two halves, for callers that time them apart: the per-row fast path, then

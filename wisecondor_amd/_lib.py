@@ -40,6 +40,7 @@ SIGNATURES = {
     "wc_newref_index_bits": (_i32, [_vp]),
     "wc_newref_set_index_bits": (_i32, [_vp, _i32]),
     "wc_slack_code_host": (_i32, [_vp, _i64, _i32, _vp, _vp]),
+    "wc_order_key_host": (_i32, [_vp, _i64, _i32, _vp, _vp]),
     "wc_newref_finish_dev": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp]),
     "wc_newref_rescore_dev": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp]),
     "wc_newref_fallback_dev": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp]),

@@ -117,6 +117,21 @@ __host__ __device__ inline double f64_from_ordered(uint64_t u) {
     return d;
 }
 
+// ---- 32-bit rank image of a row's float64-ordered distance keys -------------------
+// k_rescore orders a row's pairs by counting on this image instead of the 64-bit key.  `min_hi` is the smallest high
+// word among the row's keys, so anchor = min_hi << 32 is at most every key; the image is (key - anchor) >> sh, held at
+// 0xFFFFFFFE from there on (with sh = ORDER_KEY_SH = 24: 2^-28 relative resolution over the sixteen binades above the
+// row's smallest distance, one code for everything beyond), and 0xFFFFFFFF for the key of an entry without a distance
+// (~0: NaN or >= 1e10).  Monotone in the key, so distinct images are ordered as their keys; equal images of different
+// keys land on one slot of the counting order like equal keys and send the row through the sweep on (key, position):
+// the result never depends on sh.  Requires (key >> 32) >= min_hi.
+constexpr int ORDER_KEY_SH = 24;
+__host__ __device__ inline uint32_t order_key32(uint64_t key, uint32_t min_hi, int sh) {
+    if (key == ~0ull) return 0xFFFFFFFFu;
+    const uint64_t q = (key - ((uint64_t)min_hi << 32)) >> sh;
+    return q < 0xFFFFFFFEull ? (uint32_t)q : 0xFFFFFFFEu;
+}
+
 // ---- numpy pairwise summation ---------------------------------------------------
 // numpy's add.reduce over a contiguous float64 run of n elements
 // (loops_utils.h.src pairwise_sum): n < 8 sequential from 0; n <= 128 eight strided

@@ -1728,7 +1728,7 @@ struct RowSum {
 // fill one row) and the per-candidate reads (sixteen lanes, sixteen rows) conflict free without
 // padding; the piece addresses are loop invariants held in registers.
 // Dynamic LDS: [target row: Sp doubles][wave slabs: 8 KB each]; after the sums (one barrier) the
-// slab memory holds dk / jv (distances and candidates as computed) and sd / sj (in order).
+// slab memory holds dk / jv (distances and candidates as computed), sd / sj (in order) and rk (the rank keys).
 constexpr int SLAB_DOUBLES = 64 * ST_CH;
 // A wave's passes follow its pairs: the nb pairs of a trip fill (nb + 7) / 8 passes of eight candidate rows ((nb + 15) / 16
 // DMA groups of sixteen), and the chunk loop is instantiated on that count -- the staging registers of a pass keep
@@ -1835,6 +1835,132 @@ __device__ __forceinline__ void rescore_chunks_staged(const FinishArgs &a, RowSu
     }
 }
 
+// -- the order of a row's pairs (the tail of k_rescore) --------------------------------------
+// Smallest value of a wave (all 64 lanes active): four v_min_u32 over DPP row shifts leave a row's minimum in its last
+// lane (a lane without a source keeps the identity), the four rows meet in scalar registers.
+__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
+#define WC_MIN_SHR(N)                                                                                              \
+    {                                                                                                              \
+        const uint32_t o = (uint32_t)__builtin_amdgcn_update_dpp((int)0xFFFFFFFF, (int)v, 0x110 + N, 0xF, 0xF, false); \
+        v = o < v ? o : v;                                                                                         \
+    }
+    WC_MIN_SHR(1) WC_MIN_SHR(2) WC_MIN_SHR(4) WC_MIN_SHR(8)
+#undef WC_MIN_SHR
+    const uint32_t a = (uint32_t)__builtin_amdgcn_readlane((int)v, 15), b = (uint32_t)__builtin_amdgcn_readlane((int)v, 31);
+    const uint32_t c = (uint32_t)__builtin_amdgcn_readlane((int)v, 47), d = (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
+    const uint32_t ab = a < b ? a : b, cd = c < d ? c : d;
+    return ab < cd ? ab : cd;
+}
+
+constexpr int ORDER_OVERREAD = 64;                      // bytes behind the rank keys that order_rank may read
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(3))) u32x4 lds_u32x4_t;
+
+// #{u : rk[u] < mine} over n16 x 16 rank keys (the row's, padded with the top code to whole trips): a trip is four
+// 16-byte reads and sixteen 32-bit compares; the next trip's reads are issued in front of this trip's compares.
+__device__ __forceinline__ int order_rank(const uint32_t *rk, int n16, uint32_t mine) {
+    // Two register sets in turn, and the reads volatile: with one set and a copy, or with plain reads, the compiler
+    // moves every read down to the compares that use it and the trip waits out its whole LDS latency.  The read in
+    // front of the last trip's compares goes one trip beyond the keys, inside the slab memory (ORDER_OVERREAD); it is
+    // never counted.
+    const volatile lds_u32x4_t *rp = (const volatile lds_u32x4_t *)rk;
+    u32x4 a0 = rp[0], a1 = rp[1], a2 = rp[2], a3 = rp[3], b0, b1, b2, b3;
+    int rank = 0;
+    auto count = [&](const u32x4 &k) { rank += (k.x < mine) + (k.y < mine) + (k.z < mine) + (k.w < mine); };
+    for (int u = 1;; u += 2) {
+        b0 = rp[4], b1 = rp[5], b2 = rp[6], b3 = rp[7];
+        count(a0); count(a1); count(a2); count(a3);
+        if (u >= n16) break;
+        rp += 8;
+        a0 = rp[0], a1 = rp[1], a2 = rp[2], a3 = rp[3];
+        count(b0); count(b1); count(b2); count(b3);
+        if (u + 1 >= n16) break;
+    }
+    return rank;
+}
+
+// The row's R pairs, (my_d[t], my_j[t]) of trip t in the thread that re-scored them (pair t * ps + tid), in stable
+// (distance, position) order -> output row (wisetools.py:305-324).  `lds` is the slab memory behind the row's own
+// values, which every wave has left; `min_hi` the smallest high word among the row's keys.
+// Order by counting on the 32-bit image of the key (order_key32): element t goes to slot #{u : r_u < r_t}.  Equal
+// images -- equal distances, distances closer than the image resolves or both beyond its range, entries without a
+// distance -- are rare; they land on one slot, one of them finds the other's index there, and the row goes through a
+// second sweep on the full key with the index as tie-break.  TRIPS: the most pairs a thread may hold.
+template <int TRIPS>
+__device__ __forceinline__ void rescore_order(const PickArgs &p, double *lds, int64_t row, int R, int tid, int2 own,
+                                              uint32_t min_hi, int *clash, const unsigned long long *my_d,
+                                              const int *my_j) {
+    const FinishArgs &a = p.f;
+    asm volatile("" : "+v"(tid));       // opaque: nothing formed from the thread number lives through the chunk loop for this
+    unsigned long long *dk = reinterpret_cast<unsigned long long *>(lds);
+    unsigned long long *sd = dk + RMAX + 2;
+    int *jv = reinterpret_cast<int *>(sd + RMAX);
+    int *sj = jv + RMAX + 2;
+    uint32_t *rk = reinterpret_cast<uint32_t *>(sj + RMAX + 2);       // 16-byte aligned; RMAX is whole trips
+    uint32_t my_r[TRIPS];
+#pragma unroll
+    for (int t = 0; t < TRIPS; ++t) {
+        const int e = t * p.ps + tid;
+        if (e < R) {
+            my_r[t] = wc::order_key32(my_d[t], min_hi, wc::ORDER_KEY_SH);
+            dk[e] = my_d[t];
+            jv[e] = my_j[t];
+            rk[e] = my_r[t];
+        }
+    }
+    const int n16 = __builtin_amdgcn_readfirstlane((R + 15) >> 4);
+    if (tid < 16 && R + tid < 16 * n16) rk[R + tid] = 0xFFFFFFFFu;    // never below a real one
+    wc_sync();
+    int slot[TRIPS];
+    {
+        int t2 = 0;
+        for (int e = tid; e < R; e += p.ps, ++t2) {
+            uint32_t mine = 0;
+            unsigned long long d = 0;
+            int j = 0;
+#pragma unroll
+            for (int t = 0; t < TRIPS; ++t)
+                if (t == t2) { mine = my_r[t]; d = my_d[t]; j = my_j[t]; }
+            const int rank = order_rank(rk, n16, mine);
+            sd[rank] = d;
+            sj[rank] = j;
+#pragma unroll
+            for (int t = 0; t < TRIPS; ++t)
+                if (t == t2) slot[t] = rank;
+        }
+    }
+    wc_sync();
+    // (a flag and one barrier: __syncthreads_or is a reduction, an LDS atomic and three barriers)
+#pragma unroll
+    for (int t = 0; t < TRIPS; ++t)
+        if (t * p.ps + tid < R && sj[slot[t]] != my_j[t]) *clash = 1;  // the indexes are unique
+    wc_sync();
+    if (__builtin_amdgcn_readfirstlane(*clash)) {
+        for (int t = tid; t < R; t += p.ps) {
+            const unsigned long long mine = dk[t];
+            const int myj = jv[t];
+            int rank = 0;
+            for (int u = 0; u < R; ++u) rank += (dk[u] < mine) | ((dk[u] == mine) & (jv[u] < myj));
+            sd[rank] = mine;
+            sj[rank] = myj;
+        }
+        wc_sync();
+    }
+    const int cs = own.x, ce = own.y;
+    const int64_t orow = row - a.row_begin;
+    for (int t = tid; t < a.k; t += p.ps) {
+        int32_t oi = -1;                                 // fewer candidates than k: sentinels (wisetools.py:305-306)
+        double od = SENTINEL_DISTANCE;
+        if (t < R && sd[t] != ~0ull) {
+            const int myj = sj[t];
+            oi = (int32_t)(myj < cs ? myj : myj - (ce - cs));
+            od = wc::f64_from_ordered(sd[t]);
+        }
+        a.idx_out[orow * a.k + t] = oi;
+        a.dist_out[orow * a.k + t] = od;
+    }
+}
+
 template <bool SEQ, bool GLDS>
 __global__ __launch_bounds__(PS_MAX, (SEQ && !GLDS) ? 4 : (SEQ ? 5 : 3)) void k_rescore(PickArgs p, const double *__restrict__ Xp, int Sp) {
     const FinishArgs &a = p.f;
@@ -1855,6 +1981,9 @@ __global__ __launch_bounds__(PS_MAX, (SEQ && !GLDS) ? 4 : (SEQ ? 5 : 3)) void k_
         for (int s = tid; s < Sp; s += p.ps) xs[s] = xi[s];
     }
     if (R < 0) return;                                   // exact path (workgroup-uniform)
+    __shared__ uint32_t s_min_hi;
+    __shared__ int s_clash;                              // two pairs on one slot of the order (rescore_order)
+    if (tid == 0) { s_min_hi = 0xFFFFFFFFu; s_clash = 0; }
     wc_sync();
     const int l8 = lane & 7, r0 = lane >> 3;
     constexpr int NP = 8;                                // 8 rows per pass x 8 passes = the wave's 64 candidates
@@ -1913,67 +2042,17 @@ __global__ __launch_bounds__(PS_MAX, (SEQ && !GLDS) ? 4 : (SEQ ? 5 : 3)) void k_
         const bool ok = lane < nb && d < SENTINEL_DISTANCE;  // NaN and >= 1e10 are never admitted (wisetools.py:314)
         const unsigned long long dd = ok ? wc::f64_ordered(d) : ~0ull;
         const int jj = ok ? cj : 0x40000000 + b0 + lane;      // unique, after every real index
+        // the smallest high word of the row's keys, for the rank image: the wave's into LDS (~0 carries the identity)
+        const uint32_t hmin = wave_min_u32((uint32_t)(dd >> 32));
+        if (lane == 0) atomicMin(&s_min_hi, hmin);
 #pragma unroll
         for (int t = 0; t < TRIPS; ++t)
             if (t == trip) { my_d[t] = dd; my_j[t] = jj; }
     }
-    wc_sync();                                     // every wave is through with its slab
-    unsigned long long *dk = reinterpret_cast<unsigned long long *>(rs_dyn + Sp);
-    unsigned long long *sd = dk + RMAX + 2;
-    int *jv = reinterpret_cast<int *>(sd + RMAX);
-    int *sj = jv + RMAX + 2;
-    {
-        int t2 = 0;
-        for (int b0 = w * 64; b0 < R; b0 += p.ps, ++t2) {
-#pragma unroll
-            for (int t = 0; t < TRIPS; ++t)
-                if (t == t2 && b0 + lane < R) { dk[b0 + lane] = my_d[t]; jv[b0 + lane] = my_j[t]; }
-        }
-    }
-    // Order by counting: element t goes to slot #{u : d_u < d_t}.  Equal distances are rare; they
-    // land on one slot and leave a hole, which sends the row through a second sweep with the
-    // index as tie-break (stable (distance, position) order, wisetools.py:313-321).
-    if (tid == 0 && (R & 1)) dk[R] = ~0ull;
-    for (int t = tid; t < R; t += p.ps) sj[t] = -1;
-    wc_sync();
-    for (int t = tid; t < R; t += p.ps) {
-        const unsigned long long mine = dk[t];
-        int rank = 0;
-        for (int u = 0; u < R; u += 2) {
-            const u64x2 kk = *(const u64x2 *)&dk[u];
-            rank += kk.x < mine;
-            rank += kk.y < mine;
-        }
-        sd[rank] = mine;
-        sj[rank] = jv[t];
-    }
-    wc_sync();
-    int hole = 0;
-    for (int t = tid; t < R; t += p.ps) hole |= sj[t] == -1;
-    if (wc_sync_or(hole)) {
-        for (int t = tid; t < R; t += p.ps) {
-            const unsigned long long mine = dk[t];
-            const int myj = jv[t];
-            int rank = 0;
-            for (int u = 0; u < R; ++u) rank += (dk[u] < mine) | ((dk[u] == mine) & (jv[u] < myj));
-            sd[rank] = mine;
-            sj[rank] = myj;
-        }
-        wc_sync();
-    }
-    const int cs = own.x, ce = own.y;
-    const int64_t orow = row - a.row_begin;
-    for (int t = tid; t < a.k; t += p.ps) {
-        int32_t oi = -1;                                 // fewer candidates than k: sentinels (wisetools.py:305-306)
-        double od = SENTINEL_DISTANCE;
-        if (t < R && sd[t] != ~0ull) {
-            const int myj = sj[t];
-            oi = (int32_t)(myj < cs ? myj : myj - (ce - cs));
-            od = wc::f64_from_ordered(sd[t]);
-        }
-        a.idx_out[orow * a.k + t] = oi;
-        a.dist_out[orow * a.k + t] = od;
-    }
+    wc_sync();                                    // every wave is through with its slab
+    // (TRIPS = 1, the rows with a pair per thread at most: no selection among the trips' registers)
+    if (R <= p.ps) rescore_order<1>(p, rs_dyn + Sp, row, R, tid, own, s_min_hi, &s_clash, my_d, my_j);
+    else rescore_order<TRIPS>(p, rs_dyn + Sp, row, R, tid, own, s_min_hi, &s_clash, my_d, my_j);
 }
 
 // -- exact path: the slow filler and the selection ------------------------------------------
@@ -2797,6 +2876,17 @@ int wc_slack_code_host(const float *slack, int64_t n, int code_bits, uint32_t *c
     return WC_OK;
 }
 
+int wc_order_key_host(const uint64_t *key, int64_t n, int shift, uint32_t *image_out, uint32_t *min_hi_out) {
+    WC_CHECK(key && image_out && min_hi_out && n >= 0, WC_E_ARG, "order key: bad argument");
+    WC_CHECK(shift >= -1 && shift <= 32, WC_E_ARG, "order key: shift -1 (the kernel's) or 0..32");
+    const int sh = shift < 0 ? wc::ORDER_KEY_SH : shift;
+    uint32_t min_hi = 0xFFFFFFFFu;          // as the kernel: over every key (an entry without a distance has the top word)
+    for (int64_t i = 0; i < n; ++i) min_hi = std::min(min_hi, (uint32_t)(key[i] >> 32));
+    for (int64_t i = 0; i < n; ++i) image_out[i] = wc::order_key32(key[i], min_hi, sh);
+    *min_hi_out = min_hi;
+    return WC_OK;
+}
+
 int wc_newref_import_lists_dev(wc_ctx *ctx, void *stream, int64_t row_begin, int64_t row_end, int64_t src_cap,
                                const int32_t *src_cnt, const uint64_t *src_list) {
     WC_CHECK(ctx && ctx->nr.prepared && src_cnt && src_list && src_cap > 0, WC_E_ARG, "newref: bad argument");
@@ -2968,12 +3058,12 @@ static int newref_finish_part(wc_ctx *ctx, void *stream_, int64_t row_begin, int
         if ((rc = st.pairs.reserve(sizeof(int) * st.bins_pad * RMAX))) return rc;
         PickArgs p{a, st.pairs.as<int>(), ps};
         if (which & 5) hipLaunchKernelGGL(k_pick, dim3((rows + 3) / 4), dim3(256), 0, stream, p);
-        // wave slabs; after the sums the same memory holds dk / sd / jv / sj of the counting order.
+        // wave slabs; after the sums the same memory holds dk / sd / jv / sj / rk of the counting order (rescore_order).
         // Chunk staging: LDS-DMA for the pairwise order (100 samples x 250 kb: 0.099 vs 0.131 ms, no staging
         // registers), registers for the sequential order (0.076 vs 0.083 ms: the DMA of the next chunk can only
         // be issued after this chunk's LDS reads have returned)
         const size_t slabs = sizeof(double) * (size_t)(ps / 64) * SLAB_DOUBLES;
-        const size_t order = (sizeof(unsigned long long) + sizeof(int)) * (2 * RMAX + 4);
+        const size_t order = (sizeof(unsigned long long) + sizeof(int)) * (2 * RMAX + 4) + sizeof(uint32_t) * (RMAX + 2) + ORDER_OVERREAD;
         const size_t dyn = sizeof(double) * st.s_pad + std::max(slabs, order);
         if (!(which & 9)) {
         } else if (seq) hipLaunchKernelGGL((k_rescore<true, false>), dim3(rows), dim3(ps), dyn, stream, p,
